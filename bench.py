@@ -7,19 +7,24 @@ is already resident in HBM: ONE fused kernel launch (+ a small worklist kernel) 
 
   python bench.py --gpus 1 --steps K --warmup W            # single GPU
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # one rank per GPU
+  python bench.py --gpus 1 --steps K --warmup W --full     # + everything listed below
+  python bench.py ... --dump-outputs DIR                   # + the last timed step's outputs as DIR/*.npy
 
 Workload (BASELINE.json configs[2] / configs[4]): 7680x4320 RGBA8, 32x32 tiles, 8 frames per GPU
 (64 frames over 8 GPUs; 1.06 GB of source per GPU per step, well past the 256 MiB Infinity Cache),
 "opaque" synthetic distribution, filter Lanczos3.  `value` is weak scaling: per-GPU work is fixed and the
 timed steps are the same at every N (frames are independent: no collective on the data path).
 
-The ONE JSON line also carries, beside `value`:
+A plain run sets up, times the headline mode (--primary) alone and prints its line.  With --full the ONE JSON
+line also carries, beside `value`:
   modes.shrink_by                            the other caller (Oklab detector), same frames
   modes["shrink_directionally+encode_to_vec"]  the step followed by the device QOI + container writer: frames -> .pixlzr bytes
   strong_scaling (N > 1, or --frames-total)  BASELINE configs[4] as it is stated: a FIXED batch of 64 frames sharded over
                                              the ranks, step = shrink + device writer + gather of the files to rank 0 over
                                              RCCL, the gather of step k running under the shrink of step k + 1
-  roofline, cpu_baseline                     as the measurement contract asks
+  other_tile_sizes, decode_side, block_sweep  the same frames at 64x64 / 16x16 tiles, the way back, one 16384x16384 frame
+  cpu_baseline                               as the measurement contract asks
+The headline's own roofline (its algorithmic bytes over the timed steps) is in every line.
 """
 import argparse
 import json
@@ -60,11 +65,20 @@ def parse():
     ap.add_argument("--no-encode-mode", action="store_true", help="skip the shrink + device writer measurement")
     ap.add_argument("--no-block-sweep", action="store_true", help="skip the 16384x16384 block-size sweep (BASELINE configs[3])")
     ap.add_argument("--frames-total", type=int, default=0,
-                    help="strong-scaling leg: a fixed batch of this many frames over all ranks (default: 64 when N > 1, off at N = 1)")
+                    help="strong-scaling leg (--full): a fixed batch of this many frames over all ranks (default: 64 when N > 1, off at N = 1)")
     ap.add_argument("--strong-steps", type=int, default=20)
     ap.add_argument("--strong-timeout", type=float, default=240.0, help="seconds the strong-scaling leg may take before it is abandoned")
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling leg (shrink + writer + gather to rank 0)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure the other detector (--mode both), the shrink + device writer step, the other "
+                         "tile sizes, the decode side, the 16384x16384 block sweep, the CPU baseline and (N > 1) the strong-scaling leg; "
+                         "the --no-* options leave parts of it out.  Without it a run times the headline mode alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline mode computed in the last of them (rank 0) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def histogram(ow, oh):
@@ -91,11 +105,44 @@ def agree(dist_mod, world, device, ok):
     return bool(int(t[0]))
 
 
-def run_mode(args, handle, frames, mode_name, world, dist_mod, with_writer=False, steps=None):
+DUMP_BYTES_PER_TILE = 20          # values, width, height (f32) + pixel_sum (f64) of every tile written
+DUMP_TILE_ARRAYS_MAX = 32 << 20   # the per-tile arrays cover the first frames that fit in this many bytes ...
+DUMP_PIXELS_MAX = 28 << 20        # ... and the stored pixels of a seeded sample of their tiles this many (64 MB in all at most)
+
+
+def dump_outputs(path, out, channels, seed=0):
+    """What shrink_frames_device returned for the last timed step, as float .npy files under `path`: values, width, height
+    ([F, T]: F = the first frames whose per-tile arrays fit DUMP_TILE_ARRAYS_MAX), pixel_sum ([F, T] f64: the sum of the
+    w*h*C bytes a slot holds for its tile, so every stored pixel counts), and pixels ([K, slot bytes]) of K tiles drawn
+    with a fixed seed (pixels_tile: their index f*T + t), bytes past a tile's w*h*C zeroed: the rest of a slot is
+    unspecified (include/pixlzr_hip.h) and may differ between two correct runs."""
+    import numpy as np
+    import torch
+    vals, ow, oh, slots = out
+    N, T, S = slots.shape
+    F = max(1, min(N, DUMP_TILE_ARRAYS_MAX // (DUMP_BYTES_PER_TILE * T)))
+    nbytes = ow[:F].long() * oh[:F].long() * channels
+    col = torch.arange(S, device=slots.device)
+    pixel_sum = torch.stack([torch.where(col[None, :] < nbytes[f][:, None], slots[f], 0).sum(dim=1, dtype=torch.int64)
+                             for f in range(F)])
+    K = min(F * T, max(1, DUMP_PIXELS_MAX // (4 * S)))
+    pick = np.sort(np.random.default_rng(seed).choice(F * T, size=K, replace=False))
+    sel = torch.from_numpy(pick).to(slots.device)
+    pixels = slots[:F].reshape(F * T, S)[sel]
+    pixels = torch.where(col[None, :] < nbytes.reshape(-1)[sel][:, None], pixels, 0)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"values": vals[:F], "width": ow[:F].float(), "height": oh[:F].float(), "pixel_sum": pixel_sum.double(),
+              "pixels": pixels.float(), "pixels_tile": torch.from_numpy(pick.astype(np.float64))}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+
+
+def run_mode(args, handle, frames, mode_name, world, dist_mod, with_writer=False, steps=None, dump_dir=None):
     """Times K steps of one detector mode; returns a dict of measurements (max over ranks).
     A step is the fused hot-path launch over this rank's frames -- the same at every N: the tiles of
     different frames are independent, so the timed loop has no collective.  with_writer: the device QOI +
-    container writer (Pixlzr::encode_to_vec) follows the shrink inside every step."""
+    container writer (Pixlzr::encode_to_vec) follows the shrink inside every step.  dump_dir: rank 0 writes the
+    outputs of the last timed step there (dump_outputs)."""
     import torch
     pxz_mode, factor = MODES[mode_name]
     N, H, W, C = frames.shape
@@ -143,6 +190,8 @@ def run_mode(args, handle, frames, mode_name, world, dist_mod, with_writer=False
         t = torch.tensor([elapsed, kernel_ms, first_ms], dtype=torch.float64, device=frames.device)
         dist_mod.all_reduce(t, op=dist_mod.ReduceOp.MAX)
         elapsed, kernel_ms, first_ms = float(t[0]), float(t[1]), float(t[2])
+    if dump_dir and int(os.environ.get("RANK", "0")) == 0:
+        dump_outputs(dump_dir, out, C)
 
     tiles = ow.numel()
     out_bytes = int((ow.long() * oh.long()).sum().item()) * C
@@ -455,11 +504,13 @@ def main():
 
     names = list(MODES) if args.mode == "both" else [args.mode]
     primary = args.primary if args.primary in names else names[0]
+    if not args.full:
+        names = [primary]
     results = {}
     for name in names:
         note(f"{name}: {args.steps} steps")
-        results[name] = run_mode(args, handle, frames, name, world, dist)
-    if not args.no_encode_mode and "shrink_directionally" in names:
+        results[name] = run_mode(args, handle, frames, name, world, dist, dump_dir=args.dump_outputs if name == primary else None)
+    if args.full and not args.no_encode_mode and "shrink_directionally" in names:
         note(ENCODE_MODE)
         results[ENCODE_MODE] = run_mode(args, handle, frames, "shrink_directionally", world, dist, with_writer=True,
                                         steps=min(args.steps, 200))
@@ -498,7 +549,7 @@ def main():
 
     # not the metric: the same frames at the reference CLI's default 64x64 tiles and at 16x16
     others = {}
-    if world == 1 and not args.no_other_sizes:
+    if world == 1 and args.full and not args.no_other_sizes:
         for bs in (64, 16):
             for name, (pxz_mode, factor) in MODES.items():
                 others[f"{bs}x{bs} {name}"] = timed_shrink(frames, bs, pxz_mode, factor, ("dir" if pxz_mode == 1 else "by") + str(bs))
@@ -518,7 +569,7 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / n
 
-    if world == 1 and not args.no_other_sizes:
+    if world == 1 and args.full and not args.no_other_sizes:
         for bs in (32, 64, 16):
             suffix = "" if bs == 32 else f" {bs}x{bs}"
             vals2, ow, oh, slots = handle.shrink_frames_device(frames, bs, bs, 1, args.filter, MODES["shrink_directionally"][1])
@@ -552,7 +603,7 @@ def main():
 
     # BASELINE configs[3]: ONE 16384 x 16384 RGBA frame (1.07 GB), tiles of 16 / 32 / 64 px, both callers
     block_sweep = {}
-    if world == 1 and not args.no_other_sizes and not args.no_block_sweep:
+    if world == 1 and args.full and not args.no_other_sizes and not args.no_block_sweep:
         note("block sweep on one 16384x16384 frame")
         del frames
         torch.cuda.empty_cache()
@@ -584,7 +635,8 @@ def main():
                                    f"device-resident, one fused launch per step",
                        "mode": primary, "frames_per_gpu": nf, "tile": args.block,
                        "parallelism": f"{world} ranks x {nf} frames, frames sharded over ranks, no collective in the timed steps"
-                                      + ("; see strong_scaling for the fixed 64-frame batch with the gather to rank 0 in the step" if world > 1 else ""),
+                                      + ("; see strong_scaling for the fixed 64-frame batch with the gather to rank 0 in the step"
+                                         if world > 1 and args.full and not args.no_strong else ""),
                        "tile_size_histogram_frame0": r["histogram"]},
             # `achieved` / `frac`: the step's algorithmic bytes over the step's WALL CLOCK (the conservative figure: launch gaps and the
             # worklist kernel are inside it); the dominant kernel's own duration by HIP events -- the figure a rocprofv3 kernel trace
@@ -613,12 +665,12 @@ def main():
             line["decode_side"] = decode_side
         if block_sweep:
             line["block_sweep"] = {"workload": "1x 16384x16384 RGBA8 frame (BASELINE configs[3]), factor as in MODES, filter as --filter", **block_sweep}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             note("cpu baseline")
             line["cpu_baseline"] = cpu_baseline(args, primary, names)
 
     # the strong-scaling leg comes last and under a watchdog: whatever happens to the exchange, the line above is printed
-    frames_total = args.frames_total or (64 if world > 1 else 0)
+    frames_total = (args.frames_total or (64 if world > 1 else 0)) if args.full else 0
     failed = False
     if frames_total and not args.no_strong:
         def on_expiry():  # a leg stuck in a collective: say what is known, then the process ends non-zero (dist.exit_on_timeout)
