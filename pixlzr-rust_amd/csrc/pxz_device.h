@@ -100,6 +100,14 @@ __device__ __forceinline__ uint32_t wave_and_u32(uint32_t v)
 	return v;
 }
 
+// A 64-bit value (an address) made wave-uniform, i.e. a scalar: lane 0's two halves.  The builtin returns a signed int:
+// without the casts a low half of 2^31 and more is sign-extended over the high one.
+__device__ __forceinline__ uint64_t uniform64(uint64_t v)
+{
+	return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
+	       (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
 __device__ __forceinline__ uint32_t fbits(float f) { return __float_as_uint(f); }
 
 // reference operations.rs:128-138

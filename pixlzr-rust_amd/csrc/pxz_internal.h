@@ -105,6 +105,13 @@ struct ShrinkArgs {
 	float *lod0;             //   after the worklist, the tiles shrink32_kernel completed; each may be null
 	float *lod1;
 	uint32_t *sums;          // 2 per tile: gradient sums (directional) | f32 value bits (Oklab); -> finish_kernel
+	                         //   With clone_ahead, sums[2 t + 1] is oklab2_kernel<AHEAD>'s "tile t was copied into its slot" flag (1).
+	                         //   Every other path leaves gradient sums or value bits in that dword (a directional tile whose
+	                         //   sum_vr is 1 leaves a 1), and a tile skipped as copied keeps its (value, 1) for the next
+	                         //   launch on the handle.  Invariant: a consumer reads the flag only when clone_ahead is set in THIS
+	                         //   launch, and only for tiles that oklab2_kernel<AHEAD> took in this launch (tx < full_cols,
+	                         //   ty < full_rows <= ok_rows), which writes the flag of every tile it takes.  A tile read as copied
+	                         //   without having been copied keeps stale slot bytes and faults nothing (tests/test_gpu_handle_reuse.py).
 	uint32_t *out_w;
 	uint32_t *out_h;
 	uint8_t *out_px;

@@ -559,15 +559,12 @@ __global__ void __launch_bounds__(1024) oklab2_kernel(const ShrinkArgs a)
 			bands = 0;
 			if constexpr (AHEAD) {
 				const unsigned long long fa = reinterpret_cast<unsigned long long>(a.sums) + 8ull * ((blockIdx.x + j * gridDim.x) * kTiles + pslot) + 4ull;
-				flag1 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(fa >> 32)) << 32) |
-				        (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)fa);
+				flag1 = uniform64(fa);
 				// (in front of the conditions below, which the compiler takes to differ between lanes: set behind them the address
 				// would live in vector registers; the item number IS the tile's number in this launch, whether the tile is taken or not)
 				const unsigned long long d = reinterpret_cast<unsigned long long>(a.out_px) +
 				                             (unsigned long long)((blockIdx.x + j * gridDim.x) * kTiles + pslot) * a.slot_bytes;
-				// (the builtin returns a signed int: the low half must not be sign-extended into the high one)
-				dst1 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(d >> 32)) << 32) |
-				       (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)d);
+				dst1 = uniform64(d);  // (uniform64: the casts that keep a low half of 2^31 and more from being sign-extended)
 			}
 			if (j >= own) return nullptr;
 			uint32_t tile_g;
