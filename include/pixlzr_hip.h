@@ -171,6 +171,34 @@ int pxz_shrink_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
                              const uint8_t *d_pixels, float *d_block_value, uint32_t *d_out_w,
                              uint32_t *d_out_h, uint8_t *d_out_pixels);
 
+/* ---- factor ladder: one batch at several factors ------------------------- */
+#define PXZ_LADDER_MAX_RUNGS 16u
+
+/* Pixlzr::shrink_by | shrink_directionally of the same frames at n_factors factors (one "rung" per factor): what
+ * src/bin/whole-folder.rs:69-117 sweeps with k = i/20, in one call.  Rung r is bit-identical to pxz_shrink_frames_device
+ * with params->factor = factors[r]: values (as bits), out_w, out_h, and the valid out_w*out_h*channels bytes of every slot.
+ * params->factor is ignored; factors is a HOST array (1 <= n_factors <= PXZ_LADDER_MAX_RUNGS, each finite; any order,
+ * repeats allowed).  Outputs are rung-major: index = (r * n_frames + f) * tiles + t, slots of block_w*block_h*channels
+ * bytes as before (64-bit offsets), so the K*N rung sets are a batch of K*N frames to pxz_encode_frames_device.
+ * d_out_pixels may be NULL (values + dims).  Asynchronous on the handle's stream.
+ * Errors: PXZ_ERR_INVALID_ARG for a null factors, n_factors 0 or above the maximum, a non-finite factor; and every
+ * error pxz_shrink_frames_device returns for the same frames and params (e.g. PXZ_ERR_TILE_TOO_SMALL).
+ * shrink_by runs the detector ONCE (its result does not depend on the factor: x * factor * BASE_FACTOR, pixlzr.rs:160-162)
+ * and then one kernel that stages every tile once and resamples it once per distinct level among the rungs -- for every
+ * tile geometry whose LDS image fits (16x16, 32x32, 64x64 and most others; RGB and RGBA, any pitch).  Larger tiles, and
+ * shrink_directionally (whose detector is a few integer operations fused into the shrink kernels), run one single-factor
+ * call per rung: correct, with no amortisation. */
+int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_params *params,
+                                    const float *factors, uint32_t n_factors, const uint8_t *d_pixels,
+                                    float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels);
+
+/* The same for one host-resident image (as pxz_shrink_image: uploads, runs, downloads; synchronous).  Arrays rung-major:
+ * n_factors * tiles values / dims, n_factors * tiles slots. */
+int pxz_shrink_image_ladder(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                            uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter,
+                            const float *factors, uint32_t n_factors, float *block_value, uint32_t *out_w,
+                            uint32_t *out_h, uint8_t *out_pixels);
+
 /* The colour conversion inside get_block_variance, per pixel (operations.rs:56-59: Srgba<u8>::into_linear()
  * .into_color::<Oklaba<f32>>(), palette 0.7.6 + the platform's cbrtf): d_laba[4i..4i+3] = {l, a, b, alpha} of
  * RGBA pixel i.  The same device function the Oklab detector kernels call -- exposed so that its bits can be

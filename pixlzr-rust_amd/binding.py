@@ -20,7 +20,10 @@ EXPORTED_SYMBOLS = [
     "pxz_pack_tiles_device", "pxz_encode_frames_device", "pxz_encode_container", "pxz_qoi_encode", "pxz_qoi_bound", "pxz_synth_frames_device", "pxz_axis_table",
     "pxz_enable_timing", "pxz_last_kernel_ms", "pxz_last_first_kernel_ms", "pxz_handle_state",
     "pxz_debug_read_work", "pxz_expand_frames_device", "pxz_expand_image", "pxz_decode_frames_device", "pxz_decode_file", "pxz_decode_status", "pxz_process_frames_device", "pxz_tree_process_frames_device", "pxz_trim", "pxz_debug_read_status",
+    "pxz_shrink_ladder_frames_device", "pxz_shrink_image_ladder",
 ]
+
+LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
 
 STATUS = {0: "PXZ_OK", -1: "PXZ_ERR_INVALID_ARG", -2: "PXZ_ERR_NO_DEVICE", -3: "PXZ_ERR_HIP",
           -4: "PXZ_ERR_TILE_TOO_SMALL", -5: "PXZ_ERR_UNSUPPORTED", -6: "PXZ_ERR_NOMEM",
@@ -107,6 +110,10 @@ def load_library():
     L.pxz_fetch_packed.argtypes = [vp, vp, C.c_uint64]
     L.pxz_shrink_frames_device.restype = C.c_int
     L.pxz_shrink_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 5
+    L.pxz_shrink_ladder_frames_device.restype = C.c_int
+    L.pxz_shrink_ladder_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params), vp, u32] + [vp] * 5
+    L.pxz_shrink_image_ladder.restype = C.c_int
+    L.pxz_shrink_image_ladder.argtypes = [vp, vp] + [u32] * 8 + [vp, u32] + [vp] * 4
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -285,6 +292,23 @@ class Handle:
                                              mode, filt, C.c_float(factor), _p(vals), _p(ow), _p(oh), _p(slots)))
         return vals, ow, oh, slots
 
+    def shrink_image_ladder(self, img, bw, bh, mode, filt, factors, want_pixels=True):
+        """pxz_shrink_image_ladder: shrink_image at every factor of `factors` in one call.
+        Returns (values[K,T], w[K,T], h[K,T], slots[K,T,bw*bh*C] | None); rung r equals shrink_image(..., factors[r])."""
+        H, W, Cc = img.shape
+        assert img.dtype == np.uint8 and img.strides[2] == 1 and img.strides[1] == Cc
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        cols, rows = grid(W, H, bw, bh)
+        n = cols * rows
+        vals = np.zeros((K, n), np.float32)
+        ow = np.zeros((K, n), np.uint32)
+        oh = np.zeros((K, n), np.uint32)
+        slots = np.zeros((K, n, bw * bh * Cc), np.uint8) if want_pixels else None
+        self._check(self._L.pxz_shrink_image_ladder(self._h, C.c_void_p(img.ctypes.data), W, H, Cc, img.strides[0], bw, bh,
+                                                    mode, filt, _p(fac) if K else None, K, _p(vals), _p(ow), _p(oh), _p(slots)))
+        return vals, ow, oh, slots
+
     def shrink_image_packed(self, img, bw, bh, mode, filt, factor):
         """pxz_shrink_image_packed + pxz_fetch_packed: (values, w, h, stream) with the tiles' pixels back to back."""
         H, W, Cc = img.shape
@@ -364,6 +388,32 @@ class Handle:
         self._check(self._L.pxz_shrink_frames_device(
             self._h, C.byref(fd), C.byref(pd), C.c_void_p(frames.data_ptr()), C.c_void_p(vals.data_ptr()),
             C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()) if slots is not None else None))
+        return vals, ow, oh, slots
+
+    def shrink_ladder_frames_device(self, frames, bw, bh, mode, filt, factors, want_pixels=True, out=None, transparency_hint=False):
+        """pxz_shrink_ladder_frames_device: shrink_frames_device at every factor of `factors` (a host sequence, 1..16 of them)
+        in one call.  Returns (values[K,N,T], w[K,N,T], h[K,N,T], slots[K,N,T,bw*bh*C] | None); rung r equals
+        shrink_frames_device(..., factors[r]).  out: a 4-tuple of such tensors (slots may be None)."""
+        import torch
+        fd, (N, H, W, Cc) = self._frames_desc(frames)
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        cols, rows = grid(W, H, bw, bh)
+        T = cols * rows
+        dev = frames.device
+        if out is None:
+            vals = torch.empty((K, N, T), dtype=torch.float32, device=dev)
+            ow = torch.empty((K, N, T), dtype=torch.int32, device=dev)
+            oh = torch.empty((K, N, T), dtype=torch.int32, device=dev)
+            slots = torch.empty((K, N, T, bw * bh * Cc), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, ow, oh, slots = out
+        pd = Params(bw, bh, mode, filt, 0.0, 1 if transparency_hint else 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_shrink_ladder_frames_device(
+            self._h, C.byref(fd), C.byref(pd), _p(fac) if K else None, K, C.c_void_p(frames.data_ptr()),
+            C.c_void_p(vals.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
             C.c_void_p(slots.data_ptr()) if slots is not None else None))
         return vals, ow, oh, slots
 

@@ -34,6 +34,7 @@ bool fast32_applicable(const ShrinkArgs &a, uint32_t channels);
 bool fast64_applicable(const ShrinkArgs &a, uint32_t channels);
 bool fast16_applicable(const ShrinkArgs &a, uint32_t channels);
 hipError_t launch_expand(const ExpandArgs &a, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_ladder(const LadderArgs &a, uint32_t channels, uint32_t nw, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream);
 hipError_t launch_widen(const WidenArgs &a, hipStream_t stream);
 hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);
@@ -108,6 +109,10 @@ struct pxz_handle {
 	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, ExpandTables> expand_tables;
 	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, TreeTables> tree_tables;
 	DeviceBuffer tree_rects[2], tree_count;
+	DeviceBuffer ladder;              // factor ladder: the raw detector value of every tile, then the rungs' factors
+	float *ladder_host = nullptr;     //   pinned staging of the factors (PXZ_LADDER_MAX_RUNGS floats) ...
+	hipEvent_t ladder_copied = nullptr;  //   ... reused once the copy out of it recorded here has run
+	bool quiet_stats = false;         // the launch being set up writes no kernel-selection statistics (the ladder's detector)
 	uint32_t *host_stats = nullptr;  // pinned, device-visible: [0] = tiles with transparency the last finished 32x32 launch saw
 	uint32_t *dev_stats = nullptr;   //   (its device-side address); read without synchronisation, steers only the kernel choice
 	uint32_t last_alpha_kernel = 0, last_alpha_first = 0;  // what the last launch set up through this handle chose (pxz_handle_state)
@@ -789,7 +794,7 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 	// Transparency without the caller's hint: the last finished launch reported how many full tiles had any
 	// (one dword in pinned memory, written by the worklist kernel).  Past ~2000 tiles shrink32a_kernel pays for
 	// its launch.  Either way the results are the same; only the kernel that produces them differs.
-	a.stats = h->dev_stats;
+	a.stats = h->quiet_stats ? nullptr : h->dev_stats;
 	// (the counts are only trusted when they come from a launch of THIS configuration: the kernel writes the signature beside them)
 	uint32_t factor_bits;
 	std::memcpy(&factor_bits, &a.factor, 4);
@@ -803,8 +808,10 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 		a.alpha_kernel = 1;
 	// ... and past half of the tiles the lean kernel would only read, test and list them: the four-plane kernel goes first
 	a.alpha_first = a.alpha_kernel && seen_transparent >= a.n_tiles / 2u && seen_transparent >= 2048u && !pxz::knobs().no_alpha_first ? 1u : 0u;
-	h->last_alpha_kernel = a.alpha_kernel;
-	h->last_alpha_first = a.alpha_first;
+	if (!h->quiet_stats) {
+		h->last_alpha_kernel = a.alpha_kernel;
+		h->last_alpha_first = a.alpha_first;
+	}
 	// 32x32 fast path: which tiles are full-size, and whether every tile row of the batch is 16-byte aligned
 	a.full_cols = a.full_rows = a.ok_rows = 0;
 	const bool aligned16 = channels == 4 &&
@@ -841,7 +848,7 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 	                          a.bw, a.bh, a.edge_w, a.edge_h, a.mode, a.factor};
 	hipEvent_t e0 = nullptr, e1 = nullptr, emid = nullptr;
 	a.mid_event = nullptr;
-	const bool record = h->timing && (h->timing_count++ % h->timing_stride) == 0;
+	const bool record = !h->quiet_stats && h->timing && (h->timing_count++ % h->timing_stride) == 0;
 	if (record) {
 		if (h->events_used == h->events.size()) {
 			PXZ_HIP(h, hipEventCreate(&e0));
@@ -1055,7 +1062,7 @@ void pxz_destroy(pxz_handle *h)
 		(void)hipFree(kv.second.d_xmf64);
 	}
 	drop_tree_tables(h);
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count})
+	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder})
 		if (b->ptr) (void)hipFree(b->ptr);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
@@ -1065,6 +1072,8 @@ void pxz_destroy(pxz_handle *h)
 		(void)hipEventDestroy(ev.second);
 	}
 	for (hipEvent_t ev : h->mid_events) (void)hipEventDestroy(ev);
+	if (h->ladder_copied) (void)hipEventDestroy(h->ladder_copied);
+	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
 	if (h->host_stats) {
 		(void)hipDeviceSynchronize();  // a queued launch may still write it
 		(void)hipHostFree(h->host_stats);
@@ -1084,12 +1093,16 @@ int pxz_trim(pxz_handle *h)
 		b.ptr = nullptr;
 		b.cap = 0;
 	};
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count})
+	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder})
 		drop(*b);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
 			drop(*b);
 	drop_tree_tables(h);
+	if (h->ladder_copied) (void)hipEventDestroy(h->ladder_copied);
+	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
+	h->ladder_copied = nullptr;
+	h->ladder_host = nullptr;
 	h->packed_len = 0;
 	h->work_ready = false;  // (the worklist counters went with their buffer)
 	h->qbins_clean = nullptr;
@@ -1254,6 +1267,105 @@ int pxz_lod_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_par
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!d_pixels || !d_lod0 || !d_lod1) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
 	return run_shrink(h, frames, params, d_pixels, nullptr, nullptr, nullptr, nullptr, d_lod0, d_lod1, false);
+}
+
+// Factor ladder.  shrink_by over tiles whose LDS image fits (the generic kernel's layout with its detector planes, so
+// that the single-factor call is sure to run too): the detector once in its identity form, then ladder_kernel
+// (pxz_ladder.hip).  Everything else -- shrink_directionally, tiles beyond LDS -- is one single-factor call per rung.
+int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_params *params, const float *factors,
+                                    uint32_t n_factors, const uint8_t *d_pixels, float *d_block_value, uint32_t *d_out_w,
+                                    uint32_t *d_out_h, uint8_t *d_out_pixels)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
+	if (n_factors == 0 || n_factors > PXZ_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_LADDER_MAX_RUNGS, n_factors);
+	for (uint32_t r = 0; r < n_factors; ++r)
+		if (!std::isfinite(factors[r])) return fail(h, PXZ_ERR_INVALID_ARG, "factor %u must be finite", r);
+	if (!d_pixels || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (!frames || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null descriptor");
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz_params p = *params;
+	p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
+	int rc = check_frames(h, frames, &p);
+	if (rc != PXZ_OK) return rc;
+	const bool want = d_out_pixels != nullptr;
+	pxz::ShrinkArgs a{};
+	const bool ladder = p.mode == PXZ_MODE_SHRINK_BY && prepare(h, frames, &p, want, &a, false) == PXZ_OK && a.big_blocks == 0u &&
+	                    prepare(h, frames, &p, want, &a, true) == PXZ_OK && a.big_blocks == 0u;
+	if (!ladder) {
+		// one single-factor flow per rung: no amortisation, the same results and errors by construction
+		uint32_t cols = 0, rows = 0;
+		pxz_grid(frames->width, frames->height, p.block_w, p.block_h, &cols, &rows);
+		const size_t tiles = (size_t)cols * rows * frames->n_frames;
+		const size_t slot = (size_t)p.block_w * p.block_h * frames->channels;
+		for (uint32_t r = 0; r < n_factors; ++r) {
+			pxz_params pr = *params;
+			pr.factor = factors[r];
+			if ((rc = pxz_shrink_frames_device(h, frames, &pr, d_pixels, d_block_value + r * tiles, d_out_w + r * tiles, d_out_h + r * tiles,
+			                                   want ? d_out_pixels + r * tiles * slot : nullptr)) != PXZ_OK)
+				return rc;
+		}
+		return PXZ_OK;
+	}
+	const size_t x_bytes = ((size_t)a.n_tiles * 4u + 255u) & ~(size_t)255u;
+	if ((rc = ensure(h, h->ladder, x_bytes + PXZ_LADDER_MAX_RUNGS * 4u)) != PXZ_OK) return rc;
+	float *d_x = (float *)h->ladder.ptr;
+	float *d_factors = (float *)((uint8_t *)h->ladder.ptr + x_bytes);
+	// the factors go through pinned staging, reused once the copy queued by the previous ladder call has run
+	if (!h->ladder_host) {
+		void *hp = nullptr;
+		PXZ_HIP(h, hipHostMalloc(&hp, PXZ_LADDER_MAX_RUNGS * 4u, hipHostMallocDefault));
+		h->ladder_host = (float *)hp;
+	}
+	if (!h->ladder_copied) PXZ_HIP(h, hipEventCreateWithFlags(&h->ladder_copied, hipEventDisableTiming));
+	else PXZ_HIP(h, hipEventSynchronize(h->ladder_copied));
+	std::memcpy(h->ladder_host, factors, n_factors * 4u);
+	PXZ_HIP(h, hipMemcpyAsync(d_factors, h->ladder_host, n_factors * 4u, hipMemcpyHostToDevice, h->stream));
+	PXZ_HIP(h, hipEventRecord(h->ladder_copied, h->stream));
+	// stage 1: get_block_variance with the identity closure (factor 1, scale 1) -> x of every tile, no pixels
+	h->quiet_stats = true;
+	rc = run_shrink(h, frames, &p, d_pixels, nullptr, nullptr, nullptr, nullptr, d_x, nullptr, true);
+	h->quiet_stats = false;
+	if (rc != PXZ_OK) return rc;
+	// stage 2: every rung of every tile
+	pxz::LadderArgs l{};
+	l.src = d_pixels;
+	l.frame_stride = a.frame_stride;
+	l.pitch = a.pitch;
+	l.bw = a.bw;
+	l.bh = a.bh;
+	l.cols = a.cols;
+	l.rows = a.rows;
+	l.tiles_per_frame = a.tiles_per_frame;
+	l.n_tiles = a.n_tiles;
+	l.div_tpf = a.div_tpf;
+	l.div_cols = a.div_cols;
+	l.edge_w = a.edge_w;
+	l.edge_h = a.edge_h;
+	l.filter = a.filter;
+	l.n_rungs = n_factors;
+	l.x = d_x;
+	l.factors = d_factors;
+	l.value = d_block_value;
+	l.out_w = d_out_w;
+	l.out_h = d_out_h;
+	l.out_px = d_out_pixels;
+	l.slot_bytes = a.slot_bytes;
+	l.rs = a.rs;
+	l.plane_dw = a.plane_dw;
+	l.hps = a.hps;
+	l.tmp_dw = a.tmp_dw;
+	l.tile_dw = a.tile_dw;
+	static_assert(sizeof l.tabs == sizeof a.tabs && sizeof l.breaks == sizeof a.breaks, "ladder tables");
+	std::memcpy(l.tabs, a.tabs, sizeof l.tabs);
+	l.bounds = a.bounds;
+	l.coeffs = a.coeffs;
+	l.ksums = a.ksums;
+	std::memcpy(l.breaks, a.breaks, sizeof l.breaks);
+	std::memcpy(l.breaks_asc, a.breaks_asc, sizeof l.breaks_asc);
+	PXZ_HIP(h, pxz::launch_ladder(l, frames->channels, pxz::waves_per_tile(a.bw, a.bh), h->n_cus, h->stream));
+	return PXZ_OK;
 }
 
 // frames: the OUTPUT batch (its channels = bytes per output pixel); slot_channels: channels of the stored tiles
@@ -1855,6 +1967,42 @@ int pxz_shrink_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint3
 	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
 	rc = pxz_shrink_frames_device(h, &f, &p, (const uint8_t *)h->in.ptr, (float *)h->val.ptr, (uint32_t *)h->ow.ptr,
 	                              (uint32_t *)h->oh.ptr, out_pixels ? (uint8_t *)h->out.ptr : nullptr);
+	if (rc != PXZ_OK) return rc;
+	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(out_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(out_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
+	if (out_pixels) PXZ_HIP(h, hipMemcpyAsync(out_pixels, h->out.ptr, tiles * slot, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	return PXZ_OK;
+}
+
+int pxz_shrink_image_ladder(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                            uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter,
+                            const float *factors, uint32_t n_factors, float *block_value, uint32_t *out_w, uint32_t *out_h,
+                            uint8_t *out_pixels)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
+	if (n_factors == 0 || n_factors > PXZ_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_LADDER_MAX_RUNGS, n_factors);
+	if (!pixels || !block_value || !out_w || !out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	pxz_frames f{width, height, channels, pitch_bytes, 1, 0, 0};
+	pxz_params p{block_w, block_h, mode, filter, 1.0f, 0};
+	int rc = check_frames(h, &f, &p);
+	if (rc != PXZ_OK) return rc;
+	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p.reserved |= PXZ_HINT_TRANSPARENCY;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	uint32_t cols, rows;
+	pxz_grid(width, height, block_w, block_h, &cols, &rows);
+	const size_t tiles = (size_t)cols * rows * n_factors;
+	const size_t slot = (size_t)block_w * block_h * channels;
+	if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
+	if (out_pixels && (rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
+	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
+	rc = pxz_shrink_ladder_frames_device(h, &f, &p, factors, n_factors, (const uint8_t *)h->in.ptr, (float *)h->val.ptr,
+	                                     (uint32_t *)h->ow.ptr, (uint32_t *)h->oh.ptr, out_pixels ? (uint8_t *)h->out.ptr : nullptr);
 	if (rc != PXZ_OK) return rc;
 	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipMemcpyAsync(out_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));

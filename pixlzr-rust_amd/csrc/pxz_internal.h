@@ -139,6 +139,37 @@ struct ShrinkArgs {
 	uint32_t big_blocks;     //   of the generic kernel (0: the image is in LDS)
 };
 
+// Factor ladder (pxz_shrink_ladder_frames_device, shrink_by): ladder_kernel turns the raw detector value x of every tile into
+// the K rungs' values, sizes and slots, staging each tile once and resampling it once per distinct level.  x comes from an
+// identity launch of the ordinary flow (factor 1, scale 1, no pixels).  What that launch leaves in the handle is what a
+// pxz_lod_frames_device launch leaves: sums[] holds that launch's detector keys (sums[2t] = bits of x; clone_ahead is off
+// without pixels, so no "copied" flag of THIS launch is in sums[2t+1], and the next launch rewrites every flag it reads),
+// and the worklist counters are zeroed and switched over as after every fast-path launch.  It writes no kernel-selection
+// statistics (stats = null): the next single-factor launch sees the counts of the launch before the ladder.  ladder_kernel
+// itself touches neither sums[] nor the worklist.  Per-rung data (the factors) are in handle scratch, not in here.
+struct LadderArgs {
+	const uint8_t *src;      // frames, pitch-linear, as the caller passed them (any alignment, 3 or 4 channels)
+	uint64_t frame_stride;
+	uint32_t pitch;
+	uint32_t bw, bh, cols, rows, tiles_per_frame, n_tiles;
+	FastDiv div_tpf, div_cols;
+	uint32_t edge_w, edge_h, filter;
+	uint32_t n_rungs;        // K, 1 .. 16 (one lane per rung decides it)
+	const float *x;          // n_tiles raw detector values: x = sum of deviations / count (the identity closure)
+	const float *factors;    // n_rungs factors (device)
+	float *value;            // rung-major outputs: index (r * n_tiles + tile), 64-bit
+	uint32_t *out_w, *out_h;
+	uint8_t *out_px;         //   slots of slot_bytes; null: values and sizes only
+	uint32_t slot_bytes;
+	uint32_t rs, plane_dw, hps, tmp_dw, tile_dw;  // LDS image of a tile, as ShrinkArgs (no detector planes)
+	AxisTab tabs[4 * kMaxLevel];
+	const uint16_t *bounds;
+	const uint32_t *coeffs;
+	const int32_t *ksums;
+	uint32_t breaks[4][kMaxLevel];  // shrink_by's level decision (the thresholds' bit patterns, ShrinkArgs::breaks)
+	uint32_t breaks_asc[4];
+};
+
 // Arguments of shrink32_kernel (full 32x32 RGBA tiles only): the subset of ShrinkArgs it needs
 struct Fast32Args {
 	const uint8_t *src;
