@@ -13,7 +13,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <set>
 #include <system_error>
 #include <string>
 #include <tuple>
@@ -51,8 +50,9 @@ namespace {
 using pxz::AxisTab;
 using pxz::kMaxLevel;
 
-// device copy of the down-scaling tables for one (tile geometry, filter)
+// device copy of the down-scaling tables for one (tile geometry, filter): pxz::ShrinkTableSet
 struct TableSet {
+	void *mem = nullptr;        // the one allocation behind every device pointer below
 	std::vector<AxisTab> tabs;  // host copy, passed by value in the kernel arguments
 	uint16_t *d_bounds = nullptr;
 	uint32_t *d_coeffs = nullptr;
@@ -63,8 +63,9 @@ struct TableSet {
 	bool opaque_stays = true;    // a constant-255 alpha comes back as 255 from every window of every table
 };
 
-// decode side: up-scaling tables of every source size to the full tile size (expand_kernel)
+// decode side: up-scaling tables of every source size to the full tile size (expand_kernel): pxz::ExpandTableSet
 struct ExpandTables {
+	void *mem = nullptr;
 	pxz::ExpandTab *d_dir = nullptr;
 	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
 	int16_t *d_coeffs = nullptr;
@@ -80,8 +81,9 @@ struct DeviceBuffer {
 };
 
 // tree::process on rectangle lists: every axis table (down with the one filter, back up with the other) of every tile
-// size the recursion can reach from one (frame, block, minimum) geometry
+// size the recursion can reach from one (frame, block, minimum) geometry: pxz::TreeTableSet
 struct TreeTables {
+	void *mem = nullptr;
 	pxz::TreeAxisEntry *d_dir = nullptr;
 	int32_t *d_starts = nullptr, *d_sizes = nullptr;
 	int16_t *d_coeffs = nullptr;
@@ -142,15 +144,12 @@ int fail(pxz_handle *h, int code, const char *fmt, ...)
 	return code;
 }
 
-void drop_tree_tables(pxz_handle *h)
+// a cache of table sets (h->tables, h->expand_tables, h->tree_tables): one allocation per set
+template <class Cache>
+void free_tables(Cache &cache)
 {
-	for (auto &kv : h->tree_tables) {
-		(void)hipFree(kv.second.d_dir);
-		(void)hipFree(kv.second.d_starts);
-		(void)hipFree(kv.second.d_sizes);
-		(void)hipFree(kv.second.d_coeffs);
-	}
-	h->tree_tables.clear();
+	for (auto &kv : cache) (void)hipFree(kv.second.mem);
+	cache.clear();
 }
 
 #define PXZ_HIP(h, call)                                                                      \
@@ -181,12 +180,32 @@ pxz::FastDiv make_fastdiv(uint32_t d)
 	return pxz::FastDiv{(uint32_t)m, l < 1 ? l : 1u, l < 1 ? 0u : l - 1};
 }
 
-// reduced size for level exponent m (reference operations.rs:150-151)
-uint32_t reduced(uint32_t size, uint32_t m)
+// One array of a table set on its way to the device: its device address goes to *dst (null when the array is empty).
+struct TablePart {
+	template <class T>
+	TablePart(const std::vector<T> &v, T **d) : src(v.data()), bytes(v.size() * sizeof(T)), dst(reinterpret_cast<void **>(d)) {}
+	const void *src;
+	size_t bytes;
+	void **dst;
+};
+
+// Uploads one table set into a single allocation *mem, every array at a 256-byte aligned offset.  On failure nothing is
+// left allocated.
+int upload_tables(pxz_handle *h, std::initializer_list<TablePart> parts, void **mem)
 {
-	if (m >= 31) return 1;
-	uint64_t r = ((uint64_t)size + ((1ull << m) - 1ull)) >> m;
-	return r < 1 ? 1u : (uint32_t)r;
+	size_t total = 0;
+	for (const TablePart &p : parts) total += (p.bytes + 255) & ~(size_t)255;
+	*mem = nullptr;
+	hipError_t e = hipMalloc(mem, total);
+	uint8_t *at = static_cast<uint8_t *>(*mem);
+	for (auto p = parts.begin(); e == hipSuccess && p != parts.end(); at += (p->bytes + 255) & ~(size_t)255, ++p) {
+		*p->dst = p->bytes ? at : nullptr;
+		if (p->bytes) e = hipMemcpy(at, p->src, p->bytes, hipMemcpyHostToDevice);
+	}
+	if (e == hipSuccess) return PXZ_OK;
+	(void)hipFree(*mem);
+	*mem = nullptr;
+	return fail(h, PXZ_ERR_HIP, "uploading %zu bytes of tables: %s", total, hipGetErrorString(e));
 }
 
 int get_tables(pxz_handle *h, uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter,
@@ -194,382 +213,34 @@ int get_tables(pxz_handle *h, uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_
 {
 	auto key = std::make_tuple(bw, bh, edge_w, edge_h, filter);
 	auto it = h->tables.find(key);
-	if (it != h->tables.end()) {
-		*out = &it->second;
-		return PXZ_OK;
-	}
-	std::vector<AxisTab> tabs(2 * 2 * kMaxLevel);
-	std::vector<uint16_t> bounds;
-	std::vector<uint32_t> coeffs;
-	std::vector<int32_t> ksums;
-	std::vector<uint32_t> rows;
-	bool all_opaque_stays = true;
-	std::vector<uint32_t> mf64(4, 0u);  // offset 0 means "no table"
-	bool mf64_complete = bw == 64 && bh == 64 && filter != PXZ_FILTER_NEAREST;
-	const uint32_t sizes[2][2] = {{bw, edge_w}, {bh, edge_h}};
-	for (int axis = 0; axis < 2; ++axis) {
-		for (int cls = 0; cls < 2; ++cls) {
-			const uint32_t in = sizes[axis][cls];
-			for (int m = 0; m < kMaxLevel; ++m) {
-				AxisTab &t = tabs[(axis * 2 + cls) * kMaxLevel + m];
-				const uint32_t outsz = reduced(in, (uint32_t)m);
-				t = AxisTab{0, 0, 0, 0, 0, (uint16_t)outsz, 0, 0, (uint16_t)in, 0};
-				if (outsz == in) continue;  // identity: never looked up
-				// identical (in, out) pairs share one table: the edge class of a grid without ragged
-				// edge, and every level past the first that reaches 1 px
-				if (cls == 1 && sizes[axis][1] == sizes[axis][0]) {
-					t = tabs[(axis * 2 + 0) * kMaxLevel + m];
-					continue;
-				}
-				if (m > 0 && tabs[(axis * 2 + cls) * kMaxLevel + m - 1].out_size == outsz &&
-				    tabs[(axis * 2 + cls) * kMaxLevel + m - 1].in_size == in && reduced(in, (uint32_t)m - 1) != in) {
-					t = tabs[(axis * 2 + cls) * kMaxLevel + m - 1];
-					continue;
-				}
-				pxz::AxisWindows win;
-				if (!pxz::build_axis(in, outsz, filter, &win)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-				t.bounds_off = (uint32_t)bounds.size();
-				t.coeff_off = (uint32_t)coeffs.size();
-				t.ksum_off = (uint32_t)ksums.size();
-				t.precision = (uint16_t)win.precision;
-				if (filter == PXZ_FILTER_NEAREST) {
-					for (uint32_t o = 0; o < outsz; ++o) bounds.push_back((uint16_t)win.starts[o]);
-					continue;
-				}
-				// pad every window to whole quads of 4 source samples (8-byte aligned LDS reads)
-				uint32_t wquads = 1;
-				for (uint32_t o = 0; o < outsz; ++o) {
-					const uint32_t lead = (uint32_t)win.starts[o] & 3u;
-					const uint32_t nq = (lead + (uint32_t)win.sizes[o] + 3u) / 4u;
-					if (nq > wquads) wquads = nq;
-				}
-				t.wquads = (uint16_t)wquads;
-				t.rows_off = (uint32_t)rows.size();
-				// rows of up to 8 quads are padded with zero weights to header + 16 dwords: the fast path fetches
-				// whole rows with 16-byte loads and needs no per-quad guard
-				t.row_stride = wquads <= 8u ? 20u : (4u + wquads * 2u + 3u) & ~3u;
-				for (uint32_t o = 0; o < outsz; ++o) {
-					const uint32_t first = (uint32_t)win.starts[o], n = (uint32_t)win.sizes[o];
-					const uint32_t lead = first & 3u, nq = (lead + n + 3u) / 4u;
-					bounds.push_back((uint16_t)(first / 4u));
-					bounds.push_back((uint16_t)nq);
-					std::vector<int16_t> k(wquads * 4u, 0);
-					int32_t total = 0;
-					for (uint32_t i = 0; i < n; ++i) {
-						k[lead + i] = win.coeffs[(size_t)o * win.window + i];
-						total += k[lead + i];
-					}
-					const size_t row0 = rows.size();
-					rows.resize(row0 + t.row_stride, 0u);
-					rows[row0 + 0] = first / 4u;
-					rows[row0 + 1] = nq;
-					rows[row0 + 2] = (uint32_t)total;
-					for (uint32_t d = 0; d < wquads * 2u; ++d) {
-						const uint32_t pr = (uint32_t)(uint16_t)k[2 * d] | ((uint32_t)(uint16_t)k[2 * d + 1] << 16);
-						coeffs.push_back(pr);
-						rows[row0 + 4 + d] = pr;
-					}
-					ksums.push_back(total);
-					if ((((1 << (win.precision - 1)) + 255 * total) >> win.precision) < 255) all_opaque_stays = false;
-				}
-				// 32x32 tiles: operands for the matrix-core form of the two-pass resample (x axis table,
-				// used for both axes of a full tile)
-				if (axis == 0 && cls == 0 && bw == 32 && bh == 32 && outsz <= 16) {
-					std::vector<uint32_t> mf(pxz::kMfDwords, 0u);
-					bool fits = true, opaque_stays = true;
-					const int32_t half = 1 << (win.precision - 1);
-					for (uint32_t o = 0; o < outsz; ++o) {
-						int32_t k[32] = {0};
-						int32_t total = 0;
-						for (uint32_t i = 0; i < (uint32_t)win.sizes[o]; ++i) {
-							k[(uint32_t)win.starts[o] + i] = win.coeffs[(size_t)o * win.window + i];
-							total += k[(uint32_t)win.starts[o] + i];
-						}
-						for (uint32_t g = 0; g < 4; ++g) {
-							for (uint32_t j = 0; j < 8; ++j) {
-								const uint32_t src = j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4);
-								const int32_t lo = ((k[src] + 128) & 255) - 128, hi = (k[src] - lo) / 256;
-								if (hi < -128 || hi > 127) fits = false;
-								const uint32_t lane = g * 16 + o, dw = 2 * lane + j / 4, sh = 8 * (j & 3);
-								mf[dw] |= (uint32_t)(uint8_t)lo << sh;
-								mf[128 + dw] |= (uint32_t)(uint8_t)hi << sh;
-							}
-						}
-						mf[256 + o] = (uint32_t)(128 * total + half);
-						mf[272 + o] = (uint32_t)total;
-						const int32_t al = (half + 255 * total) >> win.precision;
-						if (al < 255) opaque_stays = false;  // clip8: above 255 is clamped to 255
-					}
-					mf[288] = opaque_stays ? 1u : 0u;
-					if (fits) {
-						t.mf_off = (uint32_t)rows.size();
-						rows.insert(rows.end(), mf.begin(), mf.end());
-					}
-				}
-				// 16x16 tiles: operands of the group-of-four matrix-core resample (resample_group16_mfma): 16 -> 8 | 4 | 2 | 1
-				if (axis == 0 && cls == 0 && bw == 16 && bh == 16 && outsz <= 8) {
-					std::vector<uint32_t> mf(pxz::kMf16Dwords, 0u);
-					bool fits = true, opaque_stays = true;
-					const int32_t half = 1 << (win.precision - 1);
-					for (uint32_t o = 0; o < outsz; ++o) {
-						int32_t k[16] = {0};
-						int32_t total = 0;
-						for (uint32_t i = 0; i < (uint32_t)win.sizes[o]; ++i) {
-							k[(uint32_t)win.starts[o] + i] = win.coeffs[(size_t)o * win.window + i];
-							total += k[(uint32_t)win.starts[o] + i];
-						}
-						for (uint32_t i = 0; i < 16; ++i) {
-							const int32_t lo = ((k[i] + 128) & 255) - 128, hi = (k[i] - lo) / 256;
-							if (hi < -128 || hi > 127) fits = false;
-							mf[o * 4 + i / 4] |= (uint32_t)(uint8_t)lo << (8 * (i & 3));
-							mf[32 + o * 4 + i / 4] |= (uint32_t)(uint8_t)hi << (8 * (i & 3));
-						}
-						mf[64 + o] = (uint32_t)(128 * total + half);
-						mf[72 + o] = (uint32_t)total;
-						if (((half + 255 * total) >> win.precision) < 255) opaque_stays = false;
-					}
-					mf[80] = opaque_stays ? 1u : 0u;
-					mf[81] = (uint32_t)win.precision;
-					if (fits && opaque_stays) {  // (the group form writes alpha 255: only where the windows keep it)
-						t.mf_off = (uint32_t)rows.size();
-						rows.insert(rows.end(), mf.begin(), mf.end());
-					}
-				}
-				// 64x64 tiles: operands of shrink64_kernel (Fast64Args), every level from 32 px down to 1 px
-				if (axis == 0 && cls == 0 && bw == 64 && bh == 64 && outsz < 64) {
-					const uint32_t nblk = outsz > 16 ? outsz / 16 : 1;
-					std::vector<uint32_t> mf((size_t)nblk * 512 + 72, 0u);
-					bool fits = true, opaque_stays = true;
-					const int32_t half = 1 << (win.precision - 1);
-					for (uint32_t o = 0; o < outsz; ++o) {
-						int32_t k[64] = {0};
-						int32_t total = 0;
-						for (uint32_t i = 0; i < (uint32_t)win.sizes[o]; ++i) {
-							k[(uint32_t)win.starts[o] + i] = win.coeffs[(size_t)o * win.window + i];
-							total += k[(uint32_t)win.starts[o] + i];
-						}
-						const uint32_t blk = o / 16, ol = o % 16;
-						for (uint32_t g = 0; g < 4; ++g) {
-							for (uint32_t j = 0; j < 16; ++j) {
-								const int32_t v = k[16 * g + j];
-								const int32_t lo = ((v + 128) & 255) - 128, hi = (v - lo) / 256;
-								if (hi < -128 || hi > 127) fits = false;
-								const uint32_t lane = g * 16 + ol, dw = blk * 512 + lane * 4 + j / 4, sh = 8 * (j & 3);
-								mf[dw] |= (uint32_t)(uint8_t)lo << sh;
-								mf[256 + dw] |= (uint32_t)(uint8_t)hi << sh;
-							}
-						}
-						mf[nblk * 512 + o] = (uint32_t)(128 * total + half);
-						mf[nblk * 512 + 32 + o] = (uint32_t)total;
-						if (((half + 255 * total) >> win.precision) < 255) opaque_stays = false;
-					}
-					mf[nblk * 512 + 64] = opaque_stays ? 1u : 0u;
-					if (fits && outsz <= 32) {
-						t.mf_off = (uint32_t)mf64.size();
-						mf64.insert(mf64.end(), mf.begin(), mf.end());
-					} else {
-						mf64_complete = false;
-					}
-				}
-			}
-		}
-	}
-	if (bounds.empty()) bounds.push_back(0);
-	if (coeffs.empty()) coeffs.push_back(0);
-	if (ksums.empty()) ksums.push_back(0);
-	rows.resize(rows.size() + 32, 0u);  // the fast path always fetches 4+16 dwords per row
+	if (it != h->tables.end()) { *out = &it->second; return PXZ_OK; }
+	pxz::ShrinkTableSet s;
+	if (!pxz::build_shrink_tables(bw, bh, edge_w, edge_h, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
 	TableSet ts;
-	ts.tabs = tabs;
-	ts.opaque_stays = all_opaque_stays;
-	PXZ_HIP(h, hipMalloc((void **)&ts.d_bounds, bounds.size() * sizeof(uint16_t)));
-	PXZ_HIP(h, hipMalloc((void **)&ts.d_coeffs, coeffs.size() * sizeof(uint32_t)));
-	PXZ_HIP(h, hipMalloc((void **)&ts.d_ksums, ksums.size() * sizeof(int32_t)));
-	PXZ_HIP(h, hipMemcpy(ts.d_bounds, bounds.data(), bounds.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-	PXZ_HIP(h, hipMemcpy(ts.d_coeffs, coeffs.data(), coeffs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	PXZ_HIP(h, hipMemcpy(ts.d_ksums, ksums.data(), ksums.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-	if (mf64_complete) {
-		PXZ_HIP(h, hipMalloc((void **)&ts.d_mf64, mf64.size() * sizeof(uint32_t)));
-		PXZ_HIP(h, hipMemcpy(ts.d_mf64, mf64.data(), mf64.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	}
-	ts.rows_dw = (uint32_t)rows.size();
-	PXZ_HIP(h, hipMalloc((void **)&ts.d_rows, rows.size() * sizeof(uint32_t)));
-	PXZ_HIP(h, hipMemcpy(ts.d_rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	h->tables[key] = ts;
-	*out = &h->tables[key];
+	ts.tabs = s.tabs;
+	ts.rows_dw = (uint32_t)s.rows.size();
+	ts.opaque_stays = s.opaque_stays;
+	const int rc = upload_tables(h, {{s.bounds, &ts.d_bounds}, {s.coeffs, &ts.d_coeffs}, {s.ksums, &ts.d_ksums}, {s.rows, &ts.d_rows},
+	                                 {s.mf64, &ts.d_mf64}}, &ts.mem);
+	if (rc != PXZ_OK) return rc;
+	*out = &(h->tables[key] = ts);
 	return PXZ_OK;
 }
 
-// Tables of the decode side: for each axis and size class (full / ragged edge) one up-scaling table per
-// source size 1 .. full-1 (PixlzrBlock::resize with the upscale flag set, block.rs:301-304).
 int get_expand_tables(pxz_handle *h, uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter,
                       const ExpandTables **out)
 {
 	auto key = std::make_tuple(bw, bh, edge_w, edge_h, filter);
 	auto it = h->expand_tables.find(key);
-	if (it != h->expand_tables.end()) {
-		*out = &it->second;
-		return PXZ_OK;
-	}
-	const uint32_t stride = (bw > bh ? bw : bh) + 1u;
-	std::vector<pxz::ExpandTab> dir(4u * stride, pxz::ExpandTab{0, 0, 0, 0});
-	std::vector<uint16_t> starts, sizes;
-	std::vector<int16_t> coeffs;
-	const uint32_t full[2][2] = {{bw, edge_w}, {bh, edge_h}};
-	for (uint32_t axis = 0; axis < 2; ++axis) {
-		for (uint32_t cls = 0; cls < 2; ++cls) {
-			const uint32_t outsz = full[axis][cls];
-			if (cls == 1 && outsz == full[axis][0]) {
-				for (uint32_t in = 0; in < stride; ++in) dir[(axis * 2 + 1) * stride + in] = dir[(axis * 2 + 0) * stride + in];
-				continue;
-			}
-			for (uint32_t in = 1; in < outsz; ++in) {
-				pxz::AxisWindows win;
-				if (!pxz::build_axis(in, outsz, filter, &win, true)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-				pxz::ExpandTab &t = dir[(axis * 2 + cls) * stride + in];
-				t.start_off = (uint32_t)starts.size();
-				t.coeff_off = (uint32_t)coeffs.size();
-				t.window = (uint16_t)win.window;
-				t.precision = (uint16_t)win.precision;
-				for (uint32_t o = 0; o < outsz; ++o) {
-					starts.push_back((uint16_t)win.starts[o]);
-					sizes.push_back((uint16_t)win.sizes[o]);
-				}
-				coeffs.insert(coeffs.end(), win.coeffs.begin(), win.coeffs.end());
-			}
-		}
-	}
-	if (starts.empty()) {
-		starts.push_back(0);
-		sizes.push_back(0);
-	}
-	if (coeffs.empty()) coeffs.push_back(0);
+	if (it != h->expand_tables.end()) { *out = &it->second; return PXZ_OK; }
+	pxz::ExpandTableSet s;
+	if (!pxz::build_expand_tables(bw, bh, edge_w, edge_h, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
 	ExpandTables et;
-	et.dir_stride = stride;
-	// 32x32 tiles: the up-scales 1, 2, 4, 8, 16 -> 32 as matrix-core operands (layout: pxz_internal.h)
-	if (bw == 32 && bh == 32 && filter != 0) {
-		std::vector<uint32_t> xmf((size_t)pxz::kXmfLevels * pxz::kXmfDw, 0u);
-		bool fits = true;
-		for (uint32_t li = 0; li < pxz::kXmfLevels; ++li) {
-			const uint32_t in = 1u << li;
-			pxz::AxisWindows win;
-			if (!pxz::build_axis(in, 32, filter, &win, true)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-			uint32_t *mf = xmf.data() + (size_t)li * pxz::kXmfDw;
-			const int32_t half = 1 << (win.precision - 1);
-			bool copies = in == 1 && win.precision < 15;
-			for (uint32_t o = 0; o < 32; ++o) {
-				int32_t k[16] = {0};
-				int32_t total = 0;
-				for (uint32_t i = 0; i < (uint32_t)win.sizes[o]; ++i) {
-					k[(uint32_t)win.starts[o] + i] = win.coeffs[(size_t)o * win.window + i];
-					total += k[(uint32_t)win.starts[o] + i];
-				}
-				if (win.sizes[o] != 1 || k[0] != (1 << win.precision)) copies = false;
-				for (uint32_t kg = 0; kg < 2; ++kg) {
-					for (uint32_t j = 0; j < 8; ++j) {
-						const int32_t v = k[pxz::xmf_src(kg, j)];
-						const int32_t lo = ((v + 128) & 255) - 128, hi = (v - lo) / 256;
-						if (hi < -128 || hi > 127) fits = false;
-						const uint32_t lane = kg * 32 + o, dw = 2 * lane + j / 4, sh = 8 * (j & 3);
-						mf[dw] |= (uint32_t)(uint8_t)lo << sh;
-						mf[128 + dw] |= (uint32_t)(uint8_t)hi << sh;
-					}
-				}
-				mf[256 + o] = (uint32_t)(128 * total + half);
-			}
-			for (uint32_t g = 0; g < 2; ++g)
-				for (uint32_t reg = 0; reg < 16; ++reg) mf[288 + 16 * g + reg] = mf[256 + pxz::xmf_row(g, reg)];
-			mf[320] = (uint32_t)win.precision;
-			mf[321] = copies ? 1u : 0u;
-		}
-		if (fits) {
-			PXZ_HIP(h, hipMalloc((void **)&et.d_xmf, xmf.size() * sizeof(uint32_t)));
-			PXZ_HIP(h, hipMemcpy(et.d_xmf, xmf.data(), xmf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		}
-	}
-	// 16x16 tiles: the up-scales 1, 2, 4, 8 -> 16 as matrix-core operands of expand16_kernel (layout: pxz_internal.h)
-	if (bw == 16 && bh == 16 && filter != 0) {
-		std::vector<uint32_t> xmf((size_t)pxz::kXmf16Levels * pxz::kXmf16Dw, 0u);
-		bool fits = true;
-		for (uint32_t li = 0; li < pxz::kXmf16Levels; ++li) {
-			const uint32_t in = 1u << li;
-			pxz::AxisWindows win;
-			if (!pxz::build_axis(in, 16, filter, &win, true)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-			uint32_t *mf = xmf.data() + (size_t)li * pxz::kXmf16Dw;
-			const int32_t half = 1 << (win.precision - 1);
-			for (uint32_t o = 0; o < 16; ++o) {
-				int32_t k[8] = {0};
-				int32_t total = 0;
-				for (uint32_t i = 0; i < (uint32_t)win.sizes[o]; ++i) {
-					k[(uint32_t)win.starts[o] + i] = win.coeffs[(size_t)o * win.window + i];
-					total += k[(uint32_t)win.starts[o] + i];
-				}
-				for (uint32_t i = 0; i < 8; ++i) {
-					const int32_t lo = ((k[i] + 128) & 255) - 128, hi = (k[i] - lo) / 256;
-					if (hi < -128 || hi > 127) fits = false;
-					mf[o * 2 + i / 4] |= (uint32_t)(uint8_t)lo << (8 * (i & 3));
-					mf[32 + o * 2 + i / 4] |= (uint32_t)(uint8_t)hi << (8 * (i & 3));
-				}
-				mf[64 + o] = (uint32_t)(128 * total + half);
-			}
-			for (uint32_t g = 0; g < 2; ++g)
-				for (uint32_t r = 0; r < 8; ++r) mf[80 + 8 * g + r] = mf[64 + (r & 3) + 8 * (r >> 2) + 4 * g];
-			mf[96] = (uint32_t)win.precision;
-		}
-		if (fits) {
-			PXZ_HIP(h, hipMalloc((void **)&et.d_xmf16, xmf.size() * sizeof(uint32_t)));
-			PXZ_HIP(h, hipMemcpy(et.d_xmf16, xmf.data(), xmf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		}
-	}
-	// 64x64 tiles: the up-scales 1 .. 32 -> 64 as matrix-core operands of expand64_kernel (layout: pxz_internal.h)
-	if (bw == 64 && bh == 64 && filter != 0) {
-		std::vector<uint32_t> xmf((size_t)pxz::kXmf64Levels * pxz::kXmf64Dw, 0u);
-		bool fits = true;
-		for (uint32_t li = 0; li < pxz::kXmf64Levels; ++li) {
-			const uint32_t in = 1u << li;
-			pxz::AxisWindows win;
-			if (!pxz::build_axis(in, 64, filter, &win, true)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-			uint32_t *mf = xmf.data() + (size_t)li * pxz::kXmf64Dw;
-			const int32_t half = 1 << (win.precision - 1);
-			for (uint32_t o = 0; o < 64; ++o) {
-				int32_t k[32] = {0};
-				int32_t total = 0;
-				for (uint32_t i = 0; i < (uint32_t)win.sizes[o]; ++i) {
-					k[(uint32_t)win.starts[o] + i] = win.coeffs[(size_t)o * win.window + i];
-					total += k[(uint32_t)win.starts[o] + i];
-				}
-				const uint32_t q = o >> 5, ol = o & 31u;
-				for (uint32_t st = 0; st < 2; ++st)
-					for (uint32_t kg = 0; kg < 2; ++kg)
-						for (uint32_t j = 0; j < 8; ++j) {
-							const int32_t v = k[16 * st + pxz::xmf_src(kg, j)];
-							const int32_t lo = ((v + 128) & 255) - 128, hi = (v - lo) / 256;
-							if (hi < -128 || hi > 127) fits = false;
-							const uint32_t lane = kg * 32 + ol, dw = ((q * 2 + st) * 2) * 128 + 2 * lane + j / 4, sh = 8 * (j & 3);
-							mf[dw] |= (uint32_t)(uint8_t)lo << sh;
-							mf[128 + dw] |= (uint32_t)(uint8_t)hi << sh;
-						}
-				mf[1024 + o] = (uint32_t)(128 * total + half);
-			}
-			for (uint32_t q = 0; q < 2; ++q)
-				for (uint32_t g = 0; g < 2; ++g)
-					for (uint32_t reg = 0; reg < 16; ++reg) mf[1088 + (q * 2 + g) * 16 + reg] = mf[1024 + 32 * q + pxz::xmf_row(g, reg)];
-			mf[1152] = (uint32_t)win.precision;
-		}
-		if (fits) {
-			PXZ_HIP(h, hipMalloc((void **)&et.d_xmf64, xmf.size() * sizeof(uint32_t)));
-			PXZ_HIP(h, hipMemcpy(et.d_xmf64, xmf.data(), xmf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		}
-	}
-	PXZ_HIP(h, hipMalloc((void **)&et.d_dir, dir.size() * sizeof(pxz::ExpandTab)));
-	PXZ_HIP(h, hipMalloc((void **)&et.d_starts, starts.size() * sizeof(uint16_t)));
-	PXZ_HIP(h, hipMalloc((void **)&et.d_sizes, sizes.size() * sizeof(uint16_t)));
-	PXZ_HIP(h, hipMalloc((void **)&et.d_coeffs, coeffs.size() * sizeof(int16_t)));
-	PXZ_HIP(h, hipMemcpy(et.d_dir, dir.data(), dir.size() * sizeof(pxz::ExpandTab), hipMemcpyHostToDevice));
-	PXZ_HIP(h, hipMemcpy(et.d_starts, starts.data(), starts.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-	PXZ_HIP(h, hipMemcpy(et.d_sizes, sizes.data(), sizes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-	PXZ_HIP(h, hipMemcpy(et.d_coeffs, coeffs.data(), coeffs.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-	h->expand_tables[key] = et;
-	*out = &h->expand_tables[key];
+	et.dir_stride = s.dir_stride;
+	const int rc = upload_tables(h, {{s.dir, &et.d_dir}, {s.starts, &et.d_starts}, {s.sizes, &et.d_sizes}, {s.coeffs, &et.d_coeffs},
+	                                 {s.xmf, &et.d_xmf}, {s.xmf16, &et.d_xmf16}, {s.xmf64, &et.d_xmf64}}, &et.mem);
+	if (rc != PXZ_OK) return rc;
+	*out = &(h->expand_tables[key] = et);
 	return PXZ_OK;
 }
 
@@ -1045,23 +716,9 @@ void pxz_destroy(pxz_handle *h)
 {
 	if (!h) return;
 	(void)hipSetDevice(h->device);
-	for (auto &kv : h->tables) {
-		(void)hipFree(kv.second.d_bounds);
-		(void)hipFree(kv.second.d_coeffs);
-		(void)hipFree(kv.second.d_ksums);
-		(void)hipFree(kv.second.d_rows);
-		(void)hipFree(kv.second.d_mf64);
-	}
-	for (auto &kv : h->expand_tables) {
-		(void)hipFree(kv.second.d_dir);
-		(void)hipFree(kv.second.d_starts);
-		(void)hipFree(kv.second.d_sizes);
-		(void)hipFree(kv.second.d_coeffs);
-		(void)hipFree(kv.second.d_xmf);
-		(void)hipFree(kv.second.d_xmf16);
-		(void)hipFree(kv.second.d_xmf64);
-	}
-	drop_tree_tables(h);
+	free_tables(h->tables);
+	free_tables(h->expand_tables);
+	free_tables(h->tree_tables);
 	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder})
 		if (b->ptr) (void)hipFree(b->ptr);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
@@ -1098,7 +755,7 @@ int pxz_trim(pxz_handle *h)
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
 			drop(*b);
-	drop_tree_tables(h);
+	free_tables(h->tree_tables);
 	if (h->ladder_copied) (void)hipEventDestroy(h->ladder_copied);
 	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
 	h->ladder_copied = nullptr;
@@ -1521,79 +1178,22 @@ int tree_process_rects(pxz_handle *h, const pxz_frames *frames, const pxz_params
 	if (levels[0].first > kMaxSide || levels[0].second > kMaxSide)
 		return fail(h, PXZ_ERR_UNSUPPORTED, "tree::process on the device takes blocks up to %ux%u (got %ux%u)", kMaxSide, kMaxSide,
 		            levels[0].first, levels[0].second);
-	// ---- every tile size of every level, per axis (split.rs:18-19 applied level after level to the sizes of the level before)
-	auto split = [](uint32_t s, uint32_t b, std::set<uint32_t> &out) {
-		const uint32_t c = (s + b - 1) / b;
-		if (c > 1) out.insert(b);
-		out.insert(s - (c - 1) * b);
-	};
-	std::set<uint32_t> all[2];
-	{
-		std::set<uint32_t> cur[2];
-		split(frames->width, levels[0].first, cur[0]);
-		split(frames->height, levels[0].second, cur[1]);
-		for (size_t l = 0;; ++l) {
-			for (int ax = 0; ax < 2; ++ax) all[ax].insert(cur[ax].begin(), cur[ax].end());
-			if (l + 1 >= levels.size()) break;
-			std::set<uint32_t> next[2];
-			for (uint32_t v : cur[0]) split(v, levels[l + 1].first, next[0]);
-			for (uint32_t v : cur[1]) split(v, levels[l + 1].second, next[1]);
-			cur[0].swap(next[0]);
-			cur[1].swap(next[1]);
-		}
-	}
 	int rc;
 	const auto key = std::make_tuple(frames->width, frames->height, levels[0].first, levels[0].second, mbw, mbh, p.filter, filter_upscale);
 	auto it = h->tree_tables.find(key);
 	if (it == h->tree_tables.end()) {
 		if (h->tree_tables.size() >= 16) {  // a cache, not a log: varying geometries (tools/fuzz_tree.py) must not grow it without bound
 			PXZ_HIP(h, hipStreamSynchronize(h->stream));  // (a queued launch may still read a table)
-			drop_tree_tables(h);
+			free_tables(h->tree_tables);
 		}
-		std::set<std::tuple<uint32_t, uint32_t, uint32_t>> pairs;  // (in, out, up)
-		for (int ax = 0; ax < 2; ++ax)
-			for (uint32_t sz : all[ax])
-				for (uint32_t m = 1; m <= 32; ++m) {
-					const uint32_t o = reduced(sz, m);
-					if (o == sz) continue;
-					pairs.insert(std::make_tuple(sz, o, 0u));
-					pairs.insert(std::make_tuple(o, sz, 1u));
-				}
-		std::vector<pxz::TreeAxisEntry> dir;
-		std::vector<int32_t> starts, sizes;
-		std::vector<int16_t> coeffs;
-		for (const auto &pr : pairs) {
-			const uint32_t in = std::get<0>(pr), out = std::get<1>(pr), up = std::get<2>(pr);
-			pxz::AxisWindows win;
-			if (!pxz::build_axis(in, out, up ? filter_upscale : p.filter, &win, up != 0)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter");
-			pxz::TreeAxisEntry e{};
-			e.in = (uint16_t)in;
-			e.out = (uint16_t)out;
-			e.up = (uint16_t)up;
-			e.window = (uint16_t)win.window;
-			e.precision = (uint32_t)win.precision;
-			e.starts_off = (uint32_t)starts.size();
-			e.coeff_off = (uint32_t)coeffs.size();
-			for (uint32_t o = 0; o < out; ++o) {
-				starts.push_back(win.starts[o]);
-				sizes.push_back(win.sizes.empty() ? 0 : win.sizes[o]);
-			}
-			coeffs.insert(coeffs.end(), win.coeffs.begin(), win.coeffs.end());
-			dir.push_back(e);
-		}
-		if (dir.empty()) dir.push_back(pxz::TreeAxisEntry{});
-		if (starts.empty()) { starts.push_back(0); sizes.push_back(0); }
-		if (coeffs.empty()) coeffs.push_back(0);
+		pxz::TreeTableSet s;
+		if (!pxz::build_tree_tables(frames->width, frames->height, levels, p.filter, filter_upscale, &s))
+			return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter");
 		TreeTables tt;
-		tt.n_dir = (uint32_t)dir.size();
-		PXZ_HIP(h, hipMalloc((void **)&tt.d_dir, dir.size() * sizeof(pxz::TreeAxisEntry)));
-		PXZ_HIP(h, hipMalloc((void **)&tt.d_starts, starts.size() * 4));
-		PXZ_HIP(h, hipMalloc((void **)&tt.d_sizes, sizes.size() * 4));
-		PXZ_HIP(h, hipMalloc((void **)&tt.d_coeffs, coeffs.size() * 2));
-		PXZ_HIP(h, hipMemcpy(tt.d_dir, dir.data(), dir.size() * sizeof(pxz::TreeAxisEntry), hipMemcpyHostToDevice));
-		PXZ_HIP(h, hipMemcpy(tt.d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice));
-		PXZ_HIP(h, hipMemcpy(tt.d_sizes, sizes.data(), sizes.size() * 4, hipMemcpyHostToDevice));
-		PXZ_HIP(h, hipMemcpy(tt.d_coeffs, coeffs.data(), coeffs.size() * 2, hipMemcpyHostToDevice));
+		tt.n_dir = (uint32_t)s.dir.size();
+		if ((rc = upload_tables(h, {{s.dir, &tt.d_dir}, {s.starts, &tt.d_starts}, {s.sizes, &tt.d_sizes}, {s.coeffs, &tt.d_coeffs}},
+		                        &tt.mem)) != PXZ_OK)
+			return rc;
 		it = h->tree_tables.emplace(key, tt).first;
 	}
 	const TreeTables &tt = it->second;

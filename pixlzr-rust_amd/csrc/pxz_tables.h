@@ -1,7 +1,10 @@
 #pragma once
 #include <stdint.h>
 
+#include <utility>
 #include <vector>
+
+#include "pxz_internal.h"
 
 namespace pxz {
 
@@ -18,5 +21,41 @@ bool build_axis(uint32_t in_size, uint32_t out_size, uint32_t filter, AxisWindow
 
 // thresholds[k] = smallest positive float v with round(log2f(v)) >= -k
 bool build_level_thresholds(float *thresholds, int count);
+
+// ---- host images of the device tables (layouts: pxz_internal.h).  The builders never call HIP and return false for an
+// unknown filter; empty arrays stay empty (no device copy, a null pointer), the others are never empty.
+// the generic kernel's down-scaling tables for one (tile geometry, filter)
+struct ShrinkTableSet {
+	std::vector<AxisTab> tabs;  // 2 axes x {full, ragged edge} x kMaxLevel, passed by value in the kernel arguments
+	std::vector<uint16_t> bounds;
+	std::vector<uint32_t> coeffs;
+	std::vector<int32_t> ksums;
+	std::vector<uint32_t> rows;  // unified rows, the 32x32 / 16x16 operand tables (AxisTab::mf_off), then 32 dwords of padding
+	std::vector<uint32_t> mf64;  // 64x64 tiles: shrink64_kernel's operand tables of every level (empty: not available)
+	bool opaque_stays = true;    // a constant-255 alpha comes back as 255 from every window of every table
+};
+bool build_shrink_tables(uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter, ShrinkTableSet *out);
+
+// decode side: up-scaling tables of every source size to the full tile size (expand_kernel)
+struct ExpandTableSet {
+	std::vector<ExpandTab> dir;  // [(axis * 2 + class) * dir_stride + source size]
+	uint32_t dir_stride = 0;
+	std::vector<uint16_t> starts, sizes;
+	std::vector<int16_t> coeffs;
+	std::vector<uint32_t> xmf;    // 32x32 tiles, convolutions: kXmfLevels * kXmfDw (empty: not available)
+	std::vector<uint32_t> xmf16;  // 16x16 tiles, convolutions: kXmf16Levels * kXmf16Dw
+	std::vector<uint32_t> xmf64;  // 64x64 tiles, convolutions: kXmf64Levels * kXmf64Dw
+};
+bool build_expand_tables(uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter, ExpandTableSet *out);
+
+// tree::process on rectangle lists: every axis table (down with `filter`, back up with `filter_upscale`) between each tile
+// size the recursion over `levels` (block sizes, level by level) reaches in a width x height frame and its reduced sizes
+struct TreeTableSet {
+	std::vector<TreeAxisEntry> dir;
+	std::vector<int32_t> starts, sizes;
+	std::vector<int16_t> coeffs;
+};
+bool build_tree_tables(uint32_t width, uint32_t height, const std::vector<std::pair<uint32_t, uint32_t>> &levels, uint32_t filter,
+                       uint32_t filter_upscale, TreeTableSet *out);
 
 }  // namespace pxz
