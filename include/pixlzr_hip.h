@@ -199,6 +199,65 @@ int pxz_shrink_image_ladder(pxz_handle *h, const uint8_t *pixels, uint32_t width
                             const float *factors, uint32_t n_factors, float *block_value, uint32_t *out_w,
                             uint32_t *out_h, uint8_t *out_pixels);
 
+/* ---- batches of differently sized images ------------------------------------ */
+
+/* One image of a varied batch: an interleaved 8-bit image (RGB8 or RGBA8, the batch's `channels`) at offset_bytes from the
+ * batch's base pointer (any alignment).  What src/bin/whole-folder.rs:69-117 holds for each file of a folder. */
+typedef struct pxz_image_desc {
+	uint32_t width, height;
+	uint32_t pitch_bytes;   /* >= width*channels */
+	uint32_t reserved;      /* 0 */
+	uint64_t offset_bytes;  /* image start relative to the batch's base pointer (any alignment) */
+} pxz_image_desc;
+
+/* Layout of a varied batch's per-tile outputs (host only: no handle, no GPU, like pxz_grid).  Image i has the grid
+ * pxz_grid(width_i, height_i, block_w, block_h); its tile t (reference row-major order, iter.rs:64-76) lives at output index
+ * tile_offsets[i] + t, and tile_offsets[n_images] is the batch's tile count.  Slots stay block_w*block_h*channels bytes,
+ * addressed with 64-bit offsets.  PXZ_ERR_INVALID_ARG for a null pointer, n_images 0, a zero block side, a zero image side
+ * or a non-zero reserved field; PXZ_ERR_UNSUPPORTED for an image side above 2^24 or more than 2^32-1 tiles in all.  The
+ * error names no image (there is no handle to carry the text); the device entry points below do. */
+int pxz_varied_layout(const pxz_image_desc *descs, uint32_t n_images, uint32_t block_w, uint32_t block_h,
+                      uint64_t *tile_offsets);
+
+/* Pixlzr::from_image + shrink_by | shrink_directionally (pixlzr.rs:155-205) of EVERY image of a batch of differently sized
+ * device-resident images, in one call whose number of kernel launches does not depend on n_images.  All images share
+ * `channels` (3 or 4) and params (block size, mode, filter, factor; params->reserved hints are ignored).  descs is a HOST
+ * array; image i starts at d_base + descs[i].offset_bytes.  Outputs in the pxz_varied_layout order: d_block_value, d_out_w,
+ * d_out_h per tile, d_out_pixels slots of block_w*block_h*channels bytes (may be NULL: values and sizes only).  Each image's
+ * results equal pxz_shrink_frames_device on that image alone, bit for bit (value bits, sizes, the valid slot bytes).
+ * Asynchronous on the handle's stream.
+ * Validation runs on the host before anything is launched, for every image, and names the failing image's index in
+ * pxz_last_error; on an error nothing is written.  The rules are pxz_shrink_frames_device's: PXZ_ERR_INVALID_ARG for null
+ * pointers, n_images 0, channels not 3|4, zero sides, a pitch below one row, a non-zero reserved field, a bad mode / filter /
+ * non-finite factor; PXZ_ERR_UNSUPPORTED for a side above 2^24 or more than 2^32-1 tiles in all; PXZ_ERR_TILE_TOO_SMALL for
+ * shrink_directionally with a tile (edge tiles included) narrower or lower than 2 px.
+ * Limit of this path: every tile is staged whole in LDS, so block_w*block_h*channels must not exceed 65536 bytes (128x128
+ * RGBA, 147x147 RGB); larger blocks give PXZ_ERR_UNSUPPORTED (the single-geometry call runs them from HBM).
+ * A varied call reads and writes none of the state the single-geometry fast paths keep in the handle (kernel-selection
+ * statistics, worklist counters, the per-tile detector scratch with its "copied" flags). */
+int pxz_shrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w,
+                                    uint32_t *d_out_h, uint8_t *d_out_pixels);
+
+/* Pixlzr::encode_to_vec (src/encoding/mod.rs:40-89) of every image of a varied batch, on the device: the tiles as
+ * pxz_shrink_varied_frames_device leaves them become one complete .pixlzr file per image, back to back in d_out; file i is
+ * [d_file_offsets[i], d_file_offsets[i+1]) (n_images + 1 u64 offsets).  Only width and height of the descriptors are read.
+ * File i equals pxz_encode_frames_device of image i alone.  If out_capacity is too small the files are truncated but the
+ * offsets are still exact (retry with d_file_offsets[n_images] bytes).  Asynchronous on the handle's stream. */
+int pxz_encode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, uint32_t filter_byte, const float *d_block_value,
+                                    const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_out,
+                                    uint64_t out_capacity, uint64_t *d_file_offsets);
+
+/* Host images in, .pixlzr files out, synchronously: what a Rust loop over a folder (whole-folder.rs:69-117) calls once
+ * instead of once per file.  pixels[i] is image i (descs[i].offset_bytes is ignored).  file_offsets (n_images + 1) are
+ * always written; the files go to out when out_capacity >= file_offsets[n_images], else the call returns
+ * PXZ_ERR_BUFFER_TOO_SMALL and writes nothing to out (retry with file_offsets[n_images] bytes; out may be NULL for that
+ * size query).  Errors and limits as pxz_shrink_varied_frames_device. */
+int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                             uint32_t channels, const pxz_params *params, uint32_t filter_byte, uint8_t *out,
+                             uint64_t out_capacity, uint64_t *file_offsets);
+
 /* The colour conversion inside get_block_variance, per pixel (operations.rs:56-59: Srgba<u8>::into_linear()
  * .into_color::<Oklaba<f32>>(), palette 0.7.6 + the platform's cbrtf): d_laba[4i..4i+3] = {l, a, b, alpha} of
  * RGBA pixel i.  The same device function the Oklab detector kernels call -- exposed so that its bits can be

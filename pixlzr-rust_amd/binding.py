@@ -21,6 +21,7 @@ EXPORTED_SYMBOLS = [
     "pxz_enable_timing", "pxz_last_kernel_ms", "pxz_last_first_kernel_ms", "pxz_handle_state",
     "pxz_debug_read_work", "pxz_expand_frames_device", "pxz_expand_image", "pxz_decode_frames_device", "pxz_decode_file", "pxz_decode_status", "pxz_process_frames_device", "pxz_tree_process_frames_device", "pxz_trim", "pxz_debug_read_status",
     "pxz_shrink_ladder_frames_device", "pxz_shrink_image_ladder",
+    "pxz_varied_layout", "pxz_shrink_varied_frames_device", "pxz_encode_varied_frames_device", "pxz_encode_varied_images",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -45,6 +46,19 @@ class Frames(C.Structure):
 class Params(C.Structure):
     _fields_ = [("block_w", C.c_uint32), ("block_h", C.c_uint32), ("mode", C.c_uint32),
                 ("filter", C.c_uint32), ("factor", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ImageDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("pitch_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("offset_bytes", C.c_uint64)]
+
+
+def image_descs(geoms):
+    """(width, height, pitch_bytes, offset_bytes[, reserved]) tuples -> a ctypes array of pxz_image_desc."""
+    arr = (ImageDesc * max(len(geoms), 1))()
+    for i, g in enumerate(geoms):
+        arr[i] = ImageDesc(g[0], g[1], g[2], g[4] if len(g) > 4 else 0, g[3])
+    return arr
 
 
 def library_path():
@@ -114,6 +128,14 @@ def load_library():
     L.pxz_shrink_ladder_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params), vp, u32] + [vp] * 5
     L.pxz_shrink_image_ladder.restype = C.c_int
     L.pxz_shrink_image_ladder.argtypes = [vp, vp] + [u32] * 8 + [vp, u32] + [vp] * 4
+    L.pxz_varied_layout.restype = C.c_int
+    L.pxz_varied_layout.argtypes = [vp, u32, u32, u32, vp]
+    L.pxz_shrink_varied_frames_device.restype = C.c_int
+    L.pxz_shrink_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 5
+    L.pxz_encode_varied_frames_device.restype = C.c_int
+    L.pxz_encode_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 5 + [C.c_uint64, vp]
+    L.pxz_encode_varied_images.restype = C.c_int
+    L.pxz_encode_varied_images.argtypes = [vp, vp, vp, u32, u32, C.POINTER(Params), u32, vp, C.c_uint64, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -169,6 +191,16 @@ def grid(width, height, bw, bh):
     if rc != 0:
         raise PxzError(rc)
     return c.value, r.value
+
+
+def varied_layout(geoms, bw, bh):
+    """pxz_varied_layout: geoms = [(width, height, pitch_bytes, offset_bytes), ...] -> uint64[n+1] tile offsets."""
+    n = len(geoms)
+    out = np.zeros(n + 1, np.uint64)
+    rc = load_library().pxz_varied_layout(C.cast(image_descs(geoms), C.c_void_p) if n else None, n, bw, bh, _p(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out
 
 
 def qoi_encode(tile):
@@ -416,6 +448,97 @@ class Handle:
             C.c_void_p(vals.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
             C.c_void_p(slots.data_ptr()) if slots is not None else None))
         return vals, ow, oh, slots
+
+    # ---- batches of differently sized images ----
+    @staticmethod
+    def _varied_batch(images, descs):
+        """images: a list of uint8 CUDA tensors [H, W, C] (rows may be padded: stride(0) is the pitch), or one uint8 CUDA
+        buffer with descs = [(width, height, pitch_bytes, offset_bytes), ...].  -> (base pointer, geoms, channels, keep-alive)"""
+        import torch
+        if descs is not None:
+            buf = images
+            assert buf.is_cuda and buf.dtype == torch.uint8
+            ch = None
+            return buf.data_ptr(), [tuple(d) for d in descs], ch, buf
+        assert len(images) > 0
+        base = min(t.data_ptr() for t in images)
+        geoms = []
+        for t in images:
+            assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.stride(2) == 1 and t.stride(1) == t.shape[2]
+            geoms.append((t.shape[1], t.shape[0], t.stride(0), t.data_ptr() - base))
+        return base, geoms, images[0].shape[2], images
+
+    def shrink_varied_frames_device(self, images, bw, bh, mode, filt, factor, want_pixels=True, descs=None, channels=None, out=None):
+        """pxz_shrink_varied_frames_device: every image of a list of differently sized CUDA images in one call.
+        Returns (tile_offsets uint64[n+1], values[T], w[T], h[T], slots[T, bw*bh*C] | None); image i's tiles are
+        [tile_offsets[i], tile_offsets[i+1]).  With descs, `images` is one uint8 CUDA buffer and channels must be given."""
+        import torch
+        base, geoms, ch, keep = self._varied_batch(images, descs)
+        ch = channels if channels is not None else ch
+        dev = torch.device("cuda", self.device_id)
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            vals = torch.empty(T, dtype=torch.float32, device=dev)
+            ow = torch.empty(T, dtype=torch.int32, device=dev)
+            oh = torch.empty(T, dtype=torch.int32, device=dev)
+            slots = torch.empty((T, bw * bh * ch), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, ow, oh, slots = out
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_shrink_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), ch, C.byref(pd), C.c_void_p(base),
+            C.c_void_p(vals.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()) if slots is not None else None))
+        del keep
+        if offs is None:  # (given outputs: the library checks the descriptors first and names a failing image)
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, ow, oh, slots
+
+    def encode_varied_frames_device(self, sizes, channels, bw, bh, vals, ow, oh, slots, filter_byte=0, out=None):
+        """pxz_encode_varied_frames_device: sizes = [(width, height), ...] of the images whose tiles (varied layout) are given.
+        Returns (file_offsets int64[n+1], bytes uint8[capacity])."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        n = len(geoms)
+        if out is None:
+            cap = 0
+            for (w, h) in sizes:
+                cols, rows = grid(w, h, bw, bh)
+                cap += 26 + rows * 4 + cols * rows * (13 + 10 + bw * bh * (channels + 1) + 8)
+            offs = torch.empty(n + 1, dtype=torch.int64, device=vals.device)
+            buf = torch.empty(cap, dtype=torch.uint8, device=vals.device)
+        else:
+            offs, buf = out
+        pd = Params(bw, bh, 0, 0, 1.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_encode_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), n, channels, C.byref(pd), filter_byte,
+            C.c_void_p(vals.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()),
+            C.c_void_p(buf.data_ptr()), buf.numel(), C.c_void_p(offs.data_ptr())))
+        return offs, buf
+
+    def encode_varied_images(self, imgs, bw, bh, mode, filt, factor, filter_byte=0):
+        """pxz_encode_varied_images: host images (numpy uint8 [H, W, C], one channel count) -> a list of .pixlzr files (bytes)."""
+        imgs = [np.ascontiguousarray(i) if i.strides[1] != i.shape[2] or i.strides[2] != 1 else i for i in imgs]
+        n = len(imgs)
+        ch = imgs[0].shape[2] if n else 4
+        geoms = [(i.shape[1], i.shape[0], i.strides[0], 0) for i in imgs]
+        ptrs = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in imgs])
+        descs = image_descs(geoms)
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        offs = np.zeros(n + 1, np.uint64)
+        buf = np.empty(sum(i.size for i in imgs) * 5 // 4 + 4096 * max(n, 1), np.uint8)
+        for attempt in range(2):  # (a second call only when the first guess at the files' size was short)
+            rc = self._L.pxz_encode_varied_images(self._h, C.cast(ptrs, C.c_void_p), C.cast(descs, C.c_void_p), n, ch,
+                                                  C.byref(pd), filter_byte, _p(buf), buf.size, _p(offs))
+            if rc != -7 or attempt == 1:
+                break
+            buf = np.empty(int(offs[-1]), np.uint8)
+        self._check(rc)
+        return [buf[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

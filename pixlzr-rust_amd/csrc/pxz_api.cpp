@@ -40,6 +40,8 @@ hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);
 hipError_t launch_pack(const PackArgs &a, hipStream_t stream);
 hipError_t launch_oklab(const ShrinkArgs &a, uint32_t n_cus, hipStream_t stream, uint32_t channels = 4);
 hipError_t launch_qoi(const QoiArgs &a, bool bins_clean, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_qoi_varied(const QoiArgs &a, const VariedWriterArgs &varied, bool bins_clean, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
@@ -90,6 +92,14 @@ struct TreeTables {
 	uint32_t n_dir = 0;
 };
 
+// batches of differently sized images: the axis tables of every (source size, level) pair of one batch: pxz::VariedTableSet
+struct VariedTables {
+	void *mem = nullptr;
+	pxz::TreeAxisEntry *d_dir = nullptr;
+	int32_t *d_starts = nullptr, *d_sizes = nullptr;
+	int16_t *d_coeffs = nullptr;
+};
+
 }  // namespace
 
 constexpr uint32_t kMaxImageSide = 1u << 24;  // see pxz_grid
@@ -114,6 +124,12 @@ struct pxz_handle {
 	DeviceBuffer ladder;              // factor ladder: the raw detector value of every tile, then the rungs' factors
 	float *ladder_host = nullptr;     //   pinned staging of the factors (PXZ_LADDER_MAX_RUNGS floats) ...
 	hipEvent_t ladder_copied = nullptr;  //   ... reused once the copy out of it recorded here has run
+	DeviceBuffer varied, varied_in, varied_out, varied_files;  // varied batches: the per-image table, the host form's images,
+	                                  //   tiles and files
+	pxz::VariedImage *varied_host = nullptr;  // pinned staging of the per-image table (varied_host_cap entries) ...
+	size_t varied_host_cap = 0;
+	hipEvent_t varied_copied = nullptr;       //   ... reused once the copy out of it recorded here has run
+	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedTables> varied_tables;  // (filter, tile sides) -> tables
 	bool quiet_stats = false;         // the launch being set up writes no kernel-selection statistics (the ladder's detector)
 	uint32_t *host_stats = nullptr;  // pinned, device-visible: [0] = tiles with transparency the last finished 32x32 launch saw
 	uint32_t *dev_stats = nullptr;   //   (its device-side address); read without synchronisation, steers only the kernel choice
@@ -719,7 +735,8 @@ void pxz_destroy(pxz_handle *h)
 	free_tables(h->tables);
 	free_tables(h->expand_tables);
 	free_tables(h->tree_tables);
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder})
+	free_tables(h->varied_tables);
+	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files})
 		if (b->ptr) (void)hipFree(b->ptr);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
@@ -731,6 +748,8 @@ void pxz_destroy(pxz_handle *h)
 	for (hipEvent_t ev : h->mid_events) (void)hipEventDestroy(ev);
 	if (h->ladder_copied) (void)hipEventDestroy(h->ladder_copied);
 	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
+	if (h->varied_copied) (void)hipEventDestroy(h->varied_copied);
+	if (h->varied_host) (void)hipHostFree(h->varied_host);
 	if (h->host_stats) {
 		(void)hipDeviceSynchronize();  // a queued launch may still write it
 		(void)hipHostFree(h->host_stats);
@@ -750,7 +769,7 @@ int pxz_trim(pxz_handle *h)
 		b.ptr = nullptr;
 		b.cap = 0;
 	};
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder})
+	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files})
 		drop(*b);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
@@ -760,6 +779,12 @@ int pxz_trim(pxz_handle *h)
 	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
 	h->ladder_copied = nullptr;
 	h->ladder_host = nullptr;
+	free_tables(h->varied_tables);
+	if (h->varied_copied) (void)hipEventDestroy(h->varied_copied);
+	if (h->varied_host) (void)hipHostFree(h->varied_host);
+	h->varied_copied = nullptr;
+	h->varied_host = nullptr;
+	h->varied_host_cap = 0;
 	h->packed_len = 0;
 	h->work_ready = false;  // (the worklist counters went with their buffer)
 	h->qbins_clean = nullptr;
@@ -2053,6 +2078,314 @@ int pxz_handle_state(pxz_handle *h, uint32_t state[4])
 	state[1] = h->host_stats ? const_cast<volatile uint32_t *>(h->host_stats)[1] : 0xffffffffu;
 	state[2] = h->last_alpha_kernel;
 	state[3] = h->last_alpha_first;
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- batches of differently sized images (pxz_varied.hip) --------------------------------------------------------------
+namespace {
+
+// The per-image table of a varied batch, checked image by image before anything is launched.  channels 0: geometry only
+// (pxz_varied_layout, the writer), no pitch or tile-size rules.
+int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t mode,
+                std::vector<pxz::VariedImage> *images, std::vector<uint32_t> *sides, uint32_t *n_rows)
+{
+	if (!d) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (bw == 0 || bh == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
+	images->resize(n);
+	std::vector<uint32_t> all = {bw, bh};
+	uint64_t tiles = 0, rows_total = 0;
+	for (uint32_t i = 0; i < n; ++i) {
+		const pxz_image_desc &g = d[i];
+		if (g.reserved != 0) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: reserved field must be 0", i);
+		if (g.width == 0 || g.height == 0) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: empty image (%ux%u)", i, g.width, g.height);
+		if (g.width > kMaxImageSide || g.height > kMaxImageSide)
+			return fail(h, PXZ_ERR_UNSUPPORTED, "image %u: image sides above 2^24 are not supported", i);
+		if (channels && (uint64_t)g.pitch_bytes < (uint64_t)g.width * channels)
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: pitch smaller than a row", i);
+		pxz::VariedImage &im = (*images)[i];
+		im.offset = g.offset_bytes;
+		im.width = g.width;
+		im.height = g.height;
+		im.pitch = g.pitch_bytes;
+		im.cols = ceil_div(g.width, bw);
+		im.rows = ceil_div(g.height, bh);
+		im.edge_w = g.width - (im.cols - 1) * bw;
+		im.edge_h = g.height - (im.rows - 1) * bh;
+		im.hdr_bytes = 26u + 4u * im.rows;
+		if (channels && mode == PXZ_MODE_SHRINK_DIRECTIONALLY && (im.edge_w < 2 || im.edge_h < 2 || bw < 2 || bh < 2))
+			return fail(h, PXZ_ERR_TILE_TOO_SMALL,
+			            "image %u: directional detector needs tiles of at least 2x2 px (edge tile is %ux%u); the reference panics here", i,
+			            im.edge_w, im.edge_h);
+		im.tile0 = (uint32_t)tiles;
+		im.row0 = (uint32_t)rows_total;
+		tiles += (uint64_t)im.cols * im.rows;
+		rows_total += im.rows;
+		if (tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "image %u: more than 2^32-1 tiles in the batch", i);
+		all.push_back(im.edge_w);
+		all.push_back(im.edge_h);
+	}
+	std::sort(all.begin(), all.end());
+	all.erase(std::unique(all.begin(), all.end()), all.end());
+	if (sides) *sides = all;
+	if (n_rows) *n_rows = (uint32_t)rows_total;
+	return PXZ_OK;
+}
+
+// the per-image table -> handle scratch, through pinned staging that is reused once the previous copy out of it has run
+int varied_upload(pxz_handle *h, const std::vector<pxz::VariedImage> &images, const pxz::VariedImage **d_images)
+{
+	const size_t bytes = images.size() * sizeof(pxz::VariedImage);
+	int rc = ensure(h, h->varied, bytes);
+	if (rc != PXZ_OK) return rc;
+	if (!h->varied_copied) PXZ_HIP(h, hipEventCreateWithFlags(&h->varied_copied, hipEventDisableTiming));
+	else PXZ_HIP(h, hipEventSynchronize(h->varied_copied));
+	if (h->varied_host_cap < images.size()) {
+		if (h->varied_host) (void)hipHostFree(h->varied_host);
+		h->varied_host = nullptr;
+		h->varied_host_cap = 0;
+		void *hp = nullptr;
+		PXZ_HIP(h, hipHostMalloc(&hp, bytes, hipHostMallocDefault));
+		h->varied_host = (pxz::VariedImage *)hp;
+		h->varied_host_cap = images.size();
+	}
+	std::memcpy(h->varied_host, images.data(), bytes);
+	PXZ_HIP(h, hipMemcpyAsync(h->varied.ptr, h->varied_host, bytes, hipMemcpyHostToDevice, h->stream));
+	PXZ_HIP(h, hipEventRecord(h->varied_copied, h->stream));
+	*d_images = (const pxz::VariedImage *)h->varied.ptr;
+	return PXZ_OK;
+}
+
+int get_varied_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t> &sides, const VariedTables **out)
+{
+	auto key = std::make_pair(filter, sides);
+	auto it = h->varied_tables.find(key);
+	if (it != h->varied_tables.end()) { *out = &it->second; return PXZ_OK; }
+	if (h->varied_tables.size() >= 16) {  // (a folder of many sizes: keep the cache bounded; queued launches may still read it)
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		free_tables(h->varied_tables);
+	}
+	pxz::VariedTableSet s;
+	if (!pxz::build_varied_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+	VariedTables vt;
+	const int rc = upload_tables(h, {{s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
+	if (rc != PXZ_OK) return rc;
+	*out = &(h->varied_tables[key] = vt);
+	return PXZ_OK;
+}
+
+// a tile image of at most this many bytes is staged whole in LDS by varied_kernel (with its second image and, for shrink_by,
+// the detector's tables: 142 KB of the 160 KB)
+constexpr uint64_t kVariedMaxTileBytes = 65536;
+
+int varied_check_params(pxz_handle *h, uint32_t channels, const pxz_params *p)
+{
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	if (p->block_w == 0 || p->block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
+	if (p->mode > 1) return fail(h, PXZ_ERR_INVALID_ARG, "mode must be 0 or 1");
+	if (p->filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter must be 0..4");
+	if (!std::isfinite(p->factor)) return fail(h, PXZ_ERR_INVALID_ARG, "factor must be finite");
+	if ((uint64_t)p->block_w * p->block_h * channels > kVariedMaxTileBytes)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "varied batches stage every tile in LDS: block_w*block_h*channels must not exceed %llu bytes",
+		            (unsigned long long)kVariedMaxTileBytes);
+	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_varied_layout(const pxz_image_desc *descs, uint32_t n_images, uint32_t block_w, uint32_t block_h, uint64_t *tile_offsets)
+{
+	if (!tile_offsets) return PXZ_ERR_INVALID_ARG;
+	std::vector<pxz::VariedImage> images;
+	const int rc = varied_plan(nullptr, descs, n_images, block_w, block_h, 0, 0, &images, nullptr, nullptr);
+	if (rc != PXZ_OK) return rc;
+	for (uint32_t i = 0; i < n_images; ++i) tile_offsets[i] = images[i].tile0;
+	tile_offsets[n_images] = (uint64_t)images.back().tile0 + (uint64_t)images.back().cols * images.back().rows;
+	return PXZ_OK;
+}
+
+int pxz_shrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w,
+                                    uint32_t *d_out_h, uint8_t *d_out_pixels)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_base || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	int rc = varied_check_params(h, channels, params);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, params->mode, &images, &sides, nullptr)) != PXZ_OK)
+		return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, params->filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::VariedArgs a{};
+	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
+	a.base = d_base;
+	a.n_images = n_images;
+	a.n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	a.bw = params->block_w;
+	a.bh = params->block_h;
+	a.mode = params->mode;
+	a.filter = params->filter;
+	a.factor = params->factor;
+	a.value = d_block_value;
+	a.out_w = d_out_w;
+	a.out_h = d_out_h;
+	a.out_px = d_out_pixels;
+	a.slot_bytes = params->block_w * params->block_h * channels;
+	a.tile_bytes = (a.slot_bytes + 15u) & ~15u;
+	a.dir = vt->d_dir;
+	a.starts = vt->d_starts;
+	a.sizes = vt->d_sizes;
+	a.coeffs = vt->d_coeffs;
+	std::memcpy(a.thresholds, h->thresholds, sizeof a.thresholds);
+	PXZ_HIP(h, pxz::launch_varied(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_encode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, uint32_t filter_byte, const float *d_block_value,
+                                    const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_out,
+                                    uint64_t out_capacity, uint64_t *d_file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params || !d_block_value || !d_tile_w || !d_tile_h || !d_slots || !d_out || !d_file_offsets)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4");
+	std::vector<pxz::VariedImage> images;
+	uint32_t n_rows = 0;
+	int rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, 0, 0, &images, nullptr, &n_rows);
+	if (rc != PXZ_OK) return rc;
+	const uint32_t n_tiles = images.back().tile0 + images.back().cols * images.back().rows, c = channels;
+	const uint64_t slot64 = (uint64_t)params->block_w * params->block_h * c;
+	if (slot64 > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
+	const uint32_t slot = (uint32_t)slot64;
+	if ((slot & 15u) != 0 && c == 4) return fail(h, PXZ_ERR_UNSUPPORTED, "RGBA slots must be 16-byte multiples");
+	// (the limits of pxz_encode_frames_device: the writer's kernels are the same)
+	const uint32_t px = params->block_w * params->block_h;
+	const uint64_t stride = 23ull + (uint64_t)px * (c + 1u) + 8ull;
+	if (stride * 4096ull > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large for the chunked scan");
+	const uint32_t n_chunks = (n_tiles + 4095u) / 4096u;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::VariedWriterArgs v{};
+	if ((rc = varied_upload(h, images, &v.images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->qscratch, pxz::qoi_scratch_bytes(n_tiles, px, c))) != PXZ_OK) return rc;
+	const size_t meta_u32 = (size_t)n_tiles * 2 + pxz::qoi_bins_dwords();
+	const size_t meta_bytes = ((meta_u32 * 4 + 7) & ~(size_t)7) + ((size_t)n_tiles + 1 + n_chunks) * 8;
+	const size_t qmeta_cap = h->qmeta.cap;
+	if ((rc = ensure(h, h->qmeta, meta_bytes)) != PXZ_OK) return rc;
+	if (h->qmeta.cap != qmeta_cap) h->qbins_clean = nullptr;
+	uint32_t *m32 = (uint32_t *)h->qmeta.ptr;
+	unsigned long long *m64 = (unsigned long long *)((uint8_t *)h->qmeta.ptr + ((meta_u32 * 4 + 7) & ~(size_t)7));
+	pxz::QoiArgs a{};
+	a.slots = d_slots;
+	a.w = d_tile_w;
+	a.h = d_tile_h;
+	a.value = d_block_value;
+	a.perm = m32;
+	a.rec_len = m32 + n_tiles;
+	a.bins = m32 + 2 * (size_t)n_tiles;
+	a.scratch = (uint8_t *)h->qscratch.ptr;
+	a.offsets = m64;
+	a.chunk_totals = m64 + n_tiles + 1;
+	a.out = d_out;
+	a.file_offsets = (unsigned long long *)d_file_offsets;
+	a.capacity = out_capacity;
+	a.n_tiles = n_tiles;
+	a.n_chunks = n_chunks;
+	// one "frame" of n_tiles tiles and no tile rows of its own: the splice puts record t at hdr_bytes + scan(t), and the
+	// per-image headers come from varied_headers_kernel
+	a.tiles_per_frame = n_tiles;
+	a.cols = 0;
+	a.rows = 0;
+	a.channels = c;
+	a.slot_bytes = slot;
+	a.hdr_bytes = images[0].hdr_bytes;
+	a.bw = params->block_w;
+	a.bh = params->block_h;
+	a.filter_byte = filter_byte;
+	v.n_images = n_images;
+	v.n_tiles = n_tiles;
+	v.n_rows = n_rows;
+	v.bw = params->block_w;
+	v.bh = params->block_h;
+	v.filter_byte = filter_byte;
+	v.rec_len = a.rec_len;
+	v.offsets = a.offsets;
+	v.chunk_totals = a.chunk_totals;
+	v.out = d_out;
+	v.file_offsets = a.file_offsets;
+	v.capacity = out_capacity;
+	const bool bins_clean = h->qbins_clean == a.bins;
+	h->qbins_clean = nullptr;
+	PXZ_HIP(h, pxz::launch_qoi_varied(a, v, bins_clean, h->n_cus, h->stream));
+	h->qbins_clean = a.bins;
+	return PXZ_OK;
+}
+
+int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                             uint32_t channels, const pxz_params *params, uint32_t filter_byte, uint8_t *out,
+                             uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!pixels || !params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	int rc = varied_check_params(h, channels, params);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, params->mode, &images, nullptr, nullptr)) != PXZ_OK)
+		return rc;
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// the images, back to back (256-byte aligned starts), and the tiles' outputs
+	std::vector<pxz_image_desc> dev(descs, descs + n_images);
+	uint64_t in_bytes = 0, raw = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		dev[i].offset_bytes = in_bytes;
+		const uint64_t bytes = (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels;
+		in_bytes += (bytes + 255u) & ~(uint64_t)255u;
+		raw += (uint64_t)descs[i].width * descs[i].height * channels;
+	}
+	const uint32_t n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	const uint64_t slot = (uint64_t)params->block_w * params->block_h * channels;
+	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
+	if ((rc = ensure(h, h->varied_in, in_bytes)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_out, meta + (uint64_t)n_tiles * slot + 8u * ((uint64_t)n_images + 1u))) != PXZ_OK) return rc;
+	uint8_t *d_in = (uint8_t *)h->varied_in.ptr, *d_out = (uint8_t *)h->varied_out.ptr;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		const uint64_t bytes = (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels;
+		PXZ_HIP(h, hipMemcpyAsync(d_in + dev[i].offset_bytes, pixels[i], bytes, hipMemcpyHostToDevice, h->stream));
+	}
+	float *d_val = (float *)d_out;
+	uint32_t *d_w = (uint32_t *)(d_out + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d_out + (uint64_t)n_tiles * 8u);
+	uint8_t *d_slots = d_out + meta;
+	uint64_t *d_offs = (uint64_t *)(d_slots + (uint64_t)n_tiles * slot);
+	if ((rc = pxz_shrink_varied_frames_device(h, dev.data(), n_images, channels, params, d_in, d_val, d_w, d_h, d_slots)) != PXZ_OK)
+		return rc;
+	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
+	uint64_t cap = raw + raw / 4u + 64ull * n_tiles + 4096ull * n_images;
+	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
+	for (int pass = 0; pass < 2; ++pass) {
+		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
+		if ((rc = pxz_encode_varied_frames_device(h, dev.data(), n_images, channels, params, filter_byte, d_val, d_w, d_h, d_slots,
+		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
+			return rc;
+		PXZ_HIP(h, hipMemcpyAsync(file_offsets, d_offs, 8u * ((size_t)n_images + 1u), hipMemcpyDeviceToHost, h->stream));
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		if (file_offsets[n_images] <= cap) break;
+		cap = file_offsets[n_images];
+	}
+	const uint64_t total = file_offsets[n_images];
+	if (!out || out_capacity < total)
+		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
+		            (unsigned long long)out_capacity);
+	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
 	return PXZ_OK;
 }
 

@@ -449,6 +449,48 @@ struct TreeRectArgs {
 	float thresholds[kNumThresholds];
 };
 
+// Batches of differently sized images (pxz_shrink_varied_frames_device, pxz_varied.hip): one flat tile space over the
+// batch.  Image i owns tiles [tile0, tile0 + cols * rows) and tile rows [row0, row0 + rows) of it.
+struct VariedImage {
+	uint64_t offset;         // bytes from the batch's base pointer to the image's first pixel
+	uint32_t tile0, row0;    // first tile / first tile row of the image in the batch
+	uint32_t width, height, pitch;
+	uint32_t cols, rows, edge_w, edge_h;
+	uint32_t hdr_bytes;      // writer: 26 + 4 * rows (mod.rs:47-48)
+};
+
+// One down-scaling table per (source size, level): dir[in * kMaxLevel + m] for every source size in of the batch's tiles
+// (the full bw, bh and each distinct edge width and height) and m = 1 .. kMaxLevel - 1, in the TreeAxisEntry format (out is
+// reduced_size(in, m); entries with out == in are never read).
+struct VariedArgs {
+	const uint8_t *base;
+	const VariedImage *images;
+	uint32_t n_images, n_tiles;
+	uint32_t bw, bh, mode, filter;
+	float factor;
+	float *value;
+	uint32_t *out_w, *out_h;
+	uint8_t *out_px;         // null: values and sizes only
+	uint32_t slot_bytes;
+	uint32_t tile_bytes;     // LDS bytes of one tile image (bw * bh * channels, rounded up to 16)
+	const TreeAxisEntry *dir;
+	const int32_t *starts, *sizes;
+	const int16_t *coeffs;
+	float thresholds[kNumThresholds];
+};
+
+// Writer of a varied batch: what the per-image headers need beside QoiArgs (record lengths, their scan, the file offsets)
+struct VariedWriterArgs {
+	const VariedImage *images;
+	uint32_t n_images, n_tiles, n_rows;  // n_rows: tile rows of the whole batch
+	uint32_t bw, bh, filter_byte;
+	uint32_t *rec_len;
+	const unsigned long long *offsets, *chunk_totals;
+	uint8_t *out;
+	unsigned long long *file_offsets;
+	unsigned long long capacity;
+};
+
 struct SynthArgs {
 	uint8_t *dst;
 	uint64_t frame_stride;

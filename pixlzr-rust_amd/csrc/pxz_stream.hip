@@ -852,7 +852,12 @@ size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels)
 }
 uint32_t qoi_bins_dwords() { return kBinDwords; }
 
-hipError_t launch_qoi(const QoiArgs &args, bool bins_clean, uint32_t n_cus, hipStream_t stream)
+hipError_t launch_varied_reclen(const VariedWriterArgs &a, hipStream_t stream);   // pxz_varied.hip
+hipError_t launch_varied_headers(const VariedWriterArgs &a, hipStream_t stream);
+
+// varied: null for a batch of equally sized frames; else the per-image header step of a varied batch (pxz_varied.hip), which
+// runs beside the same kernels: a record-length adjustment before the scan, its own headers after the splice (args.rows = 0)
+static hipError_t launch_qoi_impl(const QoiArgs &args, bool bins_clean, uint32_t n_cus, hipStream_t stream, const VariedWriterArgs *varied)
 {
 	QoiArgs a = args;
 	hipError_t e;
@@ -869,6 +874,7 @@ hipError_t launch_qoi(const QoiArgs &args, bool bins_clean, uint32_t n_cus, hipS
 	const uint32_t qb = (uint32_t)worst;
 	if (a.channels == 4) hipLaunchKernelGGL(qoi_tiles_kernel<4>, dim3(qb), dim3(64u), 0, stream, a);
 	else hipLaunchKernelGGL(qoi_tiles_kernel<3>, dim3(qb), dim3(64u), 0, stream, a);
+	if (varied && (e = launch_varied_reclen(*varied, stream)) != hipSuccess) return e;
 	// exclusive scan of the record lengths (same chunked scan as the pixel pack, sizes given)
 	PackArgs p{};
 	p.sizes = a.rec_len;
@@ -886,7 +892,21 @@ hipError_t launch_qoi(const QoiArgs &args, bool bins_clean, uint32_t n_cus, hipS
 	const unsigned long long grid = (unsigned long long)a.splice_unit_blocks + (frames * a.rows + 63u) / 64u;
 	if (grid > 0x7fffffffull) return hipErrorInvalidValue;
 	hipLaunchKernelGGL(qoi_splice_kernel, dim3((uint32_t)grid), dim3(64), 0, stream, a);
+	if (varied) {
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+		return launch_varied_headers(*varied, stream);
+	}
 	return hipGetLastError();
+}
+
+hipError_t launch_qoi(const QoiArgs &args, bool bins_clean, uint32_t n_cus, hipStream_t stream)
+{
+	return launch_qoi_impl(args, bins_clean, n_cus, stream, nullptr);
+}
+
+hipError_t launch_qoi_varied(const QoiArgs &args, const VariedWriterArgs &varied, bool bins_clean, uint32_t n_cus, hipStream_t stream)
+{
+	return launch_qoi_impl(args, bins_clean, n_cus, stream, &varied);
 }
 
 // ---------------------------------------------------------------------------

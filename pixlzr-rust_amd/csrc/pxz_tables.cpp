@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <set>
 #include <tuple>
 
@@ -542,6 +543,46 @@ bool build_tree_tables(uint32_t width, uint32_t height, const std::vector<std::p
 		}
 		s.coeffs.insert(s.coeffs.end(), win.coeffs.begin(), win.coeffs.end());
 		s.dir.push_back(e);
+	}
+	if (s.dir.empty()) s.dir.push_back(TreeAxisEntry{});
+	if (s.starts.empty()) { s.starts.push_back(0); s.sizes.push_back(0); }
+	if (s.coeffs.empty()) s.coeffs.push_back(0);
+	return true;
+}
+
+bool build_varied_tables(const std::vector<uint32_t> &sizes, uint32_t filter, VariedTableSet *out)
+{
+	VariedTableSet &s = *out;
+	s = VariedTableSet{};
+	const std::set<uint32_t> ins(sizes.begin(), sizes.end());
+	const uint32_t top = ins.empty() ? 0u : *ins.rbegin();
+	s.dir.assign((size_t)(top + 1u) * kMaxLevel, TreeAxisEntry{});
+	std::map<std::pair<uint32_t, uint32_t>, TreeAxisEntry> made;
+	for (uint32_t in : ins) {
+		if (in == 0u) continue;
+		for (uint32_t m = 1; m < (uint32_t)kMaxLevel; ++m) {
+			const uint32_t o = reduced(in, m);
+			if (o == in) continue;
+			auto it = made.find({in, o});
+			if (it == made.end()) {
+				AxisWindows win;
+				if (!build_axis(in, o, filter, &win, false)) return false;
+				TreeAxisEntry e{};
+				e.in = (uint16_t)in;
+				e.out = (uint16_t)o;
+				e.window = (uint16_t)win.window;
+				e.precision = (uint32_t)win.precision;
+				e.starts_off = (uint32_t)s.starts.size();
+				e.coeff_off = (uint32_t)s.coeffs.size();
+				for (uint32_t k = 0; k < o; ++k) {
+					s.starts.push_back(win.starts[k]);
+					s.sizes.push_back(win.sizes.empty() ? 0 : win.sizes[k]);
+				}
+				s.coeffs.insert(s.coeffs.end(), win.coeffs.begin(), win.coeffs.end());
+				it = made.emplace(std::make_pair(in, o), e).first;
+			}
+			s.dir[(size_t)in * kMaxLevel + m] = it->second;
+		}
 	}
 	if (s.dir.empty()) s.dir.push_back(TreeAxisEntry{});
 	if (s.starts.empty()) { s.starts.push_back(0); s.sizes.push_back(0); }

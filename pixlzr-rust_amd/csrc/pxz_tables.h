@@ -58,4 +58,15 @@ struct TreeTableSet {
 bool build_tree_tables(uint32_t width, uint32_t height, const std::vector<std::pair<uint32_t, uint32_t>> &levels, uint32_t filter,
                        uint32_t filter_upscale, TreeTableSet *out);
 
+// batches of differently sized images (varied_kernel): the down-scaling table of every (source size, level) pair the batch's
+// tiles can reach, dir[in * kMaxLevel + m] for in in `sizes` (tile widths and heights: the full block sides and every
+// distinct edge) and m = 1 .. kMaxLevel - 1; entries of other sizes, of level 0 and of levels that keep the size are zero.
+// One table per (in, out) pair, shared by the levels and axes that reach it.
+struct VariedTableSet {
+	std::vector<TreeAxisEntry> dir;  // (max(sizes) + 1) * kMaxLevel
+	std::vector<int32_t> starts, sizes;
+	std::vector<int16_t> coeffs;
+};
+bool build_varied_tables(const std::vector<uint32_t> &sizes, uint32_t filter, VariedTableSet *out);
+
 }  // namespace pxz

@@ -1,7 +1,9 @@
 // pxz_tables_dump — runs the table builders of libpixlzr_hip.so (pxz_tables.h) over a fixed sweep of geometries and filters
 // and prints one line per table set: the geometry, then element count and FNV-1a 64 hash of every array ("-": absent).
-// tests/test_tables_host.py pins a digest of these lines per (family, filter).
+// tests/test_tables_host.py pins a digest of these lines per (family, filter).  With the argument `varied` it prints the
+// directories of varied batches instead (tests/test_varied_host.py).
 #include <array>
+#include <cstring>
 #include <cstdio>
 #include <set>
 #include <utility>
@@ -51,8 +53,33 @@ std::vector<std::array<uint32_t, 4>> grids(bool expand)
 
 }  // namespace
 
-int main()
+// the (source size, level) directories of varied batches: sets of tile sides a batch can hold (full block sides and the
+// distinct edges of its images), every filter
+int dump_varied()
 {
+	const std::vector<std::vector<uint32_t>> side_sets = {
+	    {16}, {1, 16}, {32}, {3, 17, 32}, {64}, {1, 2, 5, 33, 64}, {20, 48}, {1, 7, 19, 20, 47, 48}, {37, 61}, {2, 36, 37, 60, 61}, {128}};
+	for (uint32_t f = 0; f < 5; ++f)
+		for (const auto &sides : side_sets) {
+			pxz::VariedTableSet s;
+			if (!pxz::build_varied_tables(sides, f, &s)) return 1;
+			uint32_t used = 0;
+			for (const pxz::TreeAxisEntry &e : s.dir) used += e.out != 0;
+			printf("varied filter=%u sides=", f);
+			for (size_t i = 0; i < sides.size(); ++i) printf(i ? ",%u" : "%u", sides[i]);
+			printf(" n_dir=%zu used=%u", s.dir.size(), used);
+			arr("dir", s.dir);
+			arr("starts", s.starts);
+			arr("sizes", s.sizes);
+			arr("coeffs", s.coeffs);
+			printf("\n");
+		}
+	return 0;
+}
+
+int main(int argc, char **argv)
+{
+	if (argc > 1 && std::strcmp(argv[1], "varied") == 0) return dump_varied();
 	for (uint32_t f = 0; f < 5; ++f)
 		for (const auto &g : grids(false)) {
 			pxz::ShrinkTableSet s;
