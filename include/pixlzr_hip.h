@@ -305,8 +305,61 @@ int pxz_decode_file(pxz_handle *h, const uint8_t *file, size_t len, uint32_t *wi
 
 /* Waits for the handle's stream; flags of the last decode-side call on this handle:
  * bit 0  pxz_expand_frames_device met a tile whose stored size is zero or exceeds its place,
- * bit 1  pxz_decode_frames_device met a malformed file or record. */
+ * bit 1  pxz_decode_frames_device met a malformed file or record.
+ * After a varied call (below) the bits are the OR over the images of its batch. */
 int pxz_decode_status(pxz_handle *h, uint32_t *flags);
+
+/* The header fields of one host-resident .pixlzr file (host only: no handle, no GPU, like pxz_grid): what pxz_decode_file
+ * returns when all its output pointers are NULL, with the same checks.  channels is the channel byte of the first record's
+ * QOI header (decode_block, mod.rs:202-242).  PXZ_ERR_INVALID_ARG for a null pointer, a file shorter than its header, a
+ * wrong magic or version, a zero image or block side, a file that ends inside its first record, a channel byte that is
+ * neither 3 nor 4.  What a caller of the varied reader needs to fill its descriptors before anything is allocated. */
+int pxz_file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h,
+                    uint32_t *channels, uint32_t *filter_byte);
+
+/* ---- decode side of batches of differently sized images ---------------------- */
+
+/* Pixlzr::decode_from_vec (encoding/mod.rs:95-165) + decode_block (:202-242) of the n_images files of a varied batch, back
+ * to back in d_files (file i = [d_file_offsets[i], d_file_offsets[i+1])), in one call whose number of kernel launches and
+ * copies does not depend on n_images: the read half of src/bin/whole-folder.rs:155-163.  All files share `channels` (3 or 4)
+ * and params->block_w / block_h (nothing else of params is used); of descs[i] only width and height are read (as by the
+ * varied writer).  Outputs in the pxz_varied_layout order: d_block_value, d_tile_w, d_tile_h per tile, d_slots of
+ * block_w*block_h*channels bytes.  Each image's results equal pxz_decode_frames_device on that file alone, bit for bit.
+ * A file whose header does not carry descs[i]'s size and the batch's block size, or that is malformed anywhere, is flagged
+ * and its unusable tiles get size 0x0 exactly as in the single-geometry call; the other images are not affected.
+ * d_image_flags (n_images dwords, may be NULL) receives 0 or 2 per image; pxz_decode_status reports the OR over the batch.
+ * Asynchronous on the handle's stream.  Descriptors are validated on the host before anything is launched, with the rules,
+ * codes and "image i" texts of pxz_shrink_varied_frames_device; on such an error nothing is written.  No limit on the
+ * block size beyond a slot of less than 4 GiB (nothing of a tile is staged). */
+int pxz_decode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, const uint8_t *d_files, const uint64_t *d_file_offsets,
+                                    float *d_block_value, uint32_t *d_tile_w, uint32_t *d_tile_h, uint8_t *d_slots,
+                                    uint32_t *d_image_flags);
+
+/* Pixlzr::expand (pixlzr.rs:77-122) + to_image (pixlzr_image.rs:24-74) of every image of a varied batch: the stored tiles
+ * (varied layout, as the call above or pxz_shrink_varied_frames_device leaves them) are resized back to their full sizes
+ * with params->filter (what to_image(filter) takes) and image i is written at d_base + descs[i].offset_bytes with
+ * descs[i].pitch_bytes between rows, any alignment.  Bytes of the buffer that belong to no image (row padding, gaps) are not
+ * written.  Each image equals pxz_expand_frames_device on its tiles alone, byte for byte.  A tile whose stored size is zero
+ * or exceeds its place is skipped (its pixels stay as they were) and flagged: d_image_flags (may be NULL) receives 0 or 1
+ * per image, pxz_decode_status the OR.  Asynchronous; validation as above (here the pitch counts too).  Limit of this path:
+ * block_w*block_h*channels <= 65536 bytes as on the encode side (PXZ_ERR_UNSUPPORTED beyond; the single-geometry call
+ * runs larger tiles), so whatever the varied writer wrote the varied reader reads. */
+int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                    const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_image_flags);
+
+/* Host files in, host images out, synchronously: what a Rust loop over a folder (whole-folder.rs:155-163) calls once
+ * instead of pxz_decode_file + pxz_expand_image per file.  files[i] / lens[i] is file i; image i is written at
+ * out_base + descs[i].offset_bytes with descs[i].pitch_bytes between rows.  Every header is parsed on the host first
+ * (pxz_file_header): a file whose size, block size or channels disagree with descs[i] and the batch is refused
+ * (PXZ_ERR_INVALID_ARG, "image i" in pxz_last_error) and nothing is written.  Files that pass that check but are malformed
+ * further in come back flagged -- image_flags[i] (may be NULL), bits as pxz_decode_status -- with the tiles that could not
+ * be read left zero; the call then returns PXZ_ERR_INVALID_ARG naming the first such image, and every other image is
+ * complete.  Errors and limits as pxz_expand_varied_frames_device. */
+int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
+                            uint32_t n_images, uint32_t channels, const pxz_params *params, uint8_t *out_base,
+                            uint32_t *image_flags);
 
 /* The same for one host-resident image (copies in, expands, copies out; PXZ_ERR_INVALID_ARG on an
  * invalid stored size). */

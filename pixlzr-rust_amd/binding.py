@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = [
     "pxz_debug_read_work", "pxz_expand_frames_device", "pxz_expand_image", "pxz_decode_frames_device", "pxz_decode_file", "pxz_decode_status", "pxz_process_frames_device", "pxz_tree_process_frames_device", "pxz_trim", "pxz_debug_read_status",
     "pxz_shrink_ladder_frames_device", "pxz_shrink_image_ladder",
     "pxz_varied_layout", "pxz_shrink_varied_frames_device", "pxz_encode_varied_frames_device", "pxz_encode_varied_images",
+    "pxz_file_header", "pxz_decode_varied_frames_device", "pxz_expand_varied_frames_device", "pxz_decode_varied_files",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -136,6 +137,15 @@ def load_library():
     L.pxz_encode_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 5 + [C.c_uint64, vp]
     L.pxz_encode_varied_images.restype = C.c_int
     L.pxz_encode_varied_images.argtypes = [vp, vp, vp, u32, u32, C.POINTER(Params), u32, vp, C.c_uint64, vp]
+    if hasattr(L, "pxz_file_header"):  # (a build of an earlier commit named by PXZ_LIB lacks the varied decode side)
+        L.pxz_file_header.restype = C.c_int
+        L.pxz_file_header.argtypes = [vp, C.c_size_t] + [C.POINTER(u32)] * 6
+        L.pxz_decode_varied_frames_device.restype = C.c_int
+        L.pxz_decode_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 7
+        L.pxz_expand_varied_frames_device.restype = C.c_int
+        L.pxz_expand_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 5
+        L.pxz_decode_varied_files.restype = C.c_int
+        L.pxz_decode_varied_files.argtypes = [vp, vp, vp, vp, u32, u32, C.POINTER(Params), vp, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -201,6 +211,16 @@ def varied_layout(geoms, bw, bh):
     if rc != 0:
         raise PxzError(rc)
     return out
+
+
+def file_header(data):
+    """pxz_file_header: one .pixlzr file (bytes) -> (width, height, block_w, block_h, channels, filter_byte).  No GPU."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    v = [C.c_uint32() for _ in range(6)]
+    rc = load_library().pxz_file_header(_p(buf) if buf.size else None, buf.size, *[C.byref(x) for x in v])
+    if rc != 0:
+        raise PxzError(rc)
+    return tuple(x.value for x in v)
 
 
 def qoi_encode(tile):
@@ -539,6 +559,77 @@ class Handle:
             buf = np.empty(int(offs[-1]), np.uint8)
         self._check(rc)
         return [buf[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+    def decode_varied_frames_device(self, files, file_offsets, sizes, channels, bw, bh, out=None, image_flags=None):
+        """pxz_decode_varied_frames_device: files = uint8 CUDA tensor holding the .pixlzr files of differently sized images
+        back to back, file_offsets int64[n+1] (CUDA), sizes = [(width, height), ...].  Returns (tile_offsets uint64[n+1],
+        values[T], w[T], h[T], slots[T, bw*bh*C]) in the varied layout; image_flags (int32[n] CUDA, optional) gets 0 | 2."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            dev = files.device
+            vals = torch.zeros(T, dtype=torch.float32, device=dev)
+            ow = torch.zeros(T, dtype=torch.int32, device=dev)
+            oh = torch.zeros(T, dtype=torch.int32, device=dev)
+            slots = torch.zeros((T, bw * bh * channels), dtype=torch.uint8, device=dev)
+        else:
+            vals, ow, oh, slots = out
+        pd = Params(bw, bh, 0, 0, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_decode_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), C.c_void_p(files.data_ptr()),
+            C.c_void_p(file_offsets.data_ptr()), C.c_void_p(vals.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()), C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, ow, oh, slots
+
+    def expand_varied_frames_device(self, descs, channels, bw, bh, filt, ow, oh, slots, out, image_flags=None):
+        """pxz_expand_varied_frames_device: the stored tiles of a varied batch (w[T], h[T], slots[T, bw*bh*C]) -> the images,
+        written into the uint8 CUDA buffer `out` at descs = [(width, height, pitch_bytes, offset_bytes), ...].  Returns out."""
+        geoms = [tuple(d) for d in descs]
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_expand_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), C.c_void_p(ow.data_ptr()),
+            C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(out.data_ptr()),
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        return out
+
+    def decode_varied_files(self, files, channels, bw, bh, filt, sizes=None, out=None, descs=None):
+        """pxz_decode_varied_files: a list of .pixlzr files (bytes) of one channel count and block size -> a list of
+        (height, width, channels) images.  sizes defaults to what the headers say (file_header); with out (a numpy uint8
+        buffer) and descs = [(width, height, pitch_bytes, offset_bytes), ...] the images are written there instead.
+        Returns (images | out, flags uint32[n]); raises PxzError (with .flags) when a file is refused or malformed."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        if sizes is None and descs is None:
+            sizes = [file_header(f)[:2] for f in files]
+        own = descs is None
+        if own:
+            descs, at = [], 0
+            for (w, h) in sizes:
+                descs.append((w, h, w * channels, at))
+                at += w * h * channels
+            out = np.zeros(max(at, 1), np.uint8)
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        flags = np.zeros(max(n, 1), np.uint32)
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        rc = self._L.pxz_decode_varied_files(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p),
+                                             C.cast(image_descs(descs), C.c_void_p), n, channels, C.byref(pd), _p(out), _p(flags))
+        if own:
+            result = [out[d[3]:d[3] + d[0] * d[1] * channels].reshape(d[1], d[0], channels) for d in descs]
+        else:
+            result = out
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.flags, err.images = flags[:n], result
+            raise err
+        return result, flags[:n]
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

@@ -35,6 +35,10 @@ bool fast16_applicable(const ShrinkArgs &a, uint32_t channels);
 hipError_t launch_expand(const ExpandArgs &a, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_ladder(const LadderArgs &a, uint32_t channels, uint32_t nw, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream);
+hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, uint32_t n_rows, uint32_t *image_flags, bool bins_clean,
+                                hipStream_t stream);
+hipError_t launch_varied_expand(const VariedExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw);
 hipError_t launch_widen(const WidenArgs &a, hipStream_t stream);
 hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);
 hipError_t launch_pack(const PackArgs &a, hipStream_t stream);
@@ -100,6 +104,16 @@ struct VariedTables {
 	int16_t *d_coeffs = nullptr;
 };
 
+// decode side of varied batches: the up-scaling table of every (full size, stored size) pair of one batch: pxz::VariedExpandTableSet
+struct VariedExpandTables {
+	void *mem = nullptr;
+	uint32_t *d_slot = nullptr;
+	pxz::ExpandTab *d_dir = nullptr;
+	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
+	int16_t *d_coeffs = nullptr;
+	uint32_t stride = 0, max_window = 0;
+};
+
 }  // namespace
 
 constexpr uint32_t kMaxImageSide = 1u << 24;  // see pxz_grid
@@ -130,6 +144,8 @@ struct pxz_handle {
 	size_t varied_host_cap = 0;
 	hipEvent_t varied_copied = nullptr;       //   ... reused once the copy out of it recorded here has run
 	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedTables> varied_tables;  // (filter, tile sides) -> tables
+	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedExpandTables> varied_expand_tables;  // the same for the decode side
+	DeviceBuffer varied_flags;        // per-image flags of a varied decode-side call whose caller passed none
 	bool quiet_stats = false;         // the launch being set up writes no kernel-selection statistics (the ladder's detector)
 	uint32_t *host_stats = nullptr;  // pinned, device-visible: [0] = tiles with transparency the last finished 32x32 launch saw
 	uint32_t *dev_stats = nullptr;   //   (its device-side address); read without synchronisation, steers only the kernel choice
@@ -736,7 +752,8 @@ void pxz_destroy(pxz_handle *h)
 	free_tables(h->expand_tables);
 	free_tables(h->tree_tables);
 	free_tables(h->varied_tables);
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files})
+	free_tables(h->varied_expand_tables);
+	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files, &h->varied_flags})
 		if (b->ptr) (void)hipFree(b->ptr);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
@@ -769,7 +786,7 @@ int pxz_trim(pxz_handle *h)
 		b.ptr = nullptr;
 		b.cap = 0;
 	};
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files})
+	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files, &h->varied_flags})
 		drop(*b);
 	for (int i = 0; i < pxz_handle::kRing; ++i)
 		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
@@ -780,6 +797,7 @@ int pxz_trim(pxz_handle *h)
 	h->ladder_copied = nullptr;
 	h->ladder_host = nullptr;
 	free_tables(h->varied_tables);
+	free_tables(h->varied_expand_tables);
 	if (h->varied_copied) (void)hipEventDestroy(h->varied_copied);
 	if (h->varied_host) (void)hipHostFree(h->varied_host);
 	h->varied_copied = nullptr;
@@ -1474,27 +1492,52 @@ int pxz_decode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
 	return PXZ_OK;
 }
 
-int pxz_decode_file(pxz_handle *h, const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w,
-                    uint32_t *block_h, uint32_t *channels, uint32_t *filter_byte, float *block_value, uint32_t *tile_w,
-                    uint32_t *tile_h, uint8_t *slots)
+// The header fields of one .pixlzr file; on PXZ_ERR_INVALID_ARG *why says what is wrong with it.
+static int file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h,
+                       uint32_t *channels, uint32_t *filter_byte, const char **why)
 {
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!file || !width || !height || !block_w || !block_h || !channels || !filter_byte) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	*why = "null pointer";
+	if (!file || !width || !height || !block_w || !block_h || !channels || !filter_byte) return PXZ_ERR_INVALID_ARG;
 	static const uint8_t magic[9] = {'P', 'I', 'X', 'L', 'Z', 'R', 0, 0, 2};
-	if (len < 26 || std::memcmp(file, magic, 9) != 0) return fail(h, PXZ_ERR_INVALID_ARG, "not a .pixlzr v0.0.2 file");
+	*why = "not a .pixlzr v0.0.2 file";
+	if (len < 26 || std::memcmp(file, magic, 9) != 0) return PXZ_ERR_INVALID_ARG;
 	auto be = [&](size_t o) { return ((uint32_t)file[o] << 24) | ((uint32_t)file[o + 1] << 16) | ((uint32_t)file[o + 2] << 8) | file[o + 3]; };
 	*filter_byte = file[9];
 	*width = be(10);
 	*height = be(14);
 	*block_w = be(18);
 	*block_h = be(22);
-	if (*width == 0 || *height == 0 || *block_w == 0 || *block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image or block in the header");
+	*why = "empty image or block in the header";
+	if (*width == 0 || *height == 0 || *block_w == 0 || *block_h == 0) return PXZ_ERR_INVALID_ARG;
 	uint32_t cols, rows;
 	pxz_grid(*width, *height, *block_w, *block_h, &cols, &rows);
 	const size_t first = 26 + (size_t)rows * 4;
-	if (len < first + 13 + 10) return fail(h, PXZ_ERR_INVALID_ARG, "file ends inside the first record");
+	*why = "file ends inside the first record";
+	if (len < first + 13 + 10) return PXZ_ERR_INVALID_ARG;
 	*channels = file[first + 21];  // the first record's QOI header (decode_block, mod.rs:202-242)
-	if (*channels != 3 && *channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "first record has %u channels", *channels);
+	*why = "first record has neither 3 nor 4 channels";
+	if (*channels != 3 && *channels != 4) return PXZ_ERR_INVALID_ARG;
+	*why = "";
+	return PXZ_OK;
+}
+
+int pxz_file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h,
+                    uint32_t *channels, uint32_t *filter_byte)
+{
+	const char *why;
+	return file_header(file, len, width, height, block_w, block_h, channels, filter_byte, &why);
+}
+
+int pxz_decode_file(pxz_handle *h, const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w,
+                    uint32_t *block_h, uint32_t *channels, uint32_t *filter_byte, float *block_value, uint32_t *tile_w,
+                    uint32_t *tile_h, uint8_t *slots)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	const char *why;
+	int hrc = file_header(file, len, width, height, block_w, block_h, channels, filter_byte, &why);
+	if (hrc != PXZ_OK) return fail(h, hrc, "%s", why);
+	uint32_t cols, rows;
+	pxz_grid(*width, *height, *block_w, *block_h, &cols, &rows);
 	if (!block_value && !tile_w && !tile_h && !slots) return PXZ_OK;  // header query
 	if (!block_value || !tile_w || !tile_h || !slots) return fail(h, PXZ_ERR_INVALID_ARG, "null output pointer");
 	PXZ_HIP(h, hipSetDevice(h->device));
@@ -2386,6 +2429,242 @@ int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const 
 		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
 		            (unsigned long long)out_capacity);
 	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- decode side of varied batches (varied_index_kernel in pxz_stream.hip, pxz_varied_expand.hip) -------------------------
+namespace {
+
+int get_varied_expand_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t> &sides, const VariedExpandTables **out)
+{
+	auto key = std::make_pair(filter, sides);
+	auto it = h->varied_expand_tables.find(key);
+	if (it != h->varied_expand_tables.end()) { *out = &it->second; return PXZ_OK; }
+	if (h->varied_expand_tables.size() >= 16) {  // (bounded as the encode side's cache; queued launches may still read it)
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		free_tables(h->varied_expand_tables);
+	}
+	pxz::VariedExpandTableSet s;
+	if (!pxz::build_varied_expand_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+	VariedExpandTables vt;
+	vt.stride = s.stride;
+	vt.max_window = s.max_window;
+	const int rc = upload_tables(h, {{s.slot, &vt.d_slot}, {s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
+	if (rc != PXZ_OK) return rc;
+	*out = &(h->varied_expand_tables[key] = vt);
+	return PXZ_OK;
+}
+
+// where the per-image flags of a varied decode-side call go: the caller's array, or handle scratch when it passed none; zeroed
+int varied_flags(pxz_handle *h, uint32_t *d_image_flags, uint32_t n_images, uint32_t **out)
+{
+	if (!d_image_flags) {
+		const int rc = ensure(h, h->varied_flags, (size_t)n_images * 4u);
+		if (rc != PXZ_OK) return rc;
+		d_image_flags = (uint32_t *)h->varied_flags.ptr;
+	}
+	PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, (size_t)n_images * 4u, h->stream));
+	*out = d_image_flags;
+	return PXZ_OK;
+}
+
+// the decode side uses neither mode nor factor (and the reader no filter): the batch's parameters with those neutral
+pxz_params varied_decode_params(const pxz_params *params, bool with_filter)
+{
+	pxz_params p = *params;
+	p.mode = 0;
+	p.factor = 0.0f;
+	if (!with_filter) p.filter = 0;
+	return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_decode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, const uint8_t *d_files, const uint64_t *d_file_offsets,
+                                    float *d_block_value, uint32_t *d_tile_w, uint32_t *d_tile_h, uint8_t *d_slots,
+                                    uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_files || !d_file_offsets || !d_block_value || !d_tile_w || !d_tile_h || !d_slots)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	const pxz_params p = varied_decode_params(params, false);
+	std::vector<pxz::VariedImage> images;
+	uint32_t n_rows = 0;
+	int rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, 0, 0, &images, nullptr, &n_rows);
+	if (rc != PXZ_OK) return rc;
+	if ((uint64_t)p.block_w * p.block_h * channels > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::DecodeArgs a{};
+	a.files = d_files;
+	a.file_offsets = reinterpret_cast<const unsigned long long *>(d_file_offsets);
+	a.value = d_block_value;
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.bw = p.block_w;
+	a.bh = p.block_h;
+	a.n_frames = n_images;  // (the end of the files buffer; the geometry fields stay zero: every image has its own)
+	a.n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	a.tiles_per_frame = a.n_tiles;
+	a.channels = channels;
+	a.slot_bytes = p.block_w * p.block_h * channels;
+	// the reader's scratch and its zeroed-bins bookkeeping, exactly as pxz_decode_frames_device keeps them
+	const size_t dmeta_cap = h->dmeta.cap;
+	if ((rc = ensure(h, h->dmeta, (size_t)a.n_tiles * 16u + 4u * pxz::qoi_bins_dwords())) != PXZ_OK) return rc;
+	if (h->dmeta.cap != dmeta_cap) h->dbins_clean = nullptr;
+	a.rec_off = (unsigned long long *)h->dmeta.ptr;
+	a.rec_len = (uint32_t *)((uint8_t *)h->dmeta.ptr + (size_t)a.n_tiles * 8u);
+	a.perm = a.rec_len + a.n_tiles;
+	a.bins = a.perm + a.n_tiles;
+	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;
+	a.status = (uint32_t *)h->status.ptr;
+	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 4, h->stream));
+	uint32_t *flags = nullptr;
+	if ((rc = varied_flags(h, d_image_flags, n_images, &flags)) != PXZ_OK) return rc;
+	const pxz::VariedImage *d_images = nullptr;
+	if ((rc = varied_upload(h, images, &d_images)) != PXZ_OK) return rc;
+	const bool bins_clean = h->dbins_clean == a.bins;
+	h->dbins_clean = nullptr;
+	PXZ_HIP(h, pxz::launch_decode_varied(a, d_images, n_rows, flags, bins_clean, h->stream));
+	h->dbins_clean = a.bins;
+	return PXZ_OK;
+}
+
+int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    const pxz_params *params, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                    const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_base) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const pxz_params p = varied_decode_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedExpandTables *vt = nullptr;
+	if ((rc = get_varied_expand_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::VariedExpandArgs a{};
+	a.n_images = n_images;
+	a.n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.base = d_base;
+	a.bw = p.block_w;
+	a.bh = p.block_h;
+	a.slot_bytes = p.block_w * p.block_h * channels;
+	a.filter = p.filter;
+	a.slot = vt->d_slot;
+	a.dir = vt->d_dir;
+	a.stride = vt->stride;
+	a.starts = vt->d_starts;
+	a.sizes = vt->d_sizes;
+	a.coeffs = vt->d_coeffs;
+	a.wdw = 1u + (vt->max_window + 1u) / 2u;
+	a.tile_dw = pxz::varied_expand_tile_dw(a.bw, a.bh, a.wdw);
+	// a wave's image beyond LDS (with the images' first tiles beside it) lives in HBM, one per wave of the grid
+	if ((uint64_t)a.tile_dw * 4u + 8192u > 160u * 1024u) {
+		const uint64_t waves = 4ull * h->n_cus;
+		if ((rc = ensure(h, h->bigscratch, (size_t)waves * a.tile_dw * 4u)) != PXZ_OK) return rc;
+		a.big_scratch = (uint32_t *)h->bigscratch.ptr;
+		a.big_waves = (uint32_t)waves;
+	}
+	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;
+	a.status = (uint32_t *)h->status.ptr;
+	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 8, h->stream));
+	if (d_image_flags) PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, (size_t)n_images * 4u, h->stream));
+	a.image_flags = d_image_flags;
+	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
+	PXZ_HIP(h, pxz::launch_varied_expand(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
+                            uint32_t n_images, uint32_t channels, const pxz_params *params, uint8_t *out_base, uint32_t *image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const pxz_params p = varied_decode_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	// every header first: a file that is not the image its descriptor announces is refused before anything is written
+	uint64_t file_bytes = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, ch, fb;
+		const char *why;
+		if ((rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why)) != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
+		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the batch expects %ux%u in %ux%u of %u",
+			            i, w, hh, bw, bh, ch, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
+		file_bytes += lens[i];
+	}
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// device side: the files back to back behind their offsets; the images tightly packed (256-byte aligned starts)
+	std::vector<pxz_image_desc> dev(descs, descs + n_images);
+	uint64_t img_bytes = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		dev[i].offset_bytes = img_bytes;
+		dev[i].pitch_bytes = descs[i].width * channels;
+		img_bytes += ((uint64_t)dev[i].pitch_bytes * descs[i].height + 255u) & ~(uint64_t)255u;
+	}
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	const uint32_t n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
+	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
+	const uint64_t flags_at = meta + (uint64_t)n_tiles * slot;
+	// (one staging buffer for both directions: the images come back only after the files have gone)
+	std::vector<uint8_t> stage((size_t)std::max(offs_bytes + file_bytes, img_bytes));
+	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
+	offs[0] = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
+		offs[i + 1] = offs[i] + lens[i];
+	}
+	if ((rc = ensure(h, h->varied_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
+	uint8_t *d_files = (uint8_t *)h->varied_files.ptr, *d_out = (uint8_t *)h->varied_out.ptr, *d_img = (uint8_t *)h->varied_in.ptr;
+	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
+	PXZ_HIP(h, hipMemsetAsync(d_out + meta, 0, (size_t)n_tiles * slot, h->stream));
+	PXZ_HIP(h, hipMemsetAsync(d_img, 0, img_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
+	float *d_val = (float *)d_out;
+	uint32_t *d_w = (uint32_t *)(d_out + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d_out + (uint64_t)n_tiles * 8u);
+	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
+	if ((rc = pxz_decode_varied_frames_device(h, dev.data(), n_images, channels, &p, d_files + offs_bytes, (const uint64_t *)d_files, d_val,
+	                                          d_w, d_h, d_out + meta, d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, channels, &p, d_w, d_h, d_out + meta, d_img, d_flags + n_images)) != PXZ_OK)
+		return rc;
+	std::vector<uint32_t> flags(2u * (size_t)n_images);
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
+	PXZ_HIP(h, hipMemcpyAsync(stage.data(), d_img, img_bytes, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	uint32_t first_bad = n_images;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		const uint32_t fl = flags[i] | flags[n_images + i];
+		if (image_flags) image_flags[i] = fl;
+		if (fl && first_bad == n_images) first_bad = i;
+		const size_t row = (size_t)descs[i].width * channels;
+		for (uint32_t y = 0; y < descs[i].height; ++y)
+			std::memcpy(out_base + descs[i].offset_bytes + (size_t)y * descs[i].pitch_bytes, stage.data() + dev[i].offset_bytes + (size_t)y * row, row);
+	}
+	if (first_bad != n_images)
+		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
+		            flags[first_bad] | flags[n_images + first_bad]);
 	return PXZ_OK;
 }
 

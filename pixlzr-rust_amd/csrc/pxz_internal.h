@@ -491,6 +491,30 @@ struct VariedWriterArgs {
 	unsigned long long capacity;
 };
 
+// Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
+// back to their places in the images.  One up-scaling table per (full size, stored size): dir[slot[full] * stride + stored]
+// (pxz_tables.h: VariedExpandTableSet).
+struct VariedExpandArgs {
+	const VariedImage *images;
+	uint32_t n_images, n_tiles;
+	const uint32_t *tile_w, *tile_h;  // per tile: stored size
+	const uint8_t *slots;             // per tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
+	uint8_t *base;                    // image i at base + images[i].offset, images[i].pitch between rows
+	uint32_t bw, bh, slot_bytes, filter;
+	const uint32_t *slot;
+	const ExpandTab *dir;
+	uint32_t stride;
+	const uint16_t *starts, *sizes;
+	const int16_t *coeffs;
+	uint32_t wdw;                     // dwords of one staged window: 1 + ceil(widest window / 2)
+	uint32_t tile_dw;                 // dwords of one wave's image: two tile-sized planes + the windows of both axes
+	uint32_t t0_dw;                   // (set by the launch) dwords of the images' first tiles kept in LDS, 0: read from `images`
+	uint32_t *status;                 // bit 0: a tile's stored size is 0 or exceeds its full size
+	uint32_t *image_flags;            // per image 1 for the same, or null
+	uint32_t *big_scratch;            // tile images beyond LDS: one of tile_dw dwords per wave of the grid in HBM
+	uint32_t big_waves;               //   (0: the images are in LDS)
+};
+
 struct SynthArgs {
 	uint8_t *dst;
 	uint64_t frame_stride;

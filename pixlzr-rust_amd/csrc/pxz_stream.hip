@@ -940,13 +940,19 @@ __device__ __forceinline__ uint32_t be32(global_byte_cptr p)
 // length fields, then the lanes check and publish those records in parallel.
 constexpr uint32_t kIdxChunk = 8192;   // bytes of a row held in LDS at a time (per wave; 0.078 ms -- 4096: 0.096, 16384: 0.090)
 constexpr uint32_t kIdxHeader = 23;    // "block" + value + length + QOI header minus its magic, up to the channel byte
-__global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
+// What one wave needs to know about its tile row: the file, the row, the geometry the file's header must carry and where the
+// row's tiles are.  pixlzr_index_kernel fills it from the one geometry of its batch, varied_index_kernel from its image's
+// entry of the per-image table; index_row is the walk both run.  VARIED: the image's own flag is set wherever the status is.
+struct IdxRow {
+	uint32_t f, r;                  // file, tile row inside it
+	uint32_t width, height;         // what the header must say
+	uint32_t cols, rows, edge_w, edge_h;
+	uint32_t t_row;                 // the row's first tile in the outputs
+};
+
+template <bool VARIED>
+__device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo, uint32_t *image_flag, uint32_t *s_chunk, uint32_t lane)
 {
-	__shared__ __attribute__((aligned(16))) uint32_t s_chunk[4][kIdxChunk / 4u + 8u];
-	// (the wave's number and everything derived from it as scalars: the walk below then runs on scalar branches)
-	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-	const uint32_t i = blockIdx.x * 4u + wave;
-	if (i >= a.n_frames * a.rows) return;
 #ifdef PXZ_STAMPS
 	unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	unsigned long long st_last = stamp_now();
@@ -957,15 +963,18 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 		}
 	};
 #endif
-	const uint32_t f = i / a.rows, r = i - f * a.rows;
+	const uint32_t f = geo.f, r = geo.r;
 	const unsigned long long f0 = a.file_offsets[f], f1 = a.file_offsets[f + 1];
 	global_byte_cptr file = (global_byte_cptr)(a.files + f0);
 	const unsigned long long flen = f1 - f0;
-	const unsigned long long hdr = 26ull + 4ull * a.rows;
-	const uint32_t t_row = f * a.tiles_per_frame + r * a.cols;
+	const unsigned long long hdr = 26ull + 4ull * geo.rows;
+	const uint32_t t_row = geo.t_row;
 	auto bad_from = [&](uint32_t c0) {  // the row is unusable from column c0 on
-		if (lane == 0) atomicOr(a.status, 2u);
-		for (uint32_t c = c0 + lane; c < a.cols; c += 64u) {
+		if (lane == 0) {
+			atomicOr(a.status, 2u);
+			if constexpr (VARIED) *image_flag = 2u;
+		}
+		for (uint32_t c = c0 + lane; c < geo.cols; c += 64u) {
 			a.rec_len[t_row + c] = 0u;
 			a.tile_w[t_row + c] = 0u;
 			a.tile_h[t_row + c] = 0u;
@@ -982,7 +991,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 		else if (lane == 8u) want = 2u;
 		else if (lane == 9u) want = got;
 		else if (lane < 26u) {
-			const uint32_t k = lane - 10u, field = k < 4u ? a.width : (k < 8u ? a.height : (k < 12u ? a.bw : a.bh));
+			const uint32_t k = lane - 10u, field = k < 4u ? geo.width : (k < 8u ? geo.height : (k < 12u ? a.bw : a.bh));
 			want = (field >> (8u * (3u - (k & 3u)))) & 255u;
 		}
 		ok = ok && __builtin_amdgcn_ballot_w64(got != want) == 0ull;
@@ -993,7 +1002,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 	}
 	// the line-length table, lane-parallel: bytes before this row, and the length of all rows (mod.rs:141)
 	unsigned long long before = 0, total = 0;
-	for (uint32_t q = lane; q < a.rows; q += 64u) {
+	for (uint32_t q = lane; q < geo.rows; q += 64u) {
 		const uint32_t len = be32(file + 26 + 4 * q);
 		if (q < r) before += len;
 		total += len;
@@ -1010,7 +1019,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 	const unsigned long long row_end = p + (uint32_t)__builtin_amdgcn_readfirstlane(be32(file + 26 + 4 * r));
 	uint32_t c = 0;
 	PXZ_STAMP(0);  // file header, line table
-	while (c < a.cols) {
+	while (c < geo.cols) {
 		// ---- stage file bytes [p, p + kIdxChunk) of the row: whole aligned 16-byte granules of the buffer, every load of the
 		// chunk issued before the first one is written to LDS (round 2 staged dwords, one load -> store round per 256 bytes: a
 		// wave walks a row of ~170 KB alone, and the kernel was 0.33 ms of chained round trips)
@@ -1045,7 +1054,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 #pragma unroll
 		for (uint32_t k = 0; k < kRounds; ++k) {
 			const uint32_t d = lane + 64u * k;
-			if (d < granules) reinterpret_cast<uint4 *>(s_chunk[wave])[d] = gv[k];
+			if (d < granules) reinterpret_cast<uint4 *>(s_chunk)[d] = gv[k];
 		}
 		tile_sync<1>();
 		PXZ_STAMP(1);  // chunk staged
@@ -1060,7 +1069,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 		uint32_t pos = 0;
 		{
 			uint32_t o = 0;
-			const uint32_t cols_left = a.cols - c, n_max = cols_left < 64u ? cols_left : 64u;
+			const uint32_t cols_left = geo.cols - c, n_max = cols_left < 64u ? cols_left : 64u;
 			// a record can be walked from o if it has room (13 + 10 + 8 bytes: o + 31 <= rem) and its header lies in the chunk
 			// (o + 23 <= have; have <= rem): o <= lim, one test
 			const bool none = rem < 31u;
@@ -1074,7 +1083,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 				}
 				// the length field: the two aligned dwords around it, shifted (one LDS instruction instead of four byte reads)
 				const uint32_t x = skew + o + 9u;
-				const uint32_t *w2 = s_chunk[wave] + (x >> 2);
+				const uint32_t *w2 = s_chunk + (x >> 2);
 				const uint32_t qlen = __builtin_amdgcn_readfirstlane(__builtin_bswap32(__builtin_amdgcn_alignbyte(w2[1], w2[0], x & 3u)));
 				++n_rec;
 				const unsigned long long next = (unsigned long long)o + 13ull + qlen;
@@ -1091,13 +1100,13 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 		if (lane < n_rec) {
 			const uint32_t o = pos;
 			const uint32_t cc = c + lane;
-			const uint32_t fw = (cc == a.cols - 1) ? a.edge_w : a.bw, fh = (r == a.rows - 1) ? a.edge_h : a.bh;
+			const uint32_t fw = (cc == geo.cols - 1) ? geo.edge_w : a.bw, fh = (r == geo.rows - 1) ? geo.edge_h : a.bh;
 			good = o + 31u <= rem;
 			if (good) {
 				// the 22 header bytes as the seven aligned dwords around them, shifted into place ("block", value, length, and of
 				// the QOI header behind its magic: width, height, channels)
 				const uint32_t x = skew + o, sh = x & 3u;
-				const uint32_t *d = s_chunk[wave] + (x >> 2);
+				const uint32_t *d = s_chunk + (x >> 2);
 				uint32_t dw[7], wd[6];
 #pragma unroll
 				for (int k = 0; k < 7; ++k) dw[k] = d[k];
@@ -1141,10 +1150,62 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 		st_acc[5] += n_rec;  // records
 #endif
 	}
-	if (p != row_end && lane == 0) atomicOr(a.status, 2u);
+	if (p != row_end && lane == 0) {
+		atomicOr(a.status, 2u);
+		if constexpr (VARIED) *image_flag = 2u;
+	}
 #ifdef PXZ_STAMPS
 	st_flush();
 #endif
+}
+
+__global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
+{
+	__shared__ __attribute__((aligned(16))) uint32_t s_chunk[4][kIdxChunk / 4u + 8u];
+	// (the wave's number and everything derived from it as scalars: the walk then runs on scalar branches)
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	const uint32_t i = blockIdx.x * 4u + wave;
+	if (i >= a.n_frames * a.rows) return;
+	const uint32_t f = i / a.rows, r = i - f * a.rows;
+	const IdxRow g{f, r, a.width, a.height, a.cols, a.rows, a.edge_w, a.edge_h, f * a.tiles_per_frame + r * a.cols};
+	index_row<false>(a, g, nullptr, s_chunk[wave], lane);
+}
+
+// The same over a batch of differently sized images (pxz_decode_varied_frames_device): one wave per tile row of the batch;
+// the wave finds its image by a binary search over the per-image table's first rows and takes the geometry from there.
+// a.n_frames is the number of images (the end of the files buffer), a.width .. a.edge_h are unused.
+__global__ void __launch_bounds__(256) varied_index_kernel(const DecodeArgs a, const VariedImage *images, uint32_t n_rows, uint32_t *image_flags)
+{
+	__shared__ __attribute__((aligned(16))) uint32_t s_chunk[4][kIdxChunk / 4u + 8u];
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	const uint32_t i = blockIdx.x * 4u + wave;
+	if (i >= n_rows) return;
+	uint32_t lo = 0, hi = a.n_frames - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (images[mid].row0 <= i) lo = mid;
+		else hi = mid - 1u;
+	}
+	const VariedImage im = images[lo];
+	const uint32_t r = i - im.row0;
+	const IdxRow g{lo, r, im.width, im.height, im.cols, im.rows, im.edge_w, im.edge_h, im.tile0 + r * im.cols};
+	index_row<true>(a, g, image_flags + lo, s_chunk[wave], lane);
+}
+
+// qoi_decode_kernel zeroes the size of a tile whose op stream runs dry (and of every tile the index left unusable): such a
+// tile's image gets its flag here, behind that kernel, which stays as it is.  One thread per tile.
+__global__ void __launch_bounds__(256) varied_decode_flags_kernel(const uint32_t *tile_w, const VariedImage *images, uint32_t n_images,
+                                                                  uint32_t n_tiles, uint32_t *image_flags)
+{
+	const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+	if (t >= n_tiles || tile_w[t] != 0u) return;
+	uint32_t lo = 0, hi = n_images - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (images[mid].tile0 <= t) lo = mid;
+		else hi = mid - 1u;
+	}
+	image_flags[lo] = 2u;
 }
 
 // What an op's first byte says (qoi_decode_kernel's look-up table, one per channel count; built at compile time):
@@ -1375,12 +1436,16 @@ __global__ void __launch_bounds__(64 * kQoiWaves) qoi_decode_kernel(const Decode
 	}
 }
 
-hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream)
+// images == null: the batch has one geometry (a.width ..); else the per-image table of a varied batch (a.n_frames images, n_rows
+// tile rows in all; image_flags: zeroed dwords that receive 2 for every image with a malformed file or record).
+static hipError_t launch_decode_impl(const DecodeArgs &a, bool bins_clean, hipStream_t stream, const VariedImage *images, uint32_t n_rows,
+                                     uint32_t *image_flags)
 {
 	// (the binning counters are left zeroed by the previous launch on the same buffer: bins_clean, as in launch_qoi)
 	hipError_t e;
 	if (!bins_clean && (e = hipMemsetAsync(a.bins, 0, kBinDwords * sizeof(uint32_t), stream)) != hipSuccess) return e;
-	hipLaunchKernelGGL(pixlzr_index_kernel, dim3((a.n_frames * a.rows + 3u) / 4u), dim3(256), 0, stream, a);
+	if (images) hipLaunchKernelGGL(varied_index_kernel, dim3((n_rows + 3u) / 4u), dim3(256), 0, stream, a, images, n_rows, image_flags);
+	else hipLaunchKernelGGL(pixlzr_index_kernel, dim3((a.n_frames * a.rows + 3u) / 4u), dim3(256), 0, stream, a);
 	const uint32_t tb = (a.n_tiles + kBinChunk - 1u) / kBinChunk;
 	QoiArgs q{};  // the encoder's binning by pixel count, on the sizes the index kernel has just read
 	q.w = a.tile_w;
@@ -1393,7 +1458,21 @@ hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t strea
 	const uint32_t qb = (a.n_tiles + 64u * kQoiWaves - 1u) / (64u * kQoiWaves);
 	if (a.channels == 4) hipLaunchKernelGGL(qoi_decode_kernel<4>, dim3(qb), dim3(64u * kQoiWaves), 0, stream, a);
 	else hipLaunchKernelGGL(qoi_decode_kernel<3>, dim3(qb), dim3(64u * kQoiWaves), 0, stream, a);
+	if (images)
+		hipLaunchKernelGGL(varied_decode_flags_kernel, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, images, a.n_frames,
+		                   a.n_tiles, image_flags);
 	return hipGetLastError();
+}
+
+hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream)
+{
+	return launch_decode_impl(a, bins_clean, stream, nullptr, 0u, nullptr);
+}
+
+hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, uint32_t n_rows, uint32_t *image_flags, bool bins_clean,
+                                hipStream_t stream)
+{
+	return launch_decode_impl(a, bins_clean, stream, images, n_rows, image_flags);
 }
 
 }  // namespace pxz

@@ -406,8 +406,26 @@ bool build_shrink_tables(uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edg
 	return true;
 }
 
-// For each axis and size class (full / ragged edge) one up-scaling table per source size 1 .. full-1 (PixlzrBlock::resize
-// with the upscale flag set, block.rs:301-304).
+// One up-scaling table, `in` stored samples -> `outsz` (PixlzrBlock::resize with the upscale flag set, block.rs:301-304),
+// appended to the arrays of an expand table set: the per-axis code of build_expand_tables and build_varied_expand_tables.
+static bool append_expand_axis(uint32_t in, uint32_t outsz, uint32_t filter, ExpandTab *t, std::vector<uint16_t> *starts,
+                               std::vector<uint16_t> *sizes, std::vector<int16_t> *coeffs)
+{
+	AxisWindows win;
+	if (!build_axis(in, outsz, filter, &win, true)) return false;
+	t->start_off = (uint32_t)starts->size();
+	t->coeff_off = (uint32_t)coeffs->size();
+	t->window = (uint16_t)win.window;
+	t->precision = (uint16_t)win.precision;
+	for (uint32_t o = 0; o < outsz; ++o) {
+		starts->push_back((uint16_t)win.starts[o]);
+		sizes->push_back((uint16_t)win.sizes[o]);
+	}
+	coeffs->insert(coeffs->end(), win.coeffs.begin(), win.coeffs.end());
+	return true;
+}
+
+// For each axis and size class (full / ragged edge) one up-scaling table per source size 1 .. full-1.
 bool build_expand_tables(uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter, ExpandTableSet *out)
 {
 	ExpandTableSet &s = *out;
@@ -423,20 +441,8 @@ bool build_expand_tables(uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edg
 				for (uint32_t in = 0; in < stride; ++in) s.dir[(axis * 2 + 1) * stride + in] = s.dir[(axis * 2 + 0) * stride + in];
 				continue;
 			}
-			for (uint32_t in = 1; in < outsz; ++in) {
-				AxisWindows win;
-				if (!build_axis(in, outsz, filter, &win, true)) return false;
-				ExpandTab &t = s.dir[(axis * 2 + cls) * stride + in];
-				t.start_off = (uint32_t)s.starts.size();
-				t.coeff_off = (uint32_t)s.coeffs.size();
-				t.window = (uint16_t)win.window;
-				t.precision = (uint16_t)win.precision;
-				for (uint32_t o = 0; o < outsz; ++o) {
-					s.starts.push_back((uint16_t)win.starts[o]);
-					s.sizes.push_back((uint16_t)win.sizes[o]);
-				}
-				s.coeffs.insert(s.coeffs.end(), win.coeffs.begin(), win.coeffs.end());
-			}
+			for (uint32_t in = 1; in < outsz; ++in)
+				if (!append_expand_axis(in, outsz, filter, &s.dir[(axis * 2 + cls) * stride + in], &s.starts, &s.sizes, &s.coeffs)) return false;
 		}
 	}
 	if (s.starts.empty()) {
@@ -586,6 +592,34 @@ bool build_varied_tables(const std::vector<uint32_t> &sizes, uint32_t filter, Va
 	}
 	if (s.dir.empty()) s.dir.push_back(TreeAxisEntry{});
 	if (s.starts.empty()) { s.starts.push_back(0); s.sizes.push_back(0); }
+	if (s.coeffs.empty()) s.coeffs.push_back(0);
+	return true;
+}
+
+bool build_varied_expand_tables(const std::vector<uint32_t> &sizes, uint32_t filter, VariedExpandTableSet *out)
+{
+	VariedExpandTableSet &s = *out;
+	s = VariedExpandTableSet{};
+	const std::set<uint32_t> fulls(sizes.begin(), sizes.end());
+	const uint32_t top = fulls.empty() ? 0u : *fulls.rbegin();
+	s.stride = top + 1u;
+	s.slot.assign(top + 1u, 0xffffffffu);
+	uint32_t n = 0;
+	for (uint32_t full : fulls)
+		if (full != 0u) s.slot[full] = n++;
+	s.dir.assign((size_t)(n ? n : 1u) * s.stride, ExpandTab{0, 0, 0, 0});
+	for (uint32_t full : fulls) {
+		if (full == 0u) continue;
+		for (uint32_t in = 1; in < full; ++in) {
+			ExpandTab &t = s.dir[(size_t)s.slot[full] * s.stride + in];
+			if (!append_expand_axis(in, full, filter, &t, &s.starts, &s.sizes, &s.coeffs)) return false;
+			if (t.window > s.max_window) s.max_window = t.window;
+		}
+	}
+	if (s.starts.empty()) {
+		s.starts.push_back(0);
+		s.sizes.push_back(0);
+	}
 	if (s.coeffs.empty()) s.coeffs.push_back(0);
 	return true;
 }

@@ -69,4 +69,18 @@ struct VariedTableSet {
 };
 bool build_varied_tables(const std::vector<uint32_t> &sizes, uint32_t filter, VariedTableSet *out);
 
+// decode side of varied batches (varied_expand_kernel): one up-scaling table per (full size, stored size) pair, for every full
+// size in `sizes` (the block sides and each distinct edge width and height of the batch) and stored sizes 1 .. full - 1:
+// dir[slot[full] * stride + stored].  Each table is the one build_expand_tables makes for that pair (the same per-axis code);
+// one table serves both axes.  Entries of stored == full (a clone) and of sizes that are not in the batch are zero.
+struct VariedExpandTableSet {
+	std::vector<uint32_t> slot;  // per full size 0 .. max(sizes): its row in dir (0xffffffff: not a size of the batch)
+	uint32_t stride = 0;         // max(sizes) + 1
+	std::vector<ExpandTab> dir;
+	std::vector<uint16_t> starts, sizes;
+	std::vector<int16_t> coeffs;
+	uint32_t max_window = 0;     // widest window of the set (sizes the kernel's staged windows)
+};
+bool build_varied_expand_tables(const std::vector<uint32_t> &sizes, uint32_t filter, VariedExpandTableSet *out);
+
 }  // namespace pxz

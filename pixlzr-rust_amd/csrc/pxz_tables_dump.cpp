@@ -1,7 +1,8 @@
 // pxz_tables_dump — runs the table builders of libpixlzr_hip.so (pxz_tables.h) over a fixed sweep of geometries and filters
 // and prints one line per table set: the geometry, then element count and FNV-1a 64 hash of every array ("-": absent).
 // tests/test_tables_host.py pins a digest of these lines per (family, filter).  With the argument `varied` it prints the
-// directories of varied batches instead (tests/test_varied_host.py).
+// directories of varied batches instead (tests/test_varied_host.py), with `varied_expand` those of their decode side
+// (tests/test_varied_decode_host.py).
 #include <array>
 #include <cstring>
 #include <cstdio>
@@ -77,9 +78,51 @@ int dump_varied()
 	return 0;
 }
 
+// One up-scaling table as a line: what a kernel reads of it (window, precision, the outputs' starts and sizes, the weights)
+namespace {
+void expand_tab_line(const char *who, uint32_t f, uint32_t full, uint32_t stored, const pxz::ExpandTab &t, const std::vector<uint16_t> &starts,
+                     const std::vector<uint16_t> &sizes, const std::vector<int16_t> &coeffs)
+{
+	const size_t nc = f == 0 ? 0 : (size_t)full * t.window;
+	printf("%s filter=%u full=%u stored=%u window=%u precision=%u starts=%016llx sizes=%016llx coeffs=%016llx\n", who, f, full, stored, t.window,
+	       t.precision, (unsigned long long)fnv(starts.data() + t.start_off, full * sizeof(uint16_t)),
+	       (unsigned long long)fnv(sizes.data() + t.start_off, full * sizeof(uint16_t)),
+	       (unsigned long long)fnv(coeffs.data() + t.coeff_off, nc * sizeof(int16_t)));
+}
+}  // namespace
+
+// The (full size, stored size) directories of the varied expand, table by table ("vexpand" lines), and beside each the table
+// build_expand_tables makes for a tile geometry whose full size is that side ("expand1" lines: axis 0, full class) -- the one
+// expand_kernel reads.  tests/test_varied_decode_host.py compares the two and pins a digest of the first.
+int dump_varied_expand()
+{
+	const std::vector<uint32_t> sides = {64, 32, 20, 17, 5, 1};
+	for (uint32_t f = 0; f < 5; ++f) {
+		pxz::VariedExpandTableSet v;
+		if (!pxz::build_varied_expand_tables(sides, f, &v)) return 1;
+		printf("vexpand-set filter=%u stride=%u max_window=%u", f, v.stride, v.max_window);
+		arr("slot", v.slot);
+		arr("dir", v.dir);
+		arr("starts", v.starts);
+		arr("sizes", v.sizes);
+		arr("coeffs", v.coeffs);
+		printf("\n");
+		for (uint32_t full : sides) {
+			pxz::ExpandTableSet s;
+			if (!pxz::build_expand_tables(full, full, full, full, f, &s)) return 1;
+			for (uint32_t stored = 1; stored < full; ++stored) {
+				expand_tab_line("vexpand", f, full, stored, v.dir[(size_t)v.slot[full] * v.stride + stored], v.starts, v.sizes, v.coeffs);
+				expand_tab_line("expand1", f, full, stored, s.dir[stored], s.starts, s.sizes, s.coeffs);
+			}
+		}
+	}
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	if (argc > 1 && std::strcmp(argv[1], "varied") == 0) return dump_varied();
+	if (argc > 1 && std::strcmp(argv[1], "varied_expand") == 0) return dump_varied_expand();
 	for (uint32_t f = 0; f < 5; ++f)
 		for (const auto &g : grids(false)) {
 			pxz::ShrinkTableSet s;
