@@ -1,6 +1,11 @@
 // pxz_api.cpp — host runtime behind the C ABI of include/pixlzr_hip.h:
 // handle, per-configuration table cache, HBM staging for the host-buffer entry
 // point, kernel launches on the caller's stream, HIP-event timing.
+//
+// Who owns what: pxz_handle.h has the owners -- DeviceBuffer (a grow-only device allocation: a scratch buffer, or the one
+// allocation behind a table set) and PinnedStaging (a pinned block and the event behind the last copy out of it); each
+// frees what it holds.  HandleScratch below is everything pxz_trim gives back, pxz_handle adds what survives a trim; the
+// table caches go through cached_tables.  The kernel units' launchers are declared in pxz_launch.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <condition_variable>
@@ -19,46 +24,21 @@
 #include <vector>
 
 #include "../../include/pixlzr_hip.h"
+#include "pxz_handle.h"
 #include "pxz_internal.h"
+#include "pxz_launch.h"
 #include "pxz_tables.h"
-
-namespace pxz {
-hipError_t launch_shrink(const ShrinkArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
-hipError_t launch_synth(const SynthArgs &s, hipStream_t stream);
-hipError_t launch_tree_decide(const TreeArgs &a, hipStream_t stream);
-hipError_t launch_tree_rects(const TreeRectArgs &a, hipStream_t stream);
-hipError_t launch_oklab_pixels(const uint32_t *px, uint32_t n, float *out, uint32_t n_cus, hipStream_t stream);
-hipError_t launch_finish(const FinishArgs &f, hipStream_t stream);
-bool fast32_applicable(const ShrinkArgs &a, uint32_t channels);
-bool fast64_applicable(const ShrinkArgs &a, uint32_t channels);
-bool fast16_applicable(const ShrinkArgs &a, uint32_t channels);
-hipError_t launch_expand(const ExpandArgs &a, uint32_t n_cus, hipStream_t stream);
-hipError_t launch_ladder(const LadderArgs &a, uint32_t channels, uint32_t nw, uint32_t n_cus, hipStream_t stream);
-hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream);
-hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, uint32_t n_rows, uint32_t *image_flags, bool bins_clean,
-                                hipStream_t stream);
-hipError_t launch_varied_expand(const VariedExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
-uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw);
-hipError_t launch_widen(const WidenArgs &a, hipStream_t stream);
-hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);
-hipError_t launch_pack(const PackArgs &a, hipStream_t stream);
-hipError_t launch_oklab(const ShrinkArgs &a, uint32_t n_cus, hipStream_t stream, uint32_t channels = 4);
-hipError_t launch_qoi(const QoiArgs &a, bool bins_clean, uint32_t n_cus, hipStream_t stream);
-hipError_t launch_qoi_varied(const QoiArgs &a, const VariedWriterArgs &varied, bool bins_clean, uint32_t n_cus, hipStream_t stream);
-hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
-size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
-uint32_t qoi_bins_dwords();
-uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
-}  // namespace pxz
 
 namespace {
 
 using pxz::AxisTab;
+using pxz::DeviceBuffer;
 using pxz::kMaxLevel;
+using pxz::PinnedStaging;
 
 // device copy of the down-scaling tables for one (tile geometry, filter): pxz::ShrinkTableSet
 struct TableSet {
-	void *mem = nullptr;        // the one allocation behind every device pointer below
+	DeviceBuffer mem;  // the one allocation behind every device pointer below
 	std::vector<AxisTab> tabs;  // host copy, passed by value in the kernel arguments
 	uint16_t *d_bounds = nullptr;
 	uint32_t *d_coeffs = nullptr;
@@ -71,7 +51,7 @@ struct TableSet {
 
 // decode side: up-scaling tables of every source size to the full tile size (expand_kernel): pxz::ExpandTableSet
 struct ExpandTables {
-	void *mem = nullptr;
+	DeviceBuffer mem;  // the one allocation behind every device pointer below
 	pxz::ExpandTab *d_dir = nullptr;
 	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
 	int16_t *d_coeffs = nullptr;
@@ -81,15 +61,10 @@ struct ExpandTables {
 	uint32_t *d_xmf64 = nullptr;  // 64x64 tiles, convolutions: the same for expand64_kernel (kXmf64Dw)
 };
 
-struct DeviceBuffer {
-	void *ptr = nullptr;
-	size_t cap = 0;
-};
-
 // tree::process on rectangle lists: every axis table (down with the one filter, back up with the other) of every tile
 // size the recursion can reach from one (frame, block, minimum) geometry: pxz::TreeTableSet
 struct TreeTables {
-	void *mem = nullptr;
+	DeviceBuffer mem;  // the one allocation behind every device pointer below
 	pxz::TreeAxisEntry *d_dir = nullptr;
 	int32_t *d_starts = nullptr, *d_sizes = nullptr;
 	int16_t *d_coeffs = nullptr;
@@ -98,7 +73,7 @@ struct TreeTables {
 
 // batches of differently sized images: the axis tables of every (source size, level) pair of one batch: pxz::VariedTableSet
 struct VariedTables {
-	void *mem = nullptr;
+	DeviceBuffer mem;  // the one allocation behind every device pointer below
 	pxz::TreeAxisEntry *d_dir = nullptr;
 	int32_t *d_starts = nullptr, *d_sizes = nullptr;
 	int16_t *d_coeffs = nullptr;
@@ -106,7 +81,7 @@ struct VariedTables {
 
 // decode side of varied batches: the up-scaling table of every (full size, stored size) pair of one batch: pxz::VariedExpandTableSet
 struct VariedExpandTables {
-	void *mem = nullptr;
+	DeviceBuffer mem;  // the one allocation behind every device pointer below
 	uint32_t *d_slot = nullptr;
 	pxz::ExpandTab *d_dir = nullptr;
 	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
@@ -114,11 +89,37 @@ struct VariedExpandTables {
 	uint32_t stride = 0, max_window = 0;
 };
 
+// The bounded caches hold at most this many table sets: caches, not logs -- varying geometries (tools/fuzz_tree.py, a
+// folder of many sizes) must not grow them without bound.
+constexpr size_t kTableCacheBound = 16;
+
+// Everything of a handle that pxz_trim gives back: assigning a fresh HandleScratch releases all of it, so a member
+// added here can be forgotten neither by pxz_trim nor by pxz_destroy.
+struct HandleScratch {
+	DeviceBuffer in, val, ow, oh, out, sums, chunks, work, qscratch, qmeta, status, dmeta, okscratch, rgba, slots4, pk, pkoff, tree, xlist, bigscratch;
+	uint64_t packed_len = 0;   // bytes of the stream pxz_shrink_image_packed left in `pk` (0: none)
+	static constexpr int kRing = 3;  // buffer sets of the pipelined host boundary (pxz_shrink_images*)
+	DeviceBuffer ring_in[kRing], ring_val[kRing], ring_ow[kRing], ring_oh[kRing], ring_out[kRing], ring_pk[kRing], ring_pkoff[kRing];
+	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, TreeTables> tree_tables;
+	DeviceBuffer tree_rects[2], tree_count;
+	DeviceBuffer ladder;              // factor ladder: the raw detector value of every tile, then the rungs' factors
+	PinnedStaging ladder_factors;     //   pinned staging of the factors (PXZ_LADDER_MAX_RUNGS floats)
+	DeviceBuffer varied, varied_in, varied_out, varied_files;  // varied batches: the per-image table, the host form's images,
+	                                  //   tiles and files
+	PinnedStaging varied_images;      // pinned staging of the per-image table
+	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedTables> varied_tables;  // (filter, tile sides) -> tables
+	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedExpandTables> varied_expand_tables;  // the same for the decode side
+	DeviceBuffer varied_flags;        // per-image flags of a varied decode-side call whose caller passed none
+	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
+	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
+	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
+};
+
 }  // namespace
 
 constexpr uint32_t kMaxImageSide = 1u << 24;  // see pxz_grid
 
-struct pxz_handle {
+struct pxz_handle : HandleScratch {
 	int device = 0;
 	uint32_t n_cus = 256;
 	hipStream_t stream = nullptr;
@@ -128,31 +129,11 @@ struct pxz_handle {
 	// level breakpoints per (mode, factor bits, bw, bh, edge_w, edge_h)
 	struct Breaks { uint32_t b[4][pxz::kMaxLevel]; uint32_t asc[4]; };
 	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, Breaks> breaks;
-	DeviceBuffer in, val, ow, oh, out, sums, chunks, work, qscratch, qmeta, status, dmeta, okscratch, rgba, slots4, pk, pkoff, tree, xlist, bigscratch;
-	uint64_t packed_len = 0;   // bytes of the stream pxz_shrink_image_packed left in `pk` (0: none)
-	static constexpr int kRing = 3;  // buffer sets of the pipelined host boundary (pxz_shrink_images*)
-	DeviceBuffer ring_in[kRing], ring_val[kRing], ring_ow[kRing], ring_oh[kRing], ring_out[kRing], ring_pk[kRing], ring_pkoff[kRing];
 	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, ExpandTables> expand_tables;
-	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, TreeTables> tree_tables;
-	DeviceBuffer tree_rects[2], tree_count;
-	DeviceBuffer ladder;              // factor ladder: the raw detector value of every tile, then the rungs' factors
-	float *ladder_host = nullptr;     //   pinned staging of the factors (PXZ_LADDER_MAX_RUNGS floats) ...
-	hipEvent_t ladder_copied = nullptr;  //   ... reused once the copy out of it recorded here has run
-	DeviceBuffer varied, varied_in, varied_out, varied_files;  // varied batches: the per-image table, the host form's images,
-	                                  //   tiles and files
-	pxz::VariedImage *varied_host = nullptr;  // pinned staging of the per-image table (varied_host_cap entries) ...
-	size_t varied_host_cap = 0;
-	hipEvent_t varied_copied = nullptr;       //   ... reused once the copy out of it recorded here has run
-	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedTables> varied_tables;  // (filter, tile sides) -> tables
-	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedExpandTables> varied_expand_tables;  // the same for the decode side
-	DeviceBuffer varied_flags;        // per-image flags of a varied decode-side call whose caller passed none
 	bool quiet_stats = false;         // the launch being set up writes no kernel-selection statistics (the ladder's detector)
 	uint32_t *host_stats = nullptr;  // pinned, device-visible: [0] = tiles with transparency the last finished 32x32 launch saw
 	uint32_t *dev_stats = nullptr;   //   (its device-side address); read without synchronisation, steers only the kernel choice
 	uint32_t last_alpha_kernel = 0, last_alpha_first = 0;  // what the last launch set up through this handle chose (pxz_handle_state)
-	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
-	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
-	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
 	uint32_t work_slot = 0;    // the counter the next 32x32 launch uses
 	bool timing = false;
 	uint32_t timing_stride = 1, timing_count = 0;  // every stride-th step is bracketed by events
@@ -176,14 +157,6 @@ int fail(pxz_handle *h, int code, const char *fmt, ...)
 	return code;
 }
 
-// a cache of table sets (h->tables, h->expand_tables, h->tree_tables): one allocation per set
-template <class Cache>
-void free_tables(Cache &cache)
-{
-	for (auto &kv : cache) (void)hipFree(kv.second.mem);
-	cache.clear();
-}
-
 #define PXZ_HIP(h, call)                                                                      \
 	do {                                                                                      \
 		hipError_t e_ = (call);                                                               \
@@ -192,12 +165,28 @@ void free_tables(Cache &cache)
 
 int ensure(pxz_handle *h, DeviceBuffer &b, size_t bytes)
 {
-	if (b.cap >= bytes) return PXZ_OK;
-	if (b.ptr) (void)hipFree(b.ptr);
-	b.ptr = nullptr;
-	b.cap = 0;
-	if (hipMalloc(&b.ptr, bytes) != hipSuccess) return fail(h, PXZ_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
-	b.cap = bytes;
+	return b.reserve(bytes) ? PXZ_OK : fail(h, PXZ_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
+}
+
+// ensure() for the buffer that holds a stream kernel's binning counters: a new allocation forgets that they were left
+// zeroed (nothing in it is zero)
+int ensure_bins(pxz_handle *h, DeviceBuffer &b, size_t bytes, const uint32_t *&bins_clean)
+{
+	const size_t cap = b.cap;
+	const int rc = ensure(h, b, bytes);
+	if (b.cap != cap) bins_clean = nullptr;
+	return rc;
+}
+
+// A launch of a stream kernel leaves its binning counters zeroed for the next one on the same buffer: launch(true) when
+// they are at `bins` already.  After a launch that failed nothing is known about them.
+template <class Launch>
+int launch_on_bins(pxz_handle *h, const uint32_t *&bins_clean, const uint32_t *bins, Launch launch)
+{
+	const bool clean = bins_clean == bins;
+	bins_clean = nullptr;
+	PXZ_HIP(h, launch(clean));
+	bins_clean = bins;
 	return PXZ_OK;
 }
 
@@ -212,6 +201,89 @@ pxz::FastDiv make_fastdiv(uint32_t d)
 	return pxz::FastDiv{(uint32_t)m, l < 1 ? l : 1u, l < 1 ? 0u : l - 1};
 }
 
+// The tile grid of a batch of equally sized frames.
+struct Grid {
+	uint32_t cols = 0, rows = 0;
+	uint32_t edge_w = 0, edge_h = 0;  // the last column's width, the last row's height
+	uint32_t tiles_per_frame = 0;
+	uint64_t tiles = 0;               // of all frames
+};
+constexpr uint64_t kAnyTiles = ~0ull;  // make_grid without a limit
+
+// Fills *g with pxz_grid's grid (the caller has checked the sides); PXZ_ERR_UNSUPPORTED when the batch has more than
+// `limit` tiles.
+int make_grid(pxz_handle *h, uint32_t width, uint32_t height, uint32_t bw, uint32_t bh, uint32_t n_frames, uint64_t limit, Grid *g)
+{
+	pxz_grid(width, height, bw, bh, &g->cols, &g->rows);
+	g->edge_w = width - (g->cols - 1) * bw;
+	g->edge_h = height - (g->rows - 1) * bh;
+	g->tiles_per_frame = g->cols * g->rows;
+	g->tiles = (uint64_t)g->cols * g->rows * n_frames;
+	return g->tiles > limit ? fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles") : PXZ_OK;
+}
+
+// a checked grid -> the geometry fields every kernel's arguments name alike
+template <class Args>
+void put_grid(const Grid &g, Args *a)
+{
+	a->cols = g.cols;
+	a->rows = g.rows;
+	a->tiles_per_frame = g.tiles_per_frame;
+	a->n_tiles = (uint32_t)g.tiles;
+	a->edge_w = g.edge_w;
+	a->edge_h = g.edge_h;
+}
+
+// val, ow and oh for `tiles` tiles, and out for their slots of slot_bytes each (0: no pixels)
+int ensure_tile_outputs(pxz_handle *h, size_t tiles, size_t slot_bytes)
+{
+	int rc = ensure(h, h->val, tiles * 4);
+	if (rc == PXZ_OK) rc = ensure(h, h->ow, tiles * 4);
+	if (rc == PXZ_OK) rc = ensure(h, h->oh, tiles * 4);
+	if (rc == PXZ_OK && slot_bytes != 0) rc = ensure(h, h->out, tiles * slot_bytes);
+	return rc;
+}
+
+// ... and their way back to the host, queued on the handle's stream (the pixels only when the caller wants them)
+int download_tile_outputs(pxz_handle *h, size_t tiles, size_t slot_bytes, float *block_value, uint32_t *tile_w, uint32_t *tile_h,
+                          uint8_t *pixels)
+{
+	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(tile_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(tile_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
+	if (pixels) PXZ_HIP(h, hipMemcpyAsync(pixels, h->out.ptr, tiles * slot_bytes, hipMemcpyDeviceToHost, h->stream));
+	return PXZ_OK;
+}
+
+// the decode side uses neither mode nor factor (and the reader no filter): the caller's parameters with those neutral
+pxz_params decode_side_params(const pxz_params *params, bool with_filter)
+{
+	pxz_params p = *params;
+	p.mode = 0;
+	p.factor = 0.0f;
+	if (!with_filter) p.filter = 0;
+	return p;
+}
+
+// these frames as tightly packed RGBA with rows of a 16-byte multiple (what the fast kernels and the block-cooperative
+// Oklab detector want)
+pxz_frames rgba16_frames(const pxz_frames *frames)
+{
+	pxz_frames f = *frames;
+	f.channels = 4;
+	f.pitch_bytes = (frames->width * 4u + 15u) & ~15u;
+	f.frame_stride_bytes = (uint64_t)f.pitch_bytes * frames->height;
+	return f;
+}
+
+// The pitch of the device copy of a host image: rows of a 16-byte multiple when the caller's do not have one (tight rows
+// of an RGBA image whose width is not a multiple of 4); the copy engine does the re-pitching for free.
+uint32_t device_pitch_of(uint32_t width, uint32_t channels, uint32_t pitch_bytes)
+{
+	if (channels == 4 && (pitch_bytes & 15u) != 0) return (uint32_t)(((size_t)width * channels + 15u) & ~(size_t)15u);
+	return pitch_bytes;
+}
+
 // One array of a table set on its way to the device: its device address goes to *dst (null when the array is empty).
 struct TablePart {
 	template <class T>
@@ -221,59 +293,70 @@ struct TablePart {
 	void **dst;
 };
 
-// Uploads one table set into a single allocation *mem, every array at a 256-byte aligned offset.  On failure nothing is
-// left allocated.
-int upload_tables(pxz_handle *h, std::initializer_list<TablePart> parts, void **mem)
+// Uploads one table set into the single allocation *mem, every array at a 256-byte aligned offset.  On failure nothing
+// is left allocated.
+int upload_tables(pxz_handle *h, std::initializer_list<TablePart> parts, DeviceBuffer *mem)
 {
 	size_t total = 0;
 	for (const TablePart &p : parts) total += (p.bytes + 255) & ~(size_t)255;
-	*mem = nullptr;
-	hipError_t e = hipMalloc(mem, total);
-	uint8_t *at = static_cast<uint8_t *>(*mem);
+	mem->release();
+	hipError_t e = mem->reserve(total) ? hipSuccess : hipErrorOutOfMemory;
+	uint8_t *at = static_cast<uint8_t *>(mem->ptr);
 	for (auto p = parts.begin(); e == hipSuccess && p != parts.end(); at += (p->bytes + 255) & ~(size_t)255, ++p) {
 		*p->dst = p->bytes ? at : nullptr;
 		if (p->bytes) e = hipMemcpy(at, p->src, p->bytes, hipMemcpyHostToDevice);
 	}
 	if (e == hipSuccess) return PXZ_OK;
-	(void)hipFree(*mem);
-	*mem = nullptr;
+	mem->release();
 	return fail(h, PXZ_ERR_HIP, "uploading %zu bytes of tables: %s", total, hipGetErrorString(e));
+}
+
+// One cache of table sets: the set under `key`, built and uploaded by build(set) when it is not there yet.  A cache
+// with a bound is emptied when it is full -- after the stream has drained: a queued launch may still read a table.
+// The sets are map nodes: a pointer handed out stays valid across later insertions.
+template <class Cache, class Build>
+int cached_tables(pxz_handle *h, Cache &cache, const typename Cache::key_type &key, size_t bound, Build build,
+                  const typename Cache::mapped_type **out)
+{
+	auto it = cache.find(key);
+	if (it == cache.end()) {
+		if (bound != 0 && cache.size() >= bound) {
+			PXZ_HIP(h, hipStreamSynchronize(h->stream));
+			cache.clear();
+		}
+		typename Cache::mapped_type set;
+		const int rc = build(set);
+		if (rc != PXZ_OK) return rc;
+		it = cache.emplace(key, std::move(set)).first;
+	}
+	*out = &it->second;
+	return PXZ_OK;
 }
 
 int get_tables(pxz_handle *h, uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter,
                const TableSet **out)
 {
-	auto key = std::make_tuple(bw, bh, edge_w, edge_h, filter);
-	auto it = h->tables.find(key);
-	if (it != h->tables.end()) { *out = &it->second; return PXZ_OK; }
-	pxz::ShrinkTableSet s;
-	if (!pxz::build_shrink_tables(bw, bh, edge_w, edge_h, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-	TableSet ts;
-	ts.tabs = s.tabs;
-	ts.rows_dw = (uint32_t)s.rows.size();
-	ts.opaque_stays = s.opaque_stays;
-	const int rc = upload_tables(h, {{s.bounds, &ts.d_bounds}, {s.coeffs, &ts.d_coeffs}, {s.ksums, &ts.d_ksums}, {s.rows, &ts.d_rows},
-	                                 {s.mf64, &ts.d_mf64}}, &ts.mem);
-	if (rc != PXZ_OK) return rc;
-	*out = &(h->tables[key] = ts);
-	return PXZ_OK;
+	return cached_tables(h, h->tables, std::make_tuple(bw, bh, edge_w, edge_h, filter), 0, [&](TableSet &ts) {
+		pxz::ShrinkTableSet s;
+		if (!pxz::build_shrink_tables(bw, bh, edge_w, edge_h, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+		ts.tabs = s.tabs;
+		ts.rows_dw = (uint32_t)s.rows.size();
+		ts.opaque_stays = s.opaque_stays;
+		return upload_tables(h, {{s.bounds, &ts.d_bounds}, {s.coeffs, &ts.d_coeffs}, {s.ksums, &ts.d_ksums}, {s.rows, &ts.d_rows},
+		                         {s.mf64, &ts.d_mf64}}, &ts.mem);
+	}, out);
 }
 
 int get_expand_tables(pxz_handle *h, uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t filter,
                       const ExpandTables **out)
 {
-	auto key = std::make_tuple(bw, bh, edge_w, edge_h, filter);
-	auto it = h->expand_tables.find(key);
-	if (it != h->expand_tables.end()) { *out = &it->second; return PXZ_OK; }
-	pxz::ExpandTableSet s;
-	if (!pxz::build_expand_tables(bw, bh, edge_w, edge_h, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-	ExpandTables et;
-	et.dir_stride = s.dir_stride;
-	const int rc = upload_tables(h, {{s.dir, &et.d_dir}, {s.starts, &et.d_starts}, {s.sizes, &et.d_sizes}, {s.coeffs, &et.d_coeffs},
-	                                 {s.xmf, &et.d_xmf}, {s.xmf16, &et.d_xmf16}, {s.xmf64, &et.d_xmf64}}, &et.mem);
-	if (rc != PXZ_OK) return rc;
-	*out = &(h->expand_tables[key] = et);
-	return PXZ_OK;
+	return cached_tables(h, h->expand_tables, std::make_tuple(bw, bh, edge_w, edge_h, filter), 0, [&](ExpandTables &et) {
+		pxz::ExpandTableSet s;
+		if (!pxz::build_expand_tables(bw, bh, edge_w, edge_h, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+		et.dir_stride = s.dir_stride;
+		return upload_tables(h, {{s.dir, &et.d_dir}, {s.starts, &et.d_starts}, {s.sizes, &et.d_sizes}, {s.coeffs, &et.d_coeffs},
+		                         {s.xmf, &et.d_xmf}, {s.xmf16, &et.d_xmf16}, {s.xmf64, &et.d_xmf64}}, &et.mem);
+	}, out);
 }
 
 // ---- level decision tables ---------------------------------------------------
@@ -360,6 +443,15 @@ void build_breaks(pxz_handle *h, pxz::ShrinkArgs *a)
 	}
 }
 
+int check_params(pxz_handle *h, const pxz_params *p)
+{
+	if (p->block_w == 0 || p->block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
+	if (p->mode > 1) return fail(h, PXZ_ERR_INVALID_ARG, "mode must be 0 or 1");
+	if (p->filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter must be 0..4");
+	if (!std::isfinite(p->factor)) return fail(h, PXZ_ERR_INVALID_ARG, "factor must be finite");
+	return PXZ_OK;
+}
+
 int check_frames(pxz_handle *h, const pxz_frames *f, const pxz_params *p)
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
@@ -371,11 +463,7 @@ int check_frames(pxz_handle *h, const pxz_frames *f, const pxz_params *p)
 	if ((uint64_t)f->pitch_bytes < (uint64_t)f->width * f->channels) return fail(h, PXZ_ERR_INVALID_ARG, "pitch smaller than a row");
 	if (f->n_frames > 1 && f->frame_stride_bytes < (uint64_t)f->pitch_bytes * f->height)
 		return fail(h, PXZ_ERR_INVALID_ARG, "frame stride smaller than a frame");
-	if (p->block_w == 0 || p->block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
-	if (p->mode > 1) return fail(h, PXZ_ERR_INVALID_ARG, "mode must be 0 or 1");
-	if (p->filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter must be 0..4");
-	if (!std::isfinite(p->factor)) return fail(h, PXZ_ERR_INVALID_ARG, "factor must be finite");
-	return PXZ_OK;
+	return check_params(h, p);
 }
 
 // Fills the kernel arguments for a batch; returns the LDS bytes needed per block.
@@ -383,15 +471,16 @@ int prepare(pxz_handle *h, const pxz_frames *f, const pxz_params *p, bool want_p
 {
 	int rc = check_frames(h, f, p);
 	if (rc != PXZ_OK) return rc;
-	uint32_t cols, rows;
-	pxz_grid(f->width, f->height, p->block_w, p->block_h, &cols, &rows);
 	const uint32_t bw = p->block_w, bh = p->block_h;
-	const uint32_t edge_w = f->width - (cols - 1) * bw, edge_h = f->height - (rows - 1) * bh;
+	Grid g;
+	const int too_many = make_grid(h, f->width, f->height, bw, bh, f->n_frames, 0xffffffffull, &g);
+	const uint32_t cols = g.cols, edge_w = g.edge_w, edge_h = g.edge_h;
+	// (the detector's refusal is reported first, also for a batch of too many tiles)
 	if (p->mode == PXZ_MODE_SHRINK_DIRECTIONALLY && (edge_w < 2 || edge_h < 2 || bw < 2 || bh < 2))
 		return fail(h, PXZ_ERR_TILE_TOO_SMALL,
 		            "directional detector needs tiles of at least 2x2 px (edge tile is %ux%u); the reference panics here",
 		            edge_w, edge_h);
-	if ((uint64_t)cols * rows * f->n_frames > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles");
+	if (too_many != PXZ_OK) return too_many;
 	if (bw > 0xffffu || bh > 0xffffu) return fail(h, PXZ_ERR_UNSUPPORTED, "block side above 65535");
 
 	auto round2 = [](uint32_t v) { return (v + 1u) & ~1u; };
@@ -431,14 +520,9 @@ int prepare(pxz_handle *h, const pxz_frames *f, const pxz_params *p, bool want_p
 	a->height = f->height;
 	a->bw = bw;
 	a->bh = bh;
-	a->cols = cols;
-	a->rows = rows;
-	a->tiles_per_frame = cols * rows;
-	a->div_tpf = make_fastdiv(cols * rows);
+	put_grid(g, a);
+	a->div_tpf = make_fastdiv(g.tiles_per_frame);
 	a->div_cols = make_fastdiv(cols);
-	a->n_tiles = cols * rows * f->n_frames;
-	a->edge_w = edge_w;
-	a->edge_h = edge_h;
 	a->mode = p->mode;
 	a->filter = p->filter;
 	a->factor = p->factor;
@@ -669,17 +753,12 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 }  // namespace
 
 namespace {
-// The pixels are here on the host: a sparse look at the alpha channel (one pixel in 61 per sampled row, every 7th
-// row) decides whether the kernels for transparent tiles are worth their launch (> 2 % of the samples).
-// Upload of a host image for the host-buffer entry points.  The device copy gets rows of a 16-byte multiple when the
-// caller's do not have one (tight rows of an RGBA image whose width is not a multiple of 4): the fast kernels and
-// the block-cooperative Oklab detector want aligned rows, and the copy engine does the re-pitching for free.
+// Upload of a host image for the host-buffer entry points, re-pitched where device_pitch_of says so.
 int upload_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,
                  uint32_t *device_pitch)
 {
 	const size_t row_bytes = (size_t)width * channels;
-	uint32_t dp = pitch_bytes;
-	if (channels == 4 && (pitch_bytes & 15u) != 0) dp = (uint32_t)((row_bytes + 15u) & ~(size_t)15u);
+	const uint32_t dp = device_pitch_of(width, channels, pitch_bytes);
 	const size_t bytes = (size_t)dp * (height - 1) + row_bytes;
 	int rc = ensure(h, h->in, bytes);
 	if (rc != PXZ_OK) return rc;
@@ -689,6 +768,8 @@ int upload_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t 
 	return PXZ_OK;
 }
 
+// The pixels are here on the host: a sparse look at the alpha channel (one pixel in 61 per sampled row, every 7th
+// row) decides whether the kernels for transparent tiles are worth their launch (> 2 % of the samples).
 bool host_image_has_transparency(const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t pitch_bytes)
 {
 	uint32_t seen = 0, looked = 0;
@@ -748,30 +829,16 @@ void pxz_destroy(pxz_handle *h)
 {
 	if (!h) return;
 	(void)hipSetDevice(h->device);
-	free_tables(h->tables);
-	free_tables(h->expand_tables);
-	free_tables(h->tree_tables);
-	free_tables(h->varied_tables);
-	free_tables(h->varied_expand_tables);
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files, &h->varied_flags})
-		if (b->ptr) (void)hipFree(b->ptr);
-	for (int i = 0; i < pxz_handle::kRing; ++i)
-		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
-			if (b->ptr) (void)hipFree(b->ptr);
 	for (auto &ev : h->events) {
 		(void)hipEventDestroy(ev.first);
 		(void)hipEventDestroy(ev.second);
 	}
 	for (hipEvent_t ev : h->mid_events) (void)hipEventDestroy(ev);
-	if (h->ladder_copied) (void)hipEventDestroy(h->ladder_copied);
-	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
-	if (h->varied_copied) (void)hipEventDestroy(h->varied_copied);
-	if (h->varied_host) (void)hipHostFree(h->varied_host);
 	if (h->host_stats) {
 		(void)hipDeviceSynchronize();  // a queued launch may still write it
 		(void)hipHostFree(h->host_stats);
 	}
-	delete h;
+	delete h;  // (every buffer, table set and staging block frees itself)
 }
 
 const char *pxz_last_error(const pxz_handle *h) { return h ? h->error.c_str() : "null handle"; }
@@ -781,32 +848,9 @@ int pxz_trim(pxz_handle *h)
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	PXZ_HIP(h, hipSetDevice(h->device));
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	auto drop = [](DeviceBuffer &b) {
-		if (b.ptr) (void)hipFree(b.ptr);
-		b.ptr = nullptr;
-		b.cap = 0;
-	};
-	for (DeviceBuffer *b : {&h->in, &h->val, &h->ow, &h->oh, &h->out, &h->sums, &h->chunks, &h->work, &h->qscratch, &h->qmeta, &h->status, &h->dmeta, &h->okscratch, &h->rgba, &h->slots4, &h->pk, &h->pkoff, &h->tree, &h->xlist, &h->bigscratch, &h->tree_rects[0], &h->tree_rects[1], &h->tree_count, &h->ladder, &h->varied, &h->varied_in, &h->varied_out, &h->varied_files, &h->varied_flags})
-		drop(*b);
-	for (int i = 0; i < pxz_handle::kRing; ++i)
-		for (DeviceBuffer *b : {&h->ring_in[i], &h->ring_val[i], &h->ring_ow[i], &h->ring_oh[i], &h->ring_out[i], &h->ring_pk[i], &h->ring_pkoff[i]})
-			drop(*b);
-	free_tables(h->tree_tables);
-	if (h->ladder_copied) (void)hipEventDestroy(h->ladder_copied);
-	if (h->ladder_host) (void)hipHostFree(h->ladder_host);
-	h->ladder_copied = nullptr;
-	h->ladder_host = nullptr;
-	free_tables(h->varied_tables);
-	free_tables(h->varied_expand_tables);
-	if (h->varied_copied) (void)hipEventDestroy(h->varied_copied);
-	if (h->varied_host) (void)hipHostFree(h->varied_host);
-	h->varied_copied = nullptr;
-	h->varied_host = nullptr;
-	h->varied_host_cap = 0;
-	h->packed_len = 0;
-	h->work_ready = false;  // (the worklist counters went with their buffer)
-	h->qbins_clean = nullptr;
-	h->dbins_clean = nullptr;
+	// the scratch and ring buffers, the bounded table caches and both pinned stagings go; packed_len, work_ready (the
+	// worklist counters went with their buffer), qbins_clean and dbins_clean start over
+	static_cast<HandleScratch &>(*h) = HandleScratch();
 	return PXZ_OK;
 }
 
@@ -865,10 +909,7 @@ static int run_shrink(pxz_handle *h, const pxz_frames *frames, const pxz_params 
 	bool rgb_must_widen = false;
 	if (rc == PXZ_ERR_UNSUPPORTED && covers_if_rgba && frames->channels == 3 && !pxz::knobs().no_widen) {
 		// the RGB layout with its own detector planes does not fit LDS; the widened RGBA one without them might
-		pxz_frames fw = *frames;
-		fw.channels = 4;
-		fw.pitch_bytes = (frames->width * 4u + 15u) & ~15u;
-		fw.frame_stride_bytes = (uint64_t)fw.pitch_bytes * frames->height;
+		const pxz_frames fw = rgba16_frames(frames);
 		if (prepare(h, &fw, params, d_out_pixels != nullptr, &a, true) == PXZ_OK) {
 			rc = PXZ_OK;
 			rgb_must_widen = true;
@@ -892,13 +933,10 @@ static int run_shrink(pxz_handle *h, const pxz_frames *frames, const pxz_params 
 	}
 	if (rgb_must_widen && !widen)
 		return fail(h, PXZ_ERR_UNSUPPORTED, "a %ux%u RGB tile needs more LDS than there is (and this filter cannot run it as RGBA)", a.bw, a.bh);
-	pxz_frames f4 = *frames;
+	const pxz_frames f4 = rgba16_frames(frames);
 	const uint8_t *src = d_pixels;
 	uint8_t *out_px = d_out_pixels;
 	if (widen) {
-		f4.channels = 4;
-		f4.pitch_bytes = (frames->width * 4u + 15u) & ~15u;
-		f4.frame_stride_bytes = (uint64_t)f4.pitch_bytes * frames->height;
 		pxz::ShrinkArgs probe{};
 		if (prepare(h, &f4, params, d_out_pixels != nullptr, &probe, covers_if_rgba) != PXZ_OK) widen = false;  // e.g. four planes of a large tile exceed LDS
 	}
@@ -923,9 +961,7 @@ static int run_shrink(pxz_handle *h, const pxz_frames *frames, const pxz_params 
 		const uint64_t fstride = frames->n_frames > 1 ? frames->frame_stride_bytes : (uint64_t)frames->pitch_bytes * frames->height;
 		const bool misaligned = ((reinterpret_cast<uintptr_t>(d_pixels) | frames->pitch_bytes | (frames->n_frames > 1 ? fstride : 0)) & 15u) != 0;
 		if (misaligned) {
-			pxz_frames fa = *frames;
-			fa.pitch_bytes = (frames->width * 4u + 15u) & ~15u;
-			fa.frame_stride_bytes = (uint64_t)fa.pitch_bytes * frames->height;
+			const pxz_frames fa = rgba16_frames(frames);
 			if ((rc = ensure(h, h->rgba, (size_t)fa.frame_stride_bytes * frames->n_frames)) != PXZ_OK) return rc;
 			for (uint32_t n = 0; n < frames->n_frames; ++n)
 				PXZ_HIP(h, hipMemcpy2DAsync((uint8_t *)h->rgba.ptr + (size_t)n * fa.frame_stride_bytes, fa.pitch_bytes,
@@ -995,9 +1031,9 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 	                    prepare(h, frames, &p, want, &a, true) == PXZ_OK && a.big_blocks == 0u;
 	if (!ladder) {
 		// one single-factor flow per rung: no amortisation, the same results and errors by construction
-		uint32_t cols = 0, rows = 0;
-		pxz_grid(frames->width, frames->height, p.block_w, p.block_h, &cols, &rows);
-		const size_t tiles = (size_t)cols * rows * frames->n_frames;
+		Grid g;
+		(void)make_grid(h, frames->width, frames->height, p.block_w, p.block_h, frames->n_frames, kAnyTiles, &g);  // (the calls below check)
+		const size_t tiles = (size_t)g.tiles;
 		const size_t slot = (size_t)p.block_w * p.block_h * frames->channels;
 		for (uint32_t r = 0; r < n_factors; ++r) {
 			pxz_params pr = *params;
@@ -1013,16 +1049,7 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 	float *d_x = (float *)h->ladder.ptr;
 	float *d_factors = (float *)((uint8_t *)h->ladder.ptr + x_bytes);
 	// the factors go through pinned staging, reused once the copy queued by the previous ladder call has run
-	if (!h->ladder_host) {
-		void *hp = nullptr;
-		PXZ_HIP(h, hipHostMalloc(&hp, PXZ_LADDER_MAX_RUNGS * 4u, hipHostMallocDefault));
-		h->ladder_host = (float *)hp;
-	}
-	if (!h->ladder_copied) PXZ_HIP(h, hipEventCreateWithFlags(&h->ladder_copied, hipEventDisableTiming));
-	else PXZ_HIP(h, hipEventSynchronize(h->ladder_copied));
-	std::memcpy(h->ladder_host, factors, n_factors * 4u);
-	PXZ_HIP(h, hipMemcpyAsync(d_factors, h->ladder_host, n_factors * 4u, hipMemcpyHostToDevice, h->stream));
-	PXZ_HIP(h, hipEventRecord(h->ladder_copied, h->stream));
+	PXZ_HIP(h, h->ladder_factors.send(factors, n_factors * 4u, d_factors, h->stream, PXZ_LADDER_MAX_RUNGS * 4u));
 	// stage 1: get_block_variance with the identity closure (factor 1, scale 1) -> x of every tile, no pixels
 	h->quiet_stats = true;
 	rc = run_shrink(h, frames, &p, d_pixels, nullptr, nullptr, nullptr, nullptr, d_x, nullptr, true);
@@ -1075,17 +1102,15 @@ static int expand_launch(pxz_handle *h, const pxz_frames *frames, uint32_t slot_
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!frames || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null descriptor");
-	pxz_params p = *params;
-	p.mode = 0;
-	p.factor = 0.0f;  // neither is used on the decode side
+	const pxz_params p = decode_side_params(params, true);
 	int rc = check_frames(h, frames, &p);
 	if (rc != PXZ_OK) return rc;
 	if (!d_tile_w || !d_tile_h || !d_slots || !d_out_pixels) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
 	PXZ_HIP(h, hipSetDevice(h->device));
 	const uint32_t bw = p.block_w, bh = p.block_h;
-	uint32_t cols, rows;
-	pxz_grid(frames->width, frames->height, bw, bh, &cols, &rows);
-	if ((uint64_t)cols * rows * frames->n_frames > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles");
+	Grid g;
+	if ((rc = make_grid(h, frames->width, frames->height, bw, bh, frames->n_frames, 0xffffffffull, &g)) != PXZ_OK) return rc;
+	const uint32_t cols = g.cols, rows = g.rows;
 	if (bw > 0xffffu || bh > 0xffffu) return fail(h, PXZ_ERR_UNSUPPORTED, "block side above 65535");
 	// one wave: source pixels + horizontal-pass result + the staged windows (5 dwords per output sample of both axes)
 	const uint64_t lds_bytes = (2ull * bw * bh + 5ull * (bw + bh) + 3ull) / 4ull * 16ull + 16ull;
@@ -1105,12 +1130,7 @@ static int expand_launch(pxz_handle *h, const pxz_frames *frames, uint32_t slot_
 	a.channels = slot_channels;
 	a.bw = bw;
 	a.bh = bh;
-	a.cols = cols;
-	a.rows = rows;
-	a.tiles_per_frame = cols * rows;
-	a.n_tiles = cols * rows * frames->n_frames;
-	a.edge_w = frames->width - (cols - 1) * bw;
-	a.edge_h = frames->height - (rows - 1) * bh;
+	put_grid(g, &a);
 	a.slot_bytes = bw * bh * slot_channels;
 	a.filter = p.filter;
 	a.out_channels = frames->channels;
@@ -1157,14 +1177,13 @@ static int expand_launch(pxz_handle *h, const pxz_frames *frames, uint32_t slot_
 		a.div_gcols = make_fastdiv(cols);
 	}
 #ifdef PXZ_STAMPS
-	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;  // (stamps behind the flag: pxz_debug_read_status)
-	a.status = (uint32_t *)h->status.ptr;
-	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 8, h->stream));
+	constexpr size_t status_bytes = 256;  // (stamps behind the flags: pxz_debug_read_status)
 #else
-	if ((rc = ensure(h, h->status, 8)) != PXZ_OK) return rc;
+	constexpr size_t status_bytes = 8;
+#endif
+	if ((rc = ensure(h, h->status, status_bytes)) != PXZ_OK) return rc;
 	a.status = (uint32_t *)h->status.ptr;
 	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 8, h->stream));
-#endif
 	PXZ_HIP(h, pxz::launch_expand(a, h->n_cus, h->stream));
 	return PXZ_OK;
 }
@@ -1192,13 +1211,10 @@ int pxz_process_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz
 	p.factor = 1.0f;
 	int rc = check_frames(h, frames, &p);
 	if (rc != PXZ_OK) return rc;
-	uint32_t cols, rows;
-	pxz_grid(frames->width, frames->height, p.block_w, p.block_h, &cols, &rows);
-	const size_t tiles = (size_t)cols * rows * frames->n_frames, slot = (size_t)p.block_w * p.block_h * frames->channels;
-	if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
+	Grid g;
+	(void)make_grid(h, frames->width, frames->height, p.block_w, p.block_h, frames->n_frames, kAnyTiles, &g);  // (run_shrink checks)
+	const size_t tiles = (size_t)g.tiles, slot = (size_t)p.block_w * p.block_h * frames->channels;
+	if ((rc = ensure_tile_outputs(h, tiles, slot)) != PXZ_OK) return rc;
 	if ((rc = run_shrink(h, frames, &p, d_pixels, (float *)h->val.ptr, (uint32_t *)h->ow.ptr, (uint32_t *)h->oh.ptr,
 	                     (uint8_t *)h->out.ptr, nullptr, nullptr, true)) != PXZ_OK)
 		return rc;
@@ -1221,30 +1237,23 @@ int tree_process_rects(pxz_handle *h, const pxz_frames *frames, const pxz_params
 	if (levels[0].first > kMaxSide || levels[0].second > kMaxSide)
 		return fail(h, PXZ_ERR_UNSUPPORTED, "tree::process on the device takes blocks up to %ux%u (got %ux%u)", kMaxSide, kMaxSide,
 		            levels[0].first, levels[0].second);
-	int rc;
-	const auto key = std::make_tuple(frames->width, frames->height, levels[0].first, levels[0].second, mbw, mbh, p.filter, filter_upscale);
-	auto it = h->tree_tables.find(key);
-	if (it == h->tree_tables.end()) {
-		if (h->tree_tables.size() >= 16) {  // a cache, not a log: varying geometries (tools/fuzz_tree.py) must not grow it without bound
-			PXZ_HIP(h, hipStreamSynchronize(h->stream));  // (a queued launch may still read a table)
-			free_tables(h->tree_tables);
-		}
+	const TreeTables *ttp = nullptr;
+	int rc = cached_tables(h, h->tree_tables,
+	                       std::make_tuple(frames->width, frames->height, levels[0].first, levels[0].second, mbw, mbh, p.filter, filter_upscale),
+	                       kTableCacheBound, [&](TreeTables &t) {
 		pxz::TreeTableSet s;
 		if (!pxz::build_tree_tables(frames->width, frames->height, levels, p.filter, filter_upscale, &s))
 			return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter");
-		TreeTables tt;
-		tt.n_dir = (uint32_t)s.dir.size();
-		if ((rc = upload_tables(h, {{s.dir, &tt.d_dir}, {s.starts, &tt.d_starts}, {s.sizes, &tt.d_sizes}, {s.coeffs, &tt.d_coeffs}},
-		                        &tt.mem)) != PXZ_OK)
-			return rc;
-		it = h->tree_tables.emplace(key, tt).first;
-	}
-	const TreeTables &tt = it->second;
+		t.n_dir = (uint32_t)s.dir.size();
+		return upload_tables(h, {{s.dir, &t.d_dir}, {s.starts, &t.d_starts}, {s.sizes, &t.d_sizes}, {s.coeffs, &t.d_coeffs}}, &t.mem);
+	}, &ttp);
+	if (rc != PXZ_OK) return rc;
+	const TreeTables &tt = *ttp;
 	// ---- level 0: the frame's own grid (split.rs:37-61)
-	uint32_t cols, rows;
-	pxz_grid(frames->width, frames->height, levels[0].first, levels[0].second, &cols, &rows);
-	if ((uint64_t)cols * rows * frames->n_frames > 0x0fffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles");
-	uint32_t n = cols * rows * frames->n_frames;
+	Grid g;
+	if ((rc = make_grid(h, frames->width, frames->height, levels[0].first, levels[0].second, frames->n_frames, 0x0fffffffull, &g)) != PXZ_OK) return rc;
+	const uint32_t cols = g.cols, rows = g.rows;
+	uint32_t n = (uint32_t)g.tiles;
 	{
 		std::vector<pxz::TreeRect> r0(n);
 		size_t i = 0;
@@ -1371,10 +1380,9 @@ int pxz_tree_process_frames_device(pxz_handle *h, const pxz_frames *frames, cons
 	uint32_t prev_cols = 0, prev_tpf = 0;
 	size_t max_tiles = 0;
 	for (auto &lv : levels) {
-		uint32_t c, r;
-		pxz_grid(frames->width, frames->height, lv.first, lv.second, &c, &r);
-		if ((uint64_t)c * r * frames->n_frames > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles");
-		max_tiles = std::max(max_tiles, (size_t)c * r * frames->n_frames);
+		Grid g;
+		if ((rc = make_grid(h, frames->width, frames->height, lv.first, lv.second, frames->n_frames, 0xffffffffull, &g)) != PXZ_OK) return rc;
+		max_tiles = std::max(max_tiles, (size_t)g.tiles);
 	}
 	// per tile: the detector's own output (the stored block value is hypot(v, v), operations.rs:154) + two sets of flags
 	if ((rc = ensure(h, h->tree, 4 * max_tiles + 2 * max_tiles)) != PXZ_OK) return rc;
@@ -1383,16 +1391,13 @@ int pxz_tree_process_frames_device(pxz_handle *h, const pxz_frames *frames, cons
 	const bool whole = p.block_w <= mbw || p.block_h <= mbh;
 	for (size_t l = 0; l < levels.size(); ++l) {
 		const uint32_t bw = levels[l].first, bh = levels[l].second;
-		uint32_t cols, rows;
-		pxz_grid(frames->width, frames->height, bw, bh, &cols, &rows);
-		const size_t tiles = (size_t)cols * rows * frames->n_frames, slot = (size_t)bw * bh * frames->channels;
-		if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
-		if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
-		if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
+		Grid g;
+		(void)make_grid(h, frames->width, frames->height, bw, bh, frames->n_frames, kAnyTiles, &g);  // (checked above)
+		const size_t tiles = (size_t)g.tiles, slot = (size_t)bw * bh * frames->channels;
+		if ((rc = ensure_tile_outputs(h, tiles, whole ? 0 : slot)) != PXZ_OK) return rc;
 		if (!whole) {
 			// get_block_variance + reduce_image_section((v, v)) of every tile of this level's grid (process/mod.rs:84-95); the
 			// tiles that do not take part are discarded by the decision below
-			if ((rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
 			pxz_params lp = p;
 			lp.block_w = bw;
 			lp.block_h = bh;
@@ -1409,12 +1414,7 @@ int pxz_tree_process_frames_device(pxz_handle *h, const pxz_frames *frames, cons
 		t.open = open_flags[l & 1];
 		t.bw = bw;
 		t.bh = bh;
-		t.cols = cols;
-		t.rows = rows;
-		t.tiles_per_frame = cols * rows;
-		t.n_tiles = (uint32_t)tiles;
-		t.edge_w = frames->width - (cols - 1) * bw;
-		t.edge_h = frames->height - (rows - 1) * bh;
+		put_grid(g, &t);
 		t.parent_cols = prev_cols;
 		t.parent_tiles_per_frame = prev_tpf;
 		t.threshold = whole ? 1.0f : std::fabs(threshold);
@@ -1428,9 +1428,25 @@ int pxz_tree_process_frames_device(pxz_handle *h, const pxz_frames *frames, cons
 			                        (const uint8_t *)h->out.ptr, d_out_rgba, true)) != PXZ_OK)
 				return rc;
 		}
-		prev_cols = cols;
-		prev_tpf = cols * rows;
+		prev_cols = g.cols;
+		prev_tpf = g.tiles_per_frame;
 	}
+	return PXZ_OK;
+}
+
+// The reader's scratch (pxz_stream.hip), for a.n_tiles tiles: rec_off, rec_len, perm and the bin counters in dmeta, and the
+// status word, zeroed, with room for the stamps of the diagnostic build behind it (pxz_debug_read_status).
+static int reader_scratch(pxz_handle *h, pxz::DecodeArgs *a)
+{
+	int rc = ensure_bins(h, h->dmeta, (size_t)a->n_tiles * 16u + 4u * pxz::qoi_bins_dwords(), h->dbins_clean);
+	if (rc != PXZ_OK) return rc;
+	a->rec_off = (unsigned long long *)h->dmeta.ptr;
+	a->rec_len = (uint32_t *)((uint8_t *)h->dmeta.ptr + (size_t)a->n_tiles * 8u);
+	a->perm = a->rec_len + a->n_tiles;
+	a->bins = a->perm + a->n_tiles;
+	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;
+	a->status = (uint32_t *)h->status.ptr;
+	PXZ_HIP(h, hipMemsetAsync(a->status, 0, 4, h->stream));
 	return PXZ_OK;
 }
 
@@ -1440,10 +1456,7 @@ int pxz_decode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!frames || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null descriptor");
-	pxz_params p = *params;
-	p.mode = 0;
-	p.factor = 0.0f;
-	p.filter = 0;
+	const pxz_params p = decode_side_params(params, false);
 	pxz_frames f = *frames;
 	f.pitch_bytes = f.width * f.channels;  // only the geometry of the frames matters here
 	f.frame_stride_bytes = (uint64_t)f.pitch_bytes * f.height;
@@ -1452,9 +1465,8 @@ int pxz_decode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
 	if (!d_files || !d_file_offsets || !d_block_value || !d_tile_w || !d_tile_h || !d_slots)
 		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
 	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	pxz_grid(f.width, f.height, p.block_w, p.block_h, &cols, &rows);
-	if ((uint64_t)cols * rows * f.n_frames > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles");
+	Grid g;
+	if ((rc = make_grid(h, f.width, f.height, p.block_w, p.block_h, f.n_frames, 0xffffffffull, &g)) != PXZ_OK) return rc;
 	pxz::DecodeArgs a{};
 	a.files = d_files;
 	a.file_offsets = reinterpret_cast<const unsigned long long *>(d_file_offsets);
@@ -1466,30 +1478,12 @@ int pxz_decode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
 	a.height = f.height;
 	a.bw = p.block_w;
 	a.bh = p.block_h;
-	a.cols = cols;
-	a.rows = rows;
-	a.tiles_per_frame = cols * rows;
+	put_grid(g, &a);
 	a.n_frames = f.n_frames;
-	a.n_tiles = cols * rows * f.n_frames;
 	a.channels = f.channels;
 	a.slot_bytes = p.block_w * p.block_h * f.channels;
-	a.edge_w = f.width - (cols - 1) * p.block_w;
-	a.edge_h = f.height - (rows - 1) * p.block_h;
-	const size_t dmeta_cap = h->dmeta.cap;
-	if ((rc = ensure(h, h->dmeta, (size_t)a.n_tiles * 16u + 4u * pxz::qoi_bins_dwords())) != PXZ_OK) return rc;  // rec_off, rec_len, perm, the bin counters
-	if (h->dmeta.cap != dmeta_cap) h->dbins_clean = nullptr;  // a new allocation: nothing in it is zero
-	a.rec_off = (unsigned long long *)h->dmeta.ptr;
-	a.rec_len = (uint32_t *)((uint8_t *)h->dmeta.ptr + (size_t)a.n_tiles * 8u);
-	a.perm = a.rec_len + a.n_tiles;
-	a.bins = a.perm + a.n_tiles;
-	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;  // (room for the stamps of the diagnostic build: pxz_debug_read_status)
-	a.status = (uint32_t *)h->status.ptr;
-	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 4, h->stream));
-	const bool bins_clean = h->dbins_clean == a.bins;
-	h->dbins_clean = nullptr;
-	PXZ_HIP(h, pxz::launch_decode(a, bins_clean, h->stream));
-	h->dbins_clean = a.bins;
-	return PXZ_OK;
+	if ((rc = reader_scratch(h, &a)) != PXZ_OK) return rc;
+	return launch_on_bins(h, h->dbins_clean, a.bins, [&](bool bins_clean) { return pxz::launch_decode(a, bins_clean, h->stream); });
 }
 
 // The header fields of one .pixlzr file; on PXZ_ERR_INVALID_ARG *why says what is wrong with it.
@@ -1536,18 +1530,15 @@ int pxz_decode_file(pxz_handle *h, const uint8_t *file, size_t len, uint32_t *wi
 	const char *why;
 	int hrc = file_header(file, len, width, height, block_w, block_h, channels, filter_byte, &why);
 	if (hrc != PXZ_OK) return fail(h, hrc, "%s", why);
-	uint32_t cols, rows;
-	pxz_grid(*width, *height, *block_w, *block_h, &cols, &rows);
 	if (!block_value && !tile_w && !tile_h && !slots) return PXZ_OK;  // header query
 	if (!block_value || !tile_w || !tile_h || !slots) return fail(h, PXZ_ERR_INVALID_ARG, "null output pointer");
 	PXZ_HIP(h, hipSetDevice(h->device));
-	const size_t tiles = (size_t)cols * rows, slot = (size_t)*block_w * *block_h * *channels;
+	Grid g;
+	(void)make_grid(h, *width, *height, *block_w, *block_h, 1, kAnyTiles, &g);
+	const size_t tiles = (size_t)g.tiles, slot = (size_t)*block_w * *block_h * *channels;
 	int rc;
 	if ((rc = ensure(h, h->in, len + 16)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
+	if ((rc = ensure_tile_outputs(h, tiles, slot)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->chunks, 16)) != PXZ_OK) return rc;
 	const uint64_t offs[2] = {0, (uint64_t)len};
 	PXZ_HIP(h, hipMemcpyAsync(h->in.ptr, file, len, hipMemcpyHostToDevice, h->stream));
@@ -1558,10 +1549,7 @@ int pxz_decode_file(pxz_handle *h, const uint8_t *file, size_t len, uint32_t *wi
 	rc = pxz_decode_frames_device(h, &f, &p, (const uint8_t *)h->in.ptr, (const uint64_t *)h->chunks.ptr, (float *)h->val.ptr,
 	                              (uint32_t *)h->ow.ptr, (uint32_t *)h->oh.ptr, (uint8_t *)h->out.ptr);
 	if (rc != PXZ_OK) return rc;
-	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(tile_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(tile_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(slots, h->out.ptr, tiles * slot, hipMemcpyDeviceToHost, h->stream));
+	if ((rc = download_tile_outputs(h, tiles, slot, block_value, tile_w, tile_h, slots)) != PXZ_OK) return rc;
 	uint32_t flags = 0;
 	if ((rc = pxz_decode_status(h, &flags)) != PXZ_OK) return rc;
 	if (flags & 2u) return fail(h, PXZ_ERR_INVALID_ARG, "malformed .pixlzr file or record");
@@ -1590,9 +1578,9 @@ int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t ch
 	int rc = check_frames(h, &f, &p);
 	if (rc != PXZ_OK) return rc;
 	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	pxz_grid(width, height, block_w, block_h, &cols, &rows);
-	const size_t tiles = (size_t)cols * rows, slot = (size_t)block_w * block_h * channels;
+	Grid g;
+	(void)make_grid(h, width, height, block_w, block_h, 1, kAnyTiles, &g);
+	const size_t tiles = (size_t)g.tiles, slot = (size_t)block_w * block_h * channels;
 	const size_t out_bytes = (size_t)pitch_bytes * (height - 1) + (size_t)width * channels;
 	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
@@ -1612,34 +1600,50 @@ int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t ch
 	return PXZ_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The host-buffer entry points of one image (pxz_shrink_image, _ladder, _packed) after their pointer checks: the checks
+// of the geometry, the transparency hint, the tile outputs of `sets` results in handle scratch (the pixels only with
+// device_px), the upload, device_call(frames with the device pitch, parameters with the hint, tiles, slot bytes), and
+// the download of the tile outputs (the pixels only with out_pixels).  The caller queues what it downloads besides
+// and synchronises.
+template <class DeviceCall>
+int shrink_host_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,
+                      pxz_params p, uint32_t sets, bool device_px, float *block_value, uint32_t *out_w, uint32_t *out_h,
+                      uint8_t *out_pixels, DeviceCall device_call)
+{
+	pxz_frames f{width, height, channels, pitch_bytes, 1, 0, 0};
+	int rc = check_frames(h, &f, &p);
+	if (rc != PXZ_OK) return rc;
+	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p.reserved |= PXZ_HINT_TRANSPARENCY;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	Grid g;
+	(void)make_grid(h, width, height, p.block_w, p.block_h, 1, kAnyTiles, &g);  // (the device call checks)
+	const size_t tiles = (size_t)g.tiles * sets;
+	const size_t slot = (size_t)p.block_w * p.block_h * channels;
+	if ((rc = ensure_tile_outputs(h, tiles, device_px ? slot : 0)) != PXZ_OK) return rc;
+	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
+	if ((rc = device_call(f, p, tiles, slot)) != PXZ_OK) return rc;
+	return download_tile_outputs(h, tiles, slot, block_value, out_w, out_h, out_pixels);
+}
+}  // namespace
+
+extern "C" {
+
 int pxz_shrink_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
                      uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter,
                      float factor, float *block_value, uint32_t *out_w, uint32_t *out_h, uint8_t *out_pixels)
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!pixels || !block_value || !out_w || !out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	pxz_frames f{width, height, channels, pitch_bytes, 1, 0, 0};
-	pxz_params p{block_w, block_h, mode, filter, factor, 0};
-	int rc = check_frames(h, &f, &p);
+	const int rc = shrink_host_image(h, pixels, width, height, channels, pitch_bytes, pxz_params{block_w, block_h, mode, filter, factor, 0}, 1,
+	                                 out_pixels != nullptr, block_value, out_w, out_h, out_pixels,
+	                                 [&](const pxz_frames &f, const pxz_params &p, size_t, size_t) {
+		return pxz_shrink_frames_device(h, &f, &p, (const uint8_t *)h->in.ptr, (float *)h->val.ptr, (uint32_t *)h->ow.ptr,
+		                                (uint32_t *)h->oh.ptr, out_pixels ? (uint8_t *)h->out.ptr : nullptr);
+	});
 	if (rc != PXZ_OK) return rc;
-	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p.reserved |= PXZ_HINT_TRANSPARENCY;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	pxz_grid(width, height, block_w, block_h, &cols, &rows);
-	const size_t tiles = (size_t)cols * rows;
-	const size_t slot = (size_t)block_w * block_h * channels;
-	if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
-	if (out_pixels && (rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
-	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
-	rc = pxz_shrink_frames_device(h, &f, &p, (const uint8_t *)h->in.ptr, (float *)h->val.ptr, (uint32_t *)h->ow.ptr,
-	                              (uint32_t *)h->oh.ptr, out_pixels ? (uint8_t *)h->out.ptr : nullptr);
-	if (rc != PXZ_OK) return rc;
-	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(out_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(out_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	if (out_pixels) PXZ_HIP(h, hipMemcpyAsync(out_pixels, h->out.ptr, tiles * slot, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	return PXZ_OK;
 }
@@ -1654,28 +1658,13 @@ int pxz_shrink_image_ladder(pxz_handle *h, const uint8_t *pixels, uint32_t width
 	if (n_factors == 0 || n_factors > PXZ_LADDER_MAX_RUNGS)
 		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_LADDER_MAX_RUNGS, n_factors);
 	if (!pixels || !block_value || !out_w || !out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	pxz_frames f{width, height, channels, pitch_bytes, 1, 0, 0};
-	pxz_params p{block_w, block_h, mode, filter, 1.0f, 0};
-	int rc = check_frames(h, &f, &p);
+	const int rc = shrink_host_image(h, pixels, width, height, channels, pitch_bytes, pxz_params{block_w, block_h, mode, filter, 1.0f, 0}, n_factors,
+	                                 out_pixels != nullptr, block_value, out_w, out_h, out_pixels,
+	                                 [&](const pxz_frames &f, const pxz_params &p, size_t, size_t) {
+		return pxz_shrink_ladder_frames_device(h, &f, &p, factors, n_factors, (const uint8_t *)h->in.ptr, (float *)h->val.ptr,
+		                                       (uint32_t *)h->ow.ptr, (uint32_t *)h->oh.ptr, out_pixels ? (uint8_t *)h->out.ptr : nullptr);
+	});
 	if (rc != PXZ_OK) return rc;
-	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p.reserved |= PXZ_HINT_TRANSPARENCY;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	pxz_grid(width, height, block_w, block_h, &cols, &rows);
-	const size_t tiles = (size_t)cols * rows * n_factors;
-	const size_t slot = (size_t)block_w * block_h * channels;
-	if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
-	if (out_pixels && (rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
-	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
-	rc = pxz_shrink_ladder_frames_device(h, &f, &p, factors, n_factors, (const uint8_t *)h->in.ptr, (float *)h->val.ptr,
-	                                     (uint32_t *)h->ow.ptr, (uint32_t *)h->oh.ptr, out_pixels ? (uint8_t *)h->out.ptr : nullptr);
-	if (rc != PXZ_OK) return rc;
-	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(out_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(out_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	if (out_pixels) PXZ_HIP(h, hipMemcpyAsync(out_pixels, h->out.ptr, tiles * slot, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	return PXZ_OK;
 }
@@ -1688,35 +1677,24 @@ int pxz_shrink_image_packed(pxz_handle *h, const uint8_t *pixels, uint32_t width
 	h->packed_len = 0;
 	if (!pixels || !block_value || !out_w || !out_h || !packed_len) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
 	*packed_len = 0;
-	pxz_frames f{width, height, channels, pitch_bytes, 1, 0, 0};
-	pxz_params p{block_w, block_h, mode, filter, factor, 0};
-	int rc = check_frames(h, &f, &p);
-	if (rc != PXZ_OK) return rc;
-	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p.reserved |= PXZ_HINT_TRANSPARENCY;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	pxz_grid(width, height, block_w, block_h, &cols, &rows);
-	const size_t tiles = (size_t)cols * rows;
-	const size_t slot = (size_t)block_w * block_h * channels;
 	const size_t most = (size_t)width * height * channels;  // no tile grows
-	if ((rc = ensure(h, h->val, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->ow, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->oh, tiles * 4)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->out, tiles * slot)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->pk, most)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->pkoff, (tiles + 1) * 8)) != PXZ_OK) return rc;
-	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
-	rc = pxz_shrink_frames_device(h, &f, &p, (const uint8_t *)h->in.ptr, (float *)h->val.ptr, (uint32_t *)h->ow.ptr,
-	                              (uint32_t *)h->oh.ptr, (uint8_t *)h->out.ptr);
-	if (rc != PXZ_OK) return rc;
-	rc = pxz_pack_tiles_device(h, (uint32_t)tiles, channels, (uint32_t)slot, (const uint32_t *)h->ow.ptr, (const uint32_t *)h->oh.ptr,
-	                           (const uint8_t *)h->out.ptr, (uint64_t *)h->pkoff.ptr, (uint8_t *)h->pk.ptr, most);
+	size_t n_tiles = 0;
+	const int rc = shrink_host_image(h, pixels, width, height, channels, pitch_bytes, pxz_params{block_w, block_h, mode, filter, factor, 0}, 1, true,
+	                                 block_value, out_w, out_h, nullptr, [&](const pxz_frames &f, const pxz_params &p, size_t tiles, size_t slot) {
+		n_tiles = tiles;
+		int rc = ensure(h, h->pk, most);
+		if (rc == PXZ_OK) rc = ensure(h, h->pkoff, (tiles + 1) * 8);
+		if (rc == PXZ_OK)
+			rc = pxz_shrink_frames_device(h, &f, &p, (const uint8_t *)h->in.ptr, (float *)h->val.ptr, (uint32_t *)h->ow.ptr,
+			                              (uint32_t *)h->oh.ptr, (uint8_t *)h->out.ptr);
+		if (rc == PXZ_OK)
+			rc = pxz_pack_tiles_device(h, (uint32_t)tiles, channels, (uint32_t)slot, (const uint32_t *)h->ow.ptr, (const uint32_t *)h->oh.ptr,
+			                           (const uint8_t *)h->out.ptr, (uint64_t *)h->pkoff.ptr, (uint8_t *)h->pk.ptr, most);
+		return rc;
+	});
 	if (rc != PXZ_OK) return rc;
 	uint64_t total = 0;
-	PXZ_HIP(h, hipMemcpyAsync(block_value, h->val.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(out_w, h->ow.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(out_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(&total, (const uint64_t *)h->pkoff.ptr + tiles, 8, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(&total, (const uint64_t *)h->pkoff.ptr + n_tiles, 8, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	if (total > most) return fail(h, PXZ_ERR_HIP, "packed stream longer than the image (%llu > %zu)", (unsigned long long)total, most);
 	h->packed_len = total;
@@ -1745,16 +1723,15 @@ static int shrink_images_impl(pxz_handle *h, const uint8_t *const *pixels, uint3
 	int rc = check_frames(h, &f, &p);
 	if (rc != PXZ_OK) return rc;
 	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	pxz_grid(width, height, block_w, block_h, &cols, &rows);
-	const size_t tiles = (size_t)cols * rows, slot = (size_t)block_w * block_h * channels;
+	Grid g;
+	(void)make_grid(h, width, height, block_w, block_h, 1, kAnyTiles, &g);  // (the device calls check)
+	const size_t tiles = (size_t)g.tiles, slot = (size_t)block_w * block_h * channels;
 	const size_t most = (size_t)width * height * channels;  // no tile grows
 	const size_t row_bytes = (size_t)width * channels;
-	uint32_t dp = pitch_bytes;
-	if (channels == 4 && (pitch_bytes & 15u) != 0) dp = (uint32_t)((row_bytes + 15u) & ~(size_t)15u);
+	const uint32_t dp = device_pitch_of(width, channels, pitch_bytes);
 	const size_t in_bytes = (size_t)dp * (height - 1) + row_bytes;
 	const bool want_px = packed || out_pixels != nullptr;
-	constexpr int R = pxz_handle::kRing;
+	constexpr int R = HandleScratch::kRing;
 	for (int i = 0; i < R; ++i) {
 		if ((rc = ensure(h, h->ring_in[i], in_bytes)) != PXZ_OK) return rc;
 		if ((rc = ensure(h, h->ring_val[i], tiles * 4)) != PXZ_OK) return rc;
@@ -1955,6 +1932,45 @@ int pxz_pack_tiles_device(pxz_handle *h, uint32_t n_tiles, uint32_t channels, ui
 	return PXZ_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The writer's scratch (pxz_stream.hip) for n_tiles tiles of bw x bh pixels in c channels, and its limits: the scratch-
+// derived part of *a -- slot_bytes, n_tiles, n_chunks; the encoder's units in qscratch; in qmeta perm | rec_len | bins as
+// u32, then offsets (n + 1) and chunk totals as u64.
+int writer_scratch(pxz_handle *h, uint32_t n_tiles, uint32_t bw, uint32_t bh, uint32_t c, pxz::QoiArgs *a)
+{
+	const uint64_t slot64 = (uint64_t)bw * bh * c;
+	if (slot64 > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
+	const uint32_t slot = (uint32_t)slot64;
+	if ((slot & 15u) != 0 && c == 4) return fail(h, PXZ_ERR_UNSUPPORTED, "RGBA slots must be 16-byte multiples");
+	// a record: 13 + 10 + at most (channels + 1) bytes per pixel + the 8-byte end marker; a chunk of the record scan holds 4096 of them
+	const uint32_t px = bw * bh;
+	const uint64_t stride = 23ull + (uint64_t)px * (c + 1u) + 8ull;
+	if (stride * 4096ull > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large for the chunked scan");
+	const uint32_t n_chunks = (n_tiles + 4095u) / 4096u;
+	int rc = ensure(h, h->qscratch, pxz::qoi_scratch_bytes(n_tiles, px, c));
+	if (rc != PXZ_OK) return rc;
+	const size_t meta_u32 = (size_t)n_tiles * 2 + pxz::qoi_bins_dwords();
+	const size_t meta_u32_bytes = (meta_u32 * 4 + 7) & ~(size_t)7;
+	if ((rc = ensure_bins(h, h->qmeta, meta_u32_bytes + ((size_t)n_tiles + 1 + n_chunks) * 8, h->qbins_clean)) != PXZ_OK) return rc;
+	uint32_t *m32 = (uint32_t *)h->qmeta.ptr;
+	unsigned long long *m64 = (unsigned long long *)((uint8_t *)h->qmeta.ptr + meta_u32_bytes);
+	a->perm = m32;
+	a->rec_len = m32 + n_tiles;
+	a->bins = m32 + 2 * (size_t)n_tiles;
+	a->scratch = (uint8_t *)h->qscratch.ptr;
+	a->offsets = m64;
+	a->chunk_totals = m64 + n_tiles + 1;
+	a->n_tiles = n_tiles;
+	a->n_chunks = n_chunks;
+	a->slot_bytes = slot;
+	return PXZ_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int pxz_encode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_params *params, uint32_t filter_byte,
                              const float *d_block_value, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
                              const uint8_t *d_slots, uint8_t *d_out, uint64_t out_capacity, uint64_t *d_file_offsets)
@@ -1965,63 +1981,31 @@ int pxz_encode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
 	if (frames->channels != 3 && frames->channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4");
 	if (params->block_w == 0 || params->block_h == 0 || frames->n_frames == 0) return fail(h, PXZ_ERR_INVALID_ARG, "bad geometry");
 	PXZ_HIP(h, hipSetDevice(h->device));
-	uint32_t cols, rows;
-	if (pxz_grid(frames->width, frames->height, params->block_w, params->block_h, &cols, &rows) != PXZ_OK)
+	if (frames->width > kMaxImageSide || frames->height > kMaxImageSide)
 		return fail(h, PXZ_ERR_UNSUPPORTED, "image sides above 2^24 are not supported");
-	const uint64_t tiles64 = (uint64_t)cols * rows * frames->n_frames;
-	if (tiles64 > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles");
-	const uint32_t n_tiles = (uint32_t)tiles64, c = frames->channels;
-	const uint32_t slot = params->block_w * params->block_h * c;
-	if ((slot & 15u) != 0 && c == 4) return fail(h, PXZ_ERR_UNSUPPORTED, "RGBA slots must be 16-byte multiples");
-	// a record: 13 + 10 + at most (channels + 1) bytes per pixel + the 8-byte end marker; a chunk of the record scan holds 4096 of them
-	const uint32_t px = params->block_w * params->block_h;
-	const uint32_t stride = 23u + px * (c + 1u) + 8u;
-	const uint32_t n_chunks = (n_tiles + 4095u) / 4096u;
-	if ((uint64_t)stride * 4096ull > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large for the chunked scan");
-	int rc;
-	// the encoder's units (pxz_stream.hip)
-	if ((rc = ensure(h, h->qscratch, pxz::qoi_scratch_bytes(n_tiles, px, c))) != PXZ_OK) return rc;
-	// perm | rec_len | bins as u32, then offsets (n+1) and chunk totals as u64
-	const size_t meta_u32 = (size_t)n_tiles * 2 + pxz::qoi_bins_dwords();
-	const size_t meta_bytes = ((meta_u32 * 4 + 7) & ~(size_t)7) + ((size_t)n_tiles + 1 + n_chunks) * 8;
-	const size_t qmeta_cap = h->qmeta.cap;
-	if ((rc = ensure(h, h->qmeta, meta_bytes)) != PXZ_OK) return rc;
-	if (h->qmeta.cap != qmeta_cap) h->qbins_clean = nullptr;  // a new allocation: nothing in it is zero
-	uint32_t *m32 = (uint32_t *)h->qmeta.ptr;
-	unsigned long long *m64 = (unsigned long long *)((uint8_t *)h->qmeta.ptr + ((meta_u32 * 4 + 7) & ~(size_t)7));
+	Grid g;
+	int rc = make_grid(h, frames->width, frames->height, params->block_w, params->block_h, frames->n_frames, 0xffffffffull, &g);
+	if (rc != PXZ_OK) return rc;
 	pxz::QoiArgs a{};
+	if ((rc = writer_scratch(h, (uint32_t)g.tiles, params->block_w, params->block_h, frames->channels, &a)) != PXZ_OK) return rc;
 	a.slots = d_slots;
 	a.w = d_tile_w;
 	a.h = d_tile_h;
 	a.value = d_block_value;
-	a.perm = m32;
-	a.rec_len = m32 + n_tiles;
-	a.bins = m32 + 2 * (size_t)n_tiles;
-	a.scratch = (uint8_t *)h->qscratch.ptr;
-	a.offsets = m64;
-	a.chunk_totals = m64 + n_tiles + 1;
 	a.out = d_out;
 	a.file_offsets = (unsigned long long *)d_file_offsets;
 	a.capacity = out_capacity;
-	a.n_tiles = n_tiles;
-	a.n_chunks = n_chunks;
-	a.tiles_per_frame = cols * rows;
-	a.cols = cols;
-	a.rows = rows;
-	a.channels = c;
-	a.slot_bytes = slot;
-	a.hdr_bytes = 26u + rows * 4u;
+	a.tiles_per_frame = g.tiles_per_frame;
+	a.cols = g.cols;
+	a.rows = g.rows;
+	a.channels = frames->channels;
+	a.hdr_bytes = 26u + g.rows * 4u;
 	a.width = frames->width;
 	a.height = frames->height;
 	a.bw = params->block_w;
 	a.bh = params->block_h;
 	a.filter_byte = filter_byte;
-	// (a launch leaves the binning counters zeroed for the next one on the same buffer)
-	const bool bins_clean = h->qbins_clean == a.bins;
-	h->qbins_clean = nullptr;
-	PXZ_HIP(h, pxz::launch_qoi(a, bins_clean, h->n_cus, h->stream));
-	h->qbins_clean = a.bins;
-	return PXZ_OK;
+	return launch_on_bins(h, h->qbins_clean, a.bins, [&](bool bins_clean) { return pxz::launch_qoi(a, bins_clean, h->n_cus, h->stream); });
 }
 
 int pxz_synth_frames_device(pxz_handle *h, const pxz_frames *frames, uint8_t *d_pixels, uint32_t first_frame_index,
@@ -2080,8 +2064,9 @@ int pxz_enable_timing(pxz_handle *h, int on)
 	return PXZ_OK;
 }
 
-// average over the launches recorded since the last call (or since enable)
-int pxz_last_kernel_ms(pxz_handle *h, float *ms)
+// average over the recorded steps of the time from each step's first event to its last (first_kernel: to the event behind
+// its first kernel)
+static int recorded_ms(pxz_handle *h, bool first_kernel, float *ms)
 {
 	if (!h || !ms) return PXZ_ERR_INVALID_ARG;
 	if (!h->timing || h->events_used == 0) return fail(h, PXZ_ERR_INVALID_ARG, "no timed launches recorded");
@@ -2089,30 +2074,24 @@ int pxz_last_kernel_ms(pxz_handle *h, float *ms)
 	double total = 0.0;
 	for (size_t i = 0; i < h->events_used; ++i) {
 		float t = 0.f;
-		PXZ_HIP(h, hipEventElapsedTime(&t, h->events[i].first, h->events[i].second));
+		PXZ_HIP(h, hipEventElapsedTime(&t, h->events[i].first, first_kernel ? h->mid_events[i] : h->events[i].second));
 		total += t;
 	}
 	*ms = (float)(total / (double)h->events_used);
-	h->events_used = 0;
 	return PXZ_OK;
+}
+
+// average over the launches recorded since the last call (or since enable)
+int pxz_last_kernel_ms(pxz_handle *h, float *ms)
+{
+	const int rc = recorded_ms(h, false, ms);
+	if (rc == PXZ_OK) h->events_used = 0;
+	return rc;
 }
 
 // the same for the FIRST kernel of each recorded step alone (shrink32/64/16_kernel, or oklab_kernel in shrink_by
 // steps): what a per-kernel profile shows for it.  Call before pxz_last_kernel_ms (which resets the record).
-int pxz_last_first_kernel_ms(pxz_handle *h, float *ms)
-{
-	if (!h || !ms) return PXZ_ERR_INVALID_ARG;
-	if (!h->timing || h->events_used == 0) return fail(h, PXZ_ERR_INVALID_ARG, "no timed launches recorded");
-	PXZ_HIP(h, hipEventSynchronize(h->events[h->events_used - 1].second));
-	double total = 0.0;
-	for (size_t i = 0; i < h->events_used; ++i) {
-		float t = 0.f;
-		PXZ_HIP(h, hipEventElapsedTime(&t, h->events[i].first, h->mid_events[i]));
-		total += t;
-	}
-	*ms = (float)(total / (double)h->events_used);
-	return PXZ_OK;
-}
+int pxz_last_first_kernel_ms(pxz_handle *h, float *ms) { return recorded_ms(h, true, ms); }
 
 int pxz_handle_state(pxz_handle *h, uint32_t state[4])
 {
@@ -2153,10 +2132,12 @@ int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw,
 		im.width = g.width;
 		im.height = g.height;
 		im.pitch = g.pitch_bytes;
-		im.cols = ceil_div(g.width, bw);
-		im.rows = ceil_div(g.height, bh);
-		im.edge_w = g.width - (im.cols - 1) * bw;
-		im.edge_h = g.height - (im.rows - 1) * bh;
+		Grid grid;
+		(void)make_grid(h, g.width, g.height, bw, bh, 1, kAnyTiles, &grid);
+		im.cols = grid.cols;
+		im.rows = grid.rows;
+		im.edge_w = grid.edge_w;
+		im.edge_h = grid.edge_h;
 		im.hdr_bytes = 26u + 4u * im.rows;
 		if (channels && mode == PXZ_MODE_SHRINK_DIRECTIONALLY && (im.edge_w < 2 || im.edge_h < 2 || bw < 2 || bh < 2))
 			return fail(h, PXZ_ERR_TILE_TOO_SMALL,
@@ -2164,7 +2145,7 @@ int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw,
 			            im.edge_w, im.edge_h);
 		im.tile0 = (uint32_t)tiles;
 		im.row0 = (uint32_t)rows_total;
-		tiles += (uint64_t)im.cols * im.rows;
+		tiles += grid.tiles;
 		rows_total += im.rows;
 		if (tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "image %u: more than 2^32-1 tiles in the batch", i);
 		all.push_back(im.edge_w);
@@ -2177,46 +2158,30 @@ int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw,
 	return PXZ_OK;
 }
 
+// the tiles of a planned batch
+uint32_t varied_n_tiles(const std::vector<pxz::VariedImage> &images)
+{
+	return images.back().tile0 + images.back().cols * images.back().rows;
+}
+
 // the per-image table -> handle scratch, through pinned staging that is reused once the previous copy out of it has run
 int varied_upload(pxz_handle *h, const std::vector<pxz::VariedImage> &images, const pxz::VariedImage **d_images)
 {
 	const size_t bytes = images.size() * sizeof(pxz::VariedImage);
 	int rc = ensure(h, h->varied, bytes);
 	if (rc != PXZ_OK) return rc;
-	if (!h->varied_copied) PXZ_HIP(h, hipEventCreateWithFlags(&h->varied_copied, hipEventDisableTiming));
-	else PXZ_HIP(h, hipEventSynchronize(h->varied_copied));
-	if (h->varied_host_cap < images.size()) {
-		if (h->varied_host) (void)hipHostFree(h->varied_host);
-		h->varied_host = nullptr;
-		h->varied_host_cap = 0;
-		void *hp = nullptr;
-		PXZ_HIP(h, hipHostMalloc(&hp, bytes, hipHostMallocDefault));
-		h->varied_host = (pxz::VariedImage *)hp;
-		h->varied_host_cap = images.size();
-	}
-	std::memcpy(h->varied_host, images.data(), bytes);
-	PXZ_HIP(h, hipMemcpyAsync(h->varied.ptr, h->varied_host, bytes, hipMemcpyHostToDevice, h->stream));
-	PXZ_HIP(h, hipEventRecord(h->varied_copied, h->stream));
+	PXZ_HIP(h, h->varied_images.send(images.data(), bytes, h->varied.ptr, h->stream));
 	*d_images = (const pxz::VariedImage *)h->varied.ptr;
 	return PXZ_OK;
 }
 
 int get_varied_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t> &sides, const VariedTables **out)
 {
-	auto key = std::make_pair(filter, sides);
-	auto it = h->varied_tables.find(key);
-	if (it != h->varied_tables.end()) { *out = &it->second; return PXZ_OK; }
-	if (h->varied_tables.size() >= 16) {  // (a folder of many sizes: keep the cache bounded; queued launches may still read it)
-		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		free_tables(h->varied_tables);
-	}
-	pxz::VariedTableSet s;
-	if (!pxz::build_varied_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-	VariedTables vt;
-	const int rc = upload_tables(h, {{s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
-	if (rc != PXZ_OK) return rc;
-	*out = &(h->varied_tables[key] = vt);
-	return PXZ_OK;
+	return cached_tables(h, h->varied_tables, std::make_pair(filter, sides), kTableCacheBound, [&](VariedTables &vt) {
+		pxz::VariedTableSet s;
+		if (!pxz::build_varied_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+		return upload_tables(h, {{s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
+	}, out);
 }
 
 // a tile image of at most this many bytes is staged whole in LDS by varied_kernel (with its second image and, for shrink_by,
@@ -2226,10 +2191,8 @@ constexpr uint64_t kVariedMaxTileBytes = 65536;
 int varied_check_params(pxz_handle *h, uint32_t channels, const pxz_params *p)
 {
 	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	if (p->block_w == 0 || p->block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
-	if (p->mode > 1) return fail(h, PXZ_ERR_INVALID_ARG, "mode must be 0 or 1");
-	if (p->filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter must be 0..4");
-	if (!std::isfinite(p->factor)) return fail(h, PXZ_ERR_INVALID_ARG, "factor must be finite");
+	const int rc = check_params(h, p);
+	if (rc != PXZ_OK) return rc;
 	if ((uint64_t)p->block_w * p->block_h * channels > kVariedMaxTileBytes)
 		return fail(h, PXZ_ERR_UNSUPPORTED, "varied batches stage every tile in LDS: block_w*block_h*channels must not exceed %llu bytes",
 		            (unsigned long long)kVariedMaxTileBytes);
@@ -2247,7 +2210,7 @@ int pxz_varied_layout(const pxz_image_desc *descs, uint32_t n_images, uint32_t b
 	const int rc = varied_plan(nullptr, descs, n_images, block_w, block_h, 0, 0, &images, nullptr, nullptr);
 	if (rc != PXZ_OK) return rc;
 	for (uint32_t i = 0; i < n_images; ++i) tile_offsets[i] = images[i].tile0;
-	tile_offsets[n_images] = (uint64_t)images.back().tile0 + (uint64_t)images.back().cols * images.back().rows;
+	tile_offsets[n_images] = varied_n_tiles(images);
 	return PXZ_OK;
 }
 
@@ -2271,7 +2234,7 @@ int pxz_shrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
 	a.base = d_base;
 	a.n_images = n_images;
-	a.n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	a.n_tiles = varied_n_tiles(images);
 	a.bw = params->block_w;
 	a.bh = params->block_h;
 	a.mode = params->mode;
@@ -2305,50 +2268,25 @@ int pxz_encode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	uint32_t n_rows = 0;
 	int rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, 0, 0, &images, nullptr, &n_rows);
 	if (rc != PXZ_OK) return rc;
-	const uint32_t n_tiles = images.back().tile0 + images.back().cols * images.back().rows, c = channels;
-	const uint64_t slot64 = (uint64_t)params->block_w * params->block_h * c;
-	if (slot64 > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
-	const uint32_t slot = (uint32_t)slot64;
-	if ((slot & 15u) != 0 && c == 4) return fail(h, PXZ_ERR_UNSUPPORTED, "RGBA slots must be 16-byte multiples");
-	// (the limits of pxz_encode_frames_device: the writer's kernels are the same)
-	const uint32_t px = params->block_w * params->block_h;
-	const uint64_t stride = 23ull + (uint64_t)px * (c + 1u) + 8ull;
-	if (stride * 4096ull > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large for the chunked scan");
-	const uint32_t n_chunks = (n_tiles + 4095u) / 4096u;
+	const uint32_t n_tiles = varied_n_tiles(images), c = channels;
 	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::QoiArgs a{};
+	if ((rc = writer_scratch(h, n_tiles, params->block_w, params->block_h, c, &a)) != PXZ_OK) return rc;
 	pxz::VariedWriterArgs v{};
 	if ((rc = varied_upload(h, images, &v.images)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->qscratch, pxz::qoi_scratch_bytes(n_tiles, px, c))) != PXZ_OK) return rc;
-	const size_t meta_u32 = (size_t)n_tiles * 2 + pxz::qoi_bins_dwords();
-	const size_t meta_bytes = ((meta_u32 * 4 + 7) & ~(size_t)7) + ((size_t)n_tiles + 1 + n_chunks) * 8;
-	const size_t qmeta_cap = h->qmeta.cap;
-	if ((rc = ensure(h, h->qmeta, meta_bytes)) != PXZ_OK) return rc;
-	if (h->qmeta.cap != qmeta_cap) h->qbins_clean = nullptr;
-	uint32_t *m32 = (uint32_t *)h->qmeta.ptr;
-	unsigned long long *m64 = (unsigned long long *)((uint8_t *)h->qmeta.ptr + ((meta_u32 * 4 + 7) & ~(size_t)7));
-	pxz::QoiArgs a{};
 	a.slots = d_slots;
 	a.w = d_tile_w;
 	a.h = d_tile_h;
 	a.value = d_block_value;
-	a.perm = m32;
-	a.rec_len = m32 + n_tiles;
-	a.bins = m32 + 2 * (size_t)n_tiles;
-	a.scratch = (uint8_t *)h->qscratch.ptr;
-	a.offsets = m64;
-	a.chunk_totals = m64 + n_tiles + 1;
 	a.out = d_out;
 	a.file_offsets = (unsigned long long *)d_file_offsets;
 	a.capacity = out_capacity;
-	a.n_tiles = n_tiles;
-	a.n_chunks = n_chunks;
 	// one "frame" of n_tiles tiles and no tile rows of its own: the splice puts record t at hdr_bytes + scan(t), and the
 	// per-image headers come from varied_headers_kernel
 	a.tiles_per_frame = n_tiles;
 	a.cols = 0;
 	a.rows = 0;
 	a.channels = c;
-	a.slot_bytes = slot;
 	a.hdr_bytes = images[0].hdr_bytes;
 	a.bw = params->block_w;
 	a.bh = params->block_h;
@@ -2365,11 +2303,8 @@ int pxz_encode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	v.out = d_out;
 	v.file_offsets = a.file_offsets;
 	v.capacity = out_capacity;
-	const bool bins_clean = h->qbins_clean == a.bins;
-	h->qbins_clean = nullptr;
-	PXZ_HIP(h, pxz::launch_qoi_varied(a, v, bins_clean, h->n_cus, h->stream));
-	h->qbins_clean = a.bins;
-	return PXZ_OK;
+	return launch_on_bins(h, h->qbins_clean, a.bins,
+	                      [&](bool bins_clean) { return pxz::launch_qoi_varied(a, v, bins_clean, h->n_cus, h->stream); });
 }
 
 int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
@@ -2395,7 +2330,7 @@ int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const 
 		in_bytes += (bytes + 255u) & ~(uint64_t)255u;
 		raw += (uint64_t)descs[i].width * descs[i].height * channels;
 	}
-	const uint32_t n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	const uint32_t n_tiles = varied_n_tiles(images);
 	const uint64_t slot = (uint64_t)params->block_w * params->block_h * channels;
 	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
 	if ((rc = ensure(h, h->varied_in, in_bytes)) != PXZ_OK) return rc;
@@ -2439,22 +2374,13 @@ namespace {
 
 int get_varied_expand_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t> &sides, const VariedExpandTables **out)
 {
-	auto key = std::make_pair(filter, sides);
-	auto it = h->varied_expand_tables.find(key);
-	if (it != h->varied_expand_tables.end()) { *out = &it->second; return PXZ_OK; }
-	if (h->varied_expand_tables.size() >= 16) {  // (bounded as the encode side's cache; queued launches may still read it)
-		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		free_tables(h->varied_expand_tables);
-	}
-	pxz::VariedExpandTableSet s;
-	if (!pxz::build_varied_expand_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
-	VariedExpandTables vt;
-	vt.stride = s.stride;
-	vt.max_window = s.max_window;
-	const int rc = upload_tables(h, {{s.slot, &vt.d_slot}, {s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
-	if (rc != PXZ_OK) return rc;
-	*out = &(h->varied_expand_tables[key] = vt);
-	return PXZ_OK;
+	return cached_tables(h, h->varied_expand_tables, std::make_pair(filter, sides), kTableCacheBound, [&](VariedExpandTables &vt) {
+		pxz::VariedExpandTableSet s;
+		if (!pxz::build_varied_expand_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+		vt.stride = s.stride;
+		vt.max_window = s.max_window;
+		return upload_tables(h, {{s.slot, &vt.d_slot}, {s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
+	}, out);
 }
 
 // where the per-image flags of a varied decode-side call go: the caller's array, or handle scratch when it passed none; zeroed
@@ -2468,16 +2394,6 @@ int varied_flags(pxz_handle *h, uint32_t *d_image_flags, uint32_t n_images, uint
 	PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, (size_t)n_images * 4u, h->stream));
 	*out = d_image_flags;
 	return PXZ_OK;
-}
-
-// the decode side uses neither mode nor factor (and the reader no filter): the batch's parameters with those neutral
-pxz_params varied_decode_params(const pxz_params *params, bool with_filter)
-{
-	pxz_params p = *params;
-	p.mode = 0;
-	p.factor = 0.0f;
-	if (!with_filter) p.filter = 0;
-	return p;
 }
 
 }  // namespace
@@ -2494,7 +2410,7 @@ int pxz_decode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	if (!d_files || !d_file_offsets || !d_block_value || !d_tile_w || !d_tile_h || !d_slots)
 		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
 	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	const pxz_params p = varied_decode_params(params, false);
+	const pxz_params p = decode_side_params(params, false);
 	std::vector<pxz::VariedImage> images;
 	uint32_t n_rows = 0;
 	int rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, 0, 0, &images, nullptr, &n_rows);
@@ -2511,30 +2427,17 @@ int pxz_decode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	a.bw = p.block_w;
 	a.bh = p.block_h;
 	a.n_frames = n_images;  // (the end of the files buffer; the geometry fields stay zero: every image has its own)
-	a.n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	a.n_tiles = varied_n_tiles(images);
 	a.tiles_per_frame = a.n_tiles;
 	a.channels = channels;
 	a.slot_bytes = p.block_w * p.block_h * channels;
-	// the reader's scratch and its zeroed-bins bookkeeping, exactly as pxz_decode_frames_device keeps them
-	const size_t dmeta_cap = h->dmeta.cap;
-	if ((rc = ensure(h, h->dmeta, (size_t)a.n_tiles * 16u + 4u * pxz::qoi_bins_dwords())) != PXZ_OK) return rc;
-	if (h->dmeta.cap != dmeta_cap) h->dbins_clean = nullptr;
-	a.rec_off = (unsigned long long *)h->dmeta.ptr;
-	a.rec_len = (uint32_t *)((uint8_t *)h->dmeta.ptr + (size_t)a.n_tiles * 8u);
-	a.perm = a.rec_len + a.n_tiles;
-	a.bins = a.perm + a.n_tiles;
-	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;
-	a.status = (uint32_t *)h->status.ptr;
-	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 4, h->stream));
+	if ((rc = reader_scratch(h, &a)) != PXZ_OK) return rc;
 	uint32_t *flags = nullptr;
 	if ((rc = varied_flags(h, d_image_flags, n_images, &flags)) != PXZ_OK) return rc;
 	const pxz::VariedImage *d_images = nullptr;
 	if ((rc = varied_upload(h, images, &d_images)) != PXZ_OK) return rc;
-	const bool bins_clean = h->dbins_clean == a.bins;
-	h->dbins_clean = nullptr;
-	PXZ_HIP(h, pxz::launch_decode_varied(a, d_images, n_rows, flags, bins_clean, h->stream));
-	h->dbins_clean = a.bins;
-	return PXZ_OK;
+	return launch_on_bins(h, h->dbins_clean, a.bins,
+	                      [&](bool bins_clean) { return pxz::launch_decode_varied(a, d_images, n_rows, flags, bins_clean, h->stream); });
 }
 
 int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -2544,7 +2447,7 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
 	if (!d_tile_w || !d_tile_h || !d_slots || !d_base) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	const pxz_params p = varied_decode_params(params, true);
+	const pxz_params p = decode_side_params(params, true);
 	int rc = varied_check_params(h, channels, &p);
 	if (rc != PXZ_OK) return rc;
 	std::vector<pxz::VariedImage> images;
@@ -2555,7 +2458,7 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	if ((rc = get_varied_expand_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
 	pxz::VariedExpandArgs a{};
 	a.n_images = n_images;
-	a.n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	a.n_tiles = varied_n_tiles(images);
 	a.tile_w = d_tile_w;
 	a.tile_h = d_tile_h;
 	a.slots = d_slots;
@@ -2594,7 +2497,7 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	const pxz_params p = varied_decode_params(params, true);
+	const pxz_params p = decode_side_params(params, true);
 	int rc = varied_check_params(h, channels, &p);
 	if (rc != PXZ_OK) return rc;
 	std::vector<pxz::VariedImage> images;
@@ -2621,7 +2524,7 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 		img_bytes += ((uint64_t)dev[i].pitch_bytes * descs[i].height + 255u) & ~(uint64_t)255u;
 	}
 	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
-	const uint32_t n_tiles = images.back().tile0 + images.back().cols * images.back().rows;
+	const uint32_t n_tiles = varied_n_tiles(images);
 	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
 	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
 	const uint64_t flags_at = meta + (uint64_t)n_tiles * slot;

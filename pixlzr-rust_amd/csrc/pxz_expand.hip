@@ -3,6 +3,7 @@
 // Compiled with -ffp-contract=off: the f32 results of the Oklab detector are
 // written into the bitstream, and the reference (Rust) never fuses a*b+c.
 #include "pxz_device.h"
+#include "pxz_launch.h"
 
 namespace pxz {
 

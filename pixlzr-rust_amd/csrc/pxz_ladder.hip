@@ -9,6 +9,7 @@
 //
 // Compiled with -ffp-contract=off: (x * k) * 10 must be two f32 roundings, as the reference's x * factor * BASE_FACTOR.
 #include "pxz_device.h"
+#include "pxz_launch.h"
 
 namespace pxz {
 

@@ -1,0 +1,36 @@
+// pxz_launch.h — the host-callable launchers and size helpers of the kernel units, declared once: pxz_api.cpp calls them and
+// every .hip file that defines one includes this header, so the compiler holds each definition against its declaration.
+// Default arguments live here only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "pxz_internal.h"
+
+namespace pxz {
+hipError_t launch_shrink(const ShrinkArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_synth(const SynthArgs &s, hipStream_t stream);
+hipError_t launch_tree_decide(const TreeArgs &a, hipStream_t stream);
+hipError_t launch_tree_rects(const TreeRectArgs &a, hipStream_t stream);
+hipError_t launch_oklab_pixels(const uint32_t *px, uint32_t n, float *out, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_finish(const FinishArgs &f, hipStream_t stream);
+bool fast32_applicable(const ShrinkArgs &a, uint32_t channels);
+bool fast64_applicable(const ShrinkArgs &a, uint32_t channels);
+bool fast16_applicable(const ShrinkArgs &a, uint32_t channels);
+hipError_t launch_expand(const ExpandArgs &a, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_ladder(const LadderArgs &a, uint32_t channels, uint32_t nw, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream);
+hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, uint32_t n_rows, uint32_t *image_flags, bool bins_clean,
+                                hipStream_t stream);
+hipError_t launch_varied_expand(const VariedExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw);
+hipError_t launch_widen(const WidenArgs &a, hipStream_t stream);
+hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);
+hipError_t launch_pack(const PackArgs &a, hipStream_t stream);
+hipError_t launch_oklab(const ShrinkArgs &a, uint32_t n_cus, hipStream_t stream, uint32_t channels = 4);
+hipError_t launch_qoi(const QoiArgs &a, bool bins_clean, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_qoi_varied(const QoiArgs &a, const VariedWriterArgs &varied, bool bins_clean, uint32_t n_cus, hipStream_t stream);
+hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
+uint32_t qoi_bins_dwords();
+uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
+}  // namespace pxz

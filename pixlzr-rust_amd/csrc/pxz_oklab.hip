@@ -5,6 +5,7 @@
 // written into the bitstream, and the reference (Rust) never fuses a*b+c.
 #include "pxz_device.h"
 #include "pxz_oklab_math.h"
+#include "pxz_launch.h"
 #include <cstdlib>
 
 namespace pxz {

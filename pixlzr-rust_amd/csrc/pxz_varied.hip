@@ -21,6 +21,7 @@
 // Compiled with -ffp-contract=off (the detector's f32 arithmetic follows the reference's unfused operations).
 #include "pxz_device.h"
 #include "pxz_oklab_math.h"
+#include "pxz_launch.h"
 
 namespace pxz {
 

@@ -17,6 +17,7 @@
 // Tiles whose image (two tile-sized planes and the windows) exceeds LDS keep it in HBM, one image per wave of the grid
 // (BIG: RGB blocks above 20 000 pixels), as expand_kernel<C, false, true> does.
 #include "pxz_device.h"
+#include "pxz_launch.h"
 
 namespace pxz {
 
