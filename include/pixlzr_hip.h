@@ -367,6 +367,56 @@ int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t ch
                      uint32_t block_w, uint32_t block_h, uint32_t filter, const uint32_t *tile_w,
                      const uint32_t *tile_h, const uint8_t *slots, uint8_t *out_pixels);
 
+/* ---- rate and distortion: what a factor costs and what it loses ---------------- */
+
+/* The squared error of stored tiles against the frames they were shrunk from.  Nothing in the reference computes it:
+ * src/bin/whole-folder.rs:69-117 writes, for every k = i/20, the .pixlzr file and the PNG that comes back, and leaves the
+ * comparison to a person.  For every tile and channel: the sum over the tile's pixels of (source - expanded)^2, where
+ * `expanded` is exactly what pxz_expand_frames_device writes for that stored tile with params->filter, i.e. Pixlzr::expand
+ * (pixlzr.rs:77-122) + to_image (pixlzr_image.rs:24-74) -- the image itself is never written.  An integer; MSE and PSNR are
+ * the caller's: 10 log10(255^2 n / sse) over n samples.
+ * `frames` describes the SOURCE frames at d_pixels; params->block_w, block_h and filter (the UP-scaling filter) are used.
+ * n_sets >= 1 stored versions of every frame's tiles are compared in one call, set-major as pxz_shrink_ladder_frames_device
+ * leaves its rungs: index (s * n_frames + f) * tiles + t of d_tile_w, d_tile_h and d_slots (slots of
+ * block_w*block_h*channels bytes).  d_tile_sse (n_sets*n_frames*tiles*channels u64, same order, channel last; may be NULL)
+ * gets the tiles' sums, d_frame_sse (n_sets*n_frames*channels u64) their totals per frame -- integer sums, so the result does
+ * not depend on the order of the additions.  A tile stored at its full size is the source (block.rs:279-281): its sums are 0
+ * and neither its slot nor the source is read.  A tile whose stored size is zero or exceeds its place follows
+ * pxz_expand_frames_device: skipped and flagged (pxz_decode_status bit 0); its d_tile_sse entries are all-ones
+ * (UINT64_MAX) and the frame's totals leave it out.
+ * Asynchronous on the handle's stream; the number of launches and copies does not depend on n_frames or n_sets; none of the
+ * state the single-geometry fast paths keep in the handle is touched.  Validation runs on the host before anything is
+ * launched, with pxz_expand_frames_device's rules and codes, and n_sets == 0 is PXZ_ERR_INVALID_ARG; on an error nothing is
+ * written.  Limit: a wave keeps the tile in LDS, so block_w*block_h*channels must not exceed 65536 bytes, and RGB blocks
+ * must stay below the size (about 19 400 pixels) where pxz_expand_varied_frames_device moves its tiles to HBM;
+ * PXZ_ERR_UNSUPPORTED beyond. */
+int pxz_distortion_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_params *params, uint32_t n_sets,
+                                 const uint8_t *d_pixels, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                 const uint8_t *d_slots, uint64_t *d_tile_sse, uint64_t *d_frame_sse);
+
+/* The same for one set of stored tiles of a batch of differently sized images (no reference line either: see above).  The
+ * images are the SOURCE, image i at d_base + descs[i].offset_bytes with descs[i].pitch_bytes between rows, any alignment;
+ * tiles in the pxz_varied_layout order.  d_tile_sse (tiles*channels u64, may be NULL), d_image_sse (n_images*channels u64).
+ * d_image_flags (n_images dwords, may be NULL) receives 0 or 1 per image as from pxz_expand_varied_frames_device.  Each
+ * image's results equal pxz_distortion_frames_device on that image alone.  Validation, "image i" texts and the limit as
+ * pxz_expand_varied_frames_device; on an error nothing is written. */
+int pxz_distortion_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                        const pxz_params *params, const uint8_t *d_base, const uint32_t *d_tile_w,
+                                        const uint32_t *d_tile_h, const uint8_t *d_slots, uint64_t *d_tile_sse,
+                                        uint64_t *d_image_sse, uint32_t *d_image_flags);
+
+/* One host-resident image in, one row per factor out: the sweep of src/bin/whole-folder.rs:83-113 as numbers instead of
+ * files.  For every factors[r] (1 <= n_factors <= PXZ_LADDER_MAX_RUNGS): file_bytes[r] is the length of the .pixlzr file
+ * Pixlzr::from_image + shrink_by | shrink_directionally (filter_down) + encode_to_vec give (filter byte 0), and
+ * sse[r*channels + c] the squared error of channel c between the image and what expand + to_image(filter_up) make of that
+ * file.  Composition only: upload, pxz_shrink_ladder_frames_device, pxz_encode_frames_device for its offsets (no file is
+ * kept), pxz_distortion_frames_device over the n_factors rung sets, one download.  Synchronous.  Errors and limits are
+ * those of the three calls. */
+int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                              uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                              uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes,
+                              uint64_t *sse);
+
 /* ---- legacy image -> image filter ------------------------ */
 
 /* process_custom (src/process/mod.rs:71-102) with the closures of process() (:107-121: |x - avg| and the

@@ -23,6 +23,7 @@ EXPORTED_SYMBOLS = [
     "pxz_shrink_ladder_frames_device", "pxz_shrink_image_ladder",
     "pxz_varied_layout", "pxz_shrink_varied_frames_device", "pxz_encode_varied_frames_device", "pxz_encode_varied_images",
     "pxz_file_header", "pxz_decode_varied_frames_device", "pxz_expand_varied_frames_device", "pxz_decode_varied_files",
+    "pxz_distortion_frames_device", "pxz_distortion_varied_frames_device", "pxz_rate_distortion_image",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -146,6 +147,13 @@ def load_library():
         L.pxz_expand_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 5
         L.pxz_decode_varied_files.restype = C.c_int
         L.pxz_decode_varied_files.argtypes = [vp, vp, vp, vp, u32, u32, C.POINTER(Params), vp, vp]
+    if hasattr(L, "pxz_distortion_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the distortion calls)
+        L.pxz_distortion_frames_device.restype = C.c_int
+        L.pxz_distortion_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params), u32] + [vp] * 6
+        L.pxz_distortion_varied_frames_device.restype = C.c_int
+        L.pxz_distortion_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 7
+        L.pxz_rate_distortion_image.restype = C.c_int
+        L.pxz_rate_distortion_image.argtypes = [vp, vp] + [u32] * 9 + [vp, u32, vp, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -251,6 +259,15 @@ def encode_container(width, height, bw, bh, channels, filter_byte, values, has_v
     if n < 0:
         raise PxzError(int(n))
     return out[:n].tobytes()
+
+
+def psnr(sse, n_samples):
+    """10 log10(255^2 n / sse) in dB for a squared error summed over n_samples 8-bit samples (pixels x channels): what a
+    caller makes of the sums the distortion calls return.  inf for an sse of 0; numpy arrays go through element by element."""
+    sse = np.asarray(sse, np.float64)
+    with np.errstate(divide="ignore"):
+        out = 10.0 * np.log10(255.0 * 255.0 * np.asarray(n_samples, np.float64) / sse)
+    return float(out) if out.ndim == 0 else out
 
 
 def axis_table(in_size, out_size, filt):
@@ -630,6 +647,72 @@ class Handle:
             err.flags, err.images = flags[:n], result
             raise err
         return result, flags[:n]
+
+    # ---- rate and distortion ----
+    def distortion_frames_device(self, frames, bw, bh, filt, ow, oh, slots, want_tiles=True, out=None):
+        """pxz_distortion_frames_device: per tile and channel the sum of (source - expanded)^2 of stored tiles against the
+        frames [N,H,W,C] they were shrunk from, `expanded` being what expand_frames_device(..., filt, ...) writes.  ow, oh:
+        [N,T] or [K,N,T] as shrink_frames_device / shrink_ladder_frames_device leave them, slots [..., bw*bh*C].  Returns
+        (tile_sse int64 [K,N,T,C] | None, frame_sse int64 [K,N,C]).  Real sums stay below 2^63; the entries of a tile whose
+        stored size is zero or exceeds its place are all-ones and read as -1 (decode_status() bit 0 is set; the frame's
+        totals leave such tiles out).  out: a (tile_sse | None, frame_sse) pair of such tensors."""
+        import torch
+        fd, (N, H, W, Cc) = self._frames_desc(frames)
+        cols, rows = grid(W, H, bw, bh)
+        T = cols * rows
+        K = ow.numel() // (N * T) if N * T else 0
+        assert ow.numel() == K * N * T and oh.numel() == ow.numel() and ow.is_contiguous() and oh.is_contiguous() and slots.is_contiguous()
+        if out is None:
+            tile_sse = torch.empty((K, N, T, Cc), dtype=torch.int64, device=frames.device) if want_tiles else None
+            frame_sse = torch.empty((K, N, Cc), dtype=torch.int64, device=frames.device)
+        else:
+            tile_sse, frame_sse = out
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_distortion_frames_device(
+            self._h, C.byref(fd), C.byref(pd), K, C.c_void_p(frames.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()), C.c_void_p(tile_sse.data_ptr()) if tile_sse is not None else None,
+            C.c_void_p(frame_sse.data_ptr())))
+        return tile_sse, frame_sse
+
+    def distortion_varied_frames_device(self, images, bw, bh, filt, ow, oh, slots, descs=None, channels=None, want_tiles=True,
+                                        out=None, image_flags=None):
+        """pxz_distortion_varied_frames_device: the same for the stored tiles (varied layout: w[T], h[T], slots[T, bw*bh*C]) of a
+        list of differently sized CUDA images, or of one uint8 CUDA buffer with descs = [(width, height, pitch_bytes,
+        offset_bytes), ...] and channels.  Returns (tile_sse int64 [T,C] | None, image_sse int64 [n,C]); all-ones entries read
+        as -1 as above, and image_flags (int32[n] CUDA, optional) gets 1 for an image that holds such a tile."""
+        import torch
+        base, geoms, ch, keep = self._varied_batch(images, descs)
+        ch = channels if channels is not None else ch
+        if out is None:
+            dev = torch.device("cuda", self.device_id)
+            tile_sse = torch.empty((ow.numel(), ch), dtype=torch.int64, device=dev) if want_tiles else None
+            image_sse = torch.empty((len(geoms), ch), dtype=torch.int64, device=dev)
+        else:
+            tile_sse, image_sse = out
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_distortion_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), ch, C.byref(pd), C.c_void_p(base), C.c_void_p(ow.data_ptr()),
+            C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(tile_sse.data_ptr()) if tile_sse is not None else None,
+            C.c_void_p(image_sse.data_ptr()), C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        del keep
+        return tile_sse, image_sse
+
+    def rate_distortion_image(self, img, bw, bh, mode, filter_down, filter_up, factors):
+        """pxz_rate_distortion_image: a host image (numpy uint8 [H,W,C]) at every factor of `factors` (1..16) ->
+        (file_bytes uint64[K], sse uint64[K,C]): the length of the .pixlzr file of each factor and the squared error per
+        channel of the image that file expands to with filter_up.  psnr(sse[r].sum(), H*W*C) is the rung's PSNR."""
+        if img.strides[2] != 1 or img.strides[1] != img.shape[2]:
+            img = np.ascontiguousarray(img)
+        H, W, Cc = img.shape
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        file_bytes = np.zeros(max(K, 1), np.uint64)
+        sse = np.zeros((max(K, 1), Cc), np.uint64)
+        self._check(self._L.pxz_rate_distortion_image(self._h, C.c_void_p(img.ctypes.data), W, H, Cc, img.strides[0], bw, bh, mode,
+                                                      filter_down, filter_up, _p(fac) if K else None, K, _p(file_bytes), _p(sse)))
+        return file_bytes[:K], sse[:K]
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

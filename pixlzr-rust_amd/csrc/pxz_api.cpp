@@ -110,6 +110,7 @@ struct HandleScratch {
 	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedTables> varied_tables;  // (filter, tile sides) -> tables
 	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedExpandTables> varied_expand_tables;  // the same for the decode side
 	DeviceBuffer varied_flags;        // per-image flags of a varied decode-side call whose caller passed none
+	DeviceBuffer rd;                  // pxz_rate_distortion_image: the files' offsets, the rungs' squared errors, the writer's room
 	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
 	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
 	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
@@ -1603,27 +1604,37 @@ int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t ch
 }  // extern "C"
 
 namespace {
-// The host-buffer entry points of one image (pxz_shrink_image, _ladder, _packed) after their pointer checks: the checks
-// of the geometry, the transparency hint, the tile outputs of `sets` results in handle scratch (the pixels only with
-// device_px), the upload, device_call(frames with the device pitch, parameters with the hint, tiles, slot bytes), and
-// the download of the tile outputs (the pixels only with out_pixels).  The caller queues what it downloads besides
-// and synchronises.
+// The front half of the host-buffer entry points of one image (pxz_shrink_image, _ladder, _packed, pxz_rate_distortion_image)
+// after their pointer checks: the checks of the geometry, the transparency hint (*p), the tile outputs of `sets` results in
+// handle scratch (the pixels only with device_px) and the upload.  *f: the frame with its device pitch; *tiles: the tiles of
+// all sets; *slot: bytes of one slot.
+int stage_host_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,
+                     pxz_params *p, uint32_t sets, bool device_px, pxz_frames *f, size_t *tiles, size_t *slot)
+{
+	*f = pxz_frames{width, height, channels, pitch_bytes, 1, 0, 0};
+	int rc = check_frames(h, f, p);
+	if (rc != PXZ_OK) return rc;
+	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p->reserved |= PXZ_HINT_TRANSPARENCY;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	Grid g;
+	(void)make_grid(h, width, height, p->block_w, p->block_h, 1, kAnyTiles, &g);  // (the device call checks)
+	*tiles = (size_t)g.tiles * sets;
+	*slot = (size_t)p->block_w * p->block_h * channels;
+	if ((rc = ensure_tile_outputs(h, *tiles, device_px ? *slot : 0)) != PXZ_OK) return rc;
+	return upload_image(h, pixels, width, height, channels, pitch_bytes, &f->pitch_bytes);
+}
+
+// ... then device_call(frames with the device pitch, parameters with the hint, tiles, slot bytes), and the download of the
+// tile outputs (the pixels only with out_pixels).  The caller queues what it downloads besides and synchronises.
 template <class DeviceCall>
 int shrink_host_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,
                       pxz_params p, uint32_t sets, bool device_px, float *block_value, uint32_t *out_w, uint32_t *out_h,
                       uint8_t *out_pixels, DeviceCall device_call)
 {
-	pxz_frames f{width, height, channels, pitch_bytes, 1, 0, 0};
-	int rc = check_frames(h, &f, &p);
+	pxz_frames f;
+	size_t tiles = 0, slot = 0;
+	int rc = stage_host_image(h, pixels, width, height, channels, pitch_bytes, &p, sets, device_px, &f, &tiles, &slot);
 	if (rc != PXZ_OK) return rc;
-	if (channels == 4 && host_image_has_transparency(pixels, width, height, pitch_bytes)) p.reserved |= PXZ_HINT_TRANSPARENCY;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	Grid g;
-	(void)make_grid(h, width, height, p.block_w, p.block_h, 1, kAnyTiles, &g);  // (the device call checks)
-	const size_t tiles = (size_t)g.tiles * sets;
-	const size_t slot = (size_t)p.block_w * p.block_h * channels;
-	if ((rc = ensure_tile_outputs(h, tiles, device_px ? slot : 0)) != PXZ_OK) return rc;
-	if ((rc = upload_image(h, pixels, width, height, channels, pitch_bytes, &f.pitch_bytes)) != PXZ_OK) return rc;
 	if ((rc = device_call(f, p, tiles, slot)) != PXZ_OK) return rc;
 	return download_tile_outputs(h, tiles, slot, block_value, out_w, out_h, out_pixels);
 }
@@ -2372,11 +2383,21 @@ int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const 
 // ---- decode side of varied batches (varied_index_kernel in pxz_stream.hip, pxz_varied_expand.hip) -------------------------
 namespace {
 
-int get_varied_expand_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t> &sides, const VariedExpandTables **out)
+// a wave's image of tile_dw dwords, with the images' first tiles beside it, exceeds LDS
+bool varied_image_beyond_lds(uint32_t tile_dw) { return (uint64_t)tile_dw * 4u + 8192u > 160u * 1024u; }
+// dwords of one staged window for tables whose widest window has max_window taps
+uint32_t varied_window_dw(uint32_t max_window) { return 1u + (max_window + 1u) / 2u; }
+
+// lds_bw x lds_bh (0: no such limit): the block of a caller whose wave's image has to fit LDS; a set that does not let it is
+// refused once it is built, before anything is uploaded or cached
+int get_varied_expand_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t> &sides, const VariedExpandTables **out,
+                             uint32_t lds_bw = 0, uint32_t lds_bh = 0)
 {
 	return cached_tables(h, h->varied_expand_tables, std::make_pair(filter, sides), kTableCacheBound, [&](VariedExpandTables &vt) {
 		pxz::VariedExpandTableSet s;
 		if (!pxz::build_varied_expand_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
+		if (lds_bw && varied_image_beyond_lds(pxz::varied_expand_tile_dw(lds_bw, lds_bh, varied_window_dw(s.max_window))))
+			return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile and its windows in LDS: they exceed what a block has", lds_bw, lds_bh);
 		vt.stride = s.stride;
 		vt.max_window = s.max_window;
 		return upload_tables(h, {{s.slot, &vt.d_slot}, {s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
@@ -2393,6 +2414,40 @@ int varied_flags(pxz_handle *h, uint32_t *d_image_flags, uint32_t n_images, uint
 	}
 	PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, (size_t)n_images * 4u, h->stream));
 	*out = d_image_flags;
+	return PXZ_OK;
+}
+
+// What the kernels that resize stored tiles of a flat tile space back to their full sizes share (VariedExpandArgs,
+// DistortionArgs: the fields both name alike): the block, the tables of the batch's tile sides, and the LDS image of one wave.
+template <class Args>
+int put_varied_expand_tables(pxz_handle *h, const pxz_params &p, uint32_t channels, const std::vector<uint32_t> &sides, Args *a,
+                             bool lds_only = false)
+{
+	const VariedExpandTables *vt = nullptr;
+	const int rc = get_varied_expand_tables(h, p.filter, sides, &vt, lds_only ? p.block_w : 0u, lds_only ? p.block_h : 0u);
+	if (rc != PXZ_OK) return rc;
+	a->bw = p.block_w;
+	a->bh = p.block_h;
+	a->slot_bytes = p.block_w * p.block_h * channels;
+	a->filter = p.filter;
+	a->slot = vt->d_slot;
+	a->dir = vt->d_dir;
+	a->stride = vt->stride;
+	a->starts = vt->d_starts;
+	a->sizes = vt->d_sizes;
+	a->coeffs = vt->d_coeffs;
+	a->wdw = varied_window_dw(vt->max_window);
+	a->tile_dw = pxz::varied_expand_tile_dw(a->bw, a->bh, a->wdw);
+	return PXZ_OK;
+}
+
+// the decode side's status word, zeroed on the stream
+int fresh_status(pxz_handle *h, uint32_t **status)
+{
+	const int rc = ensure(h, h->status, 256);
+	if (rc != PXZ_OK) return rc;
+	*status = (uint32_t *)h->status.ptr;
+	PXZ_HIP(h, hipMemsetAsync(*status, 0, 8, h->stream));
 	return PXZ_OK;
 }
 
@@ -2454,37 +2509,22 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	std::vector<uint32_t> sides;
 	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
 	PXZ_HIP(h, hipSetDevice(h->device));
-	const VariedExpandTables *vt = nullptr;
-	if ((rc = get_varied_expand_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
 	pxz::VariedExpandArgs a{};
+	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a)) != PXZ_OK) return rc;
 	a.n_images = n_images;
 	a.n_tiles = varied_n_tiles(images);
 	a.tile_w = d_tile_w;
 	a.tile_h = d_tile_h;
 	a.slots = d_slots;
 	a.base = d_base;
-	a.bw = p.block_w;
-	a.bh = p.block_h;
-	a.slot_bytes = p.block_w * p.block_h * channels;
-	a.filter = p.filter;
-	a.slot = vt->d_slot;
-	a.dir = vt->d_dir;
-	a.stride = vt->stride;
-	a.starts = vt->d_starts;
-	a.sizes = vt->d_sizes;
-	a.coeffs = vt->d_coeffs;
-	a.wdw = 1u + (vt->max_window + 1u) / 2u;
-	a.tile_dw = pxz::varied_expand_tile_dw(a.bw, a.bh, a.wdw);
 	// a wave's image beyond LDS (with the images' first tiles beside it) lives in HBM, one per wave of the grid
-	if ((uint64_t)a.tile_dw * 4u + 8192u > 160u * 1024u) {
+	if (varied_image_beyond_lds(a.tile_dw)) {
 		const uint64_t waves = 4ull * h->n_cus;
 		if ((rc = ensure(h, h->bigscratch, (size_t)waves * a.tile_dw * 4u)) != PXZ_OK) return rc;
 		a.big_scratch = (uint32_t *)h->bigscratch.ptr;
 		a.big_waves = (uint32_t)waves;
 	}
-	if ((rc = ensure(h, h->status, 256)) != PXZ_OK) return rc;
-	a.status = (uint32_t *)h->status.ptr;
-	PXZ_HIP(h, hipMemsetAsync(a.status, 0, 8, h->stream));
+	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
 	if (d_image_flags) PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, (size_t)n_images * 4u, h->stream));
 	a.image_flags = d_image_flags;
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
@@ -2568,6 +2608,141 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 	if (first_bad != n_images)
 		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
 		            flags[first_bad] | flags[n_images + first_bad]);
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- rate and distortion (pxz_distortion.hip) -----------------------------------------------------------------------------
+namespace {
+
+// Both distortion calls behind their checks: a planned flat tile space (a varied batch, or n_frames equal entries), n_sets
+// stored versions of its tiles.  One table copy, three memsets and one launch, whatever the batch holds.
+int distortion_launch(pxz_handle *h, const std::vector<pxz::VariedImage> &images, const std::vector<uint32_t> &sides, uint32_t channels,
+                      const pxz_params &p, uint32_t n_sets, const uint8_t *d_base, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                      const uint8_t *d_slots, uint64_t *d_tile_sse, uint64_t *d_image_sse, uint32_t *d_image_flags)
+{
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::DistortionArgs a{};
+	int rc = put_varied_expand_tables(h, p, channels, sides, &a, true);
+	if (rc != PXZ_OK) return rc;
+	if (varied_image_beyond_lds(a.tile_dw))  // (a cached set that a caller with another block of the same sides left)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile of %u channels and its windows in LDS: %llu bytes exceed what a block has", a.bw,
+		            a.bh, channels, (unsigned long long)a.tile_dw * 4u);
+	a.n_images = (uint32_t)images.size();
+	a.n_tiles = varied_n_tiles(images);
+	a.n_sets = n_sets;
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.base = d_base;
+	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
+	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
+	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
+	if (d_image_flags) PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, images.size() * 4u, h->stream));
+	a.image_flags = d_image_flags;
+	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * images.size() * channels * 8u, h->stream));
+	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
+	PXZ_HIP(h, pxz::launch_distortion(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_distortion_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_params *params, uint32_t n_sets,
+                                 const uint8_t *d_pixels, const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots,
+                                 uint64_t *d_tile_sse, uint64_t *d_frame_sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!frames || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null descriptor");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = check_frames(h, frames, &p);
+	if (rc != PXZ_OK) return rc;
+	if (n_sets == 0) return fail(h, PXZ_ERR_INVALID_ARG, "n_sets must be at least 1");
+	if (!d_pixels || !d_tile_w || !d_tile_h || !d_slots || !d_frame_sse) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if ((uint64_t)p.block_w * p.block_h * frames->channels > kVariedMaxTileBytes)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "every tile is staged in LDS: block_w*block_h*channels must not exceed %llu bytes",
+		            (unsigned long long)kVariedMaxTileBytes);
+	Grid g;
+	if ((rc = make_grid(h, frames->width, frames->height, p.block_w, p.block_h, frames->n_frames, 0xffffffffull, &g)) != PXZ_OK) return rc;
+	// the batch as n_frames equal entries of the per-image table
+	pxz::VariedImage im{};
+	im.width = frames->width;
+	im.height = frames->height;
+	im.pitch = frames->pitch_bytes;
+	im.cols = g.cols;
+	im.rows = g.rows;
+	im.edge_w = g.edge_w;
+	im.edge_h = g.edge_h;
+	im.hdr_bytes = 26u + 4u * g.rows;
+	std::vector<pxz::VariedImage> images(frames->n_frames, im);
+	const uint64_t stride = frames->n_frames > 1 ? frames->frame_stride_bytes : 0;
+	for (uint32_t f = 0; f < frames->n_frames; ++f) {
+		images[f].offset = f * stride;
+		images[f].tile0 = f * g.tiles_per_frame;
+		images[f].row0 = f * g.rows;
+	}
+	std::vector<uint32_t> sides = {p.block_w, p.block_h, g.edge_w, g.edge_h};
+	std::sort(sides.begin(), sides.end());
+	sides.erase(std::unique(sides.begin(), sides.end()), sides.end());
+	return distortion_launch(h, images, sides, frames->channels, p, n_sets, d_pixels, d_tile_w, d_tile_h, d_slots, d_tile_sse, d_frame_sse,
+	                         nullptr);
+}
+
+int pxz_distortion_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                        const pxz_params *params, const uint8_t *d_base, const uint32_t *d_tile_w,
+                                        const uint32_t *d_tile_h, const uint8_t *d_slots, uint64_t *d_tile_sse, uint64_t *d_image_sse,
+                                        uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_base || !d_tile_w || !d_tile_h || !d_slots || !d_image_sse) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	return distortion_launch(h, images, sides, channels, p, 1, d_base, d_tile_w, d_tile_h, d_slots, d_tile_sse, d_image_sse, d_image_flags);
+}
+
+int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                              uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                              uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
+	if (n_factors == 0 || n_factors > PXZ_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_LADDER_MAX_RUNGS, n_factors);
+	if (!pixels || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
+	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
+	int rc = check_params(h, &up);
+	if (rc != PXZ_OK) return rc;
+	pxz_frames f;
+	size_t tiles = 0, slot = 0;
+	if ((rc = stage_host_image(h, pixels, width, height, channels, pitch_bytes, &p, n_factors, true, &f, &tiles, &slot)) != PXZ_OK) return rc;
+	// the files' offsets, the rungs' sums, and the room the writer is given (none: only its offsets are wanted)
+	const size_t n_out = (size_t)n_factors + 1u + (size_t)n_factors * channels;
+	if ((rc = ensure(h, h->rd, n_out * 8u + 256u)) != PXZ_OK) return rc;
+	uint64_t *d_offs = (uint64_t *)h->rd.ptr, *d_sse = d_offs + n_factors + 1u;
+	const uint8_t *d_in = (const uint8_t *)h->in.ptr;
+	float *d_val = (float *)h->val.ptr;
+	uint32_t *d_w = (uint32_t *)h->ow.ptr, *d_h = (uint32_t *)h->oh.ptr;
+	uint8_t *d_slots = (uint8_t *)h->out.ptr;
+	if ((rc = pxz_shrink_ladder_frames_device(h, &f, &p, factors, n_factors, d_in, d_val, d_w, d_h, d_slots)) != PXZ_OK) return rc;
+	pxz_frames rungs = f;  // the rung sets as a batch of n_factors frames
+	rungs.n_frames = n_factors;
+	rungs.frame_stride_bytes = (uint64_t)f.pitch_bytes * height;
+	if ((rc = pxz_encode_frames_device(h, &rungs, &p, 0, d_val, d_w, d_h, d_slots, (uint8_t *)(d_offs + n_out), 0, d_offs)) != PXZ_OK) return rc;
+	if ((rc = pxz_distortion_frames_device(h, &f, &up, n_factors, d_in, d_w, d_h, d_slots, nullptr, d_sse)) != PXZ_OK) return rc;
+	std::vector<uint64_t> got(n_out);
+	PXZ_HIP(h, hipMemcpyAsync(got.data(), d_offs, n_out * 8u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint32_t r = 0; r < n_factors; ++r) file_bytes[r] = got[r + 1u] - got[r];
+	std::memcpy(sse, got.data() + n_factors + 1u, (size_t)n_factors * channels * 8u);
 	return PXZ_OK;
 }
 

@@ -1080,4 +1080,147 @@ __device__ __forceinline__ void list_push(uint32_t *buf, uint32_t &cnt, uint32_t
 	if (cnt == kListBatch) list_flush(buf, cnt, list, counter, lane);
 }
 
+// ---------------------------------------------------------------------------
+// One stored tile of a varied batch back at its full size, in the wave's LDS image: steps 2 and 3 of
+// varied_expand_kernel (pxz_varied_expand.hip), which distortion_kernel (pxz_distortion.hip) runs too.
+//   2. the stored pixels (tw x th at src, tightly packed) -> one dword per pixel in s_src (RGBA under a convolution
+//      alpha-premultiplied as fir does), and the windows of both axis tables -- directory entry (full size, stored size) of
+//      a.dir -- in s_wx / s_wy: per output sample a.wdw dwords, first | count << 16, then the weights as i16 pairs;
+//   3. the resize of PixlzrBlock::resize (block.rs:273-334): a clone when the sizes agree, the Nearest pick, else the
+//      horizontal then the vertical pass with i16 weights and i32 accumulators, u8 between the passes, un-premultiplied
+//      at the end.
+// Returns the plane (s_src or s_tmp) that holds the fw x fh result, one dword per pixel; wsync() has run behind its last
+// write.  stage_x / stage_y false: the windows of that axis are in s_wx / s_wy already (the same full and stored size as
+// the tile this wave resized before).  Args: VariedExpandArgs or DistortionArgs (the fields both name alike).
+// ---------------------------------------------------------------------------
+
+// the clamp spelled as an instruction: left to the compiler, clip8(a) | clip8(b) << 8 of an RGB pixel became
+// v_ashr_pk_u8_i32, whose upper half keeps what the destination held (pxz_expand.hip)
+__device__ __forceinline__ uint32_t clip8_med3(int32_t acc, int prec)
+{
+	const int32_t v = acc >> prec;
+	int32_t r;
+	asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(255));
+	return (uint32_t)r;
+}
+
+template <int C, class Args, class Sync>
+__device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uint32_t lane, const uint8_t *src, uint32_t tw, uint32_t th,
+                                                              uint32_t fw, uint32_t fh, uint32_t *s_src, uint32_t *s_tmp, uint32_t *s_wx,
+                                                              uint32_t *s_wy, bool stage_x, bool stage_y, Sync wsync)
+{
+	const bool same = tw == fw && th == fh;
+	const bool conv = a.filter != 0u && !same;
+
+	// ---- 2. stored pixels -> one dword per pixel; the windows of both axes
+	const uint32_t n = tw * th;
+	for (uint32_t i = lane; i < n; i += 64u) {
+		uint32_t px;
+		if constexpr (C == 4) {
+			px = reinterpret_cast<const uint32_t *>(src)[i];
+			if (conv) px = premultiply(px);  // fir: U8x4 is alpha-premultiplied before a convolution
+		} else {
+			// one dword from the pixel's byte address (the slot's last pixel: from a byte earlier, shifted)
+			typedef uint32_t u32_a1 __attribute__((aligned(1)));
+			if (a.slot_bytes >= 4u) {
+				const uint32_t at = 3u * i + 4u <= a.slot_bytes ? 3u * i : a.slot_bytes - 4u;
+				px = (*reinterpret_cast<const u32_a1 *>(src + at) >> (8u * (3u * i - at))) | 0xff000000u;
+			} else {  // (1x1 blocks)
+				px = (uint32_t)src[3 * i] | ((uint32_t)src[3 * i + 1] << 8) | ((uint32_t)src[3 * i + 2] << 16) | 0xff000000u;
+			}
+		}
+		s_src[i] = px;
+	}
+	ExpandTab tab_x{0, 0, 0, 0}, tab_y{0, 0, 0, 0};
+	// per output sample wdw dwords: first | count << 16, then the weights as i16 pairs (a zero in the spare half)
+	auto stage_windows = [&](uint32_t *wd, const ExpandTab &tab, uint32_t outs) {
+		for (uint32_t o = lane; o < outs; o += 64u) {
+			uint32_t *d = wd + a.wdw * o;
+			const uint32_t first = a.starts[tab.start_off + o];
+			const uint32_t cnt = a.filter == 0u ? 1u : a.sizes[tab.start_off + o];
+			d[0] = first | (cnt << 16);
+			if (a.filter != 0u) {
+				const int16_t *k = a.coeffs + tab.coeff_off + o * tab.window;
+				for (uint32_t j = 0; j < cnt; j += 2u)
+					d[1u + (j >> 1)] = (uint32_t)(uint16_t)k[j] | (j + 1u < cnt ? (uint32_t)(uint16_t)k[j + 1u] << 16 : 0u);
+			}
+		}
+	};
+	if (tw != fw) {
+		tab_x = a.dir[(size_t)a.slot[fw] * a.stride + tw];
+		if (stage_x) stage_windows(s_wx, tab_x, fw);
+	}
+	if (th != fh) {
+		tab_y = a.dir[(size_t)a.slot[fh] * a.stride + th];
+		if (stage_y) stage_windows(s_wy, tab_y, fh);
+	}
+	wsync();
+
+	// ---- 3. the resize into an image of fw x fh dwords
+	const uint32_t *out = s_src;  // block.rs:279-281: clone
+	if (same) {
+	} else if (a.filter == 0u) {  // ResizeAlg::Nearest
+		RowWalker rw(lane, 64u, fw);
+		for (uint32_t i = lane; i < fw * fh; i += 64u, rw.next()) {
+			const uint32_t x = tw == fw ? rw.col : (s_wx[a.wdw * rw.col] & 0xffffu), y = th == fh ? rw.row : (s_wy[a.wdw * rw.row] & 0xffffu);
+			s_tmp[i] = s_src[y * tw + x];
+		}
+		out = s_tmp;
+		wsync();
+	} else {
+		const bool need_h = tw != fw, need_v = th != fh;
+		if (need_h) {
+			// horizontal pass: item = (ox, y) of the th stored rows
+			const int prec = tab_x.precision;
+			const int32_t init = 1 << (prec - 1);
+			RowWalker rw(lane, 64u, fw);
+			for (uint32_t i = lane; i < fw * th; i += 64u, rw.next()) {
+				const uint32_t *wd = s_wx + a.wdw * rw.col;
+				const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
+				const uint32_t *row = s_src + rw.row * tw + first;
+				int32_t acc[4] = {init, init, init, init};
+				// two taps per v_dot2_i32_i16 (an odd count has a zero weight for the pixel read past the window, which is
+				// still inside this wave's image)
+				for (uint32_t j = 0; j < cnt; j += 2u) {
+					const uint32_t w2 = wd[1u + (j >> 1)], p0 = row[j], p1 = row[j + 1u];
+#pragma unroll
+					for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
+				}
+				uint32_t px = clip8_med3(acc[0], prec) | (clip8_med3(acc[1], prec) << 8) | (clip8_med3(acc[2], prec) << 16);
+				px |= C == 4 ? clip8_med3(acc[3], prec) << 24 : 0xff000000u;
+				if (C == 4 && !need_v) px = unpremultiply(px);
+				s_tmp[i] = px;
+			}
+			out = s_tmp;
+			wsync();
+		}
+		if (need_v) {
+			// vertical pass: item = (ox, oy); the rows it reads are fw wide (fw == tw when only this pass runs)
+			const uint32_t *cur = need_h ? s_tmp : s_src;
+			uint32_t *o = need_h ? s_src : s_tmp;
+			const int prec = tab_y.precision;
+			const int32_t init = 1 << (prec - 1);
+			RowWalker rw(lane, 64u, fw);
+			for (uint32_t i = lane; i < fw * fh; i += 64u, rw.next()) {
+				const uint32_t *wd = s_wy + a.wdw * rw.row;
+				const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
+				const uint32_t *col = cur + first * fw + rw.col;
+				int32_t acc[4] = {init, init, init, init};
+				for (uint32_t j = 0; j < cnt; j += 2u) {
+					const uint32_t w2 = wd[1u + (j >> 1)], p0 = col[j * fw], p1 = col[(j + 1u) * fw];
+#pragma unroll
+					for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
+				}
+				uint32_t px = clip8_med3(acc[0], prec) | (clip8_med3(acc[1], prec) << 8) | (clip8_med3(acc[2], prec) << 16);
+				px |= C == 4 ? clip8_med3(acc[3], prec) << 24 : 0xff000000u;
+				if constexpr (C == 4) px = unpremultiply(px);
+				o[i] = px;
+			}
+			out = o;
+			wsync();
+		}
+	}
+	return out;
+}
+
 }  // namespace pxz

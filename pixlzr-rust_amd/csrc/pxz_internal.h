@@ -515,6 +515,32 @@ struct VariedExpandArgs {
 	uint32_t big_waves;               //   (0: the images are in LDS)
 };
 
+// Squared error of stored tiles against their source (pxz_distortion_frames_device, pxz_distortion_varied_frames_device;
+// pxz_distortion.hip): the flat tile space and the tables of VariedExpandArgs (the fields varied_resize_tile reads carry the
+// same names), n_sets stored versions of every tile, set-major: set s of tile t is at index s * n_tiles + t of tile_w,
+// tile_h and slots.  The wave's image is always in LDS (no HBM form).
+struct DistortionArgs {
+	const VariedImage *images;
+	uint32_t n_images, n_tiles, n_sets;
+	const uint32_t *tile_w, *tile_h;  // per set and tile: stored size
+	const uint8_t *slots;             // per set and tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
+	const uint8_t *base;              // the source: image i at base + images[i].offset, images[i].pitch between rows
+	uint32_t bw, bh, slot_bytes, filter;
+	const uint32_t *slot;
+	const ExpandTab *dir;
+	uint32_t stride;
+	const uint16_t *starts, *sizes;
+	const int16_t *coeffs;
+	uint32_t wdw, tile_dw;            // as VariedExpandArgs
+	uint32_t t0_dw;                   // (set by the launch) dwords of the images' first tiles kept in LDS, 0: read from `images`
+	uint32_t *status;                 // bit 0: a tile's stored size is 0 or exceeds its full size
+	uint32_t *image_flags;            // per image 1 for the same, or null
+	unsigned long long *tile_sse;     // per set, tile and channel (index (s * n_tiles + t) * channels + c), or null; all-ones for a
+	                                  //   tile whose stored size is invalid
+	unsigned long long *image_sse;    // per set, image and channel (index (s * n_images + i) * channels + c): the sums over the
+	                                  //   image's valid tiles, added with atomics (zeroed before the launch)
+};
+
 struct SynthArgs {
 	uint8_t *dst;
 	uint64_t frame_stride;

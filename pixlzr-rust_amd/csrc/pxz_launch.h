@@ -23,6 +23,10 @@ hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, 
                                 hipStream_t stream);
 hipError_t launch_varied_expand(const VariedExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw);
+// the LDS form's grid for n_tiles tiles of n_images images, one wave per tile: *t0_dw = dwords of the images' first tiles a
+// block keeps in LDS (0: more images than it holds); threads == 0: one wave's image does not fit
+LaunchGeom varied_expand_geom(uint32_t n_images, uint32_t n_tiles, uint32_t tile_dw, uint32_t n_cus, uint32_t *t0_dw);
+hipError_t launch_distortion(const DistortionArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_widen(const WidenArgs &a, hipStream_t stream);
 hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);
 hipError_t launch_pack(const PackArgs &a, hipStream_t stream);

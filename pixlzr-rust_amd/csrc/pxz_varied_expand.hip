@@ -14,6 +14,7 @@
 //   4. is written to its place: every row segment once, 16 bytes per lane with streaming stores where the segment starts on
 //      a dword (any image whose offset and pitch are multiples of 4), pixel by pixel where an odd offset or pitch puts it
 //      elsewhere; RGB rows as 12-byte groups of four pixels.
+// Steps 2 and 3 are varied_resize_tile (pxz_device.h), which distortion_kernel (pxz_distortion.hip) runs too.
 // Tiles whose image (two tile-sized planes and the windows) exceeds LDS keep it in HBM, one image per wave of the grid
 // (BIG: RGB blocks above 20 000 pixels), as expand_kernel<C, false, true> does.
 #include "pxz_device.h"
@@ -44,14 +45,6 @@ __global__ void __launch_bounds__(512) varied_expand_kernel(const VariedExpandAr
 	uint32_t *s_src = BIG ? a.big_scratch + (size_t)(blockIdx.x * wpb + sub) * a.tile_dw : lds + a.t0_dw + sub * a.tile_dw;
 	uint32_t *s_tmp = s_src + a.bw * a.bh;
 	uint32_t *s_wx = s_tmp + a.bw * a.bh, *s_wy = s_wx + a.wdw * a.bw;
-	// the clamp spelled as an instruction: left to the compiler, clip8(a) | clip8(b) << 8 of an RGB pixel became
-	// v_ashr_pk_u8_i32, whose upper half keeps what the destination held (pxz_expand.hip)
-	auto clipv = [](int32_t acc, int prec) __attribute__((always_inline)) -> uint32_t {
-		const int32_t v = acc >> prec;
-		int32_t r;
-		asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(255));
-		return (uint32_t)r;
-	};
 
 	for (uint32_t t = blockIdx.x * wpb + sub; t < a.n_tiles; t += gridDim.x * wpb) {
 		// ---- 1. the image and the tile's place in it
@@ -76,117 +69,8 @@ __global__ void __launch_bounds__(512) varied_expand_kernel(const VariedExpandAr
 		}
 		uint8_t *dst = a.base + im.offset + (size_t)(ty * a.bh) * im.pitch + (size_t)(tx * a.bw) * (uint32_t)C;
 		const uint8_t *src = a.slots + (size_t)t * a.slot_bytes;
-		const bool same = tw == fw && th == fh;
-		const bool conv = a.filter != 0u && !same;
-
-		// ---- 2. stored pixels -> one dword per pixel; the windows of both axes
-		const uint32_t n = tw * th;
-		for (uint32_t i = lane; i < n; i += 64u) {
-			uint32_t px;
-			if constexpr (C == 4) {
-				px = reinterpret_cast<const uint32_t *>(src)[i];
-				if (conv) px = premultiply(px);  // fir: U8x4 is alpha-premultiplied before a convolution
-			} else {
-				// one dword from the pixel's byte address (the slot's last pixel: from a byte earlier, shifted)
-				typedef uint32_t u32_a1 __attribute__((aligned(1)));
-				if (a.slot_bytes >= 4u) {
-					const uint32_t at = 3u * i + 4u <= a.slot_bytes ? 3u * i : a.slot_bytes - 4u;
-					px = (*reinterpret_cast<const u32_a1 *>(src + at) >> (8u * (3u * i - at))) | 0xff000000u;
-				} else {  // (1x1 blocks)
-					px = (uint32_t)src[3 * i] | ((uint32_t)src[3 * i + 1] << 8) | ((uint32_t)src[3 * i + 2] << 16) | 0xff000000u;
-				}
-			}
-			s_src[i] = px;
-		}
-		ExpandTab tab_x{0, 0, 0, 0}, tab_y{0, 0, 0, 0};
-		// per output sample wdw dwords: first | count << 16, then the weights as i16 pairs (a zero in the spare half)
-		auto stage_windows = [&](uint32_t *wd, const ExpandTab &tab, uint32_t outs) {
-			for (uint32_t o = lane; o < outs; o += 64u) {
-				uint32_t *d = wd + a.wdw * o;
-				const uint32_t first = a.starts[tab.start_off + o];
-				const uint32_t cnt = a.filter == 0u ? 1u : a.sizes[tab.start_off + o];
-				d[0] = first | (cnt << 16);
-				if (a.filter != 0u) {
-					const int16_t *k = a.coeffs + tab.coeff_off + o * tab.window;
-					for (uint32_t j = 0; j < cnt; j += 2u)
-						d[1u + (j >> 1)] = (uint32_t)(uint16_t)k[j] | (j + 1u < cnt ? (uint32_t)(uint16_t)k[j + 1u] << 16 : 0u);
-				}
-			}
-		};
-		if (tw != fw) {
-			tab_x = a.dir[(size_t)a.slot[fw] * a.stride + tw];
-			stage_windows(s_wx, tab_x, fw);
-		}
-		if (th != fh) {
-			tab_y = a.dir[(size_t)a.slot[fh] * a.stride + th];
-			stage_windows(s_wy, tab_y, fh);
-		}
-		wsync();
-
-		// ---- 3. the resize into an image of fw x fh dwords
-		const uint32_t *out = s_src;  // block.rs:279-281: clone
-		if (same) {
-		} else if (a.filter == 0u) {  // ResizeAlg::Nearest
-			RowWalker rw(lane, 64u, fw);
-			for (uint32_t i = lane; i < fw * fh; i += 64u, rw.next()) {
-				const uint32_t x = tw == fw ? rw.col : (s_wx[a.wdw * rw.col] & 0xffffu), y = th == fh ? rw.row : (s_wy[a.wdw * rw.row] & 0xffffu);
-				s_tmp[i] = s_src[y * tw + x];
-			}
-			out = s_tmp;
-			wsync();
-		} else {
-			const bool need_h = tw != fw, need_v = th != fh;
-			if (need_h) {
-				// horizontal pass: item = (ox, y) of the th stored rows
-				const int prec = tab_x.precision;
-				const int32_t init = 1 << (prec - 1);
-				RowWalker rw(lane, 64u, fw);
-				for (uint32_t i = lane; i < fw * th; i += 64u, rw.next()) {
-					const uint32_t *wd = s_wx + a.wdw * rw.col;
-					const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
-					const uint32_t *row = s_src + rw.row * tw + first;
-					int32_t acc[4] = {init, init, init, init};
-					// two taps per v_dot2_i32_i16 (an odd count has a zero weight for the pixel read past the window, which is
-					// still inside this wave's image)
-					for (uint32_t j = 0; j < cnt; j += 2u) {
-						const uint32_t w2 = wd[1u + (j >> 1)], p0 = row[j], p1 = row[j + 1u];
-#pragma unroll
-						for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
-					}
-					uint32_t px = clipv(acc[0], prec) | (clipv(acc[1], prec) << 8) | (clipv(acc[2], prec) << 16);
-					px |= C == 4 ? clipv(acc[3], prec) << 24 : 0xff000000u;
-					if (C == 4 && !need_v) px = unpremultiply(px);
-					s_tmp[i] = px;
-				}
-				out = s_tmp;
-				wsync();
-			}
-			if (need_v) {
-				// vertical pass: item = (ox, oy); the rows it reads are fw wide (fw == tw when only this pass runs)
-				const uint32_t *cur = need_h ? s_tmp : s_src;
-				uint32_t *o = need_h ? s_src : s_tmp;
-				const int prec = tab_y.precision;
-				const int32_t init = 1 << (prec - 1);
-				RowWalker rw(lane, 64u, fw);
-				for (uint32_t i = lane; i < fw * fh; i += 64u, rw.next()) {
-					const uint32_t *wd = s_wy + a.wdw * rw.row;
-					const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
-					const uint32_t *col = cur + first * fw + rw.col;
-					int32_t acc[4] = {init, init, init, init};
-					for (uint32_t j = 0; j < cnt; j += 2u) {
-						const uint32_t w2 = wd[1u + (j >> 1)], p0 = col[j * fw], p1 = col[(j + 1u) * fw];
-#pragma unroll
-						for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
-					}
-					uint32_t px = clipv(acc[0], prec) | (clipv(acc[1], prec) << 8) | (clipv(acc[2], prec) << 16);
-					px |= C == 4 ? clipv(acc[3], prec) << 24 : 0xff000000u;
-					if constexpr (C == 4) px = unpremultiply(px);
-					o[i] = px;
-				}
-				out = o;
-				wsync();
-			}
-		}
+		// ---- 2., 3. the stored pixels and the windows of both axes -> LDS; the resize into an image of fw x fh dwords
+		const uint32_t *out = varied_resize_tile<C>(a, lane, src, tw, th, fw, fh, s_src, s_tmp, s_wx, s_wy, true, true, wsync);
 
 		// ---- 4. the image to its place, row segment by row segment: item = (row, group of four pixels)
 		const uint32_t q4 = (fw + 3u) >> 2;
@@ -240,12 +124,27 @@ __global__ void __launch_bounds__(512) varied_expand_kernel(const VariedExpandAr
 // LDS dwords of one wave's image: the stored pixels and the other plane (bw * bh each), then the staged windows
 uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw) { return (2u * bw * bh + wdw * (bw + bh) + 3u) & ~3u; }
 
+LaunchGeom varied_expand_geom(uint32_t n_images, uint32_t n_tiles, uint32_t tile_dw, uint32_t n_cus, uint32_t *t0_dw)
+{
+	constexpr uint32_t kLds = 160u * 1024u;
+	*t0_dw = n_images <= kVxImages ? (n_images + 3u) & ~3u : 0u;
+	const uint32_t tile_bytes = tile_dw * 4u;
+	uint32_t wpb = (kLds - *t0_dw * 4u) / tile_bytes;
+	if (wpb > 8u) wpb = 8u;
+	if (wpb < 1u) return LaunchGeom{0u, 0u, 0u};
+	const uint32_t lds_bytes = *t0_dw * 4u + wpb * tile_bytes;
+	uint32_t per_cu = kLds / lds_bytes;
+	per_cu = per_cu < 1u ? 1u : (per_cu > 4u ? 4u : per_cu);
+	// (a few waves' worth of tiles per wave: the tiles of a batch differ in cost, the grid-stride loop evens them out)
+	const uint64_t need = ((uint64_t)n_tiles + wpb - 1u) / wpb, cap = (uint64_t)n_cus * per_cu * 4u;
+	return LaunchGeom{(uint32_t)(need < cap ? need : cap), 64u * wpb, lds_bytes};
+}
+
 hipError_t launch_varied_expand(const VariedExpandArgs &args, uint32_t channels, uint32_t n_cus, hipStream_t stream)
 {
 	if (args.n_tiles == 0u) return hipSuccess;
 	VariedExpandArgs a = args;
-	constexpr uint32_t kLds = 160u * 1024u;
-	a.t0_dw = a.n_images <= kVxImages ? (a.n_images + 3u) & ~3u : 0u;
+	const LaunchGeom g = varied_expand_geom(a.n_images, a.n_tiles, a.tile_dw, n_cus, &a.t0_dw);
 	hipError_t e;
 	if (a.big_waves != 0u) {
 		// tile images in HBM: blocks of 4 waves, as many as the scratch holds images for
@@ -255,21 +154,12 @@ hipError_t launch_varied_expand(const VariedExpandArgs &args, uint32_t channels,
 		else hipLaunchKernelGGL((varied_expand_kernel<3, true>), dim3(blocks), dim3(64u * wpb), a.t0_dw * 4u, stream, a);
 		return hipGetLastError();
 	}
-	const uint32_t tile_bytes = a.tile_dw * 4u;
-	uint32_t wpb = (kLds - a.t0_dw * 4u) / tile_bytes;
-	if (wpb > 8u) wpb = 8u;
-	if (wpb < 1u) return hipErrorInvalidValue;
-	const uint32_t lds_bytes = a.t0_dw * 4u + wpb * tile_bytes;
-	uint32_t per_cu = kLds / lds_bytes;
-	per_cu = per_cu < 1u ? 1u : (per_cu > 4u ? 4u : per_cu);
-	// (a few waves' worth of tiles per wave: the tiles of a batch differ in cost, the grid-stride loop evens them out)
-	const uint64_t need = ((uint64_t)a.n_tiles + wpb - 1u) / wpb, cap = (uint64_t)n_cus * per_cu * 4u;
-	const uint32_t blocks = (uint32_t)(need < cap ? need : cap);
+	if (g.threads == 0u) return hipErrorInvalidValue;
 	auto go = [&](auto kernel) -> hipError_t {
-		if (lds_bytes > 64u * 1024u &&
-		    (e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)) != hipSuccess)
+		if (g.lds_bytes > 64u * 1024u &&
+		    (e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes)) != hipSuccess)
 			return e;
-		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * wpb), lds_bytes, stream, a);
+		hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, stream, a);
 		return hipGetLastError();
 	};
 	return channels == 4u ? go(varied_expand_kernel<4, false>) : go(varied_expand_kernel<3, false>);
