@@ -367,6 +367,77 @@ int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t ch
                      uint32_t block_w, uint32_t block_h, uint32_t filter, const uint32_t *tile_w,
                      const uint32_t *tile_h, const uint8_t *slots, uint8_t *out_pixels);
 
+/* ---- windows of files: pixel rectangles of .pixlzr files, without reading the rest ---- */
+
+/* One pixel rectangle of one file of a call.  The container is built for random access -- the header carries one length per
+ * tile row (encode_to_vec, src/encoding/mod.rs:77-82) and every record its own (encode_block, :193-197) -- and the reference
+ * never uses it: decode_from_vec (mod.rs:95-165) reads whole images.  A viewer wants a viewport of a large frame, a data
+ * loader one crop from each of a few hundred files. */
+typedef struct pxz_window {
+	uint32_t image;                 /* index into descs / the files of the call; several windows may name one image */
+	uint32_t x, y, width, height;   /* pixel rectangle in that image: non-empty, wholly inside it */
+	uint32_t pitch_bytes;           /* of the OUTPUT rows, >= width*channels */
+	uint64_t offset_bytes;          /* output start relative to the call's base pointer, any alignment */
+} pxz_window;
+
+/* Layout of the per-tile outputs of a call over windows (host only: no handle, no GPU, like pxz_varied_layout).  Window k
+ * covers tile columns x/block_w .. (x+width-1)/block_w and tile rows y/block_h .. (y+height-1)/block_h of its image; its
+ * covered tiles are numbered row-major inside that covered grid, starting at tile_offsets[k], and tile_offsets[n_windows] is
+ * the call's tile count.  A tile that two windows cover is there twice.  Slots stay block_w*block_h*channels bytes.
+ * PXZ_ERR_INVALID_ARG for a null pointer, n_windows 0, an image index out of range, an empty rectangle or one that leaves its
+ * image, and everything pxz_varied_layout refuses for the descriptors; PXZ_ERR_UNSUPPORTED for more than 2^32-1 covered tiles
+ * (and what pxz_varied_layout answers with it). */
+int pxz_window_layout(const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows,
+                      uint32_t block_w, uint32_t block_h, uint64_t *tile_offsets);
+
+/* Pixlzr::decode_from_vec (encoding/mod.rs:95-165) + decode_block (:202-242) for the covered tiles of the windows only, in
+ * the pxz_window_layout order.  The files are given as for pxz_decode_varied_frames_device: n_images files back to back in
+ * d_files, file i = [d_file_offsets[i], d_file_offsets[i+1]); of descs[i] only width and height are read, of a window its
+ * image and rectangle, of params block_w and block_h.  Asynchronous on the handle's stream; the number of launches and
+ * copies depends on neither n_images nor n_windows.  Per covered tile the outputs (value bits, stored size, the valid slot
+ * bytes) are what pxz_decode_varied_frames_device gives for that tile.
+ * What is read of a file: its 26-byte header, with the checks of the varied reader; its line table, which must sum to the
+ * file's length; and in each covered tile row the records from the row's start up to the window's last column.  Records
+ * left of the window are walked by their length fields and header-checked (a broken one ends the walk) but neither
+ * published nor decoded; records right of the window, and tile rows outside it, are not touched.
+ * So damage outside that range does not flag a window: a file that pxz_decode_varied_frames_device flags may give clean
+ * windows.  Damage inside it flags the window and gives the affected covered tiles size 0x0, exactly as the varied reader
+ * does for its image (a broken record takes the rest of its tile row with it).  d_window_flags (n_windows dwords, may be
+ * NULL) receives 0 or 2 per window; pxz_decode_status reports the OR over the windows.
+ * Validation runs on the host before anything is launched, with the codes of the varied reader and pxz_window_layout's
+ * rules; the texts name "image i" or "window k"; on an error nothing is written. */
+int pxz_decode_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows,
+                              uint32_t n_windows, uint32_t channels, const pxz_params *params, const uint8_t *d_files,
+                              const uint64_t *d_file_offsets, float *d_block_value, uint32_t *d_tile_w, uint32_t *d_tile_h,
+                              uint8_t *d_slots, uint32_t *d_window_flags);
+
+/* Pixlzr::expand (pixlzr.rs:77-122) + to_image (pixlzr_image.rs:24-74) for the windows: every covered tile (as the call above
+ * leaves them) is resized to its full size with params->filter as PixlzrBlock::resize does (block.rs:273-334), and the
+ * intersection of the tile with the window is written: pixel (px, py) of the image goes to d_base + offset_bytes +
+ * (py - y)*pitch_bytes + (px - x)*channels.  No byte outside the window's width*channels bytes per row, for height rows, is
+ * written.  Window k equals the same rectangle of what pxz_expand_varied_frames_device writes for its image, byte for byte.
+ * Overlapping output rectangles are the caller's business: which window's bytes such a place ends up with is not defined.
+ * A covered tile whose stored size is zero or exceeds its place is skipped (its pixels stay as they were) and flagged:
+ * d_window_flags (may be NULL) receives 0 or 1 per window, pxz_decode_status bit 0 the OR.  Asynchronous; validation as above
+ * (here the windows' pitches count too, and params->filter).  Limits are those of pxz_distortion_*: a wave keeps the tile in
+ * LDS, so block_w*block_h*channels must not exceed 65536 bytes and RGB blocks must stay below the size (about 19 400
+ * pixels) where pxz_expand_varied_frames_device moves its tiles to HBM; PXZ_ERR_UNSUPPORTED beyond.  There is no HBM form. */
+int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows,
+                              uint32_t n_windows, uint32_t channels, const pxz_params *params, const uint32_t *d_tile_w,
+                              const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_window_flags);
+
+/* Host files in, host crops out, synchronously.  files[i] / lens[i] is file i; window k is written at out_base +
+ * windows[k].offset_bytes with windows[k].pitch_bytes between rows, and must end inside the out_bytes bytes at out_base
+ * (PXZ_ERR_BUFFER_TOO_SMALL, "window k").  Composition only, as pxz_decode_varied_files: every header is parsed on the host
+ * first (pxz_file_header) and a file whose size, block size or channels disagree with descs[i] and the call is refused
+ * (PXZ_ERR_INVALID_ARG, "image i"), nothing written; then one upload (the files go whole), the two calls above, one download.
+ * Windows that come back flagged -- window_flags[k] (may be NULL), bits as pxz_decode_status -- have the tiles that could not
+ * be read left zero; the call then returns PXZ_ERR_INVALID_ARG naming the first such window, and every other window is
+ * complete.  Errors and limits as pxz_expand_windows_device.  pxz_trim returns the scratch. */
+int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
+                             uint32_t n_images, const pxz_window *windows, uint32_t n_windows, uint32_t channels,
+                             const pxz_params *params, uint8_t *out_base, uint64_t out_bytes, uint32_t *window_flags);
+
 /* ---- rate and distortion: what a factor costs and what it loses ---------------- */
 
 /* The squared error of stored tiles against the frames they were shrunk from.  Nothing in the reference computes it:

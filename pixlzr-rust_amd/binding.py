@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "pxz_varied_layout", "pxz_shrink_varied_frames_device", "pxz_encode_varied_frames_device", "pxz_encode_varied_images",
     "pxz_file_header", "pxz_decode_varied_frames_device", "pxz_expand_varied_frames_device", "pxz_decode_varied_files",
     "pxz_distortion_frames_device", "pxz_distortion_varied_frames_device", "pxz_rate_distortion_image",
+    "pxz_window_layout", "pxz_decode_windows_device", "pxz_expand_windows_device", "pxz_decode_windows_files",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -60,6 +61,19 @@ def image_descs(geoms):
     arr = (ImageDesc * max(len(geoms), 1))()
     for i, g in enumerate(geoms):
         arr[i] = ImageDesc(g[0], g[1], g[2], g[4] if len(g) > 4 else 0, g[3])
+    return arr
+
+
+class Window(C.Structure):
+    _fields_ = [("image", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("pitch_bytes", C.c_uint32), ("offset_bytes", C.c_uint64)]
+
+
+def window_descs(windows):
+    """(image, x, y, width, height, pitch_bytes, offset_bytes) tuples -> a ctypes array of pxz_window."""
+    arr = (Window * max(len(windows), 1))()
+    for k, w in enumerate(windows):
+        arr[k] = Window(*w)
     return arr
 
 
@@ -154,6 +168,15 @@ def load_library():
         L.pxz_distortion_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 7
         L.pxz_rate_distortion_image.restype = C.c_int
         L.pxz_rate_distortion_image.argtypes = [vp, vp] + [u32] * 9 + [vp, u32, vp, vp]
+    if hasattr(L, "pxz_window_layout"):  # (a build of an earlier commit named by PXZ_LIB lacks the windows)
+        L.pxz_window_layout.restype = C.c_int
+        L.pxz_window_layout.argtypes = [vp, u32, vp, u32, u32, u32, vp]
+        L.pxz_decode_windows_device.restype = C.c_int
+        L.pxz_decode_windows_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params)] + [vp] * 7
+        L.pxz_expand_windows_device.restype = C.c_int
+        L.pxz_expand_windows_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params)] + [vp] * 5
+        L.pxz_decode_windows_files.restype = C.c_int
+        L.pxz_decode_windows_files.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, C.c_uint64, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -216,6 +239,19 @@ def varied_layout(geoms, bw, bh):
     n = len(geoms)
     out = np.zeros(n + 1, np.uint64)
     rc = load_library().pxz_varied_layout(C.cast(image_descs(geoms), C.c_void_p) if n else None, n, bw, bh, _p(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out
+
+
+def window_layout(sizes, windows, bw, bh):
+    """pxz_window_layout: sizes = [(width, height), ...] of the images, windows = [(image, x, y, width, height, pitch_bytes,
+    offset_bytes), ...] -> uint64[n_windows+1] offsets of the windows' covered tiles.  No GPU."""
+    n, k = len(sizes), len(windows)
+    geoms = [(w, h, 0, 0) for (w, h) in sizes]
+    out = np.zeros(k + 1, np.uint64)
+    rc = load_library().pxz_window_layout(C.cast(image_descs(geoms), C.c_void_p) if n else None, n,
+                                          C.cast(window_descs(windows), C.c_void_p) if k else None, k, bw, bh, _p(out))
     if rc != 0:
         raise PxzError(rc)
     return out
@@ -647,6 +683,85 @@ class Handle:
             err.flags, err.images = flags[:n], result
             raise err
         return result, flags[:n]
+
+    # ---- windows of files ----
+    def decode_windows_device(self, files, file_offsets, sizes, windows, channels, bw, bh, out=None, window_flags=None):
+        """pxz_decode_windows_device: files / file_offsets / sizes as decode_varied_frames_device, windows = [(image, x, y,
+        width, height, pitch_bytes, offset_bytes), ...].  Only the tiles the windows cover are read: returns (tile_offsets
+        uint64[k+1], values[T], w[T], h[T], slots[T, bw*bh*C]) in the window_layout order; window_flags (int32[k] CUDA,
+        optional) gets 0 | 2.  out: a 4-tuple of such tensors."""
+        import torch
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        offs = None
+        if out is None:
+            offs = window_layout(sizes, windows, bw, bh)
+            T = int(offs[-1])
+            dev = files.device
+            vals = torch.zeros(T, dtype=torch.float32, device=dev)
+            ow = torch.zeros(T, dtype=torch.int32, device=dev)
+            oh = torch.zeros(T, dtype=torch.int32, device=dev)
+            slots = torch.zeros((T, bw * bh * channels), dtype=torch.uint8, device=dev)
+        else:
+            vals, ow, oh, slots = out
+        pd = Params(bw, bh, 0, 0, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_decode_windows_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), C.cast(window_descs(windows), C.c_void_p), len(windows),
+            channels, C.byref(pd), C.c_void_p(files.data_ptr()), C.c_void_p(file_offsets.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()),
+            C.c_void_p(window_flags.data_ptr()) if window_flags is not None else None))
+        if offs is None:
+            offs = window_layout(sizes, windows, bw, bh)
+        return offs, vals, ow, oh, slots
+
+    def expand_windows_device(self, sizes, windows, channels, bw, bh, filt, ow, oh, slots, out, window_flags=None):
+        """pxz_expand_windows_device: the covered tiles of the windows (w[T], h[T], slots[T, bw*bh*C], window_layout order)
+        -> the windows' pixels, written into the uint8 CUDA buffer `out` at each window's offset_bytes with its pitch_bytes
+        between rows.  window_flags (int32[k] CUDA, optional) gets 0 | 1.  Returns out."""
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_expand_windows_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), C.cast(window_descs(windows), C.c_void_p), len(windows),
+            channels, C.byref(pd), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()),
+            C.c_void_p(out.data_ptr()), C.c_void_p(window_flags.data_ptr()) if window_flags is not None else None))
+        return out
+
+    def decode_windows_files(self, files, windows, channels, bw, bh, filt, sizes=None, out=None):
+        """pxz_decode_windows_files: a list of .pixlzr files (bytes) of one channel count and block size, and windows =
+        [(image, x, y, width, height), ...] -> a list of (height, width, channels) crops.  sizes defaults to what the headers
+        say (file_header).  With out (a numpy uint8 buffer) the windows carry pitch_bytes and offset_bytes too and are written
+        there instead.  Returns (crops | out, flags uint32[k]); raises PxzError (with .flags, .crops) when a file is refused or
+        a window comes back flagged."""
+        n, k = len(files), len(windows)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        if sizes is None:
+            sizes = [file_header(f)[:2] for f in files]
+        own = out is None
+        if own:
+            full, at = [], 0
+            for (i, x, y, w, h) in windows:
+                full.append((i, x, y, w, h, w * channels, at))
+                at += w * h * channels
+            windows = full
+            out = np.zeros(max(at, 1), np.uint8)
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        flags = np.zeros(max(k, 1), np.uint32)
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        rc = self._L.pxz_decode_windows_files(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p),
+                                              C.cast(image_descs(geoms), C.c_void_p), n, C.cast(window_descs(windows), C.c_void_p), k,
+                                              channels, C.byref(pd), _p(out), out.size, _p(flags))
+        if own:
+            result = [out[w[6]:w[6] + w[3] * w[4] * channels].reshape(w[4], w[3], channels) for w in windows]
+        else:
+            result = out
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.flags, err.crops = flags[:k], result
+            raise err
+        return result, flags[:k]
 
     # ---- rate and distortion ----
     def distortion_frames_device(self, frames, bw, bh, filt, ow, oh, slots, want_tiles=True, out=None):

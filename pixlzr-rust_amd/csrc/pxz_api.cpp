@@ -111,6 +111,9 @@ struct HandleScratch {
 	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedExpandTables> varied_expand_tables;  // the same for the decode side
 	DeviceBuffer varied_flags;        // per-image flags of a varied decode-side call whose caller passed none
 	DeviceBuffer rd;                  // pxz_rate_distortion_image: the files' offsets, the rungs' squared errors, the writer's room
+	DeviceBuffer windows;             // pixel windows of files: the per-window table
+	PinnedStaging window_table;       //   and its pinned staging
+	DeviceBuffer window_host;         // pxz_decode_windows_files: the files, the covered tiles, the crops and the flags
 	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
 	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
 	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
@@ -2743,6 +2746,258 @@ int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t wid
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	for (uint32_t r = 0; r < n_factors; ++r) file_bytes[r] = got[r + 1u] - got[r];
 	std::memcpy(sse, got.data() + n_factors + 1u, (size_t)n_factors * channels * 8u);
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- pixel windows of files (window_index_kernel in pxz_stream.hip, pxz_window.hip) ---------------------------------------
+namespace {
+
+// The per-window table of a call, checked window by window before anything is launched.  channels 0: geometry only
+// (pxz_window_layout, the decode stage), no pitch rule.  sides: the block sides and the edge sizes of the images the windows
+// touch (what the expand tables are built for).
+int window_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *w, uint32_t n_windows, uint32_t bw,
+                uint32_t bh, uint32_t channels, std::vector<pxz::WindowEntry> *entries, std::vector<uint32_t> *sides, uint32_t *n_rows)
+{
+	if (!w) return fail(h, PXZ_ERR_INVALID_ARG, "null windows");
+	if (n_windows == 0) return fail(h, PXZ_ERR_INVALID_ARG, "no windows");
+	std::vector<pxz::VariedImage> images;
+	const int rc = varied_plan(h, descs, n_images, bw, bh, 0, 0, &images, nullptr, nullptr);
+	if (rc != PXZ_OK) return rc;
+	entries->resize(n_windows);
+	std::vector<uint32_t> all = {bw, bh};
+	uint64_t tiles = 0, rows_total = 0;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const pxz_window &g = w[k];
+		if (g.image >= n_images) return fail(h, PXZ_ERR_INVALID_ARG, "window %u: image index %u out of range (%u images)", k, g.image, n_images);
+		const pxz::VariedImage &im = images[g.image];
+		if (g.width == 0 || g.height == 0) return fail(h, PXZ_ERR_INVALID_ARG, "window %u: empty rectangle (%ux%u)", k, g.width, g.height);
+		if ((uint64_t)g.x + g.width > im.width || (uint64_t)g.y + g.height > im.height)
+			return fail(h, PXZ_ERR_INVALID_ARG, "window %u: the rectangle %ux%u at (%u, %u) leaves image %u (%ux%u)", k, g.width, g.height, g.x, g.y,
+			            g.image, im.width, im.height);
+		if (channels && (uint64_t)g.pitch_bytes < (uint64_t)g.width * channels)
+			return fail(h, PXZ_ERR_INVALID_ARG, "window %u: pitch smaller than a row", k);
+		pxz::WindowEntry &e = (*entries)[k];
+		e.offset = g.offset_bytes;
+		e.image = g.image;
+		e.x = g.x;
+		e.y = g.y;
+		e.w = g.width;
+		e.h = g.height;
+		e.pitch = g.pitch_bytes;
+		e.c0 = g.x / bw;
+		e.r0 = g.y / bh;
+		e.ccols = (g.x + g.width - 1u) / bw - e.c0 + 1u;
+		e.crows = (g.y + g.height - 1u) / bh - e.r0 + 1u;
+		e.img_w = im.width;
+		e.img_h = im.height;
+		e.cols = im.cols;
+		e.rows = im.rows;
+		e.edge_w = im.edge_w;
+		e.edge_h = im.edge_h;
+		e.tile0 = (uint32_t)tiles;
+		e.row0 = (uint32_t)rows_total;
+		tiles += (uint64_t)e.ccols * e.crows;
+		rows_total += e.crows;
+		if (tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "window %u: more than 2^32-1 covered tiles in the call", k);
+		all.push_back(im.edge_w);
+		all.push_back(im.edge_h);
+	}
+	std::sort(all.begin(), all.end());
+	all.erase(std::unique(all.begin(), all.end()), all.end());
+	if (sides) *sides = all;
+	if (n_rows) *n_rows = (uint32_t)rows_total;
+	return PXZ_OK;
+}
+
+// the covered tiles of a planned call
+uint32_t window_n_tiles(const std::vector<pxz::WindowEntry> &entries) { return entries.back().tile0 + entries.back().ccols * entries.back().crows; }
+
+// the per-window table -> handle scratch, as varied_upload sends the per-image table: one copy
+int window_upload(pxz_handle *h, const std::vector<pxz::WindowEntry> &entries, const pxz::WindowEntry **d_windows)
+{
+	const size_t bytes = entries.size() * sizeof(pxz::WindowEntry);
+	int rc = ensure(h, h->windows, bytes);
+	if (rc != PXZ_OK) return rc;
+	PXZ_HIP(h, h->window_table.send(entries.data(), bytes, h->windows.ptr, h->stream));
+	*d_windows = (const pxz::WindowEntry *)h->windows.ptr;
+	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_window_layout(const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows, uint32_t block_w,
+                      uint32_t block_h, uint64_t *tile_offsets)
+{
+	if (!tile_offsets) return PXZ_ERR_INVALID_ARG;
+	std::vector<pxz::WindowEntry> entries;
+	const int rc = window_plan(nullptr, descs, n_images, windows, n_windows, block_w, block_h, 0, &entries, nullptr, nullptr);
+	if (rc != PXZ_OK) return rc;
+	for (uint32_t k = 0; k < n_windows; ++k) tile_offsets[k] = entries[k].tile0;
+	tile_offsets[n_windows] = window_n_tiles(entries);
+	return PXZ_OK;
+}
+
+int pxz_decode_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows,
+                              uint32_t channels, const pxz_params *params, const uint8_t *d_files, const uint64_t *d_file_offsets,
+                              float *d_block_value, uint32_t *d_tile_w, uint32_t *d_tile_h, uint8_t *d_slots, uint32_t *d_window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_files || !d_file_offsets || !d_block_value || !d_tile_w || !d_tile_h || !d_slots)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	const pxz_params p = decode_side_params(params, false);
+	std::vector<pxz::WindowEntry> entries;
+	uint32_t n_rows = 0;
+	int rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, 0, &entries, nullptr, &n_rows);
+	if (rc != PXZ_OK) return rc;
+	if ((uint64_t)p.block_w * p.block_h * channels > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::DecodeArgs a{};
+	a.files = d_files;
+	a.file_offsets = reinterpret_cast<const unsigned long long *>(d_file_offsets);
+	a.value = d_block_value;
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.bw = p.block_w;
+	a.bh = p.block_h;
+	a.n_frames = n_images;  // (the end of the files buffer; the geometry fields stay zero: every window carries its image's)
+	a.n_tiles = window_n_tiles(entries);
+	a.tiles_per_frame = a.n_tiles;
+	a.channels = channels;
+	a.slot_bytes = p.block_w * p.block_h * channels;
+	if ((rc = reader_scratch(h, &a)) != PXZ_OK) return rc;
+	uint32_t *flags = nullptr;
+	if ((rc = varied_flags(h, d_window_flags, n_windows, &flags)) != PXZ_OK) return rc;
+	const pxz::WindowEntry *d_windows = nullptr;
+	if ((rc = window_upload(h, entries, &d_windows)) != PXZ_OK) return rc;
+	return launch_on_bins(h, h->dbins_clean, a.bins, [&](bool bins_clean) {
+		return pxz::launch_decode_windows(a, d_windows, n_windows, n_rows, flags, bins_clean, h->stream);
+	});
+}
+
+int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows,
+                              uint32_t channels, const pxz_params *params, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                              const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_base) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::WindowEntry> entries;
+	std::vector<uint32_t> sides;
+	if ((rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, channels, &entries, &sides, nullptr)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::WindowExpandArgs a{};
+	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a, true)) != PXZ_OK) return rc;
+	if (varied_image_beyond_lds(a.tile_dw))  // (a cached set that a caller with another block of the same sides left)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile of %u channels and its windows in LDS: %llu bytes exceed what a block has", a.bw,
+		            a.bh, channels, (unsigned long long)a.tile_dw * 4u);
+	a.n_windows = n_windows;
+	a.n_tiles = window_n_tiles(entries);
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.base = d_base;
+	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
+	if (d_window_flags) PXZ_HIP(h, hipMemsetAsync(d_window_flags, 0, (size_t)n_windows * 4u, h->stream));
+	a.window_flags = d_window_flags;
+	if ((rc = window_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
+	PXZ_HIP(h, pxz::launch_window_expand(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
+                             const pxz_window *windows, uint32_t n_windows, uint32_t channels, const pxz_params *params, uint8_t *out_base,
+                             uint64_t out_bytes, uint32_t *window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::WindowEntry> entries;
+	if ((rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, channels, &entries, nullptr, nullptr)) != PXZ_OK) return rc;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const pxz_window &g = windows[k];
+		if (g.offset_bytes > out_bytes || (uint64_t)(g.height - 1u) * g.pitch_bytes + (uint64_t)g.width * channels > out_bytes - g.offset_bytes)
+			return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "window %u: its output ends behind the %llu bytes of the buffer", k, (unsigned long long)out_bytes);
+	}
+	// every header first: a file that is not the image its descriptor announces is refused before anything is written
+	uint64_t file_bytes = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, ch, fb;
+		const char *why;
+		if ((rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why)) != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
+		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the call expects %ux%u in %ux%u of %u",
+			            i, w, hh, bw, bh, ch, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
+		file_bytes += lens[i];
+	}
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// device side, one buffer: the files back to back behind their offsets | values and sizes of the covered tiles | their
+	// slots | the crops tightly packed (256-byte aligned starts) with the two flag arrays behind them
+	auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+	std::vector<pxz_window> dev(windows, windows + n_windows);
+	uint64_t crop_bytes = 0;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		dev[k].offset_bytes = crop_bytes;
+		dev[k].pitch_bytes = windows[k].width * channels;
+		crop_bytes += up256((uint64_t)dev[k].pitch_bytes * windows[k].height);
+	}
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	const uint32_t n_tiles = window_n_tiles(entries);
+	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
+	const uint64_t meta_at = up256(offs_bytes + file_bytes + 16u), slots_at = meta_at + up256((uint64_t)n_tiles * 12u);
+	const uint64_t crops_at = slots_at + up256((uint64_t)n_tiles * slot), flags_at = crops_at + crop_bytes, down_bytes = crop_bytes + 8ull * n_windows;
+	// (one staging buffer for both directions: the crops come back only after the files have gone)
+	std::vector<uint8_t> stage((size_t)std::max(offs_bytes + file_bytes, down_bytes));
+	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
+	offs[0] = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
+		offs[i + 1] = offs[i] + lens[i];
+	}
+	if ((rc = ensure(h, h->window_host, flags_at + 8ull * n_windows)) != PXZ_OK) return rc;
+	uint8_t *d = (uint8_t *)h->window_host.ptr;
+	PXZ_HIP(h, hipMemcpyAsync(d, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
+	PXZ_HIP(h, hipMemsetAsync(d + crops_at, 0, down_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
+	float *d_val = (float *)(d + meta_at);
+	uint32_t *d_w = (uint32_t *)(d + meta_at + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d + meta_at + (uint64_t)n_tiles * 8u);
+	uint32_t *d_flags = (uint32_t *)(d + flags_at);
+	if ((rc = pxz_decode_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, d + offs_bytes, (const uint64_t *)d, d_val, d_w, d_h,
+	                                    d + slots_at, d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_expand_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, d_w, d_h, d + slots_at, d + crops_at,
+	                                    d_flags + n_windows)) != PXZ_OK)
+		return rc;
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
+	PXZ_HIP(h, hipMemcpyAsync(stage.data(), d + crops_at, down_bytes, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	const uint32_t *flags = reinterpret_cast<const uint32_t *>(stage.data() + crop_bytes);
+	uint32_t first_bad = n_windows, first_flags = 0;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const uint32_t fl = flags[k] | flags[n_windows + k];
+		if (window_flags) window_flags[k] = fl;
+		if (fl && first_bad == n_windows) {
+			first_bad = k;
+			first_flags = fl;
+		}
+		const size_t row = (size_t)windows[k].width * channels;
+		for (uint32_t y = 0; y < windows[k].height; ++y)
+			std::memcpy(out_base + windows[k].offset_bytes + (size_t)y * windows[k].pitch_bytes, stage.data() + dev[k].offset_bytes + (size_t)y * row, row);
+	}
+	if (first_bad != n_windows)
+		return fail(h, PXZ_ERR_INVALID_ARG, "window %u: malformed .pixlzr file or record in what it reads of image %u (flags %u); the other windows are complete",
+		            first_bad, windows[first_bad].image, first_flags);
 	return PXZ_OK;
 }
 

@@ -541,6 +541,40 @@ struct DistortionArgs {
 	                                  //   image's valid tiles, added with atomics (zeroed before the launch)
 };
 
+// Pixel windows of files (pxz_decode_windows_device, pxz_expand_windows_device): one entry per window of the call.  A window
+// covers tile columns [c0, c0 + ccols) and tile rows [r0, r0 + crows) of its image; its covered tiles are numbered row-major
+// inside that grid from tile0 on, its covered tile rows from row0 on (pxz_window_layout).  The entry carries its image's
+// geometry, so that the kernels read one table.
+struct WindowEntry {
+	uint64_t offset;                // bytes from the call's base pointer to the window's first output pixel
+	uint32_t tile0, row0;           // first covered tile / first covered tile row of the window in the call
+	uint32_t image;                 // the file the window reads
+	uint32_t x, y, w, h, pitch;     // the pixel rectangle in that image; bytes between OUTPUT rows
+	uint32_t c0, r0, ccols, crows;  // the covered tile grid
+	uint32_t img_w, img_h, cols, rows, edge_w, edge_h;  // the image: what its header must say, its whole grid
+};
+
+// window_expand_kernel (pxz_window.hip): the covered tiles of the call's windows back to their full sizes, and of each the
+// part inside its window to the window's output.  The tables are VariedExpandArgs' (the fields varied_resize_tile reads carry
+// the same names); the wave's image is always in LDS (no HBM form).
+struct WindowExpandArgs {
+	const WindowEntry *windows;
+	uint32_t n_windows, n_tiles;
+	const uint32_t *tile_w, *tile_h;  // per covered tile: stored size
+	const uint8_t *slots;             // per covered tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
+	uint8_t *base;                    // window k at base + windows[k].offset, windows[k].pitch between rows
+	uint32_t bw, bh, slot_bytes, filter;
+	const uint32_t *slot;
+	const ExpandTab *dir;
+	uint32_t stride;
+	const uint16_t *starts, *sizes;
+	const int16_t *coeffs;
+	uint32_t wdw, tile_dw;            // as VariedExpandArgs
+	uint32_t t0_dw;                   // (set by the launch) dwords of the windows' first tiles kept in LDS, 0: read from `windows`
+	uint32_t *status;                 // bit 0: a covered tile's stored size is 0 or exceeds its full size
+	uint32_t *window_flags;           // per window 1 for the same, or null
+};
+
 struct SynthArgs {
 	uint8_t *dst;
 	uint64_t frame_stride;

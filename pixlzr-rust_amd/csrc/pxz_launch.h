@@ -21,6 +21,10 @@ hipError_t launch_ladder(const LadderArgs &a, uint32_t channels, uint32_t nw, ui
 hipError_t launch_decode(const DecodeArgs &a, bool bins_clean, hipStream_t stream);
 hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, uint32_t n_rows, uint32_t *image_flags, bool bins_clean,
                                 hipStream_t stream);
+// the same over pixel windows: n_windows entries, n_rows covered tile rows and a.n_tiles covered tiles in all, a.n_frames files
+hipError_t launch_decode_windows(const DecodeArgs &a, const WindowEntry *windows, uint32_t n_windows, uint32_t n_rows, uint32_t *window_flags,
+                                 bool bins_clean, hipStream_t stream);
+hipError_t launch_window_expand(const WindowExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_varied_expand(const VariedExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw);
 // the LDS form's grid for n_tiles tiles of n_images images, one wave per tile: *t0_dw = dwords of the images' first tiles a

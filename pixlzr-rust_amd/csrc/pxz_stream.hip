@@ -916,6 +916,8 @@ hipError_t launch_qoi_varied(const QoiArgs &args, const VariedWriterArgs &varied
 //   pixlzr_index_kernel  one wave per (file, tile row): header check, the row's start from the line-length
 //                        table, then a walk over the row's records ("block", f32 BE value, u32 BE length,
 //                        QOI minus its magic) -> per tile value, size and body position
+//                        (varied_index_kernel: one wave per tile row of a batch of differently sized files;
+//                        window_index_kernel: per covered tile row of pixel windows, the walk over a column range)
 //   qoi_decode_kernel    one lane per tile: the QOI op stream -> pixels in the tile's slot; the 64-entry
 //                        index of every lane lives in LDS as in the encoder
 // ---------------------------------------------------------------------------
@@ -944,14 +946,19 @@ constexpr uint32_t kIdxHeader = 23;    // "block" + value + length + QOI header 
 // What one wave needs to know about its tile row: the file, the row, the geometry the file's header must carry and where the
 // row's tiles are.  pixlzr_index_kernel fills it from the one geometry of its batch, varied_index_kernel from its image's
 // entry of the per-image table; index_row is the walk both run.  VARIED: the image's own flag is set wherever the status is.
+// WINDOW (window_index_kernel): only columns [c_first, c_last] of the row are wanted.  The records left of c_first are walked
+// and checked like the others (a broken one ends the walk) but not published, column cc goes to t_row + (cc - c_first), the
+// walk ends with c_last -- nothing behind that record is looked at -- and the row's length is held against the walk only when
+// c_last is the row's last column.  The flag is the window's.
 struct IdxRow {
 	uint32_t f, r;                  // file, tile row inside it
 	uint32_t width, height;         // what the header must say
 	uint32_t cols, rows, edge_w, edge_h;
-	uint32_t t_row;                 // the row's first tile in the outputs
+	uint32_t t_row;                 // the row's first tile in the outputs (WINDOW: where column c_first goes)
+	uint32_t c_first, c_last;       // WINDOW only
 };
 
-template <bool VARIED>
+template <bool VARIED, bool WINDOW = false>
 __device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo, uint32_t *image_flag, uint32_t *s_chunk, uint32_t lane)
 {
 #ifdef PXZ_STAMPS
@@ -970,15 +977,18 @@ __device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo
 	const unsigned long long flen = f1 - f0;
 	const unsigned long long hdr = 26ull + 4ull * geo.rows;
 	const uint32_t t_row = geo.t_row;
+	// the columns the walk goes over, and the one that goes to t_row
+	const uint32_t c_end = WINDOW ? geo.c_last + 1u : geo.cols, c_pub = WINDOW ? geo.c_first : 0u;
 	auto bad_from = [&](uint32_t c0) {  // the row is unusable from column c0 on
 		if (lane == 0) {
 			atomicOr(a.status, 2u);
 			if constexpr (VARIED) *image_flag = 2u;
 		}
-		for (uint32_t c = c0 + lane; c < geo.cols; c += 64u) {
-			a.rec_len[t_row + c] = 0u;
-			a.tile_w[t_row + c] = 0u;
-			a.tile_h[t_row + c] = 0u;
+		if constexpr (WINDOW) c0 = c0 > c_pub ? c0 : c_pub;
+		for (uint32_t c = c0 + lane; c < c_end; c += 64u) {
+			a.rec_len[t_row + (c - c_pub)] = 0u;
+			a.tile_w[t_row + (c - c_pub)] = 0u;
+			a.tile_h[t_row + (c - c_pub)] = 0u;
 		}
 	};
 	// the fixed header, a byte per lane: "PIXLZR", 0, 0, 2 (constants.rs:10-11: v0.0.2, filter byte + line table), the filter byte
@@ -1020,7 +1030,7 @@ __device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo
 	const unsigned long long row_end = p + (uint32_t)__builtin_amdgcn_readfirstlane(be32(file + 26 + 4 * r));
 	uint32_t c = 0;
 	PXZ_STAMP(0);  // file header, line table
-	while (c < geo.cols) {
+	while (c < c_end) {
 		// ---- stage file bytes [p, p + kIdxChunk) of the row: whole aligned 16-byte granules of the buffer, every load of the
 		// chunk issued before the first one is written to LDS (round 2 staged dwords, one load -> store round per 256 bytes: a
 		// wave walks a row of ~170 KB alone, and the kernel was 0.33 ms of chained round trips)
@@ -1070,7 +1080,7 @@ __device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo
 		uint32_t pos = 0;
 		{
 			uint32_t o = 0;
-			const uint32_t cols_left = geo.cols - c, n_max = cols_left < 64u ? cols_left : 64u;
+			const uint32_t cols_left = c_end - c, n_max = cols_left < 64u ? cols_left : 64u;
 			// a record can be walked from o if it has room (13 + 10 + 8 bytes: o + 31 <= rem) and its header lies in the chunk
 			// (o + 23 <= have; have <= rem): o <= lim, one test
 			const bool none = rem < 31u;
@@ -1120,8 +1130,8 @@ __device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo
 				// sequential reader does not: a bad record ends the row there, see below)
 				good = magic & (qlen >= 18u) & ((unsigned long long)o + 13ull + qlen <= (unsigned long long)rem) & (ch == a.channels) &
 				       (w >= 1u) & (h >= 1u) & (w <= fw) & (h <= fh);
-				if (good) {
-					const uint32_t t = t_row + cc;
+				if (good && (!WINDOW || cc >= c_pub)) {
+					const uint32_t t = t_row + (cc - c_pub);
 					a.value[t] = __uint_as_float(value_bits);
 					a.tile_w[t] = w;
 					a.tile_h[t] = h;
@@ -1151,7 +1161,7 @@ __device__ __forceinline__ void index_row(const DecodeArgs &a, const IdxRow &geo
 		st_acc[5] += n_rec;  // records
 #endif
 	}
-	if (p != row_end && lane == 0) {
+	if ((!WINDOW || c_end == geo.cols) && p != row_end && lane == 0) {  // (a walk that ended before the row did has no length to hold)
 		atomicOr(a.status, 2u);
 		if constexpr (VARIED) *image_flag = 2u;
 	}
@@ -1168,7 +1178,7 @@ __global__ void __launch_bounds__(256) pixlzr_index_kernel(const DecodeArgs a)
 	const uint32_t i = blockIdx.x * 4u + wave;
 	if (i >= a.n_frames * a.rows) return;
 	const uint32_t f = i / a.rows, r = i - f * a.rows;
-	const IdxRow g{f, r, a.width, a.height, a.cols, a.rows, a.edge_w, a.edge_h, f * a.tiles_per_frame + r * a.cols};
+	const IdxRow g{f, r, a.width, a.height, a.cols, a.rows, a.edge_w, a.edge_h, f * a.tiles_per_frame + r * a.cols, 0u, 0u};
 	index_row<false>(a, g, nullptr, s_chunk[wave], lane);
 }
 
@@ -1189,7 +1199,7 @@ __global__ void __launch_bounds__(256) varied_index_kernel(const DecodeArgs a, c
 	}
 	const VariedImage im = images[lo];
 	const uint32_t r = i - im.row0;
-	const IdxRow g{lo, r, im.width, im.height, im.cols, im.rows, im.edge_w, im.edge_h, im.tile0 + r * im.cols};
+	const IdxRow g{lo, r, im.width, im.height, im.cols, im.rows, im.edge_w, im.edge_h, im.tile0 + r * im.cols, 0u, 0u};
 	index_row<true>(a, g, image_flags + lo, s_chunk[wave], lane);
 }
 
@@ -1207,6 +1217,45 @@ __global__ void __launch_bounds__(256) varied_decode_flags_kernel(const uint32_t
 		else hi = mid - 1u;
 	}
 	image_flags[lo] = 2u;
+}
+
+// Pixel windows of files (pxz_decode_windows_device): one wave per covered tile row of the call.  The wave finds its window
+// by a binary search over the per-window table's first rows, as varied_index_kernel finds its image, and walks its tile row
+// of that window's file up to the window's last column.  a.n_frames is the number of files (the end of the files buffer).
+__global__ void __launch_bounds__(256) window_index_kernel(const DecodeArgs a, const WindowEntry *windows, uint32_t n_windows, uint32_t n_rows,
+                                                           uint32_t *window_flags)
+{
+	__shared__ __attribute__((aligned(16))) uint32_t s_chunk[4][kIdxChunk / 4u + 8u];
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	const uint32_t i = blockIdx.x * 4u + wave;
+	if (i >= n_rows) return;
+	uint32_t lo = 0, hi = n_windows - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (windows[mid].row0 <= i) lo = mid;
+		else hi = mid - 1u;
+	}
+	const WindowEntry wn = windows[lo];
+	const uint32_t cr = i - wn.row0;
+	const IdxRow g{wn.image, wn.r0 + cr, wn.img_w, wn.img_h, wn.cols, wn.rows, wn.edge_w, wn.edge_h, wn.tile0 + cr * wn.ccols,
+	               wn.c0,    wn.c0 + wn.ccols - 1u};
+	index_row<true, true>(a, g, window_flags + lo, s_chunk[wave], lane);
+}
+
+// varied_decode_flags_kernel for windows: a covered tile that the index or qoi_decode_kernel left with size zero gives its
+// window the flag.  One thread per covered tile.
+__global__ void __launch_bounds__(256) window_decode_flags_kernel(const uint32_t *tile_w, const WindowEntry *windows, uint32_t n_windows,
+                                                                  uint32_t n_tiles, uint32_t *window_flags)
+{
+	const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+	if (t >= n_tiles || tile_w[t] != 0u) return;
+	uint32_t lo = 0, hi = n_windows - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (windows[mid].tile0 <= t) lo = mid;
+		else hi = mid - 1u;
+	}
+	window_flags[lo] = 2u;
 }
 
 // What an op's first byte says (qoi_decode_kernel's look-up table, one per channel count; built at compile time):
@@ -1438,14 +1487,17 @@ __global__ void __launch_bounds__(64 * kQoiWaves) qoi_decode_kernel(const Decode
 }
 
 // images == null: the batch has one geometry (a.width ..); else the per-image table of a varied batch (a.n_frames images, n_rows
-// tile rows in all; image_flags: zeroed dwords that receive 2 for every image with a malformed file or record).
+// tile rows in all; image_flags: zeroed dwords that receive 2 for every image with a malformed file or record).  windows: the
+// per-window table of a call over pixel windows instead (n_windows entries, n_rows covered tile rows, a.n_tiles covered tiles,
+// a.n_frames files; image_flags has one dword per window).
 static hipError_t launch_decode_impl(const DecodeArgs &a, bool bins_clean, hipStream_t stream, const VariedImage *images, uint32_t n_rows,
-                                     uint32_t *image_flags)
+                                     uint32_t *image_flags, const WindowEntry *windows = nullptr, uint32_t n_windows = 0u)
 {
 	// (the binning counters are left zeroed by the previous launch on the same buffer: bins_clean, as in launch_qoi)
 	hipError_t e;
 	if (!bins_clean && (e = hipMemsetAsync(a.bins, 0, kBinDwords * sizeof(uint32_t), stream)) != hipSuccess) return e;
-	if (images) hipLaunchKernelGGL(varied_index_kernel, dim3((n_rows + 3u) / 4u), dim3(256), 0, stream, a, images, n_rows, image_flags);
+	if (windows) hipLaunchKernelGGL(window_index_kernel, dim3((n_rows + 3u) / 4u), dim3(256), 0, stream, a, windows, n_windows, n_rows, image_flags);
+	else if (images) hipLaunchKernelGGL(varied_index_kernel, dim3((n_rows + 3u) / 4u), dim3(256), 0, stream, a, images, n_rows, image_flags);
 	else hipLaunchKernelGGL(pixlzr_index_kernel, dim3((a.n_frames * a.rows + 3u) / 4u), dim3(256), 0, stream, a);
 	const uint32_t tb = (a.n_tiles + kBinChunk - 1u) / kBinChunk;
 	QoiArgs q{};  // the encoder's binning by pixel count, on the sizes the index kernel has just read
@@ -1459,7 +1511,10 @@ static hipError_t launch_decode_impl(const DecodeArgs &a, bool bins_clean, hipSt
 	const uint32_t qb = (a.n_tiles + 64u * kQoiWaves - 1u) / (64u * kQoiWaves);
 	if (a.channels == 4) hipLaunchKernelGGL(qoi_decode_kernel<4>, dim3(qb), dim3(64u * kQoiWaves), 0, stream, a);
 	else hipLaunchKernelGGL(qoi_decode_kernel<3>, dim3(qb), dim3(64u * kQoiWaves), 0, stream, a);
-	if (images)
+	if (windows)
+		hipLaunchKernelGGL(window_decode_flags_kernel, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, windows, n_windows,
+		                   a.n_tiles, image_flags);
+	else if (images)
 		hipLaunchKernelGGL(varied_decode_flags_kernel, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, images, a.n_frames,
 		                   a.n_tiles, image_flags);
 	return hipGetLastError();
@@ -1474,6 +1529,12 @@ hipError_t launch_decode_varied(const DecodeArgs &a, const VariedImage *images, 
                                 hipStream_t stream)
 {
 	return launch_decode_impl(a, bins_clean, stream, images, n_rows, image_flags);
+}
+
+hipError_t launch_decode_windows(const DecodeArgs &a, const WindowEntry *windows, uint32_t n_windows, uint32_t n_rows, uint32_t *window_flags,
+                                 bool bins_clean, hipStream_t stream)
+{
+	return launch_decode_impl(a, bins_clean, stream, nullptr, n_rows, window_flags, windows, n_windows);
 }
 
 }  // namespace pxz
