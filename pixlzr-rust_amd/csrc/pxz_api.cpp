@@ -2122,6 +2122,29 @@ int pxz_handle_state(pxz_handle *h, uint32_t state[4])
 // ---- batches of differently sized images (pxz_varied.hip) --------------------------------------------------------------
 namespace {
 
+// the distinct tile sides a table set is built for, ascending
+std::vector<uint32_t> unique_sides(std::vector<uint32_t> sides)
+{
+	std::sort(sides.begin(), sides.end());
+	sides.erase(std::unique(sides.begin(), sides.end()), sides.end());
+	return sides;
+}
+
+// one image of width x height and its grid as an entry of the per-image table (offset, tile0 and row0 are the caller's)
+pxz::VariedImage varied_entry(uint32_t width, uint32_t height, uint32_t pitch, const Grid &g)
+{
+	pxz::VariedImage im{};
+	im.width = width;
+	im.height = height;
+	im.pitch = pitch;
+	im.cols = g.cols;
+	im.rows = g.rows;
+	im.edge_w = g.edge_w;
+	im.edge_h = g.edge_h;
+	im.hdr_bytes = 26u + 4u * g.rows;  // mod.rs:47-48
+	return im;
+}
+
 // The per-image table of a varied batch, checked image by image before anything is launched.  channels 0: geometry only
 // (pxz_varied_layout, the writer), no pitch or tile-size rules.
 int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t mode,
@@ -2141,18 +2164,11 @@ int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw,
 			return fail(h, PXZ_ERR_UNSUPPORTED, "image %u: image sides above 2^24 are not supported", i);
 		if (channels && (uint64_t)g.pitch_bytes < (uint64_t)g.width * channels)
 			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: pitch smaller than a row", i);
-		pxz::VariedImage &im = (*images)[i];
-		im.offset = g.offset_bytes;
-		im.width = g.width;
-		im.height = g.height;
-		im.pitch = g.pitch_bytes;
 		Grid grid;
 		(void)make_grid(h, g.width, g.height, bw, bh, 1, kAnyTiles, &grid);
-		im.cols = grid.cols;
-		im.rows = grid.rows;
-		im.edge_w = grid.edge_w;
-		im.edge_h = grid.edge_h;
-		im.hdr_bytes = 26u + 4u * im.rows;
+		pxz::VariedImage &im = (*images)[i];
+		im = varied_entry(g.width, g.height, g.pitch_bytes, grid);
+		im.offset = g.offset_bytes;
 		if (channels && mode == PXZ_MODE_SHRINK_DIRECTIONALLY && (im.edge_w < 2 || im.edge_h < 2 || bw < 2 || bh < 2))
 			return fail(h, PXZ_ERR_TILE_TOO_SMALL,
 			            "image %u: directional detector needs tiles of at least 2x2 px (edge tile is %ux%u); the reference panics here", i,
@@ -2165,9 +2181,7 @@ int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw,
 		all.push_back(im.edge_w);
 		all.push_back(im.edge_h);
 	}
-	std::sort(all.begin(), all.end());
-	all.erase(std::unique(all.begin(), all.end()), all.end());
-	if (sides) *sides = all;
+	if (sides) *sides = unique_sides(std::move(all));
 	if (n_rows) *n_rows = (uint32_t)rows_total;
 	return PXZ_OK;
 }
@@ -2420,9 +2434,18 @@ int varied_flags(pxz_handle *h, uint32_t *d_image_flags, uint32_t n_images, uint
 	return PXZ_OK;
 }
 
-// What the kernels that resize stored tiles of a flat tile space back to their full sizes share (VariedExpandArgs,
-// DistortionArgs: the fields both name alike): the block, the tables of the batch's tile sides, and the LDS image of one wave.
-template <class Args>
+// the optional per-owner flags of an expand-side call (null: the caller wants none), zeroed on the stream
+int zero_owner_flags(pxz_handle *h, uint32_t *d_flags, size_t n_owners)
+{
+	if (d_flags) PXZ_HIP(h, hipMemsetAsync(d_flags, 0, n_owners * 4u, h->stream));
+	return PXZ_OK;
+}
+
+// What the kernels that resize stored tiles of a flat tile space back to their full sizes share (TileResizeArgs): the block,
+// the tables of the call's tile sides, and the LDS image of one wave.  lds_only: the caller's kernel has no HBM form, and a
+// wave's image beyond LDS is refused -- when the set is built, and for a cached set that a caller with another block of the
+// same sides left.
+template <class Args>  // TileResizeArgs, or DistortionArgs (which names the same fields)
 int put_varied_expand_tables(pxz_handle *h, const pxz_params &p, uint32_t channels, const std::vector<uint32_t> &sides, Args *a,
                              bool lds_only = false)
 {
@@ -2441,6 +2464,9 @@ int put_varied_expand_tables(pxz_handle *h, const pxz_params &p, uint32_t channe
 	a->coeffs = vt->d_coeffs;
 	a->wdw = varied_window_dw(vt->max_window);
 	a->tile_dw = pxz::varied_expand_tile_dw(a->bw, a->bh, a->wdw);
+	if (lds_only && varied_image_beyond_lds(a->tile_dw))
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile of %u channels and its windows in LDS: %llu bytes exceed what a block has", a->bw,
+		            a->bh, channels, (unsigned long long)a->tile_dw * 4u);
 	return PXZ_OK;
 }
 
@@ -2452,6 +2478,100 @@ int fresh_status(pxz_handle *h, uint32_t **status)
 	*status = (uint32_t *)h->status.ptr;
 	PXZ_HIP(h, hipMemsetAsync(*status, 0, 8, h->stream));
 	return PXZ_OK;
+}
+
+// The reader's arguments for a flat tile space of n_tiles tiles over n_images files: one "frame" of n_tiles tiles, no
+// geometry of its own (every image, or every window, carries its own).  Sets the device and carves the reader's scratch.
+int flat_decode_args(pxz_handle *h, const pxz_params &p, uint32_t channels, uint32_t n_images, uint32_t n_tiles, const uint8_t *d_files,
+                     const uint64_t *d_file_offsets, float *d_block_value, uint32_t *d_tile_w, uint32_t *d_tile_h, uint8_t *d_slots,
+                     pxz::DecodeArgs *a)
+{
+	if ((uint64_t)p.block_w * p.block_h * channels > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
+	PXZ_HIP(h, hipSetDevice(h->device));
+	a->files = d_files;
+	a->file_offsets = reinterpret_cast<const unsigned long long *>(d_file_offsets);
+	a->value = d_block_value;
+	a->tile_w = d_tile_w;
+	a->tile_h = d_tile_h;
+	a->slots = d_slots;
+	a->bw = p.block_w;
+	a->bh = p.block_h;
+	a->n_frames = n_images;  // (the end of the files buffer)
+	a->n_tiles = n_tiles;
+	a->tiles_per_frame = n_tiles;
+	a->channels = channels;
+	a->slot_bytes = p.block_w * p.block_h * channels;
+	return reader_scratch(h, a);
+}
+
+// ---- what the two host-files forms share (pxz_decode_varied_files, pxz_decode_windows_files)
+
+// Every header first: a file that is not the image its descriptor announces is refused before anything is written.
+// what: who expects the image ("batch", "call").  *file_bytes: the files' lengths added up.
+int check_file_headers(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
+                       uint32_t channels, const pxz_params &p, const char *what, uint64_t *file_bytes)
+{
+	*file_bytes = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, ch, fb;
+		const char *why;
+		const int rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why);
+		if (rc != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
+		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the %s expects %ux%u in %ux%u of %u",
+			            i, w, hh, bw, bh, ch, what, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
+		*file_bytes += lens[i];
+	}
+	return PXZ_OK;
+}
+
+// the files back to back behind their table of n_images + 1 offsets, as the reader takes them: stage holds
+// max(8 * (n_images + 1) + the files' bytes, down_bytes) -- one staging buffer for both directions, the results come back
+// only after the files have gone
+std::vector<uint8_t> stage_files(const uint8_t *const *files, const size_t *lens, uint32_t n_images, uint64_t file_bytes, uint64_t down_bytes)
+{
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	std::vector<uint8_t> stage((size_t)std::max(offs_bytes + file_bytes, down_bytes));
+	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
+	offs[0] = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
+		offs[i + 1] = offs[i] + lens[i];
+	}
+	return stage;
+}
+
+// values, widths and heights of n_tiles tiles, carved from 12 * n_tiles bytes at d
+struct TileMeta {
+	float *value;
+	uint32_t *w, *h;
+};
+TileMeta carve_tile_meta(uint8_t *d, uint32_t n_tiles)
+{
+	return {(float *)d, (uint32_t *)(d + (uint64_t)n_tiles * 4u), (uint32_t *)(d + (uint64_t)n_tiles * 8u)};
+}
+
+// The way back of n owners (pxz_image_desc or pxz_window): owner k's rows, tightly packed at packed[k].offset_bytes of stage,
+// go to the caller's place and pitch (host[k]); flags holds the decode stage's n flags, then the expand stage's, merged into
+// out_flags (or null).  Returns the first owner with a flag (n: none) and, in *first_flags, what it has.
+template <class Owner>
+uint32_t copy_out_owners(const Owner *host, const Owner *packed, uint32_t n, uint32_t channels, const uint8_t *stage, uint8_t *out_base,
+                         const uint32_t *flags, uint32_t *out_flags, uint32_t *first_flags)
+{
+	uint32_t first_bad = n;
+	for (uint32_t k = 0; k < n; ++k) {
+		const uint32_t fl = flags[k] | flags[n + k];
+		if (out_flags) out_flags[k] = fl;
+		if (fl && first_bad == n) {
+			first_bad = k;
+			*first_flags = fl;
+		}
+		const size_t row = (size_t)host[k].width * channels;
+		for (uint32_t y = 0; y < host[k].height; ++y)
+			std::memcpy(out_base + host[k].offset_bytes + (size_t)y * host[k].pitch_bytes, stage + packed[k].offset_bytes + (size_t)y * row, row);
+	}
+	return first_bad;
 }
 
 }  // namespace
@@ -2473,23 +2593,10 @@ int pxz_decode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	uint32_t n_rows = 0;
 	int rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, 0, 0, &images, nullptr, &n_rows);
 	if (rc != PXZ_OK) return rc;
-	if ((uint64_t)p.block_w * p.block_h * channels > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
-	PXZ_HIP(h, hipSetDevice(h->device));
 	pxz::DecodeArgs a{};
-	a.files = d_files;
-	a.file_offsets = reinterpret_cast<const unsigned long long *>(d_file_offsets);
-	a.value = d_block_value;
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
-	a.bw = p.block_w;
-	a.bh = p.block_h;
-	a.n_frames = n_images;  // (the end of the files buffer; the geometry fields stay zero: every image has its own)
-	a.n_tiles = varied_n_tiles(images);
-	a.tiles_per_frame = a.n_tiles;
-	a.channels = channels;
-	a.slot_bytes = p.block_w * p.block_h * channels;
-	if ((rc = reader_scratch(h, &a)) != PXZ_OK) return rc;
+	if ((rc = flat_decode_args(h, p, channels, n_images, varied_n_tiles(images), d_files, d_file_offsets, d_block_value, d_tile_w, d_tile_h, d_slots,
+	                           &a)) != PXZ_OK)
+		return rc;
 	uint32_t *flags = nullptr;
 	if ((rc = varied_flags(h, d_image_flags, n_images, &flags)) != PXZ_OK) return rc;
 	const pxz::VariedImage *d_images = nullptr;
@@ -2528,7 +2635,7 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 		a.big_waves = (uint32_t)waves;
 	}
 	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if (d_image_flags) PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, (size_t)n_images * 4u, h->stream));
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
 	a.image_flags = d_image_flags;
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_varied_expand(a, channels, h->n_cus, h->stream));
@@ -2545,18 +2652,8 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 	if (rc != PXZ_OK) return rc;
 	std::vector<pxz::VariedImage> images;
 	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
-	// every header first: a file that is not the image its descriptor announces is refused before anything is written
 	uint64_t file_bytes = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
-		uint32_t w, hh, bw, bh, ch, fb;
-		const char *why;
-		if ((rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why)) != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
-		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the batch expects %ux%u in %ux%u of %u",
-			            i, w, hh, bw, bh, ch, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
-		file_bytes += lens[i];
-	}
+	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "batch", &file_bytes)) != PXZ_OK) return rc;
 	PXZ_HIP(h, hipSetDevice(h->device));
 	// device side: the files back to back behind their offsets; the images tightly packed (256-byte aligned starts)
 	std::vector<pxz_image_desc> dev(descs, descs + n_images);
@@ -2571,14 +2668,7 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
 	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
 	const uint64_t flags_at = meta + (uint64_t)n_tiles * slot;
-	// (one staging buffer for both directions: the images come back only after the files have gone)
-	std::vector<uint8_t> stage((size_t)std::max(offs_bytes + file_bytes, img_bytes));
-	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
-	offs[0] = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
-		offs[i + 1] = offs[i] + lens[i];
-	}
+	std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, img_bytes);
 	if ((rc = ensure(h, h->varied_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
@@ -2586,31 +2676,23 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
 	PXZ_HIP(h, hipMemsetAsync(d_out + meta, 0, (size_t)n_tiles * slot, h->stream));
 	PXZ_HIP(h, hipMemsetAsync(d_img, 0, img_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
-	float *d_val = (float *)d_out;
-	uint32_t *d_w = (uint32_t *)(d_out + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d_out + (uint64_t)n_tiles * 8u);
+	const TileMeta m = carve_tile_meta(d_out, n_tiles);
 	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
-	if ((rc = pxz_decode_varied_frames_device(h, dev.data(), n_images, channels, &p, d_files + offs_bytes, (const uint64_t *)d_files, d_val,
-	                                          d_w, d_h, d_out + meta, d_flags)) != PXZ_OK)
+	if ((rc = pxz_decode_varied_frames_device(h, dev.data(), n_images, channels, &p, d_files + offs_bytes, (const uint64_t *)d_files, m.value,
+	                                          m.w, m.h, d_out + meta, d_flags)) != PXZ_OK)
 		return rc;
-	if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, channels, &p, d_w, d_h, d_out + meta, d_img, d_flags + n_images)) != PXZ_OK)
+	if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, channels, &p, m.w, m.h, d_out + meta, d_img, d_flags + n_images)) != PXZ_OK)
 		return rc;
 	std::vector<uint32_t> flags(2u * (size_t)n_images);
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
 	PXZ_HIP(h, hipMemcpyAsync(stage.data(), d_img, img_bytes, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	uint32_t first_bad = n_images;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		const uint32_t fl = flags[i] | flags[n_images + i];
-		if (image_flags) image_flags[i] = fl;
-		if (fl && first_bad == n_images) first_bad = i;
-		const size_t row = (size_t)descs[i].width * channels;
-		for (uint32_t y = 0; y < descs[i].height; ++y)
-			std::memcpy(out_base + descs[i].offset_bytes + (size_t)y * descs[i].pitch_bytes, stage.data() + dev[i].offset_bytes + (size_t)y * row, row);
-	}
+	uint32_t first_flags = 0;
+	const uint32_t first_bad = copy_out_owners(descs, dev.data(), n_images, channels, stage.data(), out_base, flags.data(), image_flags, &first_flags);
 	if (first_bad != n_images)
 		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
-		            flags[first_bad] | flags[n_images + first_bad]);
+		            first_flags);
 	return PXZ_OK;
 }
 
@@ -2629,9 +2711,6 @@ int distortion_launch(pxz_handle *h, const std::vector<pxz::VariedImage> &images
 	pxz::DistortionArgs a{};
 	int rc = put_varied_expand_tables(h, p, channels, sides, &a, true);
 	if (rc != PXZ_OK) return rc;
-	if (varied_image_beyond_lds(a.tile_dw))  // (a cached set that a caller with another block of the same sides left)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile of %u channels and its windows in LDS: %llu bytes exceed what a block has", a.bw,
-		            a.bh, channels, (unsigned long long)a.tile_dw * 4u);
 	a.n_images = (uint32_t)images.size();
 	a.n_tiles = varied_n_tiles(images);
 	a.n_sets = n_sets;
@@ -2642,7 +2721,7 @@ int distortion_launch(pxz_handle *h, const std::vector<pxz::VariedImage> &images
 	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
 	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
 	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if (d_image_flags) PXZ_HIP(h, hipMemsetAsync(d_image_flags, 0, images.size() * 4u, h->stream));
+	if ((rc = zero_owner_flags(h, d_image_flags, images.size())) != PXZ_OK) return rc;
 	a.image_flags = d_image_flags;
 	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * images.size() * channels * 8u, h->stream));
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
@@ -2671,25 +2750,14 @@ int pxz_distortion_frames_device(pxz_handle *h, const pxz_frames *frames, const 
 	Grid g;
 	if ((rc = make_grid(h, frames->width, frames->height, p.block_w, p.block_h, frames->n_frames, 0xffffffffull, &g)) != PXZ_OK) return rc;
 	// the batch as n_frames equal entries of the per-image table
-	pxz::VariedImage im{};
-	im.width = frames->width;
-	im.height = frames->height;
-	im.pitch = frames->pitch_bytes;
-	im.cols = g.cols;
-	im.rows = g.rows;
-	im.edge_w = g.edge_w;
-	im.edge_h = g.edge_h;
-	im.hdr_bytes = 26u + 4u * g.rows;
-	std::vector<pxz::VariedImage> images(frames->n_frames, im);
+	std::vector<pxz::VariedImage> images(frames->n_frames, varied_entry(frames->width, frames->height, frames->pitch_bytes, g));
 	const uint64_t stride = frames->n_frames > 1 ? frames->frame_stride_bytes : 0;
 	for (uint32_t f = 0; f < frames->n_frames; ++f) {
 		images[f].offset = f * stride;
 		images[f].tile0 = f * g.tiles_per_frame;
 		images[f].row0 = f * g.rows;
 	}
-	std::vector<uint32_t> sides = {p.block_w, p.block_h, g.edge_w, g.edge_h};
-	std::sort(sides.begin(), sides.end());
-	sides.erase(std::unique(sides.begin(), sides.end()), sides.end());
+	const std::vector<uint32_t> sides = unique_sides({p.block_w, p.block_h, g.edge_w, g.edge_h});
 	return distortion_launch(h, images, sides, frames->channels, p, n_sets, d_pixels, d_tile_w, d_tile_h, d_slots, d_tile_sse, d_frame_sse,
 	                         nullptr);
 }
@@ -2804,9 +2872,7 @@ int window_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, c
 		all.push_back(im.edge_w);
 		all.push_back(im.edge_h);
 	}
-	std::sort(all.begin(), all.end());
-	all.erase(std::unique(all.begin(), all.end()), all.end());
-	if (sides) *sides = all;
+	if (sides) *sides = unique_sides(std::move(all));
 	if (n_rows) *n_rows = (uint32_t)rows_total;
 	return PXZ_OK;
 }
@@ -2855,23 +2921,10 @@ int pxz_decode_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32
 	uint32_t n_rows = 0;
 	int rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, 0, &entries, nullptr, &n_rows);
 	if (rc != PXZ_OK) return rc;
-	if ((uint64_t)p.block_w * p.block_h * channels > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
-	PXZ_HIP(h, hipSetDevice(h->device));
 	pxz::DecodeArgs a{};
-	a.files = d_files;
-	a.file_offsets = reinterpret_cast<const unsigned long long *>(d_file_offsets);
-	a.value = d_block_value;
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
-	a.bw = p.block_w;
-	a.bh = p.block_h;
-	a.n_frames = n_images;  // (the end of the files buffer; the geometry fields stay zero: every window carries its image's)
-	a.n_tiles = window_n_tiles(entries);
-	a.tiles_per_frame = a.n_tiles;
-	a.channels = channels;
-	a.slot_bytes = p.block_w * p.block_h * channels;
-	if ((rc = reader_scratch(h, &a)) != PXZ_OK) return rc;
+	if ((rc = flat_decode_args(h, p, channels, n_images, window_n_tiles(entries), d_files, d_file_offsets, d_block_value, d_tile_w, d_tile_h, d_slots,
+	                           &a)) != PXZ_OK)
+		return rc;
 	uint32_t *flags = nullptr;
 	if ((rc = varied_flags(h, d_window_flags, n_windows, &flags)) != PXZ_OK) return rc;
 	const pxz::WindowEntry *d_windows = nullptr;
@@ -2897,9 +2950,6 @@ int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32
 	PXZ_HIP(h, hipSetDevice(h->device));
 	pxz::WindowExpandArgs a{};
 	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a, true)) != PXZ_OK) return rc;
-	if (varied_image_beyond_lds(a.tile_dw))  // (a cached set that a caller with another block of the same sides left)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile of %u channels and its windows in LDS: %llu bytes exceed what a block has", a.bw,
-		            a.bh, channels, (unsigned long long)a.tile_dw * 4u);
 	a.n_windows = n_windows;
 	a.n_tiles = window_n_tiles(entries);
 	a.tile_w = d_tile_w;
@@ -2907,7 +2957,7 @@ int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32
 	a.slots = d_slots;
 	a.base = d_base;
 	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if (d_window_flags) PXZ_HIP(h, hipMemsetAsync(d_window_flags, 0, (size_t)n_windows * 4u, h->stream));
+	if ((rc = zero_owner_flags(h, d_window_flags, n_windows)) != PXZ_OK) return rc;
 	a.window_flags = d_window_flags;
 	if ((rc = window_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_window_expand(a, channels, h->n_cus, h->stream));
@@ -2930,18 +2980,8 @@ int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const s
 		if (g.offset_bytes > out_bytes || (uint64_t)(g.height - 1u) * g.pitch_bytes + (uint64_t)g.width * channels > out_bytes - g.offset_bytes)
 			return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "window %u: its output ends behind the %llu bytes of the buffer", k, (unsigned long long)out_bytes);
 	}
-	// every header first: a file that is not the image its descriptor announces is refused before anything is written
 	uint64_t file_bytes = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
-		uint32_t w, hh, bw, bh, ch, fb;
-		const char *why;
-		if ((rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why)) != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
-		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the call expects %ux%u in %ux%u of %u",
-			            i, w, hh, bw, bh, ch, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
-		file_bytes += lens[i];
-	}
+	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "call", &file_bytes)) != PXZ_OK) return rc;
 	PXZ_HIP(h, hipSetDevice(h->device));
 	// device side, one buffer: the files back to back behind their offsets | values and sizes of the covered tiles | their
 	// slots | the crops tightly packed (256-byte aligned starts) with the two flag arrays behind them
@@ -2958,43 +2998,25 @@ int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const s
 	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
 	const uint64_t meta_at = up256(offs_bytes + file_bytes + 16u), slots_at = meta_at + up256((uint64_t)n_tiles * 12u);
 	const uint64_t crops_at = slots_at + up256((uint64_t)n_tiles * slot), flags_at = crops_at + crop_bytes, down_bytes = crop_bytes + 8ull * n_windows;
-	// (one staging buffer for both directions: the crops come back only after the files have gone)
-	std::vector<uint8_t> stage((size_t)std::max(offs_bytes + file_bytes, down_bytes));
-	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
-	offs[0] = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
-		offs[i + 1] = offs[i] + lens[i];
-	}
+	std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, down_bytes);
 	if ((rc = ensure(h, h->window_host, flags_at + 8ull * n_windows)) != PXZ_OK) return rc;
 	uint8_t *d = (uint8_t *)h->window_host.ptr;
 	PXZ_HIP(h, hipMemcpyAsync(d, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
 	PXZ_HIP(h, hipMemsetAsync(d + crops_at, 0, down_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
-	float *d_val = (float *)(d + meta_at);
-	uint32_t *d_w = (uint32_t *)(d + meta_at + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d + meta_at + (uint64_t)n_tiles * 8u);
+	const TileMeta m = carve_tile_meta(d + meta_at, n_tiles);
 	uint32_t *d_flags = (uint32_t *)(d + flags_at);
-	if ((rc = pxz_decode_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, d + offs_bytes, (const uint64_t *)d, d_val, d_w, d_h,
+	if ((rc = pxz_decode_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, d + offs_bytes, (const uint64_t *)d, m.value, m.w, m.h,
 	                                    d + slots_at, d_flags)) != PXZ_OK)
 		return rc;
-	if ((rc = pxz_expand_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, d_w, d_h, d + slots_at, d + crops_at,
+	if ((rc = pxz_expand_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, m.w, m.h, d + slots_at, d + crops_at,
 	                                    d_flags + n_windows)) != PXZ_OK)
 		return rc;
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
 	PXZ_HIP(h, hipMemcpyAsync(stage.data(), d + crops_at, down_bytes, hipMemcpyDeviceToHost, h->stream));
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	const uint32_t *flags = reinterpret_cast<const uint32_t *>(stage.data() + crop_bytes);
-	uint32_t first_bad = n_windows, first_flags = 0;
-	for (uint32_t k = 0; k < n_windows; ++k) {
-		const uint32_t fl = flags[k] | flags[n_windows + k];
-		if (window_flags) window_flags[k] = fl;
-		if (fl && first_bad == n_windows) {
-			first_bad = k;
-			first_flags = fl;
-		}
-		const size_t row = (size_t)windows[k].width * channels;
-		for (uint32_t y = 0; y < windows[k].height; ++y)
-			std::memcpy(out_base + windows[k].offset_bytes + (size_t)y * windows[k].pitch_bytes, stage.data() + dev[k].offset_bytes + (size_t)y * row, row);
-	}
+	uint32_t first_flags = 0;
+	const uint32_t first_bad = copy_out_owners(windows, dev.data(), n_windows, channels, stage.data(), out_base, flags, window_flags, &first_flags);
 	if (first_bad != n_windows)
 		return fail(h, PXZ_ERR_INVALID_ARG, "window %u: malformed .pixlzr file or record in what it reads of image %u (flags %u); the other windows are complete",
 		            first_bad, windows[first_bad].image, first_flags);

@@ -1,5 +1,6 @@
 // pxz_device.h -- device-side helpers shared by the kernel files (gfx950 only): constant tables, index math,
-// packed 16-bit / dot2 / matrix-core resample helpers of the fast paths, the worklist batching, finish_tile.
+// packed 16-bit / dot2 / matrix-core resample helpers of the fast paths, the worklist batching, finish_tile, and what the
+// kernels of a flat tile space share: the owner search, the resize of a stored tile, the tile store.
 // Included by every pxz_*.hip; everything here is __device__ __forceinline__ or a file-local table.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1081,8 +1082,68 @@ __device__ __forceinline__ void list_push(uint32_t *buf, uint32_t &cnt, uint32_t
 }
 
 // ---------------------------------------------------------------------------
+// Flat tile spaces (varied batches, pixel windows): a table of owners (VariedImage, WindowEntry), each with a first tile
+// tile0 and a first tile row row0, both ascending.  Who holds a flat tile or row number finds its owner here.
+// ---------------------------------------------------------------------------
+
+// the last entry of table[0 .. n) whose key member is <= key (n >= 1, table[0]'s key is 0)
+template <class Entry>
+__device__ __forceinline__ uint32_t owner_of(const Entry *table, uint32_t n, uint32_t key, uint32_t Entry::*first)
+{
+	uint32_t lo = 0, hi = n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (table[mid].*first <= key) lo = mid;
+		else hi = mid - 1u;
+	}
+	return lo;
+}
+
+// The wave-per-tile kernels search a copy of the owners' first tiles in LDS while the call has at most kVxImages owners
+// (t0_dw dwords, set by varied_expand_geom; 0: the table itself, in global memory).  distortion_kernel (pxz_distortion.hip) has
+// its own copy of this search and of bad_stored_size: a fix here belongs there too.
+constexpr uint32_t kVxImages = 2048;  // owners whose first tiles a block keeps in LDS (8 KB)
+
+// every thread of the block calls this once, before the tile loop
+template <class Entry>
+__device__ __forceinline__ void stage_first_tiles(uint32_t *s_t0, uint32_t t0_dw, const Entry *table, uint32_t n)
+{
+	for (uint32_t i = threadIdx.x; i < t0_dw; i += blockDim.x) s_t0[i] = i < n ? table[i].tile0 : 0xffffffffu;
+	__syncthreads();
+}
+
+// owner_of by tile0 for a wave-uniform t: the compare runs on the scalar unit (the first tile read goes through
+// readfirstlane as an unsigned value; its sign extension faulted here once)
+template <class Entry>
+__device__ __forceinline__ uint32_t owner_of_tile(const uint32_t *s_t0, uint32_t t0_dw, const Entry *table, uint32_t n, uint32_t t)
+{
+	uint32_t lo = 0, hi = n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		const uint32_t t0 = t0_dw ? s_t0[mid] : table[mid].tile0;
+		if ((uint32_t)__builtin_amdgcn_readfirstlane(t0) <= t) lo = mid;
+		else hi = mid - 1u;
+	}
+	return lo;
+}
+
+// A stored size tw x th that a tile of fw x fh cannot have (zero, or beyond its place): the tile is skipped as
+// pxz_expand_frames_device skips it -- status bit 0 and, where the call has flags, the owner's.  True: skip.
+__device__ __forceinline__ bool bad_stored_size(uint32_t tw, uint32_t th, uint32_t fw, uint32_t fh, uint32_t lane, uint32_t *status,
+                                                uint32_t *flags, uint32_t owner)
+{
+	if (tw != 0u && th != 0u && tw <= fw && th <= fh) return false;
+	if (lane == 0u) {
+		atomicOr(status, 1u);
+		if (flags) flags[owner] = 1u;
+	}
+	return true;
+}
+
+// ---------------------------------------------------------------------------
 // One stored tile of a varied batch back at its full size, in the wave's LDS image: steps 2 and 3 of
-// varied_expand_kernel (pxz_varied_expand.hip), which distortion_kernel (pxz_distortion.hip) runs too.
+// varied_expand_kernel (pxz_varied_expand.hip), which distortion_kernel (pxz_distortion.hip) and window_expand_kernel
+// (pxz_window.hip) run too.
 //   2. the stored pixels (tw x th at src, tightly packed) -> one dword per pixel in s_src (RGBA under a convolution
 //      alpha-premultiplied as fir does), and the windows of both axis tables -- directory entry (full size, stored size) of
 //      a.dir -- in s_wx / s_wy: per output sample a.wdw dwords, first | count << 16, then the weights as i16 pairs;
@@ -1091,7 +1152,7 @@ __device__ __forceinline__ void list_push(uint32_t *buf, uint32_t &cnt, uint32_t
 //      at the end.
 // Returns the plane (s_src or s_tmp) that holds the fw x fh result, one dword per pixel; wsync() has run behind its last
 // write.  stage_x / stage_y false: the windows of that axis are in s_wx / s_wy already (the same full and stored size as
-// the tile this wave resized before).  Args: VariedExpandArgs or DistortionArgs (the fields both name alike).
+// the tile this wave resized before).  Args: TileResizeArgs, or DistortionArgs (which names the same fields).
 // ---------------------------------------------------------------------------
 
 // the clamp spelled as an instruction: left to the compiler, clip8(a) | clip8(b) << 8 of an RGB pixel became
@@ -1221,6 +1282,65 @@ __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uin
 		}
 	}
 	return out;
+}
+
+// ---------------------------------------------------------------------------
+// Step 4 of varied_expand_kernel and window_expand_kernel: nh rows of nw pixels of a wave's image (one dword per pixel,
+// row_dw dwords between rows, from `part`) to dst, pitch bytes between rows, C bytes per pixel.  Every row segment once:
+// item = (row, group of four pixels) -- 16 bytes per lane with streaming stores where the segment starts on a dword (RGBA,
+// dst and pitch multiples of 4), dwords at whatever address they have where it does not; RGB rows as 12-byte groups of four
+// pixels, bytes at the tail.  No form writes a byte behind column nw of a row: a window's clipped edge lies in the middle of
+// an output row, or beside another window's pixels.
+// ---------------------------------------------------------------------------
+template <int C>
+__device__ __forceinline__ void store_tile_part(uint32_t lane, const uint32_t *part, uint32_t row_dw, uint32_t nw, uint32_t nh, uint8_t *dst,
+                                                uint32_t pitch)
+{
+	const uint32_t q4 = (nw + 3u) >> 2;
+	typedef uint32_t u32_a1 __attribute__((aligned(1)));
+	if (C == 4 && ((reinterpret_cast<uintptr_t>(dst) | pitch) & 3u) == 0u) {
+		typedef uint32_t u32q __attribute__((ext_vector_type(4), aligned(4)));
+		RowWalker rw(lane, 64u, q4);
+		for (uint32_t i = lane; i < q4 * nh; i += 64u, rw.next()) {
+			const uint32_t x = 4u * rw.col;
+			const uint32_t *p = part + rw.row * row_dw + x;
+			uint8_t *d = dst + (size_t)rw.row * pitch + x * 4u;
+			if (x + 4u <= nw) {
+				const u32q v = {p[0], p[1], p[2], p[3]};
+				__builtin_nontemporal_store(v, reinterpret_cast<u32q *>(d));
+			} else {
+				for (uint32_t k = 0; x + k < nw; ++k) __builtin_nontemporal_store(p[k], reinterpret_cast<uint32_t *>(d) + k);
+			}
+		}
+	} else if (C == 4) {
+		// an odd offset or pitch: dwords at whatever byte address they have
+		RowWalker rw(lane, 64u, nw);
+		for (uint32_t i = lane; i < nw * nh; i += 64u, rw.next())
+			*reinterpret_cast<u32_a1 *>(dst + (size_t)rw.row * pitch + rw.col * 4u) = part[rw.row * row_dw + rw.col];
+	} else {
+		RowWalker rw(lane, 64u, q4);
+		for (uint32_t i = lane; i < q4 * nh; i += 64u, rw.next()) {
+			const uint32_t x = 4u * rw.col;
+			const uint32_t *p = part + rw.row * row_dw + x;
+			uint8_t *d = dst + (size_t)rw.row * pitch + x * 3u;
+			if (x + 4u <= nw) {
+				// four pixels as twelve bytes, three dwords at whatever byte address they have: the last byte written is the
+				// fourth pixel's blue, so a group that ends at column nw ends there
+				const uint32_t p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+				u32_a1 *o = reinterpret_cast<u32_a1 *>(d);
+				o[0] = (p0 & 0xffffffu) | (p1 << 24);
+				o[1] = ((p1 >> 8) & 0xffffu) | (p2 << 16);
+				o[2] = ((p2 >> 16) & 0xffu) | (p3 << 8);
+			} else {
+				for (uint32_t k = 0; x + k < nw; ++k) {
+					const uint32_t px = p[k];
+					d[3u * k] = (uint8_t)px;
+					d[3u * k + 1u] = (uint8_t)(px >> 8);
+					d[3u * k + 2u] = (uint8_t)(px >> 16);
+				}
+			}
+		}
+	}
 }
 
 }  // namespace pxz

@@ -4,12 +4,11 @@
 // `source` is the image the tile was shrunk from.  The expanded image is never written anywhere.  The reference has no such
 // function: src/bin/whole-folder.rs:69-117 writes the PNG that comes back and leaves the comparison to a person.
 //
-// distortion_kernel: varied_expand_kernel<C, false> (pxz_varied_expand.hip) with another fourth step -- the flat tile space of
-// pxz_varied_layout, one wave per tile, grid-stride, the wave's image (two tile-sized dword planes and the staged windows) in
-// LDS, the same tables and the same grid.  A tile
-//   1. finds its image and its place as there;
-//   2., 3. is staged and resized into an LDS image of its full size by varied_resize_tile (pxz_device.h), the code
-//      varied_expand_kernel runs;
+// distortion_kernel: the tile loop of varied_expand_kernel<C, false> (pxz_varied_expand.hip; steps 1 to 3, the grid and the
+// tables are described there) with another fourth step.  A tile
+//   1. finds its image and its place (its own copy of owner_of_tile and bad_stored_size, pxz_device.h: with the shared forms and
+//      the shared argument block this kernel measured 1.0-1.5 % slower);
+//   2., 3. is staged and resized;
 //   4. is compared: the lanes walk the full tile, read the source pixel at its place in the image (any pitch, any byte
 //      alignment) and add (source - expanded)^2 per channel; the wave's sums go to the tile's entries and, by 64-bit integer
 //      atomics, to the image's totals -- integer sums, so the order of the atomics does not show.
@@ -125,14 +124,7 @@ hipError_t launch_distortion(const DistortionArgs &args, uint32_t channels, uint
 	DistortionArgs a = args;
 	const LaunchGeom g = varied_expand_geom(a.n_images, a.n_tiles, a.tile_dw, n_cus, &a.t0_dw);  // launch_varied_expand's grid
 	if (g.threads == 0u) return hipErrorInvalidValue;
-	hipError_t e;
-	auto go = [&](auto kernel) -> hipError_t {
-		if (g.lds_bytes > 64u * 1024u &&
-		    (e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes)) != hipSuccess)
-			return e;
-		hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, stream, a);
-		return hipGetLastError();
-	};
+	auto go = [&](auto kernel) { return launch_with_lds(kernel, g.blocks, g.threads, g.lds_bytes, stream, a); };
 	return channels == 4u ? go(distortion_kernel<4>) : go(distortion_kernel<3>);
 }
 

@@ -491,15 +491,12 @@ struct VariedWriterArgs {
 	unsigned long long capacity;
 };
 
-// Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
-// back to their places in the images.  One up-scaling table per (full size, stored size): dir[slot[full] * stride + stored]
-// (pxz_tables.h: VariedExpandTableSet).
-struct VariedExpandArgs {
-	const VariedImage *images;
-	uint32_t n_images, n_tiles;
-	const uint32_t *tile_w, *tile_h;  // per tile: stored size
-	const uint8_t *slots;             // per tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
-	uint8_t *base;                    // image i at base + images[i].offset, images[i].pitch between rows
+// What the wave-per-tile kernels of a flat tile space share (varied_expand_kernel, window_expand_kernel; distortion_kernel
+// names the same fields in a struct of its own, see DistortionArgs):
+// the stored tiles, the block, the up-scaling tables and the LDS image of one wave -- what varied_resize_tile and the tile
+// loop read (pxz_device.h), filled by put_varied_expand_tables and the launch.  One table per (full size, stored size):
+// dir[slot[full] * stride + stored] (pxz_tables.h: VariedExpandTableSet).
+struct TileResizeArgs {
 	uint32_t bw, bh, slot_bytes, filter;
 	const uint32_t *slot;
 	const ExpandTab *dir;
@@ -508,17 +505,29 @@ struct VariedExpandArgs {
 	const int16_t *coeffs;
 	uint32_t wdw;                     // dwords of one staged window: 1 + ceil(widest window / 2)
 	uint32_t tile_dw;                 // dwords of one wave's image: two tile-sized planes + the windows of both axes
-	uint32_t t0_dw;                   // (set by the launch) dwords of the images' first tiles kept in LDS, 0: read from `images`
+	uint32_t t0_dw;                   // (set by the launch) dwords of the owners' first tiles kept in LDS, 0: read from the table
 	uint32_t *status;                 // bit 0: a tile's stored size is 0 or exceeds its full size
-	uint32_t *image_flags;            // per image 1 for the same, or null
+	uint32_t n_tiles;
+	const uint32_t *tile_w, *tile_h;  // per tile (distortion: per set and tile): stored size
+	const uint8_t *slots;             // per tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
+};
+
+// Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
+// back to their places in the images.
+struct VariedExpandArgs : TileResizeArgs {
+	const VariedImage *images;
+	uint32_t n_images;
+	uint8_t *base;                    // image i at base + images[i].offset, images[i].pitch between rows
+	uint32_t *image_flags;            // per image 1 for a tile whose stored size is invalid, or null
 	uint32_t *big_scratch;            // tile images beyond LDS: one of tile_dw dwords per wave of the grid in HBM
 	uint32_t big_waves;               //   (0: the images are in LDS)
 };
 
 // Squared error of stored tiles against their source (pxz_distortion_frames_device, pxz_distortion_varied_frames_device;
-// pxz_distortion.hip): the flat tile space and the tables of VariedExpandArgs (the fields varied_resize_tile reads carry the
-// same names), n_sets stored versions of every tile, set-major: set s of tile t is at index s * n_tiles + t of tile_w,
-// tile_h and slots.  The wave's image is always in LDS (no HBM form).
+// pxz_distortion.hip): n_sets stored versions of every tile, set-major: set s of tile t is at index s * n_tiles + t of
+// tile_w, tile_h and slots.  The wave's image is always in LDS (no HBM form).  NOT derived from TileResizeArgs: it names the
+// same fields in the order this kernel was tuned with -- derived, distortion_kernel<4> measured 1.0-1.5 % slower on 64x64 tiles
+//  -- and varied_resize_tile and put_varied_expand_tables take either struct.
 struct DistortionArgs {
 	const VariedImage *images;
 	uint32_t n_images, n_tiles, n_sets;
@@ -555,24 +564,12 @@ struct WindowEntry {
 };
 
 // window_expand_kernel (pxz_window.hip): the covered tiles of the call's windows back to their full sizes, and of each the
-// part inside its window to the window's output.  The tables are VariedExpandArgs' (the fields varied_resize_tile reads carry
-// the same names); the wave's image is always in LDS (no HBM form).
-struct WindowExpandArgs {
+// part inside its window to the window's output.  The wave's image is always in LDS (no HBM form).
+struct WindowExpandArgs : TileResizeArgs {
 	const WindowEntry *windows;
-	uint32_t n_windows, n_tiles;
-	const uint32_t *tile_w, *tile_h;  // per covered tile: stored size
-	const uint8_t *slots;             // per covered tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
+	uint32_t n_windows;
 	uint8_t *base;                    // window k at base + windows[k].offset, windows[k].pitch between rows
-	uint32_t bw, bh, slot_bytes, filter;
-	const uint32_t *slot;
-	const ExpandTab *dir;
-	uint32_t stride;
-	const uint16_t *starts, *sizes;
-	const int16_t *coeffs;
-	uint32_t wdw, tile_dw;            // as VariedExpandArgs
-	uint32_t t0_dw;                   // (set by the launch) dwords of the windows' first tiles kept in LDS, 0: read from `windows`
-	uint32_t *status;                 // bit 0: a covered tile's stored size is 0 or exceeds its full size
-	uint32_t *window_flags;           // per window 1 for the same, or null
+	uint32_t *window_flags;           // per window 1 for a covered tile whose stored size is invalid, or null
 };
 
 struct SynthArgs {

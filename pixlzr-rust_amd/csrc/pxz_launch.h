@@ -1,6 +1,6 @@
 // pxz_launch.h — the host-callable launchers and size helpers of the kernel units, declared once: pxz_api.cpp calls them and
 // every .hip file that defines one includes this header, so the compiler holds each definition against its declaration.
-// Default arguments live here only.
+// Default arguments live here only.  launch_with_lds is the launch phrase of the kernels whose dynamic LDS can exceed 64 KB.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,4 +41,19 @@ hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus,
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
+
+#ifdef __HIP__
+// A launch with dynamic LDS: above 64 KB the kernel's limit is raised first.  Returns what the launch left behind.
+template <class Kernel, class Args>
+hipError_t launch_with_lds(Kernel kernel, uint32_t blocks, uint32_t threads, uint32_t lds_bytes, hipStream_t stream, const Args &a)
+{
+	if (lds_bytes > 64u * 1024u) {
+		const hipError_t e =
+			hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, stream, a);
+	return hipGetLastError();
+}
+#endif
 }  // namespace pxz

@@ -1191,12 +1191,7 @@ __global__ void __launch_bounds__(256) varied_index_kernel(const DecodeArgs a, c
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	const uint32_t i = blockIdx.x * 4u + wave;
 	if (i >= n_rows) return;
-	uint32_t lo = 0, hi = a.n_frames - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (images[mid].row0 <= i) lo = mid;
-		else hi = mid - 1u;
-	}
+	const uint32_t lo = owner_of(images, a.n_frames, i, &VariedImage::row0);
 	const VariedImage im = images[lo];
 	const uint32_t r = i - im.row0;
 	const IdxRow g{lo, r, im.width, im.height, im.cols, im.rows, im.edge_w, im.edge_h, im.tile0 + r * im.cols, 0u, 0u};
@@ -1204,19 +1199,14 @@ __global__ void __launch_bounds__(256) varied_index_kernel(const DecodeArgs a, c
 }
 
 // qoi_decode_kernel zeroes the size of a tile whose op stream runs dry (and of every tile the index left unusable): such a
-// tile's image gets its flag here, behind that kernel, which stays as it is.  One thread per tile.
-__global__ void __launch_bounds__(256) varied_decode_flags_kernel(const uint32_t *tile_w, const VariedImage *images, uint32_t n_images,
-                                                                  uint32_t n_tiles, uint32_t *image_flags)
+// tile's owner -- its image, or its window -- gets its flag here, behind that kernel, which stays as it is.  One thread per tile.
+template <class Entry>
+__global__ void __launch_bounds__(256) decode_flags_kernel(const uint32_t *tile_w, const Entry *owners, uint32_t n_owners, uint32_t n_tiles,
+                                                           uint32_t *owner_flags)
 {
 	const uint32_t t = blockIdx.x * 256u + threadIdx.x;
 	if (t >= n_tiles || tile_w[t] != 0u) return;
-	uint32_t lo = 0, hi = n_images - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (images[mid].tile0 <= t) lo = mid;
-		else hi = mid - 1u;
-	}
-	image_flags[lo] = 2u;
+	owner_flags[owner_of(owners, n_owners, t, &Entry::tile0)] = 2u;
 }
 
 // Pixel windows of files (pxz_decode_windows_device): one wave per covered tile row of the call.  The wave finds its window
@@ -1229,33 +1219,12 @@ __global__ void __launch_bounds__(256) window_index_kernel(const DecodeArgs a, c
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	const uint32_t i = blockIdx.x * 4u + wave;
 	if (i >= n_rows) return;
-	uint32_t lo = 0, hi = n_windows - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (windows[mid].row0 <= i) lo = mid;
-		else hi = mid - 1u;
-	}
+	const uint32_t lo = owner_of(windows, n_windows, i, &WindowEntry::row0);
 	const WindowEntry wn = windows[lo];
 	const uint32_t cr = i - wn.row0;
 	const IdxRow g{wn.image, wn.r0 + cr, wn.img_w, wn.img_h, wn.cols, wn.rows, wn.edge_w, wn.edge_h, wn.tile0 + cr * wn.ccols,
 	               wn.c0,    wn.c0 + wn.ccols - 1u};
 	index_row<true, true>(a, g, window_flags + lo, s_chunk[wave], lane);
-}
-
-// varied_decode_flags_kernel for windows: a covered tile that the index or qoi_decode_kernel left with size zero gives its
-// window the flag.  One thread per covered tile.
-__global__ void __launch_bounds__(256) window_decode_flags_kernel(const uint32_t *tile_w, const WindowEntry *windows, uint32_t n_windows,
-                                                                  uint32_t n_tiles, uint32_t *window_flags)
-{
-	const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-	if (t >= n_tiles || tile_w[t] != 0u) return;
-	uint32_t lo = 0, hi = n_windows - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (windows[mid].tile0 <= t) lo = mid;
-		else hi = mid - 1u;
-	}
-	window_flags[lo] = 2u;
 }
 
 // What an op's first byte says (qoi_decode_kernel's look-up table, one per channel count; built at compile time):
@@ -1512,10 +1481,10 @@ static hipError_t launch_decode_impl(const DecodeArgs &a, bool bins_clean, hipSt
 	if (a.channels == 4) hipLaunchKernelGGL(qoi_decode_kernel<4>, dim3(qb), dim3(64u * kQoiWaves), 0, stream, a);
 	else hipLaunchKernelGGL(qoi_decode_kernel<3>, dim3(qb), dim3(64u * kQoiWaves), 0, stream, a);
 	if (windows)
-		hipLaunchKernelGGL(window_decode_flags_kernel, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, windows, n_windows,
+		hipLaunchKernelGGL(decode_flags_kernel<WindowEntry>, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, windows, n_windows,
 		                   a.n_tiles, image_flags);
 	else if (images)
-		hipLaunchKernelGGL(varied_decode_flags_kernel, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, images, a.n_frames,
+		hipLaunchKernelGGL(decode_flags_kernel<VariedImage>, dim3((a.n_tiles + 255u) / 256u), dim3(256), 0, stream, a.tile_w, images, a.n_frames,
 		                   a.n_tiles, image_flags);
 	return hipGetLastError();
 }

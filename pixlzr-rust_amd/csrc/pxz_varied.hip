@@ -1,7 +1,7 @@
 // pxz_varied.hip -- batches of differently sized images (pxz_shrink_varied_frames_device, pxz_encode_varied_frames_device).
 // The tiles of every image of the batch form one flat tile space: image i owns tiles [tile0, tile0 + cols * rows), in the
 // reference's row-major order (src/data_types/iter.rs:64-76), and each tile finds its image by a binary search over the
-// per-image table.  One launch covers the batch, whatever the number of images.
+// per-image table (owner_of, pxz_device.h).  One launch covers the batch, whatever the number of images.
 //
 // varied_kernel: one tile per block of 256 threads (grid-stride over the batch).  A tile is
 //   1. staged      into LDS as tightly packed bytes (16-byte loads where its rows are aligned, dwords or bytes otherwise);
@@ -37,17 +37,6 @@ __host__ __device__ inline uint32_t varied_lds_bytes(uint32_t mode, uint32_t til
 	const uint32_t tables = mode == 0u ? kVariedTables * 4u : 0u;
 	const uint32_t a = mode == 0u && tile_bytes < kVariedPlaneBytes ? kVariedPlaneBytes : tile_bytes;
 	return tables + tile_bytes + a;
-}
-
-__device__ __forceinline__ uint32_t varied_image_of(const VariedImage *images, uint32_t n_images, uint32_t t)
-{
-	uint32_t lo = 0, hi = n_images - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (images[mid].tile0 <= t) lo = mid;
-		else hi = mid - 1u;
-	}
-	return lo;
 }
 
 __device__ __forceinline__ uint32_t varied_pixel(const uint8_t *s_x, uint32_t i, int C)
@@ -123,7 +112,7 @@ __global__ void __launch_bounds__(kVariedThreads) varied_kernel(const VariedArgs
 	}
 
 	for (uint32_t tile_g = blockIdx.x; tile_g < a.n_tiles; tile_g += gridDim.x) {
-		const VariedImage im = a.images[varied_image_of(a.images, a.n_images, tile_g)];
+		const VariedImage im = a.images[owner_of(a.images, a.n_images, tile_g, &VariedImage::tile0)];
 		const uint32_t t = tile_g - im.tile0;
 		const uint32_t ty = t / im.cols, tx = t - ty * im.cols;
 		const uint32_t w = tx + 1u == im.cols ? im.edge_w : a.bw;  // split.rs:18
@@ -322,19 +311,12 @@ hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus,
 {
 	if (a.n_tiles == 0u) return hipSuccess;
 	const uint32_t lds = varied_lds_bytes(a.mode, a.tile_bytes);
-	auto go = [&](auto kernel) -> hipError_t {
-		if (lds > 64u * 1024u) {
-			hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			if (e != hipSuccess) return e;
-		}
-		// as many blocks as the CUs' LDS holds (at most eight of four waves per CU); the rest walk the grid-stride loop
-		uint32_t per_cu = (160u * 1024u) / lds;
-		per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
-		const uint64_t cap = (uint64_t)n_cus * per_cu;
-		const uint32_t blocks = (uint32_t)(a.n_tiles < cap ? a.n_tiles : cap);
-		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kVariedThreads), lds, stream, a);
-		return hipGetLastError();
-	};
+	// as many blocks as the CUs' LDS holds (at most eight of four waves per CU); the rest walk the grid-stride loop
+	uint32_t per_cu = (160u * 1024u) / lds;
+	per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
+	const uint64_t cap = (uint64_t)n_cus * per_cu;
+	const uint32_t blocks = (uint32_t)(a.n_tiles < cap ? a.n_tiles : cap);
+	auto go = [&](auto kernel) { return launch_with_lds(kernel, blocks, kVariedThreads, lds, stream, a); };
 	return channels == 4u ? go(varied_kernel<4>) : go(varied_kernel<3>);
 }
 
@@ -357,13 +339,7 @@ __global__ void __launch_bounds__(64) varied_headers_kernel(const VariedWriterAr
 {
 	const uint32_t rg = blockIdx.x * 64u + threadIdx.x;
 	if (rg >= a.n_rows) return;
-	uint32_t lo = 0, hi = a.n_images - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (a.images[mid].row0 <= rg) lo = mid;
-		else hi = mid - 1u;
-	}
-	const uint32_t i = lo;
+	const uint32_t i = owner_of(a.images, a.n_images, rg, &VariedImage::row0);
 	const VariedImage im = a.images[i];
 	const uint32_t r = rg - im.row0;
 	auto record_offset = [&](uint32_t t) -> unsigned long long {

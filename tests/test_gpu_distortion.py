@@ -301,14 +301,20 @@ def test_windows_kept_across_sets_that_repeat_a_stored_size(gpu, oracle):
 VARIED_SIZES = [(1, 1), (31, 33), (97, 61), (33, 2), (64, 32)]
 
 
-def varied_batch(rng, sizes, bw, bh, c, kind):
-    """images at odd offsets with padded rows in one buffer, hand-made stored sizes, random stored bytes"""
-    import torch
+def odd_layout(sizes, c):
+    """descriptors of images at odd offsets with padded rows in one buffer -> (descs, bytes)"""
     descs, at = [], 1
     for k, (w, h) in enumerate(sizes):
         pitch = w * c + 3 * (k % 3)
         descs.append((w, h, pitch, at))
         at += pitch * h + 1 + 2 * (k % 2)
+    return descs, at
+
+
+def varied_batch(rng, sizes, bw, bh, c, kind):
+    """images at odd offsets with padded rows in one buffer, hand-made stored sizes, random stored bytes"""
+    import torch
+    descs, at = odd_layout(sizes, c)
     buf = np.full(at, POISON, np.uint8)
     imgs, tws, ths, slots = [], [], [], []
     for (w, h, pitch, off) in descs:
@@ -357,6 +363,37 @@ def test_five_images_in_one_call_equal_the_frames_call_and_the_oracle(gpu, produ
                 assert st == 0 and (one[0, 0] == tiles[a:b]).all() and (one_totals[0, 0] == totals[i]).all(), f"image {i} vs the frames call"
     _, alone, _, _ = run_varied(gpu, descs, c, bw, bh, 4, dev, want_tiles=False)
     assert (alone == totals).all()
+
+
+@pytest.mark.parametrize("c", [3, 4])
+def test_2049_images_equal_the_oracle(gpu, product, oracle, c):
+    """the batch of tests/test_gpu_varied_decode.py that has more images than a block keeps first tiles of in LDS: per tile and per
+    image against the oracle's expand of every image"""
+    import torch
+    from test_gpu_varied_decode import MANY, many_images
+    m = many_images(oracle, c)
+    descs, at = odd_layout(m.sizes, c)
+    buf = np.full(at, POISON, np.uint8)
+    for (w, h, pitch, off), img in zip(descs, m.images):
+        np.lib.stride_tricks.as_strided(buf[off:], (h, w, c), (pitch, c, 1))[...] = img
+    dev = (torch.from_numpy(buf).cuda(), torch.from_numpy(m.flat[1].astype(np.int32)).cuda(), torch.from_numpy(m.flat[2].astype(np.int32)).cuda(),
+           torch.from_numpy(m.flat[3]).cuda())
+    to = product.varied_layout(descs, 4, 4)
+    assert int(to[-1]) == m.flat[1].size
+    for filt in (0, 4):
+        tiles, totals, flags, status = run_varied(gpu, descs, c, 4, 4, filt, dev)
+        assert status == 0 and (flags == 0).all()
+        exp_tiles, exp_totals = [], []
+        for img, exp in zip(m.images, m.expected(filt)):
+            d = (img.astype(np.int64) - exp.astype(np.int64)) ** 2
+            per_tile = np.array([d[y:y + fh, x:x + fw].sum(axis=(0, 1)) for (x, y, fw, fh) in tile_rects(img.shape[1], img.shape[0], 4, 4)], np.int64)
+            exp_tiles.append(per_tile.reshape(-1, c)), exp_totals.append(per_tile.reshape(-1, c).sum(axis=0))
+        exp_tiles, exp_totals = np.concatenate(exp_tiles), np.stack(exp_totals)
+        print(f"C{c} filter {filt}: {int((tiles != exp_tiles).any(axis=1).sum())} of {exp_tiles.shape[0]} tiles, "
+              f"{int((totals != exp_totals).any(axis=1).sum())} of {MANY} images differ")
+        assert exp_tiles.any() and not exp_tiles.all(axis=1).all()  # (clones and stored tiles both)
+        assert (tiles == exp_tiles).all(), f"C{c} filter {filt}: tiles {np.flatnonzero((tiles != exp_tiles).any(axis=1))[:10].tolist()}"
+        assert (totals == exp_totals).all(), f"C{c} filter {filt}: images {np.flatnonzero((totals != exp_totals).any(axis=1))[:10].tolist()}"
 
 
 # ---- invalid stored sizes -------------------------------------------------------------------------------------------------

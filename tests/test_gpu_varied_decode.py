@@ -325,6 +325,97 @@ def test_reference_container_tests_as_varied_batches(gpu, product, oracle, golde
         assert (image_of(got, d, 4) == img).all()
 
 
+# ---- more images than a block keeps first tiles of in LDS --------------------------------------------------------------------
+
+MANY = 2049                                       # one more than kVxImages (pxz_device.h): the owner search reads the table itself
+MANY_SIZES = [(4, 4), (5, 3), (3, 6), (9, 4)]     # in 4x4 blocks: 1, 2, 2 and 3 tiles, edge tiles 1 and 3 wide, 3 and 2 high
+
+
+class ManyImages:
+    """MANY images of a few pixels each in 4x4 blocks, the sizes of MANY_SIZES in turn.  Stored sizes by hand, five shapes dealt in
+    turn over the batch's tiles (full, lower, narrower, a pixel less on both axes, 1x1); random source pixels and stored bytes, a
+    tile stored at its full size holds its source (what a shrinker stores there, and what the distortion calls assume).  Every
+    file passes the oracle's reader alone, and the oracle's per-image expand is computed once per filter -- all on the CPU."""
+    bw = bh = 4
+
+    def __init__(self, oracle, c):
+        rng = np.random.default_rng(2049 * c)
+        self.oracle, self.c, self._expected = oracle, c, {}
+        self.sizes = [MANY_SIZES[i % len(MANY_SIZES)] for i in range(MANY)]
+        self.images, self.tiles, self.files, rank = [], [], [], 0
+        for (w, h) in self.sizes:
+            img = rng.integers(0, 256, (h, w, c), dtype=np.uint8)
+            cols, rows = -(-w // 4), -(-h // 4)
+            n = cols * rows
+            vals = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32).view(np.float32)
+            tw, th, slots = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 16 * c), np.uint8)
+            for t in range(n):
+                x, y = t % cols * 4, t // cols * 4
+                fw, fh = min(4, w - x), min(4, h - y)
+                sw, sh = [(fw, fh), (fw, max(fh // 2, 1)), (max(fw // 2, 1), fh), (max(fw - 1, 1), max(fh - 1, 1)), (1, 1)][rank % 5]
+                rank += 1
+                tw[t], th[t] = sw, sh
+                px = img[y:y + fh, x:x + fw] if (sw, sh) == (fw, fh) else rng.integers(0, 256, (sh, sw, c), dtype=np.uint8)
+                slots[t, :sw * sh * c] = px.reshape(-1)
+            raw = oracle.encode_container(w, h, 4, 4, c, 0, vals, None, tw, th, slots)
+            d = oracle.decode_container(raw)  # valid for the reference alone: nothing refused, every tile as written
+            assert (d["tw"] == tw).all() and (d["th"] == th).all() and (d["values"].view(np.uint32) == vals.view(np.uint32)).all()
+            self.images.append(img), self.tiles.append((vals, tw, th, slots)), self.files.append(raw)
+        self.flat = tuple(np.concatenate([t[k] for t in self.tiles]) for k in range(4))
+        counts = {n: sum(1 for t in self.tiles if t[1].size == n) for n in (1, 2, 3)}
+        assert all(counts.values()) and sum(counts.values()) == MANY, counts
+        full = self.flat[1] * self.flat[2] == 16
+        assert full.any() and (self.flat[1] == 1).any() and (self.flat[1] == 3).any() and not full.all()
+
+    def expected(self, filt):
+        """the oracle's expand of every image"""
+        if filt not in self._expected:
+            self._expected[filt] = [self.oracle.expand_image(w, h, 4, 4, self.c, filt, t[1], t[2], t[3]) for (w, h), t in zip(self.sizes, self.tiles)]
+        return self._expected[filt]
+
+
+_many = {}
+
+
+def many_images(oracle, c):
+    if c not in _many:
+        _many[c] = ManyImages(oracle, c)
+    return _many[c]
+
+
+@pytest.mark.parametrize("c", [3, 4])
+def test_2049_images_find_their_tiles_in_the_table_itself(gpu, product, oracle, c):
+    """reader (one wave per tile row, one thread per tile) and expand (Nearest, Lanczos3) of MANY images: every tile as written,
+    every image byte for byte the oracle's; then the LAST image's first tile with stored width 0: its flag alone"""
+    m = many_images(oracle, c)
+    to, host, flags, status, dev = decode_varied(gpu, product, m.files, m.sizes, c, 4, 4)
+    assert status == 0 and (flags == 0).all()
+    assert int(to[-1]) == m.flat[1].size
+    assert_tiles_equal(host, m.flat, c, f"C{c} {MANY} images vs what was written")
+    descs, total = layout(m.sizes, c, pad=3, misalign=1)
+    covered = np.zeros(total, bool)
+    for (w, h, pitch, off) in descs:
+        for y in range(h):
+            covered[off + y * pitch: off + y * pitch + w * c] = True
+    for filt in (0, 4):
+        buf, fl, st = expand_varied(gpu, descs, total, c, 4, 4, filt, dev)
+        assert st == 0 and (fl == 0).all(), f"filter {filt}: status {st}, flags of {np.flatnonzero(fl).tolist()}"
+        bad = [i for i, (d, exp) in enumerate(zip(descs, m.expected(filt))) if not (image_of(buf, d, c) == exp).all()]
+        print(f"C{c} filter {filt}: {len(bad)} of {MANY} images differ from the oracle")
+        assert not bad, f"C{c} filter {filt}: images {bad[:10]} differ from the oracle"
+        assert (buf[~covered] == POISON).all(), f"C{c} filter {filt}: bytes outside the images were written"
+    last = MANY - 1
+    assert int(to[last + 1]) - int(to[last]) == 1  # (a 4x4 image: one tile)
+    ow = dev[1].clone()
+    ow[int(to[last])] = 0
+    buf, fl, st = expand_varied(gpu, descs, total, c, 4, 4, 4, (dev[0], ow, dev[2], dev[3]))
+    assert st == 1 and fl.tolist() == [0] * last + [1]
+    assert (image_of(buf, descs[last], c) == POISON).all()
+    bad = [i for i in range(last) if not (image_of(buf, descs[i], c) == m.expected(4)[i]).all()]
+    assert not bad, f"C{c}: images {bad[:10]} beside the flagged one are not complete"
+    assert (buf[~covered] == POISON).all()
+
+
 # ---- malformed files in a batch ------------------------------------------------------------------------------------------
 
 def one_tile_file(w, h, bw, bh, c, ops):

@@ -282,6 +282,50 @@ def test_windows_of_three_differently_sized_files_in_one_call(gpu, product, orac
         check_windows(buf, files, windows, filt, full_images(gpu, files, filt, full_dev), f"three files {kind} filter {filt}")
 
 
+# ---- more windows than a block keeps first tiles of in LDS ------------------------------------------------------------------
+
+MANY = 2049  # one more than kVxImages (pxz_device.h): the owner search reads the table itself
+
+
+def many_windows(rng, files, c):
+    """MANY windows of 1 .. 11 px on a side over the files in turn, each starting inside a tile on both axes, its output at an odd
+    byte offset with a pitch one byte above its row -> (windows, bytes)"""
+    windows, at = [], 7
+    for k in range(MANY):
+        f = files[k % len(files)]
+        x, y = int(rng.integers(1, f.w)), int(rng.integers(1, f.h))
+        x, y = x - (x % f.bw == 0), y - (y % f.bh == 0)
+        w, h = int(rng.integers(1, min(11, f.w - x) + 1)), int(rng.integers(1, min(11, f.h - y) + 1))
+        at |= 1
+        windows.append((k % len(files), x, y, w, h, w * c + 1, at))
+        at += (w * c + 1) * h + 3
+    return windows, at + 7
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_2049_windows_find_their_tiles_in_the_table_itself(gpu, product, oracle, kind):
+    bw = bh = 8
+    files = [File(oracle, bw, bh, w, h, kind, seed=11) for (w, h) in ((29, 23), (40, 17), (13, 35))]
+    c = files[0].c
+    windows, total = many_windows(np.random.default_rng(2049 + c), files, c)
+    # conditions on the inputs, checked before the GPU is used
+    assert len(windows) == MANY
+    assert all(x % bw and y % bh and 1 <= w <= 11 and 1 <= h <= 11 and off % 2 == 1 and pitch == w * c + 1 for (_, x, y, w, h, pitch, off) in windows)
+    assert {len(covered_tiles(files[i], (x, y, w, h))) for (i, x, y, w, h, _, _) in windows} >= {1, 2, 4}
+    assert any(w == 11 and h == 11 for (_, _, _, w, h, _, _) in windows) and any(w == 1 for (_, _, _, w, _, _, _) in windows)
+    for f in files:
+        f.image(0), f.image(4)  # (the oracle reads and expands every file alone)
+    full_to, full, _, full_status, _ = full_decode(gpu, product, files)
+    assert full_status == 0
+    to, got, flags, status, dev = decode_windows(gpu, product, files, windows)
+    assert status == 0 and (flags == 0).all(), f"decode: status {status}, flags of {np.flatnonzero(flags).tolist()}"
+    assert_covered_tiles_equal(files, windows, to, got, full_to, full, f"{MANY} windows {kind}")
+    for filt in (0, 4):
+        buf, flags, status = expand_windows(gpu, files, windows, total, filt, dev)
+        assert status == 0 and (flags == 0).all(), f"filter {filt}: status {status}, flags of {np.flatnonzero(flags).tolist()}"
+        check_windows(buf, files, windows, filt, None, f"{MANY} windows {kind} filter {filt}")
+
+
 # ---- what is read of a file, and what that means for damage --------------------------------------------------------------
 
 def record_at(raw, rows, ty, tx):
