@@ -2,7 +2,7 @@
 // and prints one line per table set: the geometry, then element count and FNV-1a 64 hash of every array ("-": absent).
 // tests/test_tables_host.py pins a digest of these lines per (family, filter).  With the argument `varied` it prints the
 // directories of varied batches instead (tests/test_varied_host.py), with `varied_expand` those of their decode side
-// (tests/test_varied_decode_host.py).
+// (tests/test_varied_decode_host.py), with `thresholds` the level decision's float thresholds as bit patterns.
 #include <array>
 #include <cstring>
 #include <cstdio>
@@ -119,8 +119,23 @@ int dump_varied_expand()
 	return 0;
 }
 
+// build_level_thresholds: one line per k, the threshold's bit pattern in hex (tests/test_tables_host.py holds them against the
+// oracle's reduce_dims)
+int dump_thresholds()
+{
+	float t[pxz::kNumThresholds];
+	if (!pxz::build_level_thresholds(t, pxz::kNumThresholds)) return 1;
+	for (int k = 0; k < pxz::kNumThresholds; ++k) {
+		uint32_t bits;
+		std::memcpy(&bits, &t[k], 4);
+		printf("threshold k=%d bits=%08x\n", k, bits);
+	}
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc > 1 && std::strcmp(argv[1], "thresholds") == 0) return dump_thresholds();
 	if (argc > 1 && std::strcmp(argv[1], "varied") == 0) return dump_varied();
 	if (argc > 1 && std::strcmp(argv[1], "varied_expand") == 0) return dump_varied_expand();
 	for (uint32_t f = 0; f < 5; ++f)

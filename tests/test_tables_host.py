@@ -74,3 +74,39 @@ def test_operand_tables_go_to_the_matrix_core_tiles_only(table_sets):
             elif family == "expand":
                 for key, tile in (("xmf", "32x32"), ("xmf16", "16x16"), ("xmf64", "64x64")):
                     assert (f[key] != "-") == (conv and f["tile"] == tile), line
+
+
+def test_level_thresholds_are_the_oracles_breakpoints(product, oracle):
+    """build_level_thresholds against the oracle's reduce_dims (operations.rs:145-151), bit for bit: with a side of 2^31 the
+    reduced side is 2^(31-k) at the k-th threshold and half of that at the float just below it, and the level is constant over
+    the 4096 bit patterns on either side."""
+    import numpy as np
+    product.build_library()
+    r = subprocess.run([TOOL, "thresholds"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    bits = {}
+    for line in r.stdout.splitlines():
+        f = _fields(line)
+        bits[int(f["k"])] = int(f["bits"], 16)
+    assert sorted(bits) == list(range(32))
+    side = 1 << 31
+
+    def reduced(b):
+        v = np.array([b], np.uint32).view(np.float32)[0]
+        nw, nh, _ = oracle.reduce_dims(v, v, side, side)
+        assert nw == nh
+        return nw
+
+    for k in range(31):
+        t = bits[k]
+        at, below = side >> k, side >> (k + 1)
+        assert reduced(t) == at and reduced(t - 1) == below, (k, hex(t), reduced(t), reduced(t - 1))
+        for d in range(1, 4097):
+            assert reduced(t + d - 1) == at and reduced(t - d) == below, (k, hex(t), d)
+
+
+def test_breakpoint_helpers_of_the_gpu_tests(oracle):
+    """the bisection and the tile builder of tests/test_gpu_level_breakpoints.py need the oracle only: the same check here,
+    where a broken helper shows without a GPU"""
+    import test_gpu_level_breakpoints as helpers
+    helpers.test_helper_finds_the_known_flips(oracle)
