@@ -1,7 +1,8 @@
 """Randomized parity of the device .pixlzr writer and reader against the oracle on adversarial tile content: few colours
 (INDEX hits), long and short runs (incl. runs of one and tiles that open with opaque black), gradients (DIFF / LUMA),
 alpha flicker (RGBA ops), noise (RGB ops).  Tiles stay unshrunk (factor picks 'clone') or shrink, both sizes of files
-are compared byte for byte, then the files are read back on the device.  Not part of the suite."""
+are compared byte for byte, then the files are read back on the device.  Not part of the suite.
+The deterministic part is tests/test_gpu_stream_seams.py: one event at every pixel position of a tile."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
