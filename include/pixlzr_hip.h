@@ -258,6 +258,28 @@ int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const 
                              uint32_t channels, const pxz_params *params, uint32_t filter_byte, uint8_t *out,
                              uint64_t out_capacity, uint64_t *file_offsets);
 
+/* Varied ladder: the sweep of src/bin/whole-folder.rs:69-117 -- a folder of differently sized images x several factors -- in
+ * ONE launch, whatever n_images and n_factors are.  Every tile is staged and measured once (the detector's raw result does
+ * not depend on the factor, in either mode); each rung only decides its levels, and a tile is resampled once per distinct
+ * pair of levels among its rungs.  params->factor is ignored; factors is a HOST array (1 <= n_factors <=
+ * PXZ_VARIED_LADDER_MAX_RUNGS, each finite; any order, repeats allowed).  Outputs are rung-major: with tile_offsets and
+ * tiles = tile_offsets[n_images] from pxz_varied_layout, rung r of tile t of image i is index r*tiles + tile_offsets[i] + t
+ * of d_block_value, d_out_w, d_out_h and of the slots of d_out_pixels (block_w*block_h*channels bytes each, 64-bit offsets;
+ * may be NULL: values and sizes only).  That is the layout of a varied batch of n_factors*n_images images whose descriptors
+ * are descs repeated n_factors times, so pxz_encode_varied_frames_device and pxz_distortion_varied_frames_device take the
+ * result as it is.  Rung r equals pxz_shrink_varied_frames_device with factor = factors[r] bit for bit (value bits, sizes,
+ * the valid bytes of every slot).  Asynchronous on the handle's stream.
+ * Validation runs on the host before anything is launched; on an error nothing is written.  Codes and "image i" texts are
+ * pxz_shrink_varied_frames_device's, its limit (block_w*block_h*channels <= 65536 bytes) included; PXZ_ERR_INVALID_ARG for
+ * factors null, n_factors 0 or above the maximum, or a non-finite factor; PXZ_ERR_UNSUPPORTED when n_factors * tiles exceeds
+ * 2^32-1.  The call reads and writes none of the state the single-geometry fast paths keep in the handle; pxz_trim gives
+ * back what it grew.  PXZ_LADDER_MAX_RUNGS and the single-geometry ladder are not affected. */
+#define PXZ_VARIED_LADDER_MAX_RUNGS 32u   /* the reference's sweep of 20 fits */
+int pxz_shrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                           const pxz_params *params, const float *factors, uint32_t n_factors,
+                                           const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                           uint8_t *d_out_pixels);
+
 /* The colour conversion inside get_block_variance, per pixel (operations.rs:56-59: Srgba<u8>::into_linear()
  * .into_color::<Oklaba<f32>>(), palette 0.7.6 + the platform's cbrtf): d_laba[4i..4i+3] = {l, a, b, alpha} of
  * RGBA pixel i.  The same device function the Oklab detector kernels call -- exposed so that its bits can be
@@ -487,6 +509,17 @@ int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t wid
                               uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
                               uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes,
                               uint64_t *sse);
+
+/* The same table for a folder: host-resident images of different sizes in, one row per (factor, image) out.  pixels[i] is
+ * image i (descs[i].offset_bytes is ignored).  file_bytes[r*n_images + i] and sse[(r*n_images + i)*channels + c] are what
+ * pxz_rate_distortion_image gives for image i at factors[r] (1 <= n_factors <= PXZ_VARIED_LADDER_MAX_RUNGS).  Composition
+ * only: upload, pxz_shrink_varied_ladder_frames_device, pxz_encode_varied_frames_device over the descriptors repeated
+ * n_factors times for its offsets (no file is kept), pxz_distortion_varied_frames_device over the same descriptors, one
+ * download.  Synchronous.  Errors and limits are those of the calls it composes. */
+int pxz_rate_distortion_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs,
+                                      uint32_t n_images, uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode,
+                                      uint32_t filter_down, uint32_t filter_up, const float *factors, uint32_t n_factors,
+                                      uint64_t *file_bytes, uint64_t *sse);
 
 /* ---- legacy image -> image filter ------------------------ */
 

@@ -11,7 +11,7 @@ from .binding import (  # noqa: F401
     MODE_SHRINK_BY, MODE_SHRINK_DIRECTIONALLY,
     DIST_OPAQUE, DIST_ALPHA, DIST_FLAT, DIST_NOISE,
     PxzError, Handle, build_library, library_path, load_library, grid, encode_container, qoi_encode, axis_table,
-    EXPORTED_SYMBOLS, LADDER_MAX_RUNGS, varied_layout, image_descs, file_header, psnr,
+    EXPORTED_SYMBOLS, LADDER_MAX_RUNGS, VARIED_LADDER_MAX_RUNGS, varied_layout, image_descs, file_header, psnr,
     Window, window_descs, window_layout,
 )
 from . import dist  # noqa: E402,F401  (torch.distributed plumbing: frame sharding + block-stream gather)

@@ -24,10 +24,12 @@ EXPORTED_SYMBOLS = [
     "pxz_varied_layout", "pxz_shrink_varied_frames_device", "pxz_encode_varied_frames_device", "pxz_encode_varied_images",
     "pxz_file_header", "pxz_decode_varied_frames_device", "pxz_expand_varied_frames_device", "pxz_decode_varied_files",
     "pxz_distortion_frames_device", "pxz_distortion_varied_frames_device", "pxz_rate_distortion_image",
+    "pxz_shrink_varied_ladder_frames_device", "pxz_rate_distortion_varied_images",
     "pxz_window_layout", "pxz_decode_windows_device", "pxz_expand_windows_device", "pxz_decode_windows_files",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
+VARIED_LADDER_MAX_RUNGS = 32  # PXZ_VARIED_LADDER_MAX_RUNGS
 
 STATUS = {0: "PXZ_OK", -1: "PXZ_ERR_INVALID_ARG", -2: "PXZ_ERR_NO_DEVICE", -3: "PXZ_ERR_HIP",
           -4: "PXZ_ERR_TILE_TOO_SMALL", -5: "PXZ_ERR_UNSUPPORTED", -6: "PXZ_ERR_NOMEM",
@@ -177,6 +179,11 @@ def load_library():
         L.pxz_expand_windows_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params)] + [vp] * 5
         L.pxz_decode_windows_files.restype = C.c_int
         L.pxz_decode_windows_files.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, C.c_uint64, vp]
+    if hasattr(L, "pxz_shrink_varied_ladder_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the varied ladder)
+        L.pxz_shrink_varied_ladder_frames_device.restype = C.c_int
+        L.pxz_shrink_varied_ladder_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), vp, u32] + [vp] * 5
+        L.pxz_rate_distortion_varied_images.restype = C.c_int
+        L.pxz_rate_distortion_varied_images.argtypes = [vp, vp, vp] + [u32] * 7 + [vp, u32, vp, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -570,6 +577,41 @@ class Handle:
             offs = varied_layout(geoms, bw, bh)
         return offs, vals, ow, oh, slots
 
+    def shrink_varied_ladder_frames_device(self, images, bw, bh, mode, filt, factors, want_pixels=True, descs=None, channels=None,
+                                           out=None, n_factors=None):
+        """pxz_shrink_varied_ladder_frames_device: shrink_varied_frames_device at every factor of `factors` (a host sequence,
+        1..32 of them) in one launch.  Returns (tile_offsets uint64[n+1], values[K,T], w[K,T], h[K,T], slots[K,T,bw*bh*C] |
+        None); rung r equals shrink_varied_frames_device(..., factors[r]), and the arrays flattened are the varied layout of
+        the images repeated K times.  out: a 4-tuple of such tensors (slots may be None).  factors None with n_factors passes
+        a null pointer."""
+        import torch
+        base, geoms, ch, keep = self._varied_batch(images, descs)
+        ch = channels if channels is not None else ch
+        fac = None if factors is None else np.ascontiguousarray(factors, np.float32)
+        K = n_factors if n_factors is not None else (0 if fac is None else fac.size)
+        dev = torch.device("cuda", self.device_id)
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            vals = torch.empty((K, T), dtype=torch.float32, device=dev)
+            ow = torch.empty((K, T), dtype=torch.int32, device=dev)
+            oh = torch.empty((K, T), dtype=torch.int32, device=dev)
+            slots = torch.empty((K, T, bw * bh * ch), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, ow, oh, slots = out
+        pd = Params(bw, bh, mode, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_shrink_varied_ladder_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), ch, C.byref(pd),
+            _p(fac) if fac is not None and fac.size else None, K, C.c_void_p(base),
+            C.c_void_p(vals.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()) if slots is not None else None))
+        del keep
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, ow, oh, slots
+
     def encode_varied_frames_device(self, sizes, channels, bw, bh, vals, ow, oh, slots, filter_byte=0, out=None):
         """pxz_encode_varied_frames_device: sizes = [(width, height), ...] of the images whose tiles (varied layout) are given.
         Returns (file_offsets int64[n+1], bytes uint8[capacity])."""
@@ -828,6 +870,23 @@ class Handle:
         self._check(self._L.pxz_rate_distortion_image(self._h, C.c_void_p(img.ctypes.data), W, H, Cc, img.strides[0], bw, bh, mode,
                                                       filter_down, filter_up, _p(fac) if K else None, K, _p(file_bytes), _p(sse)))
         return file_bytes[:K], sse[:K]
+
+    def rate_distortion_varied_images(self, imgs, bw, bh, mode, filter_down, filter_up, factors):
+        """pxz_rate_distortion_varied_images: host images (numpy uint8 [H,W,C], one channel count) at every factor of `factors`
+        (1..32) -> (file_bytes uint64[K,n], sse uint64[K,n,C]): what rate_distortion_image gives per image and factor."""
+        imgs = [np.ascontiguousarray(i) if i.strides[1] != i.shape[2] or i.strides[2] != 1 else i for i in imgs]
+        n = len(imgs)
+        ch = imgs[0].shape[2] if n else 4
+        geoms = [(i.shape[1], i.shape[0], i.strides[0], 0) for i in imgs]
+        ptrs = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in imgs])
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        file_bytes = np.zeros((max(K, 1), max(n, 1)), np.uint64)
+        sse = np.zeros((max(K, 1), max(n, 1), ch), np.uint64)
+        self._check(self._L.pxz_rate_distortion_varied_images(
+            self._h, C.cast(ptrs, C.c_void_p), C.cast(image_descs(geoms), C.c_void_p), n, ch, bw, bh, mode, filter_down, filter_up,
+            _p(fac) if K else None, K, _p(file_bytes), _p(sse)))
+        return file_bytes[:K, :n], sse[:K, :n]
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

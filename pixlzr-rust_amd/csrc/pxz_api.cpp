@@ -2227,6 +2227,64 @@ int varied_check_params(pxz_handle *h, uint32_t channels, const pxz_params *p)
 	return PXZ_OK;
 }
 
+// The host forms' images (checked, none null) into handle scratch, back to back with 256-byte aligned starts: *dev are their
+// descriptors there, *raw the bytes of their pixels.
+int varied_send_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                       std::vector<pxz_image_desc> *dev, uint64_t *raw)
+{
+	dev->assign(descs, descs + n_images);
+	auto bytes_of = [&](uint32_t i) { return (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels; };
+	uint64_t in_bytes = 0;
+	*raw = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		(*dev)[i].offset_bytes = in_bytes;
+		in_bytes += (bytes_of(i) + 255u) & ~(uint64_t)255u;
+		*raw += (uint64_t)descs[i].width * descs[i].height * channels;
+	}
+	const int rc = ensure(h, h->varied_in, in_bytes);
+	if (rc != PXZ_OK) return rc;
+	uint8_t *d_in = (uint8_t *)h->varied_in.ptr;
+	for (uint32_t i = 0; i < n_images; ++i)
+		PXZ_HIP(h, hipMemcpyAsync(d_in + (*dev)[i].offset_bytes, pixels[i], bytes_of(i), hipMemcpyHostToDevice, h->stream));
+	return PXZ_OK;
+}
+
+// the ladder's rules for a host array of factors
+int check_factors(pxz_handle *h, const float *factors, uint32_t n_factors, uint32_t max_rungs)
+{
+	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
+	if (n_factors == 0 || n_factors > max_rungs) return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", max_rungs, n_factors);
+	for (uint32_t r = 0; r < n_factors; ++r)
+		if (!std::isfinite(factors[r])) return fail(h, PXZ_ERR_INVALID_ARG, "factor %u must be finite", r);
+	return PXZ_OK;
+}
+
+// what varied_kernel and varied_ladder_kernel are told about a planned batch (a->images is varied_upload's)
+void varied_fill_args(pxz_handle *h, const std::vector<pxz::VariedImage> &images, uint32_t channels, const pxz_params *params,
+                      const VariedTables *vt, const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                      uint8_t *d_out_pixels, pxz::VariedArgs *a)
+{
+	a->base = d_base;
+	a->n_images = (uint32_t)images.size();
+	a->n_tiles = varied_n_tiles(images);
+	a->bw = params->block_w;
+	a->bh = params->block_h;
+	a->mode = params->mode;
+	a->filter = params->filter;
+	a->factor = params->factor;
+	a->value = d_block_value;
+	a->out_w = d_out_w;
+	a->out_h = d_out_h;
+	a->out_px = d_out_pixels;
+	a->slot_bytes = params->block_w * params->block_h * channels;
+	a->tile_bytes = (a->slot_bytes + 15u) & ~15u;
+	a->dir = vt->d_dir;
+	a->starts = vt->d_starts;
+	a->sizes = vt->d_sizes;
+	a->coeffs = vt->d_coeffs;
+	std::memcpy(a->thresholds, h->thresholds, sizeof a->thresholds);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2260,26 +2318,41 @@ int pxz_shrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	if ((rc = get_varied_tables(h, params->filter, sides, &vt)) != PXZ_OK) return rc;
 	pxz::VariedArgs a{};
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
-	a.base = d_base;
-	a.n_images = n_images;
-	a.n_tiles = varied_n_tiles(images);
-	a.bw = params->block_w;
-	a.bh = params->block_h;
-	a.mode = params->mode;
-	a.filter = params->filter;
-	a.factor = params->factor;
-	a.value = d_block_value;
-	a.out_w = d_out_w;
-	a.out_h = d_out_h;
-	a.out_px = d_out_pixels;
-	a.slot_bytes = params->block_w * params->block_h * channels;
-	a.tile_bytes = (a.slot_bytes + 15u) & ~15u;
-	a.dir = vt->d_dir;
-	a.starts = vt->d_starts;
-	a.sizes = vt->d_sizes;
-	a.coeffs = vt->d_coeffs;
-	std::memcpy(a.thresholds, h->thresholds, sizeof a.thresholds);
+	varied_fill_args(h, images, channels, params, vt, d_base, d_block_value, d_out_w, d_out_h, d_out_pixels, &a);
 	PXZ_HIP(h, pxz::launch_varied(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_shrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                           const pxz_params *params, const float *factors, uint32_t n_factors,
+                                           const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                           uint8_t *d_out_pixels)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!d_base || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	pxz_params p = *params;
+	p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
+	if ((rc = varied_check_params(h, channels, &p)) != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	if ((uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	// (cannot happen within the tile limit above; the kernel's own layout has the last word)
+	if (pxz::varied_ladder_lds_limit_bytes(p.mode, p.block_w, p.block_h, channels) > 160u * 1024u)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a %ux%u tile and its resampled images do not fit in LDS", p.block_w, p.block_h);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::VariedLadderArgs a{};
+	if ((rc = varied_upload(h, images, &a.v.images)) != PXZ_OK) return rc;
+	varied_fill_args(h, images, channels, &p, vt, d_base, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.v);
+	a.n_factors = n_factors;
+	std::memcpy(a.factors, factors, n_factors * sizeof(float));
+	PXZ_HIP(h, pxz::launch_varied_ladder(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
 }
 
@@ -2349,25 +2422,15 @@ int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const 
 	for (uint32_t i = 0; i < n_images; ++i)
 		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
 	PXZ_HIP(h, hipSetDevice(h->device));
-	// the images, back to back (256-byte aligned starts), and the tiles' outputs
-	std::vector<pxz_image_desc> dev(descs, descs + n_images);
-	uint64_t in_bytes = 0, raw = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		dev[i].offset_bytes = in_bytes;
-		const uint64_t bytes = (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels;
-		in_bytes += (bytes + 255u) & ~(uint64_t)255u;
-		raw += (uint64_t)descs[i].width * descs[i].height * channels;
-	}
+	// the images, back to back, and the tiles' outputs
+	std::vector<pxz_image_desc> dev;
+	uint64_t raw = 0;
+	if ((rc = varied_send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
 	const uint32_t n_tiles = varied_n_tiles(images);
 	const uint64_t slot = (uint64_t)params->block_w * params->block_h * channels;
 	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
-	if ((rc = ensure(h, h->varied_in, in_bytes)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->varied_out, meta + (uint64_t)n_tiles * slot + 8u * ((uint64_t)n_images + 1u))) != PXZ_OK) return rc;
 	uint8_t *d_in = (uint8_t *)h->varied_in.ptr, *d_out = (uint8_t *)h->varied_out.ptr;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		const uint64_t bytes = (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels;
-		PXZ_HIP(h, hipMemcpyAsync(d_in + dev[i].offset_bytes, pixels[i], bytes, hipMemcpyHostToDevice, h->stream));
-	}
 	float *d_val = (float *)d_out;
 	uint32_t *d_w = (uint32_t *)(d_out + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d_out + (uint64_t)n_tiles * 8u);
 	uint8_t *d_slots = d_out + meta;
@@ -2814,6 +2877,62 @@ int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t wid
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	for (uint32_t r = 0; r < n_factors; ++r) file_bytes[r] = got[r + 1u] - got[r];
 	std::memcpy(sse, got.data() + n_factors + 1u, (size_t)n_factors * channels * 8u);
+	return PXZ_OK;
+}
+
+int pxz_rate_distortion_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                      uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                      uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!pixels || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
+	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
+	if ((rc = check_params(h, &up)) != PXZ_OK) return rc;
+	if ((rc = varied_check_params(h, channels, &p)) != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, block_w, block_h, channels, mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
+	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * varied_n_tiles(images);
+	if (tiles > 0xffffffffull || n_sets > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	std::vector<pxz_image_desc> dev;
+	uint64_t raw = 0;
+	if ((rc = varied_send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
+	// every rung's tiles, then the files' offsets, the sums, and the room the writer is given (none: only its offsets are wanted)
+	const uint64_t slot = (uint64_t)block_w * block_h * channels;
+	const uint64_t meta = (tiles * 12u + 255u) & ~(uint64_t)255u;
+	const size_t n_out = (size_t)n_sets + 1u + (size_t)n_sets * channels;
+	if ((rc = ensure(h, h->varied_out, meta + tiles * slot)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->rd, n_out * 8u + 256u)) != PXZ_OK) return rc;
+	const uint8_t *d_in = (const uint8_t *)h->varied_in.ptr;
+	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
+	float *d_val = (float *)d_out;
+	uint32_t *d_w = (uint32_t *)(d_out + tiles * 4u), *d_h = (uint32_t *)(d_out + tiles * 8u);
+	uint8_t *d_slots = d_out + meta;
+	uint64_t *d_offs = (uint64_t *)h->rd.ptr, *d_sse = d_offs + n_sets + 1u;
+	if ((rc = pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, channels, &p, factors, n_factors, d_in, d_val, d_w, d_h,
+	                                                 d_slots)) != PXZ_OK)
+		return rc;
+	// the rung sets as a varied batch of n_factors * n_images images
+	std::vector<pxz_image_desc> rungs;
+	rungs.reserve((size_t)n_sets);
+	for (uint32_t r = 0; r < n_factors; ++r) rungs.insert(rungs.end(), dev.begin(), dev.end());
+	if ((rc = pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &p, 0, d_val, d_w, d_h, d_slots,
+	                                          (uint8_t *)(d_offs + n_out), 0, d_offs)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &up, d_in, d_w, d_h, d_slots, nullptr, d_sse,
+	                                              nullptr)) != PXZ_OK)
+		return rc;
+	std::vector<uint64_t> got(n_out);
+	PXZ_HIP(h, hipMemcpyAsync(got.data(), d_offs, n_out * 8u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint64_t k = 0; k < n_sets; ++k) file_bytes[k] = got[k + 1u] - got[k];
+	std::memcpy(sse, got.data() + n_sets + 1u, (size_t)n_sets * channels * 8u);
 	return PXZ_OK;
 }
 

@@ -479,6 +479,15 @@ struct VariedArgs {
 	float thresholds[kNumThresholds];
 };
 
+// Varied ladder (pxz_shrink_varied_ladder_frames_device, pxz_varied_ladder.hip): the varied call's arguments (v.factor is
+// unused) and the rungs' factors.  Rung r of tile t writes value, sizes and slot r * v.n_tiles + t.
+constexpr uint32_t kVariedLadderMaxRungs = 32;  // PXZ_VARIED_LADDER_MAX_RUNGS
+struct VariedLadderArgs {
+	VariedArgs v;
+	uint32_t n_factors;
+	float factors[kVariedLadderMaxRungs];
+};
+
 // Writer of a varied batch: what the per-image headers need beside QoiArgs (record lengths, their scan, the file offsets)
 struct VariedWriterArgs {
 	const VariedImage *images;
