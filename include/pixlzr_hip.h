@@ -383,6 +383,58 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
                             uint32_t n_images, uint32_t channels, const pxz_params *params, uint8_t *out_base,
                             uint32_t *image_flags);
 
+/* ---- re-shrink: .pixlzr tiles to .pixlzr tiles without the image --------------- */
+
+/* The reference CLI's pix_to_pix (src/bin/main.rs:233-265: to_image(filter), from_image, shrink) on the stored tiles of a
+ * varied batch, for a block size that stays the same: tile t of the rebuilt image is then exactly the expansion of stored
+ * tile t, so every tile is expanded to its full size in LDS, measured, and resampled into its new slot by one kernel, and
+ * nothing of image size is read, written or allocated.  Inputs d_tile_w, d_tile_h, d_slots and outputs d_block_value,
+ * d_out_w, d_out_h, d_out_pixels are in the pxz_varied_layout order with slots of block_w*block_h*channels bytes: the
+ * inputs are what pxz_decode_varied_frames_device or a varied shrink leaves.  Of descs[i] only width and height are read.
+ * expand_filter is what to_image(filter) takes; params carries what the shrink takes (block size, mode, filter, factor).
+ * For every image without a flagged tile the results equal, bit for bit (value bits, sizes, the valid bytes of every slot),
+ * pxz_expand_varied_frames_device with expand_filter into a tightly packed image followed by
+ * pxz_shrink_varied_frames_device with params on that image.
+ * A tile whose stored size is zero or exceeds its place is flagged as by pxz_expand_varied_frames_device -- d_image_flags
+ * (n_images dwords, may be NULL) receives 0 or 1 per image, pxz_decode_status reports bit 0 -- and gets d_out_w = d_out_h =
+ * 0 and value bits 0; its slot is left as it was.  d_out_pixels may be NULL (values and sizes only).
+ * In place: d_out_w, d_out_h and d_out_pixels may be d_tile_w, d_tile_h and d_slots themselves.  Tile t's inputs are read
+ * only by the block that writes tile t's outputs, into LDS and before its first store.
+ * Asynchronous on the handle's stream; the number of launches does not depend on n_images.  Validation runs on the host
+ * before anything is launched, with the rules, codes and "image i" texts of pxz_shrink_varied_frames_device
+ * (PXZ_ERR_TILE_TOO_SMALL included), and PXZ_ERR_INVALID_ARG for an expand_filter above 4; on an error nothing is written.
+ * Limit of this path: a tile is expanded as one dword per pixel in two LDS planes, for RGB as for RGBA, so
+ * block_w*block_h*4 must not exceed 65536 bytes (128x128); larger blocks give PXZ_ERR_UNSUPPORTED, and so does a block so
+ * oblong (block_w + block_h above about 900) that the staged windows of both axes no longer fit beside the planes
+ * (pxz_reshrink_lds_bytes says which).
+ * The call reads and writes none of the state the single-geometry fast paths keep in the handle; pxz_trim gives back what it
+ * grew. */
+int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                      const pxz_params *params, uint32_t expand_filter, const uint32_t *d_tile_w,
+                                      const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w,
+                                      uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags);
+
+/* LDS bytes of one block of the call above for blocks of block_w x block_h (host only: no handle, no GPU): what the entry
+ * point holds against the CU's 160 KB before it launches, from the function the launch itself uses.  A value above
+ * 163840 (0xffffffff beyond the documented limit) means PXZ_ERR_UNSUPPORTED.  PXZ_ERR_INVALID_ARG for a null pointer, a zero
+ * side, a mode above 1 or a filter above 4. */
+int pxz_reshrink_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes);
+
+/* pix_to_pix for a folder, host files in, host files out, synchronously.  Every header is parsed on the host first
+ * (pxz_file_header); the files must share channels and block size (PXZ_ERR_INVALID_ARG, "image i" otherwise), and the
+ * descriptors come from the headers.  When the files' block size equals params->block_w / block_h the files go through the
+ * varied reader, the re-shrink above in place and the varied writer: no allocation of image size anywhere.  With another
+ * block size (the CLI's -b on a .pix input) they go through the varied reader at their own geometry,
+ * pxz_expand_varied_frames_device into a scratch image batch of the handle, pxz_shrink_varied_frames_device at the new
+ * geometry and the writer.  filter_byte goes into the new headers.  file_offsets (n_images + 1) are always written; the
+ * files go to out when out_capacity >= file_offsets[n_images], else the call returns PXZ_ERR_BUFFER_TOO_SMALL and writes
+ * nothing to out (out may be NULL for that size query), as pxz_encode_varied_images.  All or nothing: a malformed file or a
+ * flagged tile gives PXZ_ERR_INVALID_ARG naming the first such image, and nothing is written to out or file_offsets.
+ * Errors and limits otherwise as the calls it is made of. */
+int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                               const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
+                               uint64_t out_capacity, uint64_t *file_offsets);
+
 /* The same for one host-resident image (copies in, expands, copies out; PXZ_ERR_INVALID_ARG on an
  * invalid stored size). */
 int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,

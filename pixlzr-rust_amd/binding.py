@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "pxz_distortion_frames_device", "pxz_distortion_varied_frames_device", "pxz_rate_distortion_image",
     "pxz_shrink_varied_ladder_frames_device", "pxz_rate_distortion_varied_images",
     "pxz_window_layout", "pxz_decode_windows_device", "pxz_expand_windows_device", "pxz_decode_windows_files",
+    "pxz_reshrink_varied_frames_device", "pxz_reshrink_lds_bytes", "pxz_transcode_varied_files",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -184,6 +185,13 @@ def load_library():
         L.pxz_shrink_varied_ladder_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), vp, u32] + [vp] * 5
         L.pxz_rate_distortion_varied_images.restype = C.c_int
         L.pxz_rate_distortion_varied_images.argtypes = [vp, vp, vp] + [u32] * 7 + [vp, u32, vp, vp]
+    if hasattr(L, "pxz_reshrink_varied_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the re-shrink)
+        L.pxz_reshrink_varied_frames_device.restype = C.c_int
+        L.pxz_reshrink_varied_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 8
+        L.pxz_reshrink_lds_bytes.restype = C.c_int
+        L.pxz_reshrink_lds_bytes.argtypes = [u32] * 4 + [C.POINTER(u32)]
+        L.pxz_transcode_varied_files.restype = C.c_int
+        L.pxz_transcode_varied_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, C.c_uint64, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -262,6 +270,15 @@ def window_layout(sizes, windows, bw, bh):
     if rc != 0:
         raise PxzError(rc)
     return out
+
+
+def reshrink_lds_bytes(bw, bh, mode, expand_filter):
+    """pxz_reshrink_lds_bytes: LDS bytes of one block of the re-shrink kernel (host only; above 163840: unsupported)."""
+    out = C.c_uint32(0)
+    rc = load_library().pxz_reshrink_lds_bytes(bw, bh, mode, expand_filter, C.byref(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out.value
 
 
 def file_header(data):
@@ -725,6 +742,67 @@ class Handle:
             err.flags, err.images = flags[:n], result
             raise err
         return result, flags[:n]
+
+    # ---- re-shrink: stored tiles to stored tiles ----
+    def reshrink_varied_frames_device(self, sizes, channels, bw, bh, mode, filt, factor, expand_filter, ow, oh, slots,
+                                      want_pixels=True, out=None, image_flags=None):
+        """pxz_reshrink_varied_frames_device: the stored tiles (w[T], h[T], slots[T, bw*bh*C], varied layout) of the images
+        sizes = [(width, height), ...] expanded with expand_filter and shrunk again with (mode, filt, factor), without the
+        images.  Returns (tile_offsets uint64[n+1], values[T], w[T], h[T], slots | None).  out: a 4-tuple of such tensors
+        (slots may be None); its w, h and slots may be the inputs themselves (in place).  image_flags (int32[n] CUDA,
+        optional) gets 0 | 1."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            dev = ow.device
+            vals = torch.empty(T, dtype=torch.float32, device=dev)
+            nw = torch.empty(T, dtype=torch.int32, device=dev)
+            nh = torch.empty(T, dtype=torch.int32, device=dev)
+            nslots = torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, nw, nh, nslots = out
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_reshrink_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), expand_filter,
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, nw, nh, nslots
+
+    def transcode_varied_files(self, files, bw, bh, mode, filt, factor, expand_filter, filter_byte=0, out=None):
+        """pxz_transcode_varied_files: a list of .pixlzr files (bytes) of one channel count and block size -> the list of the
+        files re-shrunk with (bw, bh, mode, filt, factor) after to_image(expand_filter).  out: a numpy uint8 buffer to write
+        into (the call raises PxzError -7 with .needed when it is too small; out of size 0 is the size query), else the
+        buffer is sized by a first call."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        offs = np.zeros(n + 1, np.uint64)
+
+        def call(buf):
+            return self._L.pxz_transcode_varied_files(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd),
+                                                      expand_filter, filter_byte, _p(buf) if buf is not None and buf.size else None,
+                                                      0 if buf is None else buf.size, _p(offs))
+        if out is None:
+            rc = call(None)
+            if rc == -7:
+                out = np.empty(int(offs[-1]), np.uint8)
+                rc = call(out)
+        else:
+            rc = call(out)
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.needed = int(offs[-1])
+            raise err
+        return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
 
     # ---- windows of files ----
     def decode_windows_device(self, files, file_offsets, sizes, windows, channels, bw, bh, out=None, window_flags=None):

@@ -114,6 +114,7 @@ struct HandleScratch {
 	DeviceBuffer windows;             // pixel windows of files: the per-window table
 	PinnedStaging window_table;       //   and its pinned staging
 	DeviceBuffer window_host;         // pxz_decode_windows_files: the files, the covered tiles, the crops and the flags
+	DeviceBuffer transcode_files, transcode_tiles;  // pxz_transcode_varied_files: the files that come in; their tiles when the block size changes
 	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
 	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
 	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
@@ -2756,6 +2757,213 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 	if (first_bad != n_images)
 		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
 		            first_flags);
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- re-shrink of stored tiles (pxz_reshrink.hip): the reference CLI's pix_to_pix (src/bin/main.rs:233-265) ---------------
+namespace {
+
+constexpr uint32_t kLdsPerCu = 160u * 1024u;
+
+// the one place that says whether reshrink_kernel takes a block: its LDS footprint (what the launch asks for) against the CU's
+int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t wdw)
+{
+	if (pxz::reshrink_lds_bytes(mode, bw, bh, wdw) > kLdsPerCu)
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "a re-shrink keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 bytes, "
+		            "the whole 160 KB (%ux%u)", bw, bh);
+	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_reshrink_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes)
+{
+	if (!lds_bytes || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, 1u);
+	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
+	pxz::VariedExpandTableSet s;
+	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, varied_window_dw(s.max_window));
+	return PXZ_OK;
+}
+
+int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                      const pxz_params *params, uint32_t expand_filter, const uint32_t *d_tile_w,
+                                      const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w,
+                                      uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	int rc = check_params(h, params);
+	if (rc != PXZ_OK) return rc;
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if ((rc = reshrink_check_block(h, params->mode, params->block_w, params->block_h, 1u)) != PXZ_OK) return rc;
+	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
+	std::vector<pxz_image_desc> sized(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, sized.data(), n_images, params->block_w, params->block_h, channels, params->mode, &images, &sides, nullptr)) != PXZ_OK)
+		return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, params->filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::ReshrinkArgs a{};
+	pxz_params xp = *params;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.x)) != PXZ_OK) return rc;
+	if ((rc = reshrink_check_block(h, params->mode, params->block_w, params->block_h, a.x.wdw)) != PXZ_OK) return rc;
+	if ((rc = fresh_status(h, &a.x.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.image_flags = d_image_flags;
+	if ((rc = varied_upload(h, images, &a.v.images)) != PXZ_OK) return rc;
+	varied_fill_args(h, images, channels, params, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.v);
+	a.v.tile_bytes = (params->block_w * params->block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is expanded
+	a.x.n_tiles = a.v.n_tiles;
+	a.x.tile_w = d_tile_w;
+	a.x.tile_h = d_tile_h;
+	a.x.slots = d_slots;
+	PXZ_HIP(h, pxz::launch_reshrink(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                               const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
+                               uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	// every header first: the files must share channels and block size
+	std::vector<pxz_image_desc> descs(n_images);
+	uint32_t fbw = 0, fbh = 0, ch = 0;
+	uint64_t file_bytes = 0, raw = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, c, fb;
+		const char *why;
+		const int hrc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &c, &fb, &why);
+		if (hrc != PXZ_OK) return fail(h, hrc, "image %u: %s", i, why);
+		if (i == 0) {
+			fbw = bw;
+			fbh = bh;
+			ch = c;
+		} else if (bw != fbw || bh != fbh || c != ch) {
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u blocks of %u channels, image 0 holds %ux%u of %u", i, bw, bh, c, fbw, fbh, ch);
+		}
+		descs[i] = pxz_image_desc{w, hh, w * c, 0, 0};
+		file_bytes += lens[i];
+		raw += (uint64_t)w * hh * c;
+	}
+	const bool same_block = fbw == params->block_w && fbh == params->block_h;
+	pxz_params pin = *params;  // the files' own geometry
+	pin.block_w = fbw;
+	pin.block_h = fbh;
+	pin.filter = expand_filter;
+	int rc;
+	if (same_block) {
+		if ((rc = check_params(h, params)) != PXZ_OK) return rc;
+		if ((rc = reshrink_check_block(h, params->mode, fbw, fbh, 1u)) != PXZ_OK) return rc;
+	} else {
+		const pxz_params px = decode_side_params(&pin, true);
+		if ((rc = varied_check_params(h, ch, &px)) != PXZ_OK) return rc;
+		if ((rc = varied_check_params(h, ch, params)) != PXZ_OK) return rc;
+	}
+	std::vector<pxz::VariedImage> images_in, images_out;
+	if ((rc = varied_plan(h, descs.data(), n_images, fbw, fbh, 0, 0, &images_in, nullptr, nullptr)) != PXZ_OK) return rc;
+	if ((rc = varied_plan(h, descs.data(), n_images, params->block_w, params->block_h, ch, params->mode, &images_out, nullptr, nullptr)) != PXZ_OK)
+		return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+
+	// the files back to back behind their offsets
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	const std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, 0);
+	if ((rc = ensure(h, h->transcode_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
+	uint8_t *d_files = (uint8_t *)h->transcode_files.ptr;
+	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
+
+	// the tiles that go to the writer: values, sizes, slots, then the files' offsets and the flags of both stages
+	const uint32_t n_out = varied_n_tiles(images_out), n_in = varied_n_tiles(images_in);
+	const uint64_t slot_out = (uint64_t)params->block_w * params->block_h * ch;
+	const uint64_t meta_out = ((uint64_t)n_out * 12u + 255u) & ~(uint64_t)255u;
+	const uint64_t offs_at = (meta_out + (uint64_t)n_out * slot_out + 7u) & ~(uint64_t)7u;
+	const uint64_t flags_at = offs_at + offs_bytes;
+	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
+	const TileMeta m = carve_tile_meta(d_out, n_out);
+	uint8_t *d_slots = d_out + meta_out;
+	uint64_t *d_offs = (uint64_t *)(d_out + offs_at);
+	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
+
+	if (same_block) {
+		// reader -> re-shrink in place -> writer: nothing of image size anywhere
+		PXZ_HIP(h, hipMemsetAsync(d_out, 0, meta_out, h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
+		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, m.value, m.w,
+		                                          m.h, d_slots, d_flags)) != PXZ_OK)
+			return rc;
+		if ((rc = pxz_reshrink_varied_frames_device(h, descs.data(), n_images, ch, params, expand_filter, m.w, m.h, d_slots, m.value, m.w, m.h,
+		                                            d_slots, d_flags + n_images)) != PXZ_OK)
+			return rc;
+	} else {
+		// another block size: reader at the files' geometry -> the images in handle scratch -> the varied shrink at the new one
+		const uint64_t slot_in = (uint64_t)fbw * fbh * ch;
+		const uint64_t meta_in = ((uint64_t)n_in * 12u + 255u) & ~(uint64_t)255u;
+		if ((rc = ensure(h, h->transcode_tiles, meta_in + (uint64_t)n_in * slot_in)) != PXZ_OK) return rc;
+		uint8_t *d_tin = (uint8_t *)h->transcode_tiles.ptr;
+		const TileMeta mi = carve_tile_meta(d_tin, n_in);
+		std::vector<pxz_image_desc> dev = descs;
+		uint64_t img_bytes = 0;
+		for (uint32_t i = 0; i < n_images; ++i) {
+			dev[i].offset_bytes = img_bytes;
+			img_bytes += ((uint64_t)dev[i].pitch_bytes * dev[i].height + 255u) & ~(uint64_t)255u;
+		}
+		if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
+		uint8_t *d_img = (uint8_t *)h->varied_in.ptr;
+		PXZ_HIP(h, hipMemsetAsync(d_tin, 0, meta_in, h->stream));
+		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, mi.value,
+		                                          mi.w, mi.h, d_tin + meta_in, d_flags)) != PXZ_OK)
+			return rc;
+		if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, ch, &pin, mi.w, mi.h, d_tin + meta_in, d_img, d_flags + n_images)) != PXZ_OK)
+			return rc;
+		if ((rc = pxz_shrink_varied_frames_device(h, dev.data(), n_images, ch, params, d_img, m.value, m.w, m.h, d_slots)) != PXZ_OK) return rc;
+	}
+	// all or nothing: a malformed file or a tile that cannot be stops the call before the writer runs
+	std::vector<uint32_t> flags(2u * (size_t)n_images);
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (flags[i] | flags[n_images + i])
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); nothing was written", i,
+			            flags[i] | flags[n_images + i]);
+
+	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
+	uint64_t cap = raw + raw / 4u + 64ull * n_out + 4096ull * n_images;
+	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
+	for (int pass = 0; pass < 2; ++pass) {
+		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
+		if ((rc = pxz_encode_varied_frames_device(h, descs.data(), n_images, ch, params, filter_byte, m.value, m.w, m.h, d_slots,
+		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
+			return rc;
+		PXZ_HIP(h, hipMemcpyAsync(file_offsets, d_offs, offs_bytes, hipMemcpyDeviceToHost, h->stream));
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		if (file_offsets[n_images] <= cap) break;
+		cap = file_offsets[n_images];
+	}
+	const uint64_t total = file_offsets[n_images];
+	if (!out || out_capacity < total)
+		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
+		            (unsigned long long)out_capacity);
+	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
 	return PXZ_OK;
 }
 

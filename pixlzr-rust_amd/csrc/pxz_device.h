@@ -1153,6 +1153,8 @@ __device__ __forceinline__ bool bad_stored_size(uint32_t tw, uint32_t th, uint32
 // Returns the plane (s_src or s_tmp) that holds the fw x fh result, one dword per pixel; wsync() has run behind its last
 // write.  stage_x / stage_y false: the windows of that axis are in s_wx / s_wy already (the same full and stored size as
 // the tile this wave resized before).  Args: TileResizeArgs, or DistortionArgs (which names the same fields).
+// reshrink_kernel (pxz_reshrink.hip) has a block-wide copy of steps 2 and 3 (256 threads, __syncthreads() for wsync): A FIX
+// TO THE ARITHMETIC HERE BELONGS THERE TOO, and the other way round.
 // ---------------------------------------------------------------------------
 
 // the clamp spelled as an instruction: left to the compiler, clip8(a) | clip8(b) << 8 of an RGB pixel became

@@ -521,6 +521,17 @@ struct TileResizeArgs {
 	const uint8_t *slots;             // per tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
 };
 
+// Re-shrink of stored tiles (pxz_reshrink_varied_frames_device, pxz_reshrink.hip): the stored tiles of a flat tile space
+// expanded to their full sizes in LDS and shrunk again, one tile per block.  v is the shrink side as varied_kernel takes it
+// (v.base is unused, v.tile_bytes is one LDS plane of bw * bh dwords, rounded up to 16 bytes); x is the expand side: the
+// tables of put_varied_expand_tables, the stored sizes and slots that are read, and the status word (x.tile_dw and x.t0_dw are
+// unused: the block's LDS is reshrink_lds_bytes').  The outputs of v may be the inputs of x (pxz_reshrink.hip: in place).
+struct ReshrinkArgs {
+	VariedArgs v;
+	TileResizeArgs x;
+	uint32_t *image_flags;            // per image 1 for a tile whose stored size is invalid, or null
+};
+
 // Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
 // back to their places in the images.
 struct VariedExpandArgs : TileResizeArgs {

@@ -41,6 +41,10 @@ hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus,
 hipError_t launch_varied_ladder(const VariedLadderArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 // LDS bytes of one block of varied_ladder_kernel (what the host holds against the CU's 160 KB before it launches)
 uint32_t varied_ladder_lds_limit_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels);
+hipError_t launch_reshrink(const ReshrinkArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+// LDS bytes of one block of reshrink_kernel for blocks of bw x bh whose staged windows take wdw dwords (what the host holds
+// against the CU's 160 KB before it launches, and what the launch asks for); 0xffffffff: a plane of bw * bh dwords above 64 KB
+uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t wdw);
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
