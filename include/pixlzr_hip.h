@@ -435,6 +435,57 @@ int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const
                                const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
                                uint64_t out_capacity, uint64_t *file_offsets);
 
+/* Re-shrink ladder: pxz_reshrink_varied_frames_device at several factors in ONE launch, whatever n_images and n_factors are --
+ * an archive of .pixlzr files, no source images, and the question how far it can be squeezed.  Every stored tile is expanded
+ * once and measured once (neither depends on the factor); each rung only decides its levels, and a tile is resampled once per
+ * distinct pair of levels among its rungs.  params->factor is ignored; factors is a HOST array (1 <= n_factors <=
+ * PXZ_VARIED_LADDER_MAX_RUNGS, each finite; any order, repeats allowed).  Inputs as pxz_reshrink_varied_frames_device.  Outputs
+ * are rung-major, exactly as pxz_shrink_varied_ladder_frames_device lays them out: rung r of tile t of image i is index
+ * r*tiles + tile_offsets[i] + t of d_block_value, d_out_w, d_out_h and of the slots of d_out_pixels (64-bit offsets; may be
+ * NULL), so the writer takes them with descs repeated n_factors times.  Rung r equals pxz_reshrink_varied_frames_device with
+ * factor = factors[r] bit for bit (value bits, sizes, the valid bytes of every slot).
+ * A flagged tile (stored size zero or beyond its place) sets d_image_flags and status bit 0 as there, and gets 0 x 0 and
+ * value bits 0 at EVERY rung; every rung's slot is left as it was.
+ * In place: rung 0 of d_out_w, d_out_h and d_out_pixels may be d_tile_w, d_tile_h and d_slots themselves (the arrays then
+ * hold n_factors*tiles entries, the inputs in the first tiles of them).  Tile t's inputs are read only by tile t's block,
+ * into registers and LDS before its first store, and the rungs from 1 on lie beyond the inputs.
+ * Asynchronous on the handle's stream.  Validation runs on the host before anything is launched; on an error nothing is
+ * written.  Rules, codes and "image i" texts are pxz_reshrink_varied_frames_device's; PXZ_ERR_INVALID_ARG for factors null,
+ * n_factors 0 or above the maximum, a non-finite factor, or an expand_filter above 4; PXZ_ERR_UNSUPPORTED beyond the LDS
+ * limit -- block_w*block_h*4 <= 65536 bytes for RGB and RGBA alike, and the oblong-block caveat of the re-shrink
+ * (pxz_reshrink_ladder_lds_bytes says which) -- or when n_factors * tiles exceeds 2^32-1.  Of the handle's state the call
+ * touches what the re-shrink touches: the varied scratch, none of what the single-geometry fast paths keep; pxz_trim gives
+ * back what it grew. */
+int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                             const pxz_params *params, uint32_t expand_filter, const float *factors,
+                                             uint32_t n_factors, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                             const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                             uint8_t *d_out_pixels, uint32_t *d_image_flags);
+
+/* LDS bytes of one block of the call above (host only: no handle, no GPU), from the layout function the kernel and its launch
+ * use; conventions of pxz_reshrink_lds_bytes: above 163840 (0xffffffff beyond the documented limit) means
+ * PXZ_ERR_UNSUPPORTED.  The footprint depends on the channel count: beside the two planes of a dword per pixel, a block keeps
+ * its resampled images, in the plane the expand leaves free when they fit there.  PXZ_ERR_INVALID_ARG for a null pointer, a
+ * zero side, channels other than 3 or 4, a mode above 1 or a filter above 4. */
+int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode, uint32_t expand_filter,
+                                  uint32_t *lds_bytes);
+
+/* pxz_transcode_varied_files at several factors: host files in, host files out, synchronously.  params->factor is ignored;
+ * factors as above.  The new files are rung-major: file_offsets has n_factors*n_images + 1 entries, and the file of image i at
+ * factors[r] is out[file_offsets[r*n_images + i] .. file_offsets[r*n_images + i + 1]), byte for byte what
+ * pxz_transcode_varied_files gives for it at that factor.  With out == NULL or out_capacity below the last offset the call
+ * returns PXZ_ERR_BUFFER_TOO_SMALL with the offsets exact and nothing written to out: that size query is the rate table -- file
+ * length per file and factor, no file kept -- as pxz_rate_distortion_varied_images gives its lengths.  There is no distortion
+ * column: a squared error needs the rebuilt image, and not having it is the point of this path.
+ * Same block size: the varied reader into rung 0 of the handle's tile scratch, the re-shrink ladder in place, the varied writer
+ * over the descriptors repeated n_factors times.  Another block size: reader, pxz_expand_varied_frames_device,
+ * pxz_shrink_varied_ladder_frames_device, writer.  All or nothing as pxz_transcode_varied_files: a malformed file or a flagged
+ * tile gives PXZ_ERR_INVALID_ARG naming the first such image, and nothing is written to out or file_offsets.  Errors and limits
+ * otherwise as the calls it is made of. */
+int pxz_transcode_varied_ladder_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                      const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors,
+                                      uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets);
+
 /* The same for one host-resident image (copies in, expands, copies out; PXZ_ERR_INVALID_ARG on an
  * invalid stored size). */
 int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,

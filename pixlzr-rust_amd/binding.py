@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "pxz_shrink_varied_ladder_frames_device", "pxz_rate_distortion_varied_images",
     "pxz_window_layout", "pxz_decode_windows_device", "pxz_expand_windows_device", "pxz_decode_windows_files",
     "pxz_reshrink_varied_frames_device", "pxz_reshrink_lds_bytes", "pxz_transcode_varied_files",
+    "pxz_reshrink_varied_ladder_frames_device", "pxz_reshrink_ladder_lds_bytes", "pxz_transcode_varied_ladder_files",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -192,6 +193,13 @@ def load_library():
         L.pxz_reshrink_lds_bytes.argtypes = [u32] * 4 + [C.POINTER(u32)]
         L.pxz_transcode_varied_files.restype = C.c_int
         L.pxz_transcode_varied_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, C.c_uint64, vp]
+    if hasattr(L, "pxz_reshrink_varied_ladder_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the re-shrink ladder)
+        L.pxz_reshrink_varied_ladder_frames_device.restype = C.c_int
+        L.pxz_reshrink_varied_ladder_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32, vp, u32] + [vp] * 8
+        L.pxz_reshrink_ladder_lds_bytes.restype = C.c_int
+        L.pxz_reshrink_ladder_lds_bytes.argtypes = [u32] * 5 + [C.POINTER(u32)]
+        L.pxz_transcode_varied_ladder_files.restype = C.c_int
+        L.pxz_transcode_varied_ladder_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, vp, u32, u32, vp, C.c_uint64, vp]
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -276,6 +284,16 @@ def reshrink_lds_bytes(bw, bh, mode, expand_filter):
     """pxz_reshrink_lds_bytes: LDS bytes of one block of the re-shrink kernel (host only; above 163840: unsupported)."""
     out = C.c_uint32(0)
     rc = load_library().pxz_reshrink_lds_bytes(bw, bh, mode, expand_filter, C.byref(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out.value
+
+
+def reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter):
+    """pxz_reshrink_ladder_lds_bytes: LDS bytes of one block of the re-shrink ladder kernel (host only; above 163840:
+    unsupported)."""
+    out = C.c_uint32(0)
+    rc = load_library().pxz_reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter, C.byref(out))
     if rc != 0:
         raise PxzError(rc)
     return out.value
@@ -803,6 +821,75 @@ class Handle:
             err.needed = int(offs[-1])
             raise err
         return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+    # ---- re-shrink ladder: stored tiles to stored tiles at several factors ----
+    def reshrink_varied_ladder_frames_device(self, sizes, channels, bw, bh, mode, filt, factors, expand_filter, ow, oh, slots,
+                                             want_pixels=True, out=None, image_flags=None, n_factors=None):
+        """pxz_reshrink_varied_ladder_frames_device: reshrink_varied_frames_device at every factor of `factors` (a host
+        sequence, 1..32 of them) in one launch.  Returns (tile_offsets uint64[n+1], values[K,T], w[K,T], h[K,T],
+        slots[K,T,bw*bh*C] | None); rung r equals reshrink_varied_frames_device(..., factors[r], ...).  out: a 4-tuple of such
+        tensors (slots may be None); ow, oh and slots may be rung 0 of its w, h and slots (in place).  factors None with
+        n_factors passes a null pointer."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        fac = None if factors is None else np.ascontiguousarray(factors, np.float32)
+        K = n_factors if n_factors is not None else (0 if fac is None else fac.size)
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            dev = ow.device
+            vals = torch.empty((K, T), dtype=torch.float32, device=dev)
+            nw = torch.empty((K, T), dtype=torch.int32, device=dev)
+            nh = torch.empty((K, T), dtype=torch.int32, device=dev)
+            nslots = torch.empty((K, T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, nw, nh, nslots = out
+        pd = Params(bw, bh, mode, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_reshrink_varied_ladder_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), expand_filter,
+            _p(fac) if fac is not None and fac.size else None, K,
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, nw, nh, nslots
+
+    def transcode_varied_ladder_files(self, files, bw, bh, mode, filt, factors, expand_filter, filter_byte=0, out=None, sizes_only=False):
+        """pxz_transcode_varied_ladder_files: transcode_varied_files at every factor of `factors` -> a list per rung of the
+        list of new files.  sizes_only: the size query alone -- returns the rate table, int64[K, n] file lengths, and keeps no
+        file.  out: a numpy uint8 buffer to write into (PxzError -7 with .needed and .offsets when it is too small), else
+        the buffer is sized by a first call."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        pd = Params(bw, bh, mode, filt, 0.0, 0)
+        offs = np.zeros(K * n + 1, np.uint64)
+
+        def call(buf):
+            return self._L.pxz_transcode_varied_ladder_files(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd),
+                                                             expand_filter, _p(fac) if K else None, K, filter_byte,
+                                                             _p(buf) if buf is not None and buf.size else None,
+                                                             0 if buf is None else buf.size, _p(offs))
+        if out is None:
+            rc = call(None)
+            if rc == -7 and sizes_only:
+                return np.diff(offs.astype(np.int64)).reshape(K, n)
+            if rc == -7:
+                out = np.empty(int(offs[-1]), np.uint8)
+                rc = call(out)
+        else:
+            rc = call(out)
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.needed, err.offsets = int(offs[-1]), offs.copy()
+            raise err
+        return [[out[int(offs[r * n + i]):int(offs[r * n + i + 1])].tobytes() for i in range(n)] for r in range(K)]
 
     # ---- windows of files ----
     def decode_windows_device(self, files, file_offsets, sizes, windows, channels, bw, bh, out=None, window_flags=None):

@@ -2777,6 +2777,16 @@ int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh,
 	return PXZ_OK;
 }
 
+// the same for reshrink_ladder_kernel, whose footprint depends on the channel count too (its resampled images)
+int reshrink_ladder_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t wdw)
+{
+	if (pxz::reshrink_ladder_lds_bytes(mode, bw, bh, channels, wdw) > kLdsPerCu)
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "a re-shrink ladder keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
+		            "bytes, the whole 160 KB (%ux%u)", bw, bh);
+	return PXZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2836,12 +2846,85 @@ int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs
 	return PXZ_OK;
 }
 
-int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
-                               const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
-                               uint64_t out_capacity, uint64_t *file_offsets)
+int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode, uint32_t expand_filter,
+                                  uint32_t *lds_bytes)
+{
+	if (!lds_bytes || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::reshrink_ladder_lds_bytes(mode, block_w, block_h, channels, 1u);
+	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
+	pxz::VariedExpandTableSet s;
+	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::reshrink_ladder_lds_bytes(mode, block_w, block_h, channels, varied_window_dw(s.max_window));
+	return PXZ_OK;
+}
+
+int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                             const pxz_params *params, uint32_t expand_filter, const float *factors,
+                                             uint32_t n_factors, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                             const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                             uint8_t *d_out_pixels, uint32_t *d_image_flags)
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!files || !lens || !params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	pxz_params p = *params;
+	p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
+	if ((rc = check_params(h, &p)) != PXZ_OK) return rc;
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if ((rc = reshrink_ladder_check_block(h, p.mode, p.block_w, p.block_h, channels, 1u)) != PXZ_OK) return rc;
+	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
+	std::vector<pxz_image_desc> sized(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	if ((uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::ReshrinkLadderArgs a{};
+	pxz_params xp = p;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r.x)) != PXZ_OK) return rc;
+	if ((rc = reshrink_ladder_check_block(h, p.mode, p.block_w, p.block_h, channels, a.r.x.wdw)) != PXZ_OK) return rc;
+	if ((rc = fresh_status(h, &a.r.x.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.r.image_flags = d_image_flags;
+	if ((rc = varied_upload(h, images, &a.r.v.images)) != PXZ_OK) return rc;
+	varied_fill_args(h, images, channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.r.v);
+	a.r.x.n_tiles = a.r.v.n_tiles;
+	a.r.x.tile_w = d_tile_w;
+	a.r.x.tile_h = d_tile_h;
+	a.r.x.slots = d_slots;
+	a.n_factors = n_factors;
+	std::memcpy(a.factors, factors, n_factors * sizeof(float));
+	PXZ_HIP(h, pxz::launch_reshrink_ladder(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Both host forms of pix_to_pix behind one body: factors == nullptr is pxz_transcode_varied_files (one rung, the caller's
+// params->factor, the one-factor calls); otherwise pxz_transcode_varied_ladder_files (n_factors rungs, the ladder calls, the
+// outputs rung-major and the writer over the descriptors repeated n_factors times).
+int transcode_varied(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *user_params,
+                     uint32_t expand_filter, const float *factors, uint32_t n_factors, uint32_t filter_byte, uint8_t *out,
+                     uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !user_params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const bool ladder = factors != nullptr;
+	pxz_params ladder_params = *user_params;
+	ladder_params.factor = 1.0f;  // (ignored by the ladder calls)
+	const pxz_params *params = ladder ? &ladder_params : user_params;
 	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
 	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
 	// every header first: the files must share channels and block size
@@ -2873,7 +2956,8 @@ int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const
 	int rc;
 	if (same_block) {
 		if ((rc = check_params(h, params)) != PXZ_OK) return rc;
-		if ((rc = reshrink_check_block(h, params->mode, fbw, fbh, 1u)) != PXZ_OK) return rc;
+		if ((rc = ladder ? reshrink_ladder_check_block(h, params->mode, fbw, fbh, ch, 1u) : reshrink_check_block(h, params->mode, fbw, fbh, 1u)) != PXZ_OK)
+			return rc;
 	} else {
 		const pxz_params px = decode_side_params(&pin, true);
 		if ((rc = varied_check_params(h, ch, &px)) != PXZ_OK) return rc;
@@ -2883,6 +2967,9 @@ int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const
 	if ((rc = varied_plan(h, descs.data(), n_images, fbw, fbh, 0, 0, &images_in, nullptr, nullptr)) != PXZ_OK) return rc;
 	if ((rc = varied_plan(h, descs.data(), n_images, params->block_w, params->block_h, ch, params->mode, &images_out, nullptr, nullptr)) != PXZ_OK)
 		return rc;
+	const uint32_t n_out = varied_n_tiles(images_out), n_in = varied_n_tiles(images_in);
+	if ((uint64_t)n_factors * n_out > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	const uint32_t n_all = n_factors * n_out, n_files = n_factors * n_images;  // (n_files: 2^32-1 at most, a file has a tile)
 	PXZ_HIP(h, hipSetDevice(h->device));
 
 	// the files back to back behind their offsets
@@ -2892,28 +2979,30 @@ int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const
 	uint8_t *d_files = (uint8_t *)h->transcode_files.ptr;
 	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
 
-	// the tiles that go to the writer: values, sizes, slots, then the files' offsets and the flags of both stages
-	const uint32_t n_out = varied_n_tiles(images_out), n_in = varied_n_tiles(images_in);
+	// the tiles that go to the writer, rung-major: values, sizes, slots, then the new files' offsets and the flags of both stages
 	const uint64_t slot_out = (uint64_t)params->block_w * params->block_h * ch;
-	const uint64_t meta_out = ((uint64_t)n_out * 12u + 255u) & ~(uint64_t)255u;
-	const uint64_t offs_at = (meta_out + (uint64_t)n_out * slot_out + 7u) & ~(uint64_t)7u;
-	const uint64_t flags_at = offs_at + offs_bytes;
+	const uint64_t meta_out = ((uint64_t)n_all * 12u + 255u) & ~(uint64_t)255u;
+	const uint64_t offs_at = (meta_out + (uint64_t)n_all * slot_out + 7u) & ~(uint64_t)7u;
+	const uint64_t out_offs_bytes = 8ull * ((uint64_t)n_files + 1u);
+	const uint64_t flags_at = offs_at + out_offs_bytes;
 	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
 	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
-	const TileMeta m = carve_tile_meta(d_out, n_out);
+	const TileMeta m = carve_tile_meta(d_out, n_all);  // (the reader fills rung 0 of each array)
 	uint8_t *d_slots = d_out + meta_out;
 	uint64_t *d_offs = (uint64_t *)(d_out + offs_at);
 	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
 
 	if (same_block) {
-		// reader -> re-shrink in place -> writer: nothing of image size anywhere
+		// reader -> re-shrink in place (the ladder: in place on rung 0) -> writer: nothing of image size anywhere
 		PXZ_HIP(h, hipMemsetAsync(d_out, 0, meta_out, h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
 		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, m.value, m.w,
 		                                          m.h, d_slots, d_flags)) != PXZ_OK)
 			return rc;
-		if ((rc = pxz_reshrink_varied_frames_device(h, descs.data(), n_images, ch, params, expand_filter, m.w, m.h, d_slots, m.value, m.w, m.h,
-		                                            d_slots, d_flags + n_images)) != PXZ_OK)
-			return rc;
+		rc = ladder ? pxz_reshrink_varied_ladder_frames_device(h, descs.data(), n_images, ch, params, expand_filter, factors, n_factors, m.w, m.h,
+		                                                       d_slots, m.value, m.w, m.h, d_slots, d_flags + n_images)
+		            : pxz_reshrink_varied_frames_device(h, descs.data(), n_images, ch, params, expand_filter, m.w, m.h, d_slots, m.value, m.w, m.h,
+		                                                d_slots, d_flags + n_images);
+		if (rc != PXZ_OK) return rc;
 	} else {
 		// another block size: reader at the files' geometry -> the images in handle scratch -> the varied shrink at the new one
 		const uint64_t slot_in = (uint64_t)fbw * fbh * ch;
@@ -2935,7 +3024,9 @@ int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const
 			return rc;
 		if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, ch, &pin, mi.w, mi.h, d_tin + meta_in, d_img, d_flags + n_images)) != PXZ_OK)
 			return rc;
-		if ((rc = pxz_shrink_varied_frames_device(h, dev.data(), n_images, ch, params, d_img, m.value, m.w, m.h, d_slots)) != PXZ_OK) return rc;
+		rc = ladder ? pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, ch, params, factors, n_factors, d_img, m.value, m.w, m.h, d_slots)
+		            : pxz_shrink_varied_frames_device(h, dev.data(), n_images, ch, params, d_img, m.value, m.w, m.h, d_slots);
+		if (rc != PXZ_OK) return rc;
 	}
 	// all or nothing: a malformed file or a tile that cannot be stops the call before the writer runs
 	std::vector<uint32_t> flags(2u * (size_t)n_images);
@@ -2947,24 +3038,48 @@ int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const
 			            flags[i] | flags[n_images + i]);
 
 	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
-	uint64_t cap = raw + raw / 4u + 64ull * n_out + 4096ull * n_images;
+	std::vector<pxz_image_desc> rung_descs;  // the descriptors once per rung
+	rung_descs.reserve(n_files);
+	for (uint32_t r = 0; r < n_factors; ++r) rung_descs.insert(rung_descs.end(), descs.begin(), descs.end());
+	uint64_t cap = (raw + raw / 4u + 64ull * n_out + 4096ull * n_images) * n_factors;
 	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
 	for (int pass = 0; pass < 2; ++pass) {
 		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
-		if ((rc = pxz_encode_varied_frames_device(h, descs.data(), n_images, ch, params, filter_byte, m.value, m.w, m.h, d_slots,
+		if ((rc = pxz_encode_varied_frames_device(h, rung_descs.data(), n_files, ch, params, filter_byte, m.value, m.w, m.h, d_slots,
 		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
 			return rc;
-		PXZ_HIP(h, hipMemcpyAsync(file_offsets, d_offs, offs_bytes, hipMemcpyDeviceToHost, h->stream));
+		PXZ_HIP(h, hipMemcpyAsync(file_offsets, d_offs, out_offs_bytes, hipMemcpyDeviceToHost, h->stream));
 		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		if (file_offsets[n_images] <= cap) break;
-		cap = file_offsets[n_images];
+		if (file_offsets[n_files] <= cap) break;
+		cap = file_offsets[n_files];
 	}
-	const uint64_t total = file_offsets[n_images];
+	const uint64_t total = file_offsets[n_files];
 	if (!out || out_capacity < total)
 		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
 		            (unsigned long long)out_capacity);
 	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
 	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                               const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
+                               uint64_t out_capacity, uint64_t *file_offsets)
+{
+	return transcode_varied(h, files, lens, n_images, params, expand_filter, nullptr, 1u, filter_byte, out, out_capacity, file_offsets);
+}
+
+int pxz_transcode_varied_ladder_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                      const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors,
+                                      uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	return transcode_varied(h, files, lens, n_images, params, expand_filter, factors, n_factors, filter_byte, out, out_capacity, file_offsets);
 }
 
 }  // extern "C"

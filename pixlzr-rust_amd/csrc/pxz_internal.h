@@ -532,6 +532,15 @@ struct ReshrinkArgs {
 	uint32_t *image_flags;            // per image 1 for a tile whose stored size is invalid, or null
 };
 
+// Re-shrink ladder (pxz_reshrink_varied_ladder_frames_device, pxz_reshrink_ladder.hip): the re-shrink's arguments (r.v.factor
+// and r.v.tile_bytes are unused: the block's LDS is reshrink_ladder_lds') and the rungs' factors.  Rung q of tile t writes
+// value, sizes and slot q * r.v.n_tiles + t; a flagged tile writes 0 x 0 and value bits 0 to every rung.
+struct ReshrinkLadderArgs {
+	ReshrinkArgs r;
+	uint32_t n_factors;
+	float factors[kVariedLadderMaxRungs];
+};
+
 // Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
 // back to their places in the images.
 struct VariedExpandArgs : TileResizeArgs {

@@ -45,6 +45,10 @@ hipError_t launch_reshrink(const ReshrinkArgs &a, uint32_t channels, uint32_t n_
 // LDS bytes of one block of reshrink_kernel for blocks of bw x bh whose staged windows take wdw dwords (what the host holds
 // against the CU's 160 KB before it launches, and what the launch asks for); 0xffffffff: a plane of bw * bh dwords above 64 KB
 uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t wdw);
+hipError_t launch_reshrink_ladder(const ReshrinkLadderArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+// LDS bytes of one block of reshrink_ladder_kernel, from the layout function the kernel and its launch use; 0xffffffff: a plane
+// of bw * bh dwords above 64 KB
+uint32_t reshrink_ladder_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t wdw);
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);

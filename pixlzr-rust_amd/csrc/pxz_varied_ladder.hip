@@ -48,7 +48,8 @@ __host__ __device__ inline VariedLadderLds varied_ladder_lds(uint32_t mode, uint
 	return l;
 }
 
-// ---- this kernel's copies of varied_kernel's staging, detectors and un-premultiply loop (pxz_varied_tile.h says why)
+// ---- this kernel's copy of varied_kernel's staging (pxz_varied_tile.h says why; the detectors up to their raw results and the
+// un-premultiply loop, which the re-shrink ladder runs too, are there)
 
 // A tile of w x h pixels at src (rows pitch bytes apart) into LDS, tightly packed: 16-byte loads where its rows are
 // aligned, dwords or bytes otherwise.
@@ -75,121 +76,6 @@ __device__ __forceinline__ void varied_stage(uint8_t *s_x, const uint8_t *src, u
 			const uint32_t row = i / rb, col = i - row * rb;
 			s_x[i] = src[(size_t)row * pitch + col];
 		}
-	}
-}
-
-// get_block_variance with |x - avg| (operations.rs:26-126) up to its raw result x = total / count, the same in every thread:
-// the detector kernels' own colour conversion (pxz_oklab_math.h), 1024 pixels at a time into s_plane ([4][kVariedChunk]),
-// and four lanes that add them up in pixel order, twice -- the two sequential f32 sums of the reference.  s_acc: 4 floats.
-template <int C>
-__device__ __forceinline__ float varied_oklab_raw(const uint8_t *s_x, uint32_t n, const float4 *s_lms, const float *s_alpha,
-                                                  const double *s_scale, float *s_plane, float *s_acc, uint32_t tid)
-{
-	const float count = (float)n;  // operations.rs:51
-	float mean = 0.0f;
-	for (int pass = 0; pass < 2; ++pass) {
-		float acc = 0.0f;
-		for (uint32_t base = 0; base < n; base += kVariedChunk) {
-			const uint32_t first = base + tid * 4u;
-			uint32_t px[4];
-#pragma unroll
-			for (int j = 0; j < 4; ++j) px[j] = first + (uint32_t)j < n ? varied_pixel(s_x, first + (uint32_t)j, C) : 0u;
-#pragma unroll
-			for (int j = 0; j < 4; j += 2) {
-				float o0[3], o1[3];
-				oklab_pair(px[j], px[j + 1], s_lms, s_scale, o0, o1);
-				const uint32_t k = tid * 4u + (uint32_t)j;
-#pragma unroll
-				for (int c = 0; c < 3; ++c) {
-					s_plane[c * kVariedChunk + k] = o0[c];
-					s_plane[c * kVariedChunk + k + 1u] = o1[c];
-				}
-				s_plane[3 * kVariedChunk + k] = s_alpha[px[j] >> 24];
-				s_plane[3 * kVariedChunk + k + 1u] = s_alpha[px[j + 1] >> 24];
-			}
-			__syncthreads();
-			if (tid < 4u) {
-				// chains a, b, l, alpha: one lane each, in pixel order (operations.rs:60-63, :80-83)
-				const uint32_t m = n - base < kVariedChunk ? n - base : kVariedChunk;
-				const float *v = s_plane + tid * kVariedChunk;
-				const uint32_t m4 = m & ~3u;
-				if (pass == 0) {
-					for (uint32_t i = 0; i < m4; i += 4u) {
-						const float4 q = *reinterpret_cast<const float4 *>(v + i);
-						acc += q.x; acc += q.y; acc += q.z; acc += q.w;
-					}
-					for (uint32_t i = m4; i < m; ++i) acc += v[i];
-				} else {
-					for (uint32_t i = 0; i < m4; i += 4u) {
-						const float4 q = *reinterpret_cast<const float4 *>(v + i);
-						acc += fabsf(q.x - mean); acc += fabsf(q.y - mean); acc += fabsf(q.z - mean); acc += fabsf(q.w - mean);
-					}
-					for (uint32_t i = m4; i < m; ++i) acc += fabsf(v[i] - mean);
-				}
-			}
-			__syncthreads();
-		}
-		if (tid < 4u) {
-			if (pass == 0) mean = __fdiv_rn(acc, count);  // :65-68
-			else s_acc[tid] = acc;
-		}
-	}
-	__syncthreads();
-	const float total = C == 4 ? ((s_acc[0] + s_acc[1]) + s_acc[2]) + s_acc[3] : (s_acc[0] + s_acc[1]) + s_acc[2];  // :89 / :124
-	return __fdiv_rn(total, count);
-}
-
-// get_block_variance_directionally (operations.rs:192-259): the Sobel-like integer sums over the (w - 2) x (h - 2) interior,
-// the same in every thread.  s_red: 2 dwords per wave.
-template <int C>
-__device__ __forceinline__ void varied_sobel_sums(const uint8_t *s_x, uint32_t w, uint32_t h, uint32_t *s_red, uint32_t tid, uint32_t &shz,
-                                                  uint32_t &svr)
-{
-	shz = svr = 0;
-	if (w > 2u && h > 2u) {
-		const uint32_t iw = w - 2u, rb = w * (uint32_t)C;
-		for (uint32_t i = tid; i < iw * (h - 2u); i += kVariedThreads) {
-			const uint32_t y = i / iw, x = i - y * iw;
-			const uint8_t *p0 = s_x + y * rb + x * (uint32_t)C, *p1 = p0 + rb, *p2 = p1 + rb;
-#pragma unroll
-			for (int c = 0; c < 3; ++c) {
-				const int32_t hz = -(int32_t)p0[c] - 2 * (int32_t)p0[C + c] - (int32_t)p0[2 * C + c] + (int32_t)p2[c] +
-				                   2 * (int32_t)p2[C + c] + (int32_t)p2[2 * C + c];
-				const int32_t vr = -(int32_t)p0[c] - 2 * (int32_t)p1[c] - (int32_t)p2[c] + (int32_t)p0[2 * C + c] +
-				                   2 * (int32_t)p1[2 * C + c] + (int32_t)p2[2 * C + c];
-				shz += (uint32_t)(hz < 0 ? -hz : hz);
-				svr += (uint32_t)(vr < 0 ? -vr : vr);
-			}
-		}
-	}
-	for (int d = 32; d >= 1; d >>= 1) {
-		shz += (uint32_t)__shfl_xor((int)shz, d, 64);
-		svr += (uint32_t)__shfl_xor((int)svr, d, 64);
-	}
-	if ((tid & 63u) == 0u) {
-		s_red[2u * (tid >> 6)] = shz;
-		s_red[2u * (tid >> 6) + 1u] = svr;
-	}
-	__syncthreads();
-	shz = svr = 0;
-#pragma unroll
-	for (uint32_t q = 0; q < kVariedThreads / 64u; ++q) {
-		shz += s_red[2u * q];
-		svr += s_red[2u * q + 1u];
-	}
-}
-
-// fir's un-premultiply of `count` RGBA pixels in LDS, in place (the reciprocal table's division)
-__device__ __forceinline__ void varied_unpremultiply(uint32_t *p32, uint32_t count, uint32_t tid)
-{
-	for (uint32_t i = tid; i < count; i += kVariedThreads) {
-		const uint32_t px = p32[i], al = px >> 24;
-		const uint32_t rc = kRecipAlpha.v[al];
-		uint32_t r = ((px & 255u) * rc + 128u) >> 8, g = (((px >> 8) & 255u) * rc + 128u) >> 8, b = (((px >> 16) & 255u) * rc + 128u) >> 8;
-		r = r > 255u ? 255u : r;
-		g = g > 255u ? 255u : g;
-		b = b > 255u ? 255u : b;
-		p32[i] = r | (g << 8) | (b << 16) | (al << 24);
 	}
 }
 
