@@ -2765,25 +2765,86 @@ int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const si
 // ---- re-shrink of stored tiles (pxz_reshrink.hip): the reference CLI's pix_to_pix (src/bin/main.rs:233-265) ---------------
 namespace {
 
-constexpr uint32_t kLdsPerCu = 160u * 1024u;
+using pxz::kLdsPerCu;
 
-// the one place that says whether reshrink_kernel takes a block: its LDS footprint (what the launch asks for) against the CU's
-int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t wdw)
+// the one place that says whether the re-shrink kernels take a block: the LDS footprint (what the launch asks for) against the
+// CU's.  rung_channels: 0 for reshrink_kernel, the tiles' channel count for reshrink_ladder_kernel, whose footprint depends on it
+// (its resampled images)
+int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
 {
-	if (pxz::reshrink_lds_bytes(mode, bw, bh, wdw) > kLdsPerCu)
+	if (pxz::reshrink_lds_bytes(mode, bw, bh, rung_channels, wdw) > kLdsPerCu)
 		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "a re-shrink keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 bytes, "
-		            "the whole 160 KB (%ux%u)", bw, bh);
+		            "a re-shrink%s keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
+		            "bytes, the whole 160 KB (%ux%u)", rung_channels ? " ladder" : "", bw, bh);
 	return PXZ_OK;
 }
 
-// the same for reshrink_ladder_kernel, whose footprint depends on the channel count too (its resampled images)
-int reshrink_ladder_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t wdw)
+// both size queries: the footprint with the windows of expand_filter's tables
+int reshrink_lds_query(uint32_t block_w, uint32_t block_h, uint32_t rung_channels, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes)
 {
-	if (pxz::reshrink_ladder_lds_bytes(mode, bw, bh, channels, wdw) > kLdsPerCu)
-		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "a re-shrink ladder keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
-		            "bytes, the whole 160 KB (%ux%u)", bw, bh);
+	if (!lds_bytes || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, rung_channels, 1u);
+	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
+	pxz::VariedExpandTableSet s;
+	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, rung_channels, varied_window_dw(s.max_window));
+	return PXZ_OK;
+}
+
+// Both device forms of the re-shrink behind one body, from the check of the device pointers on (h, params and the ladder's
+// factors are checked by the entry points): factors == nullptr is pxz_reshrink_varied_frames_device (params->factor,
+// reshrink_kernel; n_factors is not read); otherwise pxz_reshrink_varied_ladder_frames_device (n_factors rungs, reshrink_ladder_kernel, outputs
+// rung-major).
+int reshrink_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, const pxz_params *params,
+                    uint32_t expand_filter, const float *factors, uint32_t n_factors, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                    const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels,
+                    uint32_t *d_image_flags)
+{
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	const bool ladder = factors != nullptr;
+	pxz_params p = *params;
+	if (ladder) p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
+	const uint32_t rung_channels = ladder ? channels : 0u;
+	int rc = check_params(h, &p);
+	if (rc != PXZ_OK) return rc;
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, rung_channels, 1u)) != PXZ_OK) return rc;
+	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
+	std::vector<pxz_image_desc> sized(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	if (ladder && (uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::ReshrinkLadderArgs a{};  // (the one-factor call launches its a.r)
+	pxz_params xp = p;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r.x)) != PXZ_OK) return rc;
+	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, rung_channels, a.r.x.wdw)) != PXZ_OK) return rc;
+	if ((rc = fresh_status(h, &a.r.x.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.r.image_flags = d_image_flags;
+	if ((rc = varied_upload(h, images, &a.r.v.images)) != PXZ_OK) return rc;
+	varied_fill_args(h, images, channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.r.v);
+	a.r.x.n_tiles = a.r.v.n_tiles;
+	a.r.x.tile_w = d_tile_w;
+	a.r.x.tile_h = d_tile_h;
+	a.r.x.slots = d_slots;
+	if (!ladder) {
+		a.r.v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is expanded
+		PXZ_HIP(h, pxz::launch_reshrink(a.r, channels, h->n_cus, h->stream));
+		return PXZ_OK;
+	}
+	a.n_factors = n_factors;
+	std::memcpy(a.factors, factors, n_factors * sizeof(float));
+	PXZ_HIP(h, pxz::launch_reshrink_ladder(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
 }
 
@@ -2793,13 +2854,14 @@ extern "C" {
 
 int pxz_reshrink_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes)
 {
-	if (!lds_bytes || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, 1u);
-	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
-	pxz::VariedExpandTableSet s;
-	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, varied_window_dw(s.max_window));
-	return PXZ_OK;
+	return reshrink_lds_query(block_w, block_h, 0u, mode, expand_filter, lds_bytes);
+}
+
+int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode, uint32_t expand_filter,
+                                  uint32_t *lds_bytes)
+{
+	if (channels != 3 && channels != 4) return PXZ_ERR_INVALID_ARG;
+	return reshrink_lds_query(block_w, block_h, channels, mode, expand_filter, lds_bytes);
 }
 
 int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -2809,53 +2871,8 @@ int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
-	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	int rc = check_params(h, params);
-	if (rc != PXZ_OK) return rc;
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	if ((rc = reshrink_check_block(h, params->mode, params->block_w, params->block_h, 1u)) != PXZ_OK) return rc;
-	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
-	std::vector<pxz_image_desc> sized(n_images);
-	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
-	std::vector<pxz::VariedImage> images;
-	std::vector<uint32_t> sides;
-	if ((rc = varied_plan(h, sized.data(), n_images, params->block_w, params->block_h, channels, params->mode, &images, &sides, nullptr)) != PXZ_OK)
-		return rc;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	const VariedTables *vt = nullptr;
-	if ((rc = get_varied_tables(h, params->filter, sides, &vt)) != PXZ_OK) return rc;
-	pxz::ReshrinkArgs a{};
-	pxz_params xp = *params;
-	xp.filter = expand_filter;
-	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.x)) != PXZ_OK) return rc;
-	if ((rc = reshrink_check_block(h, params->mode, params->block_w, params->block_h, a.x.wdw)) != PXZ_OK) return rc;
-	if ((rc = fresh_status(h, &a.x.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.image_flags = d_image_flags;
-	if ((rc = varied_upload(h, images, &a.v.images)) != PXZ_OK) return rc;
-	varied_fill_args(h, images, channels, params, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.v);
-	a.v.tile_bytes = (params->block_w * params->block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is expanded
-	a.x.n_tiles = a.v.n_tiles;
-	a.x.tile_w = d_tile_w;
-	a.x.tile_h = d_tile_h;
-	a.x.slots = d_slots;
-	PXZ_HIP(h, pxz::launch_reshrink(a, channels, h->n_cus, h->stream));
-	return PXZ_OK;
-}
-
-int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode, uint32_t expand_filter,
-                                  uint32_t *lds_bytes)
-{
-	if (!lds_bytes || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::reshrink_ladder_lds_bytes(mode, block_w, block_h, channels, 1u);
-	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
-	pxz::VariedExpandTableSet s;
-	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::reshrink_ladder_lds_bytes(mode, block_w, block_h, channels, varied_window_dw(s.max_window));
-	return PXZ_OK;
+	return reshrink_varied(h, descs, n_images, channels, params, expand_filter, nullptr, 0u, d_tile_w, d_tile_h, d_slots, d_block_value, d_out_w,
+	                       d_out_h, d_out_pixels, d_image_flags);
 }
 
 int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -2866,46 +2883,10 @@ int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
 	if (rc != PXZ_OK) return rc;
-	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	pxz_params p = *params;
-	p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
-	if ((rc = check_params(h, &p)) != PXZ_OK) return rc;
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	if ((rc = reshrink_ladder_check_block(h, p.mode, p.block_w, p.block_h, channels, 1u)) != PXZ_OK) return rc;
-	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
-	std::vector<pxz_image_desc> sized(n_images);
-	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
-	std::vector<pxz::VariedImage> images;
-	std::vector<uint32_t> sides;
-	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
-	if ((uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
-	PXZ_HIP(h, hipSetDevice(h->device));
-	const VariedTables *vt = nullptr;
-	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
-	pxz::ReshrinkLadderArgs a{};
-	pxz_params xp = p;
-	xp.filter = expand_filter;
-	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r.x)) != PXZ_OK) return rc;
-	if ((rc = reshrink_ladder_check_block(h, p.mode, p.block_w, p.block_h, channels, a.r.x.wdw)) != PXZ_OK) return rc;
-	if ((rc = fresh_status(h, &a.r.x.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.r.image_flags = d_image_flags;
-	if ((rc = varied_upload(h, images, &a.r.v.images)) != PXZ_OK) return rc;
-	varied_fill_args(h, images, channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.r.v);
-	a.r.x.n_tiles = a.r.v.n_tiles;
-	a.r.x.tile_w = d_tile_w;
-	a.r.x.tile_h = d_tile_h;
-	a.r.x.slots = d_slots;
-	a.n_factors = n_factors;
-	std::memcpy(a.factors, factors, n_factors * sizeof(float));
-	PXZ_HIP(h, pxz::launch_reshrink_ladder(a, channels, h->n_cus, h->stream));
-	return PXZ_OK;
+	return reshrink_varied(h, descs, n_images, channels, params, expand_filter, factors, n_factors, d_tile_w, d_tile_h, d_slots, d_block_value,
+	                       d_out_w, d_out_h, d_out_pixels, d_image_flags);
 }
 
 }  // extern "C"
@@ -2956,8 +2937,7 @@ int transcode_varied(pxz_handle *h, const uint8_t *const *files, const size_t *l
 	int rc;
 	if (same_block) {
 		if ((rc = check_params(h, params)) != PXZ_OK) return rc;
-		if ((rc = ladder ? reshrink_ladder_check_block(h, params->mode, fbw, fbh, ch, 1u) : reshrink_check_block(h, params->mode, fbw, fbh, 1u)) != PXZ_OK)
-			return rc;
+		if ((rc = reshrink_check_block(h, params->mode, fbw, fbh, ladder ? ch : 0u, 1u)) != PXZ_OK) return rc;
 	} else {
 		const pxz_params px = decode_side_params(&pin, true);
 		if ((rc = varied_check_params(h, ch, &px)) != PXZ_OK) return rc;

@@ -1141,9 +1141,11 @@ __device__ __forceinline__ bool bad_stored_size(uint32_t tw, uint32_t th, uint32
 }
 
 // ---------------------------------------------------------------------------
-// One stored tile of a varied batch back at its full size, in the wave's LDS image: steps 2 and 3 of
-// varied_expand_kernel (pxz_varied_expand.hip), which distortion_kernel (pxz_distortion.hip) and window_expand_kernel
-// (pxz_window.hip) run too.
+// One stored tile of a varied batch back at its full size, in an LDS image: steps 2 and 3 of varied_expand_kernel
+// (pxz_varied_expand.hip), which distortion_kernel (pxz_distortion.hip) and window_expand_kernel (pxz_window.hip) run too, one
+// wave per tile (G = 64, `lane` the lane, wsync a wave barrier), and reshrink_ladder_kernel with a whole block per tile
+// (reshrink_tile_image, pxz_varied_tile.h: G = 256, `lane` the thread, wsync = __syncthreads()).  G is the number of threads
+// that share the tile; all of them make the call.
 //   2. the stored pixels (tw x th at src, tightly packed) -> one dword per pixel in s_src (RGBA under a convolution
 //      alpha-premultiplied as fir does), and the windows of both axis tables -- directory entry (full size, stored size) of
 //      a.dir -- in s_wx / s_wy: per output sample a.wdw dwords, first | count << 16, then the weights as i16 pairs;
@@ -1152,9 +1154,11 @@ __device__ __forceinline__ bool bad_stored_size(uint32_t tw, uint32_t th, uint32
 //      at the end.
 // Returns the plane (s_src or s_tmp) that holds the fw x fh result, one dword per pixel; wsync() has run behind its last
 // write.  stage_x / stage_y false: the windows of that axis are in s_wx / s_wy already (the same full and stored size as
-// the tile this wave resized before).  Args: TileResizeArgs, or DistortionArgs (which names the same fields).
-// reshrink_kernel (pxz_reshrink.hip) has a block-wide copy of steps 2 and 3 (256 threads, __syncthreads() for wsync): A FIX
-// TO THE ARITHMETIC HERE BELONGS THERE TOO, and the other way round.
+// the tile these threads resized before).  Args: TileResizeArgs, or DistortionArgs (which names the same fields).
+// Of global memory, step 2 reads the tile's own slot and the tables and nothing else: an RGB pixel is one unaligned dword from
+// its byte address, and the address is clamped at slot_bytes - 4 (the slot's last pixel is read from a byte earlier and
+// shifted), so no load reaches behind the slot.  The re-shrink's in-place guarantee -- a block reads only its own tile's slot,
+// and before its first store -- rests on that.
 // ---------------------------------------------------------------------------
 
 // the clamp spelled as an instruction: left to the compiler, clip8(a) | clip8(b) << 8 of an RGB pixel became
@@ -1167,7 +1171,7 @@ __device__ __forceinline__ uint32_t clip8_med3(int32_t acc, int prec)
 	return (uint32_t)r;
 }
 
-template <int C, class Args, class Sync>
+template <int C, uint32_t G = 64u, class Args, class Sync>
 __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uint32_t lane, const uint8_t *src, uint32_t tw, uint32_t th,
                                                               uint32_t fw, uint32_t fh, uint32_t *s_src, uint32_t *s_tmp, uint32_t *s_wx,
                                                               uint32_t *s_wy, bool stage_x, bool stage_y, Sync wsync)
@@ -1177,7 +1181,7 @@ __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uin
 
 	// ---- 2. stored pixels -> one dword per pixel; the windows of both axes
 	const uint32_t n = tw * th;
-	for (uint32_t i = lane; i < n; i += 64u) {
+	for (uint32_t i = lane; i < n; i += G) {
 		uint32_t px;
 		if constexpr (C == 4) {
 			px = reinterpret_cast<const uint32_t *>(src)[i];
@@ -1197,7 +1201,7 @@ __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uin
 	ExpandTab tab_x{0, 0, 0, 0}, tab_y{0, 0, 0, 0};
 	// per output sample wdw dwords: first | count << 16, then the weights as i16 pairs (a zero in the spare half)
 	auto stage_windows = [&](uint32_t *wd, const ExpandTab &tab, uint32_t outs) {
-		for (uint32_t o = lane; o < outs; o += 64u) {
+		for (uint32_t o = lane; o < outs; o += G) {
 			uint32_t *d = wd + a.wdw * o;
 			const uint32_t first = a.starts[tab.start_off + o];
 			const uint32_t cnt = a.filter == 0u ? 1u : a.sizes[tab.start_off + o];
@@ -1223,8 +1227,8 @@ __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uin
 	const uint32_t *out = s_src;  // block.rs:279-281: clone
 	if (same) {
 	} else if (a.filter == 0u) {  // ResizeAlg::Nearest
-		RowWalker rw(lane, 64u, fw);
-		for (uint32_t i = lane; i < fw * fh; i += 64u, rw.next()) {
+		RowWalker rw(lane, G, fw);
+		for (uint32_t i = lane; i < fw * fh; i += G, rw.next()) {
 			const uint32_t x = tw == fw ? rw.col : (s_wx[a.wdw * rw.col] & 0xffffu), y = th == fh ? rw.row : (s_wy[a.wdw * rw.row] & 0xffffu);
 			s_tmp[i] = s_src[y * tw + x];
 		}
@@ -1236,14 +1240,14 @@ __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uin
 			// horizontal pass: item = (ox, y) of the th stored rows
 			const int prec = tab_x.precision;
 			const int32_t init = 1 << (prec - 1);
-			RowWalker rw(lane, 64u, fw);
-			for (uint32_t i = lane; i < fw * th; i += 64u, rw.next()) {
+			RowWalker rw(lane, G, fw);
+			for (uint32_t i = lane; i < fw * th; i += G, rw.next()) {
 				const uint32_t *wd = s_wx + a.wdw * rw.col;
 				const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
 				const uint32_t *row = s_src + rw.row * tw + first;
 				int32_t acc[4] = {init, init, init, init};
 				// two taps per v_dot2_i32_i16 (an odd count has a zero weight for the pixel read past the window, which is
-				// still inside this wave's image)
+				// still inside the image: tw < fw)
 				for (uint32_t j = 0; j < cnt; j += 2u) {
 					const uint32_t w2 = wd[1u + (j >> 1)], p0 = row[j], p1 = row[j + 1u];
 #pragma unroll
@@ -1263,8 +1267,8 @@ __device__ __forceinline__ const uint32_t *varied_resize_tile(const Args &a, uin
 			uint32_t *o = need_h ? s_src : s_tmp;
 			const int prec = tab_y.precision;
 			const int32_t init = 1 << (prec - 1);
-			RowWalker rw(lane, 64u, fw);
-			for (uint32_t i = lane; i < fw * fh; i += 64u, rw.next()) {
+			RowWalker rw(lane, G, fw);
+			for (uint32_t i = lane; i < fw * fh; i += G, rw.next()) {
 				const uint32_t *wd = s_wy + a.wdw * rw.row;
 				const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
 				const uint32_t *col = cur + first * fw + rw.col;

@@ -523,9 +523,9 @@ struct TileResizeArgs {
 
 // Re-shrink of stored tiles (pxz_reshrink_varied_frames_device, pxz_reshrink.hip): the stored tiles of a flat tile space
 // expanded to their full sizes in LDS and shrunk again, one tile per block.  v is the shrink side as varied_kernel takes it
-// (v.base is unused, v.tile_bytes is one LDS plane of bw * bh dwords, rounded up to 16 bytes); x is the expand side: the
-// tables of put_varied_expand_tables, the stored sizes and slots that are read, and the status word (x.tile_dw and x.t0_dw are
-// unused: the block's LDS is reshrink_lds_bytes').  The outputs of v may be the inputs of x (pxz_reshrink.hip: in place).
+// (v.base is unused, v.tile_bytes is one LDS plane of bw * bh dwords, rounded up to 16 bytes); x is the expand side: the tables
+// of put_varied_expand_tables, the stored sizes and slots that are read, and the status word (x.tile_dw and x.t0_dw are
+// unused: the block's LDS is reshrink_lds', pxz_varied_tile.h).  The outputs of v may be the inputs of x (pxz_reshrink.hip: in place).
 struct ReshrinkArgs {
 	VariedArgs v;
 	TileResizeArgs x;
@@ -533,7 +533,7 @@ struct ReshrinkArgs {
 };
 
 // Re-shrink ladder (pxz_reshrink_varied_ladder_frames_device, pxz_reshrink_ladder.hip): the re-shrink's arguments (r.v.factor
-// and r.v.tile_bytes are unused: the block's LDS is reshrink_ladder_lds') and the rungs' factors.  Rung q of tile t writes
+// and r.v.tile_bytes are unused) and the rungs' factors.  Rung q of tile t writes
 // value, sizes and slot q * r.v.n_tiles + t; a flagged tile writes 0 x 0 and value bits 0 to every rung.
 struct ReshrinkLadderArgs {
 	ReshrinkArgs r;

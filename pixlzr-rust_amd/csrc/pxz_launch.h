@@ -42,16 +42,25 @@ hipError_t launch_varied_ladder(const VariedLadderArgs &a, uint32_t channels, ui
 // LDS bytes of one block of varied_ladder_kernel (what the host holds against the CU's 160 KB before it launches)
 uint32_t varied_ladder_lds_limit_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels);
 hipError_t launch_reshrink(const ReshrinkArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
-// LDS bytes of one block of reshrink_kernel for blocks of bw x bh whose staged windows take wdw dwords (what the host holds
-// against the CU's 160 KB before it launches, and what the launch asks for); 0xffffffff: a plane of bw * bh dwords above 64 KB
-uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t wdw);
 hipError_t launch_reshrink_ladder(const ReshrinkLadderArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
-// LDS bytes of one block of reshrink_ladder_kernel, from the layout function the kernel and its launch use; 0xffffffff: a plane
-// of bw * bh dwords above 64 KB
-uint32_t reshrink_ladder_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t wdw);
+// LDS bytes of one block of reshrink_kernel (rung_channels 0) or of reshrink_ladder_kernel (rung_channels: the tiles' channel
+// count) for blocks of bw x bh whose staged windows take wdw dwords, from the layout function the kernels and their launches
+// use (what the host holds against kLdsPerCu before it launches); 0xffffffff: a plane of bw * bh dwords above 64 KB
+uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw);
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
+
+// The grid of a tile-per-block kernel (four waves, grid-stride over n_tiles) whose block takes lds_bytes of a CU's LDS: as many
+// blocks as the CUs hold at once, at most eight per CU; the rest of the tiles walk the grid-stride loop.
+constexpr uint32_t kLdsPerCu = 160u * 1024u;
+inline uint32_t tile_blocks(uint32_t n_tiles, uint32_t lds_bytes, uint32_t n_cus)
+{
+	uint32_t per_cu = kLdsPerCu / lds_bytes;
+	per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
+	const uint64_t cap = (uint64_t)n_cus * per_cu;
+	return (uint32_t)(n_tiles < cap ? n_tiles : cap);
+}
 
 #ifdef __HIP__
 // A launch with dynamic LDS: above 64 KB the kernel's limit is raised first.  Returns what the launch left behind.

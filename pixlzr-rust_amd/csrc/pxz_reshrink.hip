@@ -4,30 +4,30 @@
 // flow is per-tile work and nothing of image size touches HBM: stored bytes in, stored bytes out.
 //
 // reshrink_kernel: one tile per block of 256 threads, grid-stride over the flat tile space of pxz_varied_layout, owners by
-// owner_of (pxz_device.h), the grid sized as launch_varied sizes it.  A tile
+// owner_of (pxz_device.h), the grid of tile_blocks (pxz_launch.h).  A tile
 //   1. reads     its stored size (tw, th) and, from its owner's grid, its full size (fw, fh);
 //   2. is flagged and skipped when its stored size cannot be (zero, or beyond its place), as bad_stored_size does it: status
 //                bit 0, the image's flag, outputs 0 x 0 with value bits 0, its slot left as it was;
 //   3. is cloned in when it is stored at full size (block.rs:279-281): the slot's bytes go straight into the tile image;
 //   4. is expanded otherwise: the arithmetic of varied_resize_tile step 3 (pxz_device.h), done by the whole block -- stride
-//                256, __syncthreads() where the wave form has wsync.  A FIX TO THE ARITHMETIC THERE BELONGS HERE TOO, and the
-//                other way round.  RGBA under a convolution is premultiplied, horizontal pass, vertical pass (i16 weights,
-//                i32 accumulators, u8 between the passes), un-premultiplied at the end; the Nearest pick from the same tables;
-//                one pass when only one axis differs.  The clamp is clip8_med3 (left to the compiler this code shape became
-//                v_ashr_pk_u8_i32).  The result is one dword per pixel; RGB is then packed to 3 bytes, so
-//                that what follows reads the tile image varied_kernel reads;
+//                256, __syncthreads() where the wave form has wsync.  THIS KERNEL KEEPS ITS OWN COPY of steps 3 and 4
+//                (reshrink_tile_image, pxz_varied_tile.h, is the text the re-shrink ladder runs) and of the detectors: on the
+//                shared functions its shrink_by rows measured 0.5-1 % slower than before, outside the rule of DESIGN.md 8g, and
+//                on the shared tile image alone 4-7 %.  A FIX TO THE ARITHMETIC THERE BELONGS HERE TOO, and the
+//                other way round.  The result is one dword per pixel; RGB is then packed to 3 bytes, so that what follows reads
+//                the tile image varied_kernel reads;
 //   5. is measured, decided, resampled and stored: steps 2 and 3 of varied_kernel (pxz_varied.hip), unchanged in arithmetic
-//                (copied, not called: varied_kernel gains registers when they are functions; the pass and the
-//                store are pxz_varied_tile.h's).
+//                (copied, not called; the pass and the store are pxz_varied_tile.h's).
 // In place: tile t's stored size and slot are read only by the block that writes tile t's outputs, into registers and LDS
 // and before its first store (barriers lie between), so out_w / out_h / out_px may be the input arrays.
 //
-// LDS of one block (reshrink_lds_bytes):
+// LDS of one block (reshrink_lds with no rung channels, pxz_varied_tile.h: the launch and the host take it from there; the kernel
+// derives the same offsets from v.tile_bytes = one plane, the pointer arithmetic it was measured with):
 //   [oklab tables, shrink_by only: 14 336 B] [P0: plane] [P1: plane] [windows of both axes: (bw + bh) * wdw dwords]
 //   [the detector's planes, shrink_by with planes below 16 KB only: 16 KB]
 // A plane is bw * bh dwords (the expand works on one dword per pixel for both channel counts), so the call's limit is
 // block_w * block_h * 4 <= 65536 for RGB and RGBA alike: 128 KB + 14 KB + 5 KB (wdw <= 5: an up-scaling window has at most
-// 7 taps) at 128x128, under the CU's 160 KB.  Beyond a 64 KB plane reshrink_lds_bytes answers "does not fit"; within it only
+// 7 taps) at 128x128, under the CU's 160 KB.  Beyond a 64 KB plane reshrink_lds answers "does not fit"; within it only
 // the windows of a very oblong block (bw + bh above about 900) can still exceed the CU.
 //
 // Compiled with -ffp-contract=off (the detector's f32 arithmetic follows the reference's unfused operations).
@@ -35,19 +35,6 @@
 #include "pxz_launch.h"
 
 namespace pxz {
-
-constexpr uint32_t kReshrinkMaxPlaneBytes = 65536;
-
-// LDS bytes of one block for blocks of bw x bh with staged windows of wdw dwords; 0xffffffff: a plane beyond the call's limit
-uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t wdw)
-{
-	const uint64_t plane = ((uint64_t)bw * bh * 4u + 15u) & ~(uint64_t)15u;
-	if (bw == 0u || bh == 0u || plane > kReshrinkMaxPlaneBytes) return 0xffffffffu;
-	const uint32_t tables = mode == 0u ? kVariedTables * 4u : 0u;
-	const uint32_t windows = (((bw + bh) * wdw + 3u) & ~3u) * 4u;
-	const uint32_t scratch = mode == 0u && plane < kVariedPlaneBytes ? kVariedPlaneBytes : 0u;
-	return tables + 2u * (uint32_t)plane + windows + scratch;
-}
 
 template <int C>
 __global__ void __launch_bounds__(kVariedThreads) reshrink_kernel(const ReshrinkArgs r)
@@ -411,15 +398,15 @@ __global__ void __launch_bounds__(kVariedThreads) reshrink_kernel(const Reshrink
 hipError_t launch_reshrink(const ReshrinkArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream)
 {
 	if (a.v.n_tiles == 0u) return hipSuccess;
-	const uint32_t lds = reshrink_lds_bytes(a.v.mode, a.v.bw, a.v.bh, a.x.wdw);
-	if (lds > 160u * 1024u) return hipErrorInvalidValue;
-	// as many blocks as the CUs' LDS holds (at most eight of four waves per CU); the rest walk the grid-stride loop
-	uint32_t per_cu = (160u * 1024u) / lds;
-	per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
-	const uint64_t cap = (uint64_t)n_cus * per_cu;
-	const uint32_t blocks = (uint32_t)(a.v.n_tiles < cap ? a.v.n_tiles : cap);
-	auto go = [&](auto kernel) { return launch_with_lds(kernel, blocks, kVariedThreads, lds, stream, a); };
+	const uint32_t lds = reshrink_lds(a.v.mode, a.v.bw, a.v.bh, 0u, a.x.wdw).total;
+	if (lds > kLdsPerCu) return hipErrorInvalidValue;
+	auto go = [&](auto kernel) { return launch_with_lds(kernel, tile_blocks(a.v.n_tiles, lds, n_cus), kVariedThreads, lds, stream, a); };
 	return channels == 4u ? go(reshrink_kernel<4>) : go(reshrink_kernel<3>);
+}
+
+uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
+{
+	return reshrink_lds(mode, bw, bh, rung_channels, wdw).total;
 }
 
 }  // namespace pxz

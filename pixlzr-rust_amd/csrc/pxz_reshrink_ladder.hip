@@ -5,25 +5,22 @@
 // per distinct pair of levels among its rungs.
 //
 // reshrink_ladder_kernel: one tile per block of 256 threads, grid-stride over the flat tile space of pxz_varied_layout, owners by
-// owner_of (pxz_device.h), the grid sized as launch_varied sizes it.  A tile
+// owner_of (pxz_device.h), the grid of tile_blocks (pxz_launch.h).  A tile
 //   1. reads      its stored size (tw, th) and, from its owner's grid, its full size (fw, fh);
 //   2. is flagged and skipped when its stored size cannot be (zero, or beyond its place), as reshrink_kernel does it: status bit
 //                 0, the image's flag, and for EVERY rung outputs 0 x 0 with value bits 0; every rung's slot is left as it was;
-//   3. is cloned in when it is stored at full size, or
-//   4. is expanded otherwise: steps 3 and 4 of reshrink_kernel, COPIED UNCHANGED -- A FIX TO THE ARITHMETIC THERE (or in
-//                 varied_resize_tile, pxz_device.h) BELONGS HERE TOO, and the other way round.  RGB is packed to 3 bytes, so that
-//                 what follows reads the tile image varied_ladder_kernel reads.  X is the plane the result lies in;
-//   5. is measured once: x = total / count, or the two integer sums (varied_oklab_raw, varied_sobel_sums: pxz_varied_tile.h);
-//   6. is decided per rung, by thread r for rung r: value and sizes go to index r * n_tiles + tile, the pair of levels that shrink
-//                 to LDS; cloned to the slot of every rung that keeps both sizes, before the premultiply; premultiplied once, in
-//                 place, and only if some rung shrinks; resampled once per distinct pair of levels (X -> I -> F, or X -> A alone)
-//                 and stored to every rung with that pair: steps 3 to 6 of varied_ladder_kernel, with varied_pass and
-//                 varied_store of pxz_varied_tile.h.
-// X is never written after the premultiply, so it serves every pair.  In place: tile t's stored size and slot are read only by
-// the block of tile t, into registers and LDS and before its first store (barriers lie between), and rungs of 1 and above lie
-// beyond the inputs, so rung 0 of out_w / out_h / out_px may be the input arrays.
+//   3., 4. is cloned in when it is stored at full size, or expanded otherwise: reshrink_tile_image (pxz_varied_tile.h).
+//                 reshrink_kernel has an inline copy of these two steps (pxz_reshrink.hip says why).  X is the plane the result lies in;
+//   5. is measured once: x = total / count, or the two integer sums (varied_oklab_raw, varied_sobel_sums);
+//   6. is decided per rung, by thread r for rung r, cloned, premultiplied once and resampled once per distinct pair of levels:
+//                 steps 3 to 6 of varied_ladder_kernel.  THIS KERNEL KEEPS ITS OWN COPY of varied_ladder_tail (pxz_varied_tile.h),
+//                 unchanged in arithmetic: with the tile image and the tail both called as functions its shrink_by rows measured
+//                 2-3.5 % slower, with either one alone they do not.  A fix to the tail there belongs here too.
+// In place: tile t's stored size and slot are read only by the block of tile t, into registers and LDS and before its first store
+// (barriers lie between), and rungs of 1 and above lie beyond the inputs, so rung 0 of out_w / out_h / out_px may be the input
+// arrays.
 //
-// LDS of one block (reshrink_ladder_lds):
+// LDS of one block (reshrink_lds with the tile's channel count, pxz_varied_tile.h):
 //   [oklab tables, shrink_by only: 14 336 B] [P0: plane] [P1: plane] [windows of both axes: (bw + bh) * wdw dwords] [A, if own]
 // A plane is bw * bh dwords, as in reshrink_kernel.  After the expand X is P0 or P1 (which one depends on the tile) and the other
 // plane is free; it serves as A: the detector's planes [4][kVariedChunk], then the passes' I at its start and F behind I
@@ -38,40 +35,6 @@
 
 namespace pxz {
 
-constexpr uint32_t kReshrinkLadderMaxPlaneBytes = 65536;
-
-// Where a block of reshrink_ladder_kernel keeps its images: byte offsets into its dynamic LDS, and their sum (0xffffffff: a plane
-// beyond the call's limit).  The kernel, its launcher and the host's limit check all take the layout from here.
-struct ReshrinkLadderLds {
-	uint32_t p0, p1, wx;  // the two planes and the staged windows
-	uint32_t own;         // A's own region, or 0: A is the plane the expand leaves free
-	uint32_t f;           // F, from the start of A (= the room of I)
-	uint32_t total;
-};
-
-__host__ __device__ inline ReshrinkLadderLds reshrink_ladder_lds(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t wdw)
-{
-	auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
-	ReshrinkLadderLds l{0, 0, 0, 0, 0, 0xffffffffu};
-	const uint64_t plane64 = ((uint64_t)bw * bh * 4u + 15u) & ~(uint64_t)15u;
-	if (bw == 0u || bh == 0u || plane64 > kReshrinkLadderMaxPlaneBytes) return l;
-	const uint32_t plane = (uint32_t)plane64;
-	// A: the widest horizontal result I and the result F behind it, or a vertical-only result (varied_ladder_lds)
-	const uint32_t hw = bw > 1u ? (bw + 1u) / 2u : 0u, hh = bh > 1u ? (bh + 1u) / 2u : 0u;
-	const uint32_t i_bytes = up16(hw * bh * channels);
-	const uint32_t hv = i_bytes + up16(hw * hh * channels), v_only = up16(bw * hh * channels);
-	uint32_t a_bytes = hv > v_only ? hv : v_only;
-	if (mode == 0u && a_bytes < kVariedPlaneBytes) a_bytes = kVariedPlaneBytes;  // the detector's planes
-	l.p0 = mode == 0u ? kVariedTables * 4u : 0u;
-	l.p1 = l.p0 + plane;
-	l.wx = l.p1 + plane;
-	const uint32_t after = l.wx + (((bw + bh) * wdw + 3u) & ~3u) * 4u;
-	l.own = a_bytes > plane ? after : 0u;
-	l.f = i_bytes;
-	l.total = a_bytes > plane ? after + a_bytes : after;
-	return l;
-}
-
 template <int C>
 __global__ void __launch_bounds__(kVariedThreads) reshrink_ladder_kernel(const ReshrinkLadderArgs la)
 {
@@ -84,7 +47,7 @@ __global__ void __launch_bounds__(kVariedThreads) reshrink_ladder_kernel(const R
 	const uint32_t tid = threadIdx.x, n_rungs = la.n_factors;
 	const bool oklab = a.mode == 0u;
 	const bool nearest = a.filter == 0u;
-	const ReshrinkLadderLds l = reshrink_ladder_lds(a.mode, a.bw, a.bh, (uint32_t)C, x.wdw);
+	const ReshrinkLds l = reshrink_lds(a.mode, a.bw, a.bh, (uint32_t)C, x.wdw);
 	float4 *s_lms = reinterpret_cast<float4 *>(lds);
 	float *s_alpha = reinterpret_cast<float *>(s_lms + 768);
 	double *s_scale = reinterpret_cast<double *>(s_alpha + 256);
@@ -123,156 +86,12 @@ __global__ void __launch_bounds__(kVariedThreads) reshrink_ladder_kernel(const R
 			continue;
 		}
 
-		uint8_t *s_x, *s_o;  // the tile image X, tightly packed, and the plane the expand leaves free
-		if (tw == w && th == h) {
-			// ---- 3. clone in: the slot's bytes are the tile image (as varied_kernel stages a tile whose pitch is one row)
-			const uint32_t bytes = n * (uint32_t)C;
-			uint32_t head = 0;
-			if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
-				head = bytes & ~15u;
-				uint4 *d = reinterpret_cast<uint4 *>(s_p0);
-				for (uint32_t i = tid; i < head / 16u; i += kVariedThreads) d[i] = reinterpret_cast<const uint4 *>(src)[i];
-			} else if ((reinterpret_cast<uintptr_t>(src) & 3u) == 0u) {
-				head = bytes & ~3u;
-				uint32_t *d = reinterpret_cast<uint32_t *>(s_p0);
-				for (uint32_t i = tid; i < head / 4u; i += kVariedThreads) d[i] = reinterpret_cast<const uint32_t *>(src)[i];
-			}
-			for (uint32_t i = head + tid; i < bytes; i += kVariedThreads) s_p0[i] = src[i];
-			s_x = s_p0;
-			s_o = s_p1;
-			__syncthreads();
-		} else {
-			// ---- 4. expand: varied_resize_tile (pxz_device.h) by the whole block.  Stored pixels -> one dword per pixel in P0
-			// (RGBA under a convolution alpha-premultiplied as fir does); the windows of both axis tables -- directory entry
-			// (full size, stored size) -- per output sample wdw dwords: first | count << 16, then the weights as i16 pairs
-			uint32_t *s_src = reinterpret_cast<uint32_t *>(s_p0), *s_tmp = reinterpret_cast<uint32_t *>(s_p1);
-			const bool conv = x.filter != 0u;
-			for (uint32_t i = tid; i < tw * th; i += kVariedThreads) {
-				uint32_t px;
-				if constexpr (C == 4) {
-					px = reinterpret_cast<const uint32_t *>(src)[i];
-					if (conv) px = premultiply(px);  // fir: U8x4 is alpha-premultiplied before a convolution
-				} else {
-					px = (uint32_t)src[3u * i] | ((uint32_t)src[3u * i + 1u] << 8) | ((uint32_t)src[3u * i + 2u] << 16) | 0xff000000u;
-				}
-				s_src[i] = px;
-			}
-			ExpandTab tab_x{0, 0, 0, 0}, tab_y{0, 0, 0, 0};
-			auto stage_windows = [&](uint32_t *wd, const ExpandTab &tab, uint32_t outs) {
-				for (uint32_t o = tid; o < outs; o += kVariedThreads) {
-					uint32_t *d = wd + x.wdw * o;
-					const uint32_t first = x.starts[tab.start_off + o];
-					const uint32_t cnt = conv ? x.sizes[tab.start_off + o] : 1u;
-					d[0] = first | (cnt << 16);
-					if (conv) {
-						const int16_t *k = x.coeffs + tab.coeff_off + o * tab.window;
-						for (uint32_t j = 0; j < cnt; j += 2u)
-							d[1u + (j >> 1)] = (uint32_t)(uint16_t)k[j] | (j + 1u < cnt ? (uint32_t)(uint16_t)k[j + 1u] << 16 : 0u);
-					}
-				}
-			};
-			if (tw != w) {
-				tab_x = x.dir[(size_t)x.slot[w] * x.stride + tw];
-				stage_windows(s_wx, tab_x, w);
-			}
-			if (th != h) {
-				tab_y = x.dir[(size_t)x.slot[h] * x.stride + th];
-				stage_windows(s_wy, tab_y, h);
-			}
-			__syncthreads();
-
-			uint32_t *out;
-			if (!conv) {  // ResizeAlg::Nearest
-				RowWalker rw(tid, kVariedThreads, w);
-				for (uint32_t i = tid; i < n; i += kVariedThreads, rw.next()) {
-					const uint32_t sx = tw == w ? rw.col : (s_wx[x.wdw * rw.col] & 0xffffu), sy = th == h ? rw.row : (s_wy[x.wdw * rw.row] & 0xffffu);
-					s_tmp[i] = s_src[sy * tw + sx];
-				}
-				out = s_tmp;
-				__syncthreads();
-			} else {
-				const bool need_h = tw != w, need_v = th != h;
-				out = s_src;
-				if (need_h) {
-					// horizontal pass: item = (ox, y) of the th stored rows
-					const int prec = tab_x.precision;
-					const int32_t init = 1 << (prec - 1);
-					RowWalker rw(tid, kVariedThreads, w);
-					for (uint32_t i = tid; i < w * th; i += kVariedThreads, rw.next()) {
-						const uint32_t *wd = s_wx + x.wdw * rw.col;
-						const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
-						const uint32_t *row = s_src + rw.row * tw + first;
-						int32_t acc[4] = {init, init, init, init};
-						// two taps per v_dot2_i32_i16 (an odd count has a zero weight for the pixel read past the window, which is
-						// still inside the plane: tw < w)
-						for (uint32_t j = 0; j < cnt; j += 2u) {
-							const uint32_t w2 = wd[1u + (j >> 1)], p0 = row[j], p1 = row[j + 1u];
-#pragma unroll
-							for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
-						}
-						uint32_t px = clip8_med3(acc[0], prec) | (clip8_med3(acc[1], prec) << 8) | (clip8_med3(acc[2], prec) << 16);
-						px |= C == 4 ? clip8_med3(acc[3], prec) << 24 : 0xff000000u;
-						if (C == 4 && !need_v) px = unpremultiply(px);
-						s_tmp[i] = px;
-					}
-					out = s_tmp;
-					__syncthreads();
-				}
-				if (need_v) {
-					// vertical pass: item = (ox, oy); the rows it reads are w wide (w == tw when only this pass runs; the row an odd
-					// count reads past the window is still inside the plane: th < h)
-					const uint32_t *cur = need_h ? s_tmp : s_src;
-					uint32_t *o = need_h ? s_src : s_tmp;
-					const int prec = tab_y.precision;
-					const int32_t init = 1 << (prec - 1);
-					RowWalker rw(tid, kVariedThreads, w);
-					for (uint32_t i = tid; i < n; i += kVariedThreads, rw.next()) {
-						const uint32_t *wd = s_wy + x.wdw * rw.row;
-						const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
-						const uint32_t *col = cur + first * w + rw.col;
-						int32_t acc[4] = {init, init, init, init};
-						for (uint32_t j = 0; j < cnt; j += 2u) {
-							const uint32_t w2 = wd[1u + (j >> 1)], p0 = col[j * w], p1 = col[(j + 1u) * w];
-#pragma unroll
-							for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
-						}
-						uint32_t px = clip8_med3(acc[0], prec) | (clip8_med3(acc[1], prec) << 8) | (clip8_med3(acc[2], prec) << 16);
-						px |= C == 4 ? clip8_med3(acc[3], prec) << 24 : 0xff000000u;
-						if constexpr (C == 4) px = unpremultiply(px);
-						o[i] = px;
-					}
-					out = o;
-					__syncthreads();
-				}
-			}
-			uint32_t *other = out == s_src ? s_tmp : s_src;
-			if constexpr (C == 4) {
-				s_x = reinterpret_cast<uint8_t *>(out);
-				s_o = reinterpret_cast<uint8_t *>(other);
-			} else {
-				// RGB: the dwords packed to 3 bytes in the other plane (four pixels as three dwords, bytes at the tail)
-				const uint32_t n4 = n >> 2;
-				for (uint32_t q = tid; q < n4; q += kVariedThreads) {
-					const uint32_t p0 = out[4u * q], p1 = out[4u * q + 1u], p2 = out[4u * q + 2u], p3 = out[4u * q + 3u];
-					other[3u * q] = (p0 & 0xffffffu) | (p1 << 24);
-					other[3u * q + 1u] = ((p1 >> 8) & 0xffffu) | (p2 << 16);
-					other[3u * q + 2u] = ((p2 >> 16) & 0xffu) | (p3 << 8);
-				}
-				uint8_t *ob = reinterpret_cast<uint8_t *>(other);
-				for (uint32_t i = 4u * n4 + tid; i < n; i += kVariedThreads) {
-					const uint32_t px = out[i];
-					ob[3u * i] = (uint8_t)px;
-					ob[3u * i + 1u] = (uint8_t)(px >> 8);
-					ob[3u * i + 2u] = (uint8_t)(px >> 16);
-				}
-				s_x = ob;
-				s_o = reinterpret_cast<uint8_t *>(out);
-				__syncthreads();
-			}
-		}
+		// ---- 3., 4. the tile image X, tightly packed, and the plane the expand leaves free: cloned in, or expanded
+		const ReshrinkTileImage ti = reshrink_tile_image<C>(x, src, tw, th, w, h, s_p0, s_p1, s_wx, s_wy, tid);
+		uint8_t *s_x = ti.x, *s_o = ti.free;
 		uint8_t *s_a = l.own != 0u ? reinterpret_cast<uint8_t *>(lds) + l.own : s_o;  // I, or a vertical-only result
-		uint8_t *s_f = s_a + l.f;                                                       // F
-		float *s_plane = reinterpret_cast<float *>(s_a);                                // [4][kVariedChunk] (the detector, before A holds a pass)
+		uint8_t *s_f = s_a + l.f;                                                         // F
+		float *s_plane = reinterpret_cast<float *>(s_a);                                  // [4][kVariedChunk] (the detector, before A holds a pass)
 
 		// ---- 5. the detector up to what the factor has not entered, once
 		float xr = 0.0f;
@@ -372,20 +191,10 @@ __global__ void __launch_bounds__(kVariedThreads) reshrink_ladder_kernel(const R
 hipError_t launch_reshrink_ladder(const ReshrinkLadderArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream)
 {
 	if (a.r.v.n_tiles == 0u || a.n_factors == 0u) return hipSuccess;
-	const uint32_t lds = reshrink_ladder_lds(a.r.v.mode, a.r.v.bw, a.r.v.bh, channels, a.r.x.wdw).total;
-	if (lds > 160u * 1024u) return hipErrorInvalidValue;
-	// as many blocks as the CUs' LDS holds (at most eight of four waves per CU); the rest walk the grid-stride loop
-	uint32_t per_cu = (160u * 1024u) / lds;
-	per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
-	const uint64_t cap = (uint64_t)n_cus * per_cu;
-	const uint32_t blocks = (uint32_t)(a.r.v.n_tiles < cap ? a.r.v.n_tiles : cap);
-	auto go = [&](auto kernel) { return launch_with_lds(kernel, blocks, kVariedThreads, lds, stream, a); };
+	const uint32_t lds = reshrink_lds(a.r.v.mode, a.r.v.bw, a.r.v.bh, channels, a.r.x.wdw).total;
+	if (lds > kLdsPerCu) return hipErrorInvalidValue;
+	auto go = [&](auto kernel) { return launch_with_lds(kernel, tile_blocks(a.r.v.n_tiles, lds, n_cus), kVariedThreads, lds, stream, a); };
 	return channels == 4u ? go(reshrink_ladder_kernel<4>) : go(reshrink_ladder_kernel<3>);
-}
-
-uint32_t reshrink_ladder_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t wdw)
-{
-	return reshrink_ladder_lds(mode, bw, bh, channels, wdw).total;
 }
 
 }  // namespace pxz

@@ -253,12 +253,7 @@ hipError_t launch_varied(const VariedArgs &a, uint32_t channels, uint32_t n_cus,
 {
 	if (a.n_tiles == 0u) return hipSuccess;
 	const uint32_t lds = varied_lds_bytes(a.mode, a.tile_bytes);
-	// as many blocks as the CUs' LDS holds (at most eight of four waves per CU); the rest walk the grid-stride loop
-	uint32_t per_cu = (160u * 1024u) / lds;
-	per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
-	const uint64_t cap = (uint64_t)n_cus * per_cu;
-	const uint32_t blocks = (uint32_t)(a.n_tiles < cap ? a.n_tiles : cap);
-	auto go = [&](auto kernel) { return launch_with_lds(kernel, blocks, kVariedThreads, lds, stream, a); };
+	auto go = [&](auto kernel) { return launch_with_lds(kernel, tile_blocks(a.n_tiles, lds, n_cus), kVariedThreads, lds, stream, a); };
 	return channels == 4u ? go(varied_kernel<4>) : go(varied_kernel<3>);
 }
 

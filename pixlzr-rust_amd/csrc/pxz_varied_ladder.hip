@@ -13,6 +13,7 @@
 //   5. premultiplied once, in place (RGBA under a convolution, and only when some rung shrinks);
 //   6. resampled   once per distinct pair of levels: horizontal pass X -> I, vertical pass I -> F (or X -> I alone, or X -> A
 //                  alone), un-premultiplied where it ends and stored to the slot of every rung with that pair.
+// Steps 3 to 6 are varied_ladder_tail (pxz_varied_tile.h), which reshrink_ladder_kernel runs too.
 // X is never written after step 5, so it serves every pair.  LDS of one block (varied_ladder_lds):
 //   [oklab tables, shrink_by only] [X: the tile] [A: the detector's planes, then I at its start and F behind I]
 // with I = ceil(bw/2) * bh * C bytes (the widest horizontal result: reduced_size(w, m >= 1) <= ceil(w/2)), F = ceil(bw/2) *
@@ -48,8 +49,7 @@ __host__ __device__ inline VariedLadderLds varied_ladder_lds(uint32_t mode, uint
 	return l;
 }
 
-// ---- this kernel's copy of varied_kernel's staging (pxz_varied_tile.h says why; the detectors up to their raw results and the
-// un-premultiply loop, which the re-shrink ladder runs too, are there)
+// ---- this kernel's copy of varied_kernel's staging (pxz_varied_tile.h says why)
 
 // A tile of w x h pixels at src (rows pitch bytes apart) into LDS, tightly packed: 16-byte loads where its rows are
 // aligned, dwords or bytes otherwise.
@@ -89,7 +89,6 @@ __global__ void __launch_bounds__(kVariedThreads) varied_ladder_kernel(const Var
 	const VariedArgs &a = la.v;
 	const uint32_t tid = threadIdx.x, n_rungs = la.n_factors;
 	const bool oklab = a.mode == 0u;
-	const bool nearest = a.filter == 0u;
 	const VariedLadderLds l = varied_ladder_lds(a.mode, a.bw, a.bh, (uint32_t)C);
 	float4 *s_lms = reinterpret_cast<float4 *>(lds);
 	float *s_alpha = reinterpret_cast<float *>(s_lms + 768);
@@ -122,91 +121,8 @@ __global__ void __launch_bounds__(kVariedThreads) varied_ladder_kernel(const Var
 		if (oklab) x = varied_oklab_raw<C>(s_x, n, s_lms, s_alpha, s_scale, s_plane, s_acc, tid);
 		else varied_sobel_sums<C>(s_x, w, h, s_red, tid, shz, svr);
 
-		// ---- 3. every rung's decision: thread r decides rung r
-		if (tid < n_rungs) {
-			const float k = la.factors[tid];
-			float v0, v1;
-			if (oklab) {
-				v0 = v1 = parse_value((x * k) * 10.0f);  // pixlzr.rs:162 (BASE_FACTOR, :15), :177-178
-			} else {
-				const uint64_t fac = (uint64_t)(w - 2u) * (uint64_t)(h - 2u) * 4096ull;  // operations.rs:253-254
-				if (fac == 0ull || w < 2u || h < 2u) {
-					v0 = v1 = 0.0f;  // 0/0: the negative default NaN, which parse_value turns into 0 (finish_tile)
-				} else {
-					const double dfac = (double)fac;
-					v0 = parse_value((float)((double)shz / dfac) * k);  // :256-257, pixlzr.rs:199
-					v1 = parse_value((float)((double)svr / dfac) * k);
-				}
-			}
-			// level_count against the thresholds (round(log2f(v)) >= -k), as the single-geometry call decides it
-			uint32_t mx = 0, my = 0;
-#pragma unroll
-			for (int j = 0; j < kMaxLevel; ++j) {
-				mx += v0 < a.thresholds[j] ? 1u : 0u;
-				my += v1 < a.thresholds[j] ? 1u : 0u;
-			}
-			const uint32_t nw = reduced_size(w, mx), nh = reduced_size(h, my);  // operations.rs:150-151
-			const size_t at = (size_t)tid * a.n_tiles + tile_g;
-			a.value[at] = hypot_f32(v0, v1);  // operations.rs:154
-			a.out_w[at] = nw;
-			a.out_h[at] = nh;
-			s_key[tid] = (nw != w ? mx : 0u) | ((nh != h ? my : 0u) << 8);
-		}
-		__syncthreads();  // the keys: the same in every wave from here on
-
-		if (a.out_px != nullptr) {
-			auto slot_of = [&](uint32_t r) { return a.out_px + ((uint64_t)r * a.n_tiles + tile_g) * (uint64_t)a.slot_bytes; };
-			// ---- 4. the clones (block.rs:279-281), while X still holds the staged bytes
-			bool shrinks = false;
-			for (uint32_t r = 0; r < n_rungs; ++r) {
-				if (s_key[r] == 0u) varied_store(slot_of(r), s_x, n * (uint32_t)C, tid);
-				else shrinks = true;
-			}
-			if (shrinks) {
-				__syncthreads();  // the clones have read X
-				// ---- 5. ResizeAlg::Convolution, default options: U8x4 is alpha-premultiplied first
-				if (C == 4 && !nearest) {
-					uint32_t *p32 = reinterpret_cast<uint32_t *>(s_x);
-					for (uint32_t i = tid; i < n; i += kVariedThreads) p32[i] = premultiply(p32[i]);
-					__syncthreads();
-				}
-				// ---- 6. one resample per distinct pair of levels; X is only read
-				for (uint32_t r = 0; r < n_rungs; ++r) {
-					const uint32_t key = s_key[r];
-					if (key == 0u) continue;
-					bool done = false;
-					for (uint32_t q = 0; q < r; ++q) done = done || s_key[q] == key;
-					if (done) continue;
-					const uint32_t mx = key & 255u, my = key >> 8;
-					const bool need_h = mx != 0u, need_v = my != 0u;
-					const uint32_t nw = need_h ? reduced_size(w, mx) : w, nh = need_v ? reduced_size(h, my) : h;
-					const uint32_t lx = mx < (uint32_t)kMaxLevel ? mx : (uint32_t)kMaxLevel - 1u;
-					const uint32_t ly = my < (uint32_t)kMaxLevel ? my : (uint32_t)kMaxLevel - 1u;
-					const uint8_t *cur = s_x;
-					if (need_h) {
-						const TreeAxisEntry ex = a.dir[w * (uint32_t)kMaxLevel + lx];
-						varied_pass<C>(a, ex, nearest, s_x, (uint32_t)C, w * (uint32_t)C, s_a, (uint32_t)C, nw * (uint32_t)C, h, tid);
-						__syncthreads();
-						cur = s_a;
-					}
-					if (need_v) {
-						const TreeAxisEntry ey = a.dir[h * (uint32_t)kMaxLevel + ly];
-						uint8_t *o = need_h ? s_f : s_a;
-						// one "line" per column of the nw-wide image, samples a row apart
-						varied_pass<C>(a, ey, nearest, cur, nw * (uint32_t)C, (uint32_t)C, o, nw * (uint32_t)C, (uint32_t)C, nw, tid);
-						__syncthreads();
-						cur = o;
-					}
-					if (C == 4 && !nearest) {
-						varied_unpremultiply(reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(cur)), nw * nh, tid);
-						__syncthreads();
-					}
-					for (uint32_t q = r; q < n_rungs; ++q)
-						if (s_key[q] == key) varied_store(slot_of(q), cur, nw * nh * (uint32_t)C, tid);
-					__syncthreads();  // the next pair reuses I and F
-				}
-			}
-		}
+		// ---- 3.-6. the rungs: decisions, clones, the premultiply, resamples, stores (pxz_varied_tile.h)
+		varied_ladder_tail<C>(a, la.factors, n_rungs, tile_g, w, h, x, shz, svr, s_key, s_x, s_a, s_f, tid);
 		__syncthreads();  // the next tile reuses LDS
 	}
 }
@@ -215,12 +131,7 @@ hipError_t launch_varied_ladder(const VariedLadderArgs &a, uint32_t channels, ui
 {
 	if (a.v.n_tiles == 0u || a.n_factors == 0u) return hipSuccess;
 	const uint32_t lds = varied_ladder_lds(a.v.mode, a.v.bw, a.v.bh, channels).total;
-	// as many blocks as the CUs' LDS holds (at most eight of four waves per CU); the rest walk the grid-stride loop
-	uint32_t per_cu = (160u * 1024u) / lds;
-	per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
-	const uint64_t cap = (uint64_t)n_cus * per_cu;
-	const uint32_t blocks = (uint32_t)(a.v.n_tiles < cap ? a.v.n_tiles : cap);
-	auto go = [&](auto kernel) { return launch_with_lds(kernel, blocks, kVariedThreads, lds, stream, a); };
+	auto go = [&](auto kernel) { return launch_with_lds(kernel, tile_blocks(a.v.n_tiles, lds, n_cus), kVariedThreads, lds, stream, a); };
 	return channels == 4u ? go(varied_ladder_kernel<4>) : go(varied_ladder_kernel<3>);
 }
 

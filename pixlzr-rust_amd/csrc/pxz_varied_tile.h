@@ -1,10 +1,17 @@
-// pxz_varied_tile.h -- what varied_kernel (pxz_varied.hip: one factor) and varied_ladder_kernel (pxz_varied_ladder.hip:
-// several factors per staged tile) share of one tile's work in a block of 256 threads: the detector's LDS constants, the
-// pixel read, one resample pass along one axis and the store to a slot.  Every function is called by all 256 threads of the
-// block; the pass and the store do not end in a barrier.  (Staging, the detectors and the un-premultiply loop stay in the units
-// of varied_kernel and reshrink_kernel: varied_kernel gains registers when they are called as functions -- DESIGN.md 8h.  The
-// ladder kernels' forms of the detectors and of that loop are at the end of this header; the one-factor kernels never call
-// them, and their instruction streams are the same with and without -- DESIGN.md 8j.)
+// pxz_varied_tile.h -- one tile's work in a block of 256 threads, written once for the four tile-per-block kernels of the flat
+// tile space: varied_kernel (pxz_varied.hip), varied_ladder_kernel (pxz_varied_ladder.hip), reshrink_kernel (pxz_reshrink.hip)
+// and reshrink_ladder_kernel (pxz_reshrink_ladder.hip).
+//   all four:          the detector's LDS constants, varied_pixel, varied_pass (one resample pass along one axis), varied_store;
+//   the two ladders:   the detectors up to their raw results (varied_oklab_raw, varied_sobel_sums) and varied_unpremultiply;
+//   the re-shrinks:    the block's LDS layout (reshrink_lds: both kernels' launches and the host's limit check);
+//   reshrink_ladder_kernel: the tile image of a stored tile (reshrink_tile_image: clone-in, or varied_resize_tile of pxz_device.h
+//                      by the whole block, and the RGB pack);
+//   varied_ladder_kernel: everything behind the detector (varied_ladder_tail: the rungs' decisions, clones, resamples and
+//                      stores).
+// Every function is called by all 256 threads of the block.  What is still copied, and why (each copy says so where it stands):
+// varied_kernel keeps its staging, the two detectors and the un-premultiply loop inline -- 101 -> 124 VGPRs as functions
+// (DESIGN.md 8h); reshrink_kernel keeps the tile image and the detectors inline, and reshrink_ladder_kernel the ladder's tail --
+// same registers, but measurably slower on the shared text.  A fix to the arithmetic here belongs there too.
 #pragma once
 #include "pxz_device.h"
 #include "pxz_oklab_math.h"
@@ -69,9 +76,7 @@ __device__ __forceinline__ void varied_store(uint8_t *slot, const uint8_t *s, ui
 	for (uint32_t i = head + tid; i < bytes; i += kVariedThreads) slot[i] = s[i];
 }
 
-
-// ---- what the two ladder kernels (pxz_varied_ladder.hip, pxz_reshrink_ladder.hip) share beyond that: a tile measured once,
-// up to what the factor has not entered, and the un-premultiply of a resampled image
+// ---- a tile measured up to what the factor has not entered, and the un-premultiply of a resampled image
 
 // get_block_variance with |x - avg| (operations.rs:26-126) up to its raw result x = total / count, the same in every thread:
 // the detector kernels' own colour conversion (pxz_oklab_math.h), 1024 pixels at a time into s_plane ([4][kVariedChunk]),
@@ -185,6 +190,201 @@ __device__ __forceinline__ void varied_unpremultiply(uint32_t *p32, uint32_t cou
 		g = g > 255u ? 255u : g;
 		b = b > 255u ? 255u : b;
 		p32[i] = r | (g << 8) | (b << 16) | (al << 24);
+	}
+}
+
+// ---- the re-shrinks: a stored tile back at its full size in LDS
+
+// Where a block of reshrink_kernel or reshrink_ladder_kernel keeps its images: byte offsets into its dynamic LDS, and their sum
+// (0xffffffff: a plane beyond the calls' limit).  The kernels, their launchers and the host's limit check all take the layout
+// from here.  After reshrink_tile_image the tile image X is P0 or P1 and the other plane is free; it serves as A -- the
+// detector's planes [4][kVariedChunk], then, in the ladder, the passes' I at its start and F behind I (varied_ladder_lds' sizes)
+// -- unless A is larger than a plane: then A has a region of its own behind the windows.  rung_channels: the ladder's channel
+// count, or 0 for reshrink_kernel, whose passes go from plane to plane and whose A holds the detector's planes only.
+constexpr uint32_t kReshrinkMaxPlaneBytes = 65536;
+struct ReshrinkLds {
+	uint32_t p0, p1, wx;  // the two planes and the staged windows
+	uint32_t own;         // A's own region, or 0: A is the plane the expand leaves free
+	uint32_t f;           // F, from the start of A (= the room of I)
+	uint32_t total;
+};
+
+__host__ __device__ inline ReshrinkLds reshrink_lds(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
+{
+	auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+	ReshrinkLds l{0, 0, 0, 0, 0, 0xffffffffu};
+	const uint64_t plane64 = ((uint64_t)bw * bh * 4u + 15u) & ~(uint64_t)15u;
+	if (bw == 0u || bh == 0u || plane64 > kReshrinkMaxPlaneBytes) return l;
+	const uint32_t plane = (uint32_t)plane64;
+	// A: the widest horizontal result I and the result F behind it, or a vertical-only result (varied_ladder_lds)
+	const uint32_t hw = bw > 1u ? (bw + 1u) / 2u : 0u, hh = bh > 1u ? (bh + 1u) / 2u : 0u;
+	const uint32_t i_bytes = up16(hw * bh * rung_channels);
+	const uint32_t hv = i_bytes + up16(hw * hh * rung_channels), v_only = up16(bw * hh * rung_channels);
+	uint32_t a_bytes = hv > v_only ? hv : v_only;
+	if (mode == 0u && a_bytes < kVariedPlaneBytes) a_bytes = kVariedPlaneBytes;  // the detector's planes
+	l.p0 = mode == 0u ? kVariedTables * 4u : 0u;
+	l.p1 = l.p0 + plane;
+	l.wx = l.p1 + plane;
+	const uint32_t after = l.wx + (((bw + bh) * wdw + 3u) & ~3u) * 4u;
+	l.own = a_bytes > plane ? after : 0u;
+	l.f = i_bytes;
+	l.total = a_bytes > plane ? after + a_bytes : after;
+	return l;
+}
+
+// The tile image of stored tile (tw x th at src, tightly packed) of full size w x h, in the planes p0 / p1 of the block's LDS:
+// C bytes per pixel, tightly packed, as varied_kernel stages a tile.  Stored at full size it is cloned in (block.rs:279-281; 16-,
+// 4- or 1-byte loads by the slot's alignment); otherwise varied_resize_tile (pxz_device.h) expands it, by the whole block, to one
+// dword per pixel, and RGB is packed to 3 bytes into the other plane.  x: the image; free: the other plane.  Ends in a barrier.
+struct ReshrinkTileImage {
+	uint8_t *x, *free;
+};
+
+template <int C>
+__device__ __forceinline__ ReshrinkTileImage reshrink_tile_image(const TileResizeArgs &x, const uint8_t *src, uint32_t tw, uint32_t th, uint32_t w,
+                                                                 uint32_t h, uint8_t *s_p0, uint8_t *s_p1, uint32_t *s_wx, uint32_t *s_wy, uint32_t tid)
+{
+	const uint32_t n = w * h;
+	if (tw == w && th == h) {
+		const uint32_t bytes = n * (uint32_t)C;
+		uint32_t head = 0;
+		if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {
+			head = bytes & ~15u;
+			uint4 *d = reinterpret_cast<uint4 *>(s_p0);
+			for (uint32_t i = tid; i < head / 16u; i += kVariedThreads) d[i] = reinterpret_cast<const uint4 *>(src)[i];
+		} else if ((reinterpret_cast<uintptr_t>(src) & 3u) == 0u) {
+			head = bytes & ~3u;
+			uint32_t *d = reinterpret_cast<uint32_t *>(s_p0);
+			for (uint32_t i = tid; i < head / 4u; i += kVariedThreads) d[i] = reinterpret_cast<const uint32_t *>(src)[i];
+		}
+		for (uint32_t i = head + tid; i < bytes; i += kVariedThreads) s_p0[i] = src[i];
+		__syncthreads();
+		return {s_p0, s_p1};
+	}
+	uint32_t *s_src = reinterpret_cast<uint32_t *>(s_p0), *s_tmp = reinterpret_cast<uint32_t *>(s_p1);
+	uint32_t *out = const_cast<uint32_t *>(
+		varied_resize_tile<C, kVariedThreads>(x, tid, src, tw, th, w, h, s_src, s_tmp, s_wx, s_wy, true, true, [] { __syncthreads(); }));
+	uint32_t *other = out == s_src ? s_tmp : s_src;
+	if constexpr (C == 4) {
+		return {reinterpret_cast<uint8_t *>(out), reinterpret_cast<uint8_t *>(other)};
+	} else {
+		// RGB: the dwords packed to 3 bytes in the other plane (four pixels as three dwords, bytes at the tail)
+		const uint32_t n4 = n >> 2;
+		for (uint32_t q = tid; q < n4; q += kVariedThreads) {
+			const uint32_t p0 = out[4u * q], p1 = out[4u * q + 1u], p2 = out[4u * q + 2u], p3 = out[4u * q + 3u];
+			other[3u * q] = (p0 & 0xffffffu) | (p1 << 24);
+			other[3u * q + 1u] = ((p1 >> 8) & 0xffffu) | (p2 << 16);
+			other[3u * q + 2u] = ((p2 >> 16) & 0xffu) | (p3 << 8);
+		}
+		uint8_t *ob = reinterpret_cast<uint8_t *>(other);
+		for (uint32_t i = 4u * n4 + tid; i < n; i += kVariedThreads) {
+			const uint32_t px = out[i];
+			ob[3u * i] = (uint8_t)px;
+			ob[3u * i + 1u] = (uint8_t)(px >> 8);
+			ob[3u * i + 2u] = (uint8_t)(px >> 16);
+		}
+		__syncthreads();
+		return {ob, reinterpret_cast<uint8_t *>(out)};
+	}
+}
+
+// ---- the ladders: everything behind the detector (steps 3 to 6 of varied_ladder_kernel, pxz_varied_ladder.hip)
+// Tile tile_g of w x h pixels, its image in X and its raw detector result in x (shrink_by) or shz / svr (directional), the same in
+// every thread.  Thread r decides rung r with factors[r]: value and sizes go to index r * n_tiles + tile_g, the pair of levels
+// that shrink (0 for an axis that keeps its size) to s_key[r], where every wave reads the same keys.  Then the clones, to the slot
+// of every rung that keeps both sizes, before X is premultiplied; the premultiply, once and in place (RGBA under a convolution,
+// and only when some rung shrinks); and one resample per distinct pair of levels -- X -> I -> F, or X -> I alone, or X -> A alone,
+// with I at the start of A -- un-premultiplied where it ends and stored to the slot of every rung with that pair.  X is never
+// written after the premultiply, so it serves every pair.  Does not end in a barrier.
+template <int C>
+__device__ __forceinline__ void varied_ladder_tail(const VariedArgs &a, const float *factors, uint32_t n_rungs, uint32_t tile_g, uint32_t w,
+                                                   uint32_t h, float x, uint32_t shz, uint32_t svr, uint32_t *s_key, uint8_t *s_x, uint8_t *s_a,
+                                                   uint8_t *s_f, uint32_t tid)
+{
+	const uint32_t n = w * h;
+	const bool nearest = a.filter == 0u;
+	// ---- 3. every rung's decision: thread r decides rung r
+	if (tid < n_rungs) {
+		const float k = factors[tid];
+		float v0, v1;
+		if (a.mode == 0u) {
+			v0 = v1 = parse_value((x * k) * 10.0f);  // pixlzr.rs:162 (BASE_FACTOR, :15), :177-178
+		} else {
+			const uint64_t fac = (uint64_t)(w - 2u) * (uint64_t)(h - 2u) * 4096ull;  // operations.rs:253-254
+			if (fac == 0ull || w < 2u || h < 2u) {
+				v0 = v1 = 0.0f;  // 0/0: the negative default NaN, which parse_value turns into 0 (finish_tile)
+			} else {
+				const double dfac = (double)fac;
+				v0 = parse_value((float)((double)shz / dfac) * k);  // :256-257, pixlzr.rs:199
+				v1 = parse_value((float)((double)svr / dfac) * k);
+			}
+		}
+		// level_count against the thresholds (round(log2f(v)) >= -k), as the single-geometry call decides it
+		uint32_t mx = 0, my = 0;
+#pragma unroll
+		for (int j = 0; j < kMaxLevel; ++j) {
+			mx += v0 < a.thresholds[j] ? 1u : 0u;
+			my += v1 < a.thresholds[j] ? 1u : 0u;
+		}
+		const uint32_t nw = reduced_size(w, mx), nh = reduced_size(h, my);  // operations.rs:150-151
+		const size_t at = (size_t)tid * a.n_tiles + tile_g;
+		a.value[at] = hypot_f32(v0, v1);  // operations.rs:154
+		a.out_w[at] = nw;
+		a.out_h[at] = nh;
+		s_key[tid] = (nw != w ? mx : 0u) | ((nh != h ? my : 0u) << 8);
+	}
+	__syncthreads();  // the keys: the same in every wave from here on
+	if (a.out_px == nullptr) return;
+
+	auto slot_of = [&](uint32_t r) { return a.out_px + ((uint64_t)r * a.n_tiles + tile_g) * (uint64_t)a.slot_bytes; };
+	// ---- 4. the clones (block.rs:279-281), while X still holds the tile's bytes
+	bool shrinks = false;
+	for (uint32_t r = 0; r < n_rungs; ++r) {
+		if (s_key[r] == 0u) varied_store(slot_of(r), s_x, n * (uint32_t)C, tid);
+		else shrinks = true;
+	}
+	if (!shrinks) return;
+	__syncthreads();  // the clones have read X
+	// ---- 5. ResizeAlg::Convolution, default options: U8x4 is alpha-premultiplied first
+	if (C == 4 && !nearest) {
+		uint32_t *p32 = reinterpret_cast<uint32_t *>(s_x);
+		for (uint32_t i = tid; i < n; i += kVariedThreads) p32[i] = premultiply(p32[i]);
+		__syncthreads();
+	}
+	// ---- 6. one resample per distinct pair of levels; X is only read
+	for (uint32_t r = 0; r < n_rungs; ++r) {
+		const uint32_t key = s_key[r];
+		if (key == 0u) continue;
+		bool done = false;
+		for (uint32_t q = 0; q < r; ++q) done = done || s_key[q] == key;
+		if (done) continue;
+		const uint32_t mx = key & 255u, my = key >> 8;
+		const bool need_h = mx != 0u, need_v = my != 0u;
+		const uint32_t nw = need_h ? reduced_size(w, mx) : w, nh = need_v ? reduced_size(h, my) : h;
+		const uint32_t lx = mx < (uint32_t)kMaxLevel ? mx : (uint32_t)kMaxLevel - 1u;
+		const uint32_t ly = my < (uint32_t)kMaxLevel ? my : (uint32_t)kMaxLevel - 1u;
+		const uint8_t *cur = s_x;
+		if (need_h) {
+			const TreeAxisEntry ex = a.dir[w * (uint32_t)kMaxLevel + lx];
+			varied_pass<C>(a, ex, nearest, s_x, (uint32_t)C, w * (uint32_t)C, s_a, (uint32_t)C, nw * (uint32_t)C, h, tid);
+			__syncthreads();
+			cur = s_a;
+		}
+		if (need_v) {
+			const TreeAxisEntry ey = a.dir[h * (uint32_t)kMaxLevel + ly];
+			uint8_t *o = need_h ? s_f : s_a;
+			// one "line" per column of the nw-wide image, samples a row apart
+			varied_pass<C>(a, ey, nearest, cur, nw * (uint32_t)C, (uint32_t)C, o, nw * (uint32_t)C, (uint32_t)C, nw, tid);
+			__syncthreads();
+			cur = o;
+		}
+		if (C == 4 && !nearest) {
+			varied_unpremultiply(reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(cur)), nw * nh, tid);
+			__syncthreads();
+		}
+		for (uint32_t q = r; q < n_rungs; ++q)
+			if (s_key[q] == key) varied_store(slot_of(q), cur, nw * nh * (uint32_t)C, tid);
+		__syncthreads();  // the next pair reuses I and F
 	}
 }
 

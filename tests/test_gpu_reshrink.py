@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 
 from test_gpu_varied_decode import POISON, assert_tiles_equal, poisoned
-from test_reshrink_host import (CASES, DIRECTIONAL, FILTER_PAIRS, LANCZOS3, LIMIT_BLOCK, NEAREST, SHRINK_BY, Case, cached_case, case_id,
-                                full_sizes)
+from test_reshrink_host import (CASES, DIRECTIONAL, FILTER_PAIRS, LANCZOS3, LIMIT_BLOCK, NEAREST, SHRINK_BY, TRIANGLE, Case, cached_case,
+                                case_id, full_sizes)
+from test_reshrink_ladder_host import FACTORS, oracle_rungs
 from test_varied_decode_host import ANY, FULL, HALVED, draw_tiles
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +100,20 @@ def check_case(gpu, case, what, with_chain=True):
     return dev, got
 
 
+def drawn_case(oracle, sizes, tile, c, mode, expand_filter, filt, classes, seed):
+    """images of drawn tiles (random bytes, stored at the sizes their classes say), as a Case without the one-factor expectation"""
+    case = Case.__new__(Case)
+    bw, bh = tile
+    rng = np.random.default_rng(seed)
+    case.family, case.mode, case.bw, case.bh, case.c, case.expand_filter, case.filt, case.factor = "B", mode, bw, bh, c, expand_filter, filt, None
+    case.sizes, case.inputs, case.full = list(sizes), [], []
+    for (w, h), cl in zip(sizes, classes):
+        vals, tw, th, slots, _ = draw_tiles(rng, w, h, bw, bh, c, None if cl is None else np.array(cl))
+        case.inputs.append((vals, tw, th, slots))
+        case.full.append(full_sizes(w, h, bw, bh))
+    return case
+
+
 # ---- parity ---------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("case", CASES, ids=case_id)
@@ -128,6 +143,44 @@ def test_in_place_equals_out_of_place(gpu, mode, c):
     assert status == 0 and (flags == 0).all()
     assert_tiles_equal(together, apart, c, "in place against out of place")
     assert_tiles_equal(together, cat_expected(case.expected), c, "in place against the oracle")
+
+
+# ---- tiny odd blocks ------------------------------------------------------------------------------------------------------
+
+TINY = [((3, 5), 4, (7, 11), SHRINK_BY), ((5, 3), 3, (23, 11), SHRINK_BY), ((5, 3), 3, (23, 11), DIRECTIONAL), ((3, 3), 4, (7, 7), SHRINK_BY)]
+
+
+def check_drawn(gpu, oracle, case, factors, what):
+    """drawn tiles at every factor of the list against the oracle composition; some tile of the batch must be expanded"""
+    fw, fh = case.cat(case.full, 0), case.cat(case.full, 1)
+    tw, th = case.cat(case.inputs, 1), case.cat(case.inputs, 2)
+    assert ((tw < fw) | (th < fh)).any(), f"{what}: every tile is stored at its full size"
+    dev = upload_tiles(case.inputs)
+    for f, exp in zip(factors, oracle_rungs(oracle, case, factors)):
+        got, flags, status = reshrink(gpu, case, dev, factor=f)
+        assert status == 0 and (flags == 0).all(), f"{what} factor {f}: status {status}, flags {flags}"
+        assert_tiles_equal(got, exp, case.c, f"{what} factor {f} against the oracle")
+        valid = got[1].astype(np.int64) * got[2] * case.c
+        beyond = np.arange(got[3].shape[1])[None, :] >= valid[:, None]
+        assert (got[3][beyond] == POISON).all(), f"{what} factor {f}: bytes beyond the stored tiles were written"
+
+
+@pytest.mark.parametrize("tile,c,size,mode", TINY, ids=lambda v: str(v).replace(" ", ""))
+def test_tiny_odd_blocks(gpu, oracle, tile, c, size, mode):
+    """blocks of a few pixels whose rows are no multiple of a dword, noise tiles stored at mixed sizes: the expand reads RGB
+    pixels at every byte alignment, and the planes are smaller than the detector's.  (The 1-px edge tiles of
+    7x11 and 7x7 are for shrink_by only: the directional detector refuses them.)"""
+    for (xf, sf) in [(LANCZOS3, LANCZOS3), (NEAREST, TRIANGLE), (TRIANGLE, NEAREST)]:
+        case = drawn_case(oracle, [size, size], tile, c, mode, xf, sf, [None, None], seed=tile[0] * 100 + tile[1] * 10 + c)
+        check_drawn(gpu, oracle, case, FACTORS[mode], f"{tile} c{c} in {size} mode {mode} filters {xf}/{sf}")
+
+
+def test_slots_of_45_bytes_meet_every_alignment(gpu, oracle):
+    """3x5 RGB: slot t starts at a multiple of 45 bytes, so the expand's loads and the store meet every alignment of a slot"""
+    case = drawn_case(oracle, [(7, 11), (6, 10)], (3, 5), 3, SHRINK_BY, LANCZOS3, LANCZOS3, [None, None], seed=45)
+    T = sum(x[1].size for x in case.inputs)
+    assert {(t * 45) % 4 for t in range(T)} == {0, 1, 2, 3}
+    check_drawn(gpu, oracle, case, FACTORS[SHRINK_BY], "45-byte slots")
 
 
 # ---- the tile loop --------------------------------------------------------------------------------------------------------

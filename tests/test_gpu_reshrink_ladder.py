@@ -8,11 +8,11 @@ they must exercise are those of tests/test_reshrink_ladder_host.py, which holds 
 import numpy as np
 import pytest
 
-from test_gpu_reshrink import SIZE_POISON, VAL_POISON, assert_still_poisoned, reshrink, to_host, upload_tiles
+from test_gpu_reshrink import SIZE_POISON, TINY, VAL_POISON, assert_still_poisoned, drawn_case, reshrink, to_host, upload_tiles
 from test_gpu_varied_decode import POISON, assert_tiles_equal, poisoned
-from test_reshrink_host import CASES, DIRECTIONAL, FILTER_PAIRS, LANCZOS3, NEAREST, SHRINK_BY, TRIANGLE, Case, cached_case, case_id, full_sizes
+from test_reshrink_host import CASES, DIRECTIONAL, FILTER_PAIRS, LANCZOS3, NEAREST, SHRINK_BY, TRIANGLE, Case, cached_case, case_id
 from test_reshrink_ladder_host import FACTORS, cached_ladder, oracle_rungs
-from test_varied_decode_host import ANY, FULL, HALVED, draw_tiles
+from test_varied_decode_host import ANY, FULL, HALVED
 
 pytestmark = pytest.mark.gpu
 
@@ -76,20 +76,6 @@ def check_ladder(gpu, case, factors, expected, what, against_single=True):
     return rungs
 
 
-def drawn_case(oracle, sizes, tile, c, mode, expand_filter, filt, classes, seed):
-    """images of drawn tiles (random bytes, stored at the sizes their classes say), as a Case without the one-factor expectation"""
-    case = Case.__new__(Case)
-    bw, bh = tile
-    rng = np.random.default_rng(seed)
-    case.family, case.mode, case.bw, case.bh, case.c, case.expand_filter, case.filt, case.factor = "B", mode, bw, bh, c, expand_filter, filt, None
-    case.sizes, case.inputs, case.full = list(sizes), [], []
-    for (w, h), cl in zip(sizes, classes):
-        vals, tw, th, slots, _ = draw_tiles(rng, w, h, bw, bh, c, None if cl is None else np.array(cl))
-        case.inputs.append((vals, tw, th, slots))
-        case.full.append(full_sizes(w, h, bw, bh))
-    return case
-
-
 def mixed_rungs(case, expected):
     """tiles that are stored reduced, and tiles with a clone rung beside a reduced one, among the expected rungs"""
     fw, fh = case.cat(case.full, 0), case.cat(case.full, 1)
@@ -110,9 +96,6 @@ def test_every_rung_equals_the_single_call_and_the_oracle(gpu, case):
 
 
 # ---- 2. tiny odd blocks ---------------------------------------------------------------------------------------------------
-
-TINY = [((3, 5), 4, (7, 11), SHRINK_BY), ((5, 3), 3, (23, 11), SHRINK_BY), ((5, 3), 3, (23, 11), DIRECTIONAL), ((3, 3), 4, (7, 7), SHRINK_BY)]
-
 
 @pytest.mark.parametrize("tile,c,size,mode", TINY, ids=lambda v: str(v).replace(" ", ""))
 def test_tiny_odd_blocks(gpu, oracle, tile, c, size, mode):

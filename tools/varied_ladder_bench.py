@@ -98,7 +98,8 @@ def main():
                             times[f].append(e0.elapsed_time(e1))
                 tl, tb = statistics.median(times[run_ladder]), statistics.median(times[run_baseline])
                 row = dict(tile=f"{bw}x{bh}", mode=mode, K=K, tiles=T, ladder_ms=round(tl, 3), k_varied_calls_ms=round(tb, 3),
-                           speedup=round(tb / tl, 3), bit_exact=True)
+                           speedup=round(tb / tl, 3), bit_exact=True, ladder_samples=[round(t, 3) for t in times[run_ladder]],
+                           k_varied_calls_samples=[round(t, 3) for t in times[run_baseline]])
                 rows.append(row)
                 print(json.dumps(row), flush=True)
             del out
