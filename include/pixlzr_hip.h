@@ -624,6 +624,82 @@ int pxz_rate_distortion_varied_images(pxz_handle *h, const uint8_t *const *pixel
                                       uint32_t filter_down, uint32_t filter_up, const float *factors, uint32_t n_factors,
                                       uint64_t *file_bytes, uint64_t *sse);
 
+/* ---- fit to a budget: each image at the factor its target picks ---------------------------------------------- */
+
+/* What a caller asks of the table above: "this file in at most N bytes" or "with at least Q dB".  The reference has no line
+ * for it either (whole-folder.rs:83-113 writes every factor and leaves the choice to a person).  Per image, over its rungs
+ * r = 0 .. n_factors-1, with bytes[r] the length of its file at factors[r] and sse[r] the sum over its channels of the squared
+ * error (uint64 integers throughout):
+ *   PXZ_FIT_BYTES  target = the largest file length allowed.  Eligible: bytes[r] <= target.  Among the eligible rungs the
+ *                  smallest sse, ties by the smaller bytes, then the lower r.  None eligible: the smallest bytes, ties by the
+ *                  smaller sse, then the lower r, and bit 0 of the image's fit flags is set.
+ *   PXZ_FIT_SSE    target = the largest summed squared error allowed (a PSNR of q dB over n samples is
+ *                  sse <= 255^2 n / 10^(q/10)).  Eligible: sse[r] <= target.  Among the eligible rungs the smallest bytes,
+ *                  ties by the smaller sse, then the lower r.  None eligible: the smallest sse, ties by the smaller bytes,
+ *                  then the lower r, and bit 0 is set.
+ * Ties are ordinary: neighbouring factors often give every tile the same pair of levels, hence the same length and error. */
+typedef enum { PXZ_FIT_BYTES = 0, PXZ_FIT_SSE = 1 } pxz_fit;
+
+/* The rule on the host (no handle, no GPU, like pxz_grid and pxz_varied_layout), over a table laid out as
+ * pxz_rate_distortion_varied_images returns it: file_bytes[r*n_images + i], sse[(r*n_images + i)*channels + c]; targets,
+ * choice and fit_flags have n_images entries.  choice[i] is the rung of image i, fit_flags[i] 0 or 1 (bit 0: no rung met the
+ * target).  PXZ_ERR_INVALID_ARG for a null pointer, n_images 0, n_factors 0 or above PXZ_VARIED_LADDER_MAX_RUNGS, channels
+ * not 3|4 or an unknown criterion; on an error nothing is written.  The device call below runs the same text of the rule. */
+int pxz_fit_select(uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion, const uint64_t *targets,
+                   const uint64_t *file_bytes, const uint64_t *sse, uint32_t *choice, uint32_t *fit_flags);
+
+/* The rule on the device, over what pxz_encode_varied_frames_device (d_file_offsets: n_factors*n_images + 1 offsets; file
+ * r*n_images + i is [k], [k+1]) and pxz_distortion_varied_frames_device (d_image_sse: n_factors*n_images*channels sums) leave
+ * for the descriptors repeated n_factors times -- a varied ladder's result.  targets is a HOST array of n_images entries; it
+ * travels with the call through a handle buffer that pxz_trim gives back.  d_choice and d_fit_flags (n_images dwords each)
+ * equal pxz_fit_select on the downloaded table.  One launch; asynchronous on the handle's stream; none of the state the
+ * single-geometry fast paths keep in the handle is touched.  Validation as pxz_fit_select, and PXZ_ERR_INVALID_ARG for a null
+ * handle or device pointer; on an error nothing is written. */
+int pxz_fit_varied_ladder_device(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion,
+                                 const uint64_t *targets, const uint64_t *d_file_offsets, const uint64_t *d_image_sse,
+                                 uint32_t *d_choice, uint32_t *d_fit_flags);
+
+/* One rung per image out of a varied ladder's result, as an ordinary varied batch: a batch in which every image has its own
+ * factor.  The inputs are rung-major as pxz_shrink_varied_ladder_frames_device writes them (n_factors rungs); the outputs are
+ * in the pxz_varied_layout order of the n_images images.  With tile_offsets and tiles = tile_offsets[n_images]: output tile
+ * tile_offsets[i] + t is input tile d_choice[i]*tiles + tile_offsets[i] + t -- the value's bits, both sizes, and exactly the
+ * out_w*out_h*channels valid bytes of the slot (never more than a slot); the rest of the output slot is not written.
+ * d_out_pixels may be NULL: values and sizes only (d_slots is not read then).  Only block_w and block_h of params are read.
+ * A choice of n_factors or more is read as n_factors-1, so nothing is read out of bounds, and sets bit 1 of
+ * d_image_flags[i] (n_images dwords, may be NULL); the flags are otherwise written as 0.  One launch, whatever n_images and
+ * n_factors are; slots of block_w*block_h*channels bytes, addressed with 64-bit offsets.  Outputs must not overlap inputs
+ * (not checked).  pxz_encode_varied_frames_device takes the result as it is.  Asynchronous on the handle's stream; none of the
+ * state the single-geometry fast paths keep in the handle is touched.
+ * Validation runs on the host before anything is launched; on an error nothing is written.  Codes and "image i" texts are
+ * pxz_shrink_varied_ladder_frames_device's (no factors are passed, and no mode: no tile is too small).  No tile is staged, so
+ * there is no LDS limit on the block; PXZ_ERR_UNSUPPORTED for a slot above 2^32-1 bytes or n_factors * tiles above 2^32-1. */
+int pxz_gather_varied_rungs_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                   const pxz_params *params, uint32_t n_factors, const uint32_t *d_choice,
+                                   const float *d_block_value, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                   const uint8_t *d_slots, float *d_out_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                   uint8_t *d_out_pixels, uint32_t *d_image_flags);
+
+/* Host images in, one .pixlzr file per image out, each at the factor the rule picks for it; synchronous.  pixels[i] is image
+ * i (descs[i].offset_bytes is ignored); factors (1 <= n_factors <= PXZ_VARIED_LADDER_MAX_RUNGS, each finite, any order) are
+ * the candidates, targets[i] the budget of image i under `criterion`.  Composition only: upload,
+ * pxz_shrink_varied_ladder_frames_device, pxz_encode_varied_frames_device over the n_factors*n_images rung images with no
+ * room (for its offsets), pxz_distortion_varied_frames_device over the same (filter_up), pxz_fit_varied_ladder_device,
+ * pxz_gather_varied_rungs_device, pxz_encode_varied_frames_device over the n_images gathered images, one download.  Nothing
+ * is shrunk or uploaded twice, and nothing comes back to the host before the files and their table.
+ * File i is, byte for byte, what pxz_encode_varied_images gives for image i alone at factors[choice[i]] with filter_down and
+ * filter_byte.  The output follows pxz_encode_varied_images' protocol: file_offsets (n_images + 1), choice and fit_flags
+ * (n_images each; see pxz_fit_select) and, where given, table_bytes (n_factors*n_images) and table_sse
+ * (n_factors*n_images*channels) -- what pxz_rate_distortion_varied_images returns -- are always written; the files go to out
+ * when out_capacity >= file_offsets[n_images], else the call returns PXZ_ERR_BUFFER_TOO_SMALL and writes nothing to out (out
+ * may be NULL for that size query).  Errors and limits are those of the calls it composes (block_w*block_h*channels <= 65536
+ * bytes among them); on any other error nothing is written. */
+int pxz_encode_varied_images_fit(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                 uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                 uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                 const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity,
+                                 uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes /* may be NULL */,
+                                 uint64_t *table_sse /* may be NULL */);
+
 /* ---- legacy image -> image filter ------------------------ */
 
 /* process_custom (src/process/mod.rs:71-102) with the closures of process() (:107-121: |x - avg| and the

@@ -28,10 +28,12 @@ EXPORTED_SYMBOLS = [
     "pxz_window_layout", "pxz_decode_windows_device", "pxz_expand_windows_device", "pxz_decode_windows_files",
     "pxz_reshrink_varied_frames_device", "pxz_reshrink_lds_bytes", "pxz_transcode_varied_files",
     "pxz_reshrink_varied_ladder_frames_device", "pxz_reshrink_ladder_lds_bytes", "pxz_transcode_varied_ladder_files",
+    "pxz_fit_select", "pxz_fit_varied_ladder_device", "pxz_gather_varied_rungs_device", "pxz_encode_varied_images_fit",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
 VARIED_LADDER_MAX_RUNGS = 32  # PXZ_VARIED_LADDER_MAX_RUNGS
+FIT_BYTES, FIT_SSE = 0, 1  # pxz_fit
 
 STATUS = {0: "PXZ_OK", -1: "PXZ_ERR_INVALID_ARG", -2: "PXZ_ERR_NO_DEVICE", -3: "PXZ_ERR_HIP",
           -4: "PXZ_ERR_TILE_TOO_SMALL", -5: "PXZ_ERR_UNSUPPORTED", -6: "PXZ_ERR_NOMEM",
@@ -200,6 +202,15 @@ def load_library():
         L.pxz_reshrink_ladder_lds_bytes.argtypes = [u32] * 5 + [C.POINTER(u32)]
         L.pxz_transcode_varied_ladder_files.restype = C.c_int
         L.pxz_transcode_varied_ladder_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, vp, u32, u32, vp, C.c_uint64, vp]
+    if hasattr(L, "pxz_fit_select"):  # (a build of an earlier commit named by PXZ_LIB lacks the fit)
+        L.pxz_fit_select.restype = C.c_int
+        L.pxz_fit_select.argtypes = [u32] * 4 + [vp] * 5
+        L.pxz_fit_varied_ladder_device.restype = C.c_int
+        L.pxz_fit_varied_ladder_device.argtypes = [vp] + [u32] * 4 + [vp] * 5
+        L.pxz_gather_varied_rungs_device.restype = C.c_int
+        L.pxz_gather_varied_rungs_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 10
+        L.pxz_encode_varied_images_fit.restype = C.c_int
+        L.pxz_encode_varied_images_fit.argtypes = [vp, vp, vp] + [u32] * 7 + [vp, u32, u32, vp, u32, vp, C.c_uint64] + [vp] * 5
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -346,6 +357,42 @@ def psnr(sse, n_samples):
     with np.errstate(divide="ignore"):
         out = 10.0 * np.log10(255.0 * 255.0 * np.asarray(n_samples, np.float64) / sse)
     return float(out) if out.ndim == 0 else out
+
+
+def sse_for_psnr(db, n_samples):
+    """The inverse of psnr, rounded down: the largest summed squared error (a Python int, at most 2^64-1) over n_samples
+    8-bit samples that still has a PSNR of at least db -- the target of FIT_SSE for "at least db dB":
+    psnr(sse_for_psnr(q, n), n) >= q > psnr(sse_for_psnr(q, n) + 1, n)."""
+    top = 2 ** 64 - 1
+    est = 255.0 * 255.0 * float(n_samples) / 10.0 ** (float(db) / 10.0)
+    s = top if est >= float(top) else max(int(est), 0)
+    for _ in range(8):  # (the estimate is an ulp or two off at the most; psnr itself has the last word)
+        if s > 0 and psnr(s, n_samples) < db:
+            s -= 1
+        elif s < top and psnr(s + 1, n_samples) >= db:
+            s += 1
+        else:
+            break
+    return s
+
+
+def fit_select(file_bytes, sse, criterion, targets, n_images=None, n_factors=None, channels=None, out=None):
+    """pxz_fit_select: the rung of every image under its target, on the host.  file_bytes uint64[K, n] and sse uint64[K, n, C]
+    as rate_distortion_varied_images returns them, targets n integers (a budget in bytes under FIT_BYTES, a summed squared
+    error under FIT_SSE) -> (choice uint32[n], fit_flags uint32[n]; bit 0: no rung met the target).  No GPU.  n_images,
+    n_factors and channels override what the shapes say, None among the arrays passes a null pointer, and out = (choice,
+    fit_flags) is written in place (all for the error cases)."""
+    fb = None if file_bytes is None else np.ascontiguousarray(file_bytes, np.uint64)
+    ss = None if sse is None else np.ascontiguousarray(sse, np.uint64)
+    tg = None if targets is None else np.array([int(t) for t in targets], np.uint64)
+    K = n_factors if n_factors is not None else fb.shape[0]
+    n = n_images if n_images is not None else fb.shape[1]
+    ch = channels if channels is not None else ss.shape[2]
+    choice, flags = out if out is not None else (np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32))
+    rc = load_library().pxz_fit_select(n, K, ch, criterion, _p(tg), _p(fb), _p(ss), _p(choice), _p(flags))
+    if rc != 0:
+        raise PxzError(rc)
+    return choice[:n], flags[:n]
 
 
 def axis_table(in_size, out_size, filt):
@@ -1052,6 +1099,87 @@ class Handle:
             self._h, C.cast(ptrs, C.c_void_p), C.cast(image_descs(geoms), C.c_void_p), n, ch, bw, bh, mode, filter_down, filter_up,
             _p(fac) if K else None, K, _p(file_bytes), _p(sse)))
         return file_bytes[:K, :n], sse[:K, :n]
+
+    # ---- fit to a budget ----
+    def fit_varied_ladder_device(self, file_offsets, image_sse, criterion, targets, n_images=None, n_factors=None, channels=None,
+                                 out=None):
+        """pxz_fit_varied_ladder_device: fit_select on the device.  file_offsets int64[K*n + 1] (encode_varied_frames_device
+        over the images repeated K times) and image_sse int64[K, n, C] (distortion_varied_frames_device over the same) are
+        CUDA tensors, targets n host integers -> (choice int32[n], fit_flags int32[n]) CUDA tensors, or out = such a pair.
+        n_images, n_factors and channels override what image_sse's shape says; None for targets or a tensor passes a null
+        pointer."""
+        import torch
+        K = n_factors if n_factors is not None else image_sse.shape[0]
+        n = n_images if n_images is not None else image_sse.shape[1]
+        ch = channels if channels is not None else image_sse.shape[2]
+        tg = None if targets is None else np.array([int(t) for t in targets], np.uint64)
+        if out is None:
+            dev = torch.device("cuda", self.device_id)
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        choice, flags = out
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_fit_varied_ladder_device(self._h, n, K, ch, criterion, _p(tg), ptr(file_offsets), ptr(image_sse),
+                                                         ptr(choice), ptr(flags)))
+        return choice, flags
+
+    def gather_varied_rungs_device(self, sizes, channels, bw, bh, n_factors, choice, vals, ow, oh, slots, out=None, image_flags=None,
+                                   want_pixels=True):
+        """pxz_gather_varied_rungs_device: sizes = [(width, height), ...] of the images (or full (width, height, pitch_bytes,
+        offset_bytes[, reserved]) tuples), choice int32[n] CUDA, and the rung-major tensors of
+        shrink_varied_ladder_frames_device (values[K,T], w[K,T], h[K,T], slots[K,T,bw*bh*C]) -> (values[T], w[T], h[T],
+        slots[T, bw*bh*C] | None) in the varied layout of the images: tile t of image i from rung choice[i].  out: such a
+        4-tuple; image_flags (int32[n] CUDA, optional) gets 2 for an image whose choice was n_factors or more, else 0."""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        if out is None:
+            T = int(varied_layout(geoms, bw, bh)[-1])
+            dev = vals.device
+            out = (torch.empty(T, dtype=torch.float32, device=dev), torch.empty(T, dtype=torch.int32, device=dev),
+                   torch.empty(T, dtype=torch.int32, device=dev),
+                   torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None)
+        o_vals, o_w, o_h, o_slots = out
+        pd = Params(bw, bh, 0, 0, 0.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_gather_varied_rungs_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), n_factors, ptr(choice), ptr(vals),
+            ptr(ow), ptr(oh), ptr(slots), ptr(o_vals), ptr(o_w), ptr(o_h), ptr(o_slots), ptr(image_flags)))
+        return o_vals, o_w, o_h, o_slots
+
+    def encode_varied_images_fit(self, imgs, bw, bh, mode, filter_down, filter_up, factors, criterion, targets, filter_byte=0,
+                                 want_table=False):
+        """pxz_encode_varied_images_fit: host images (numpy uint8 [H, W, C], one channel count) -> one .pixlzr file per image,
+        each at the factor of `factors` (1..32) that fit_select picks under targets[i] (n host integers).  Returns (files: a
+        list of bytes, choice uint32[n], fit_flags uint32[n]) and, with want_table, (file_bytes uint64[K,n], sse
+        uint64[K,n,C]) as rate_distortion_varied_images returns them."""
+        imgs = [np.ascontiguousarray(i) if i.strides[1] != i.shape[2] or i.strides[2] != 1 else i for i in imgs]
+        n = len(imgs)
+        ch = imgs[0].shape[2] if n else 4
+        geoms = [(i.shape[1], i.shape[0], i.strides[0], 0) for i in imgs]
+        ptrs = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in imgs])
+        descs = image_descs(geoms)
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        tg = np.array([int(t) for t in targets], np.uint64)
+        offs = np.zeros(n + 1, np.uint64)
+        choice, flags = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        table_bytes = np.zeros((max(K, 1), max(n, 1)), np.uint64) if want_table else None
+        table_sse = np.zeros((max(K, 1), max(n, 1), ch), np.uint64) if want_table else None
+        buf = np.empty(sum(i.size for i in imgs) * 5 // 4 + 4096 * max(n, 1), np.uint8)
+        for attempt in range(2):  # (a second call only when the first guess at the files' size was short)
+            rc = self._L.pxz_encode_varied_images_fit(
+                self._h, C.cast(ptrs, C.c_void_p), C.cast(descs, C.c_void_p), n, ch, bw, bh, mode, filter_down, filter_up,
+                _p(fac) if K else None, K, criterion, _p(tg) if tg.size else None, filter_byte, _p(buf), buf.size, _p(offs), _p(choice),
+                _p(flags), _p(table_bytes), _p(table_sse))
+            if rc != -7 or attempt == 1:
+                break
+            buf = np.empty(int(offs[-1]), np.uint8)
+        self._check(rc)
+        files = [buf[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+        if want_table:
+            return files, choice[:n], flags[:n], table_bytes[:K, :n], table_sse[:K, :n]
+        return files, choice[:n], flags[:n]
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

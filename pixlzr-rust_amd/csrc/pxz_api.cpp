@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/pixlzr_hip.h"
+#include "pxz_fit.h"
 #include "pxz_handle.h"
 #include "pxz_internal.h"
 #include "pxz_launch.h"
@@ -115,6 +116,9 @@ struct HandleScratch {
 	PinnedStaging window_table;       //   and its pinned staging
 	DeviceBuffer window_host;         // pxz_decode_windows_files: the files, the covered tiles, the crops and the flags
 	DeviceBuffer transcode_files, transcode_tiles;  // pxz_transcode_varied_files: the files that come in; their tiles when the block size changes
+	DeviceBuffer fit;                 // pxz_fit_varied_ladder_device: the images' targets
+	PinnedStaging fit_targets;        //   and their pinned staging
+	DeviceBuffer fit_tiles;           // pxz_encode_varied_images_fit: the chosen rungs' tiles
 	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
 	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
 	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
@@ -3236,6 +3240,209 @@ int pxz_rate_distortion_varied_images(pxz_handle *h, const uint8_t *const *pixel
 	PXZ_HIP(h, hipStreamSynchronize(h->stream));
 	for (uint64_t k = 0; k < n_sets; ++k) file_bytes[k] = got[k + 1u] - got[k];
 	std::memcpy(sse, got.data() + n_sets + 1u, (size_t)n_sets * channels * 8u);
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- fit to a budget: one rung per image, chosen and gathered on the device (pxz_fit.h, pxz_fit.hip) ----------------------
+namespace {
+
+// what pxz_fit_select and pxz_fit_varied_ladder_device check of their sizes (h may be null: the host form has no handle)
+int fit_check(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion)
+{
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (n_factors == 0 || n_factors > PXZ_VARIED_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_VARIED_LADDER_MAX_RUNGS, n_factors);
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
+		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_fit_select(uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion, const uint64_t *targets,
+                   const uint64_t *file_bytes, const uint64_t *sse, uint32_t *choice, uint32_t *fit_flags)
+{
+	if (!targets || !file_bytes || !sse || !choice || !fit_flags) return PXZ_ERR_INVALID_ARG;
+	const int rc = fit_check(nullptr, n_images, n_factors, channels, criterion);
+	if (rc != PXZ_OK) return rc;
+	const uint64_t n = n_images;
+	for (uint64_t i = 0; i < n; ++i) {
+		const pxz::FitPick p = pxz::fit_pick(
+			n_factors, criterion, targets[i], [&](uint32_t r) { return file_bytes[r * n + i]; },
+			[&](uint32_t r) {
+				uint64_t sum = 0;
+				for (uint32_t c = 0; c < channels; ++c) sum += sse[(r * n + i) * channels + c];
+				return sum;
+			});
+		choice[i] = p.choice;
+		fit_flags[i] = p.flags;
+	}
+	return PXZ_OK;
+}
+
+int pxz_fit_varied_ladder_device(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion,
+                                 const uint64_t *targets, const uint64_t *d_file_offsets, const uint64_t *d_image_sse,
+                                 uint32_t *d_choice, uint32_t *d_fit_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!d_file_offsets || !d_image_sse || !d_choice || !d_fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	int rc = fit_check(h, n_images, n_factors, channels, criterion);
+	if (rc != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const size_t bytes = (size_t)n_images * 8u;
+	if ((rc = ensure(h, h->fit, bytes)) != PXZ_OK) return rc;
+	PXZ_HIP(h, h->fit_targets.send(targets, bytes, h->fit.ptr, h->stream));
+	pxz::FitArgs a{};
+	a.n_images = n_images;
+	a.n_factors = n_factors;
+	a.channels = channels;
+	a.criterion = criterion;
+	a.targets = (const unsigned long long *)h->fit.ptr;
+	a.file_offsets = (const unsigned long long *)d_file_offsets;
+	a.image_sse = (const unsigned long long *)d_image_sse;
+	a.choice = d_choice;
+	a.flags = d_fit_flags;
+	PXZ_HIP(h, pxz::launch_fit_select(a, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_gather_varied_rungs_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                   const pxz_params *params, uint32_t n_factors, const uint32_t *d_choice, const float *d_block_value,
+                                   const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_out_value,
+                                   uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (n_factors == 0 || n_factors > PXZ_VARIED_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_VARIED_LADDER_MAX_RUNGS, n_factors);
+	if (!d_choice || !d_block_value || !d_tile_w || !d_tile_h || !d_out_value || !d_out_w || !d_out_h || (d_out_pixels && !d_slots))
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	std::vector<pxz::VariedImage> images;
+	// (mode 0: no detector runs here, so no tile is too small for one)
+	int rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, 0, &images, nullptr, nullptr);
+	if (rc != PXZ_OK) return rc;
+	const uint64_t slot = (uint64_t)params->block_w * params->block_h * channels;
+	if (slot > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a slot of %ux%u px takes more than 2^32-1 bytes", params->block_w, params->block_h);
+	if ((uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::GatherArgs a{};
+	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
+	a.n_images = n_images;
+	a.n_tiles = varied_n_tiles(images);
+	a.n_factors = n_factors;
+	a.slot_bytes = (uint32_t)slot;
+	a.choice = d_choice;
+	a.value = (const uint32_t *)d_block_value;
+	a.w = d_tile_w;
+	a.h = d_tile_h;
+	a.slots = d_slots;
+	a.out_value = (uint32_t *)d_out_value;
+	a.out_w = d_out_w;
+	a.out_h = d_out_h;
+	a.out_slots = d_out_pixels;
+	a.image_flags = d_image_flags;
+	PXZ_HIP(h, pxz::launch_gather_rungs(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_encode_varied_images_fit(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                 uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                 uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                 const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity,
+                                 uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes, uint64_t *table_sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!pixels || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
+	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
+	if ((rc = check_params(h, &up)) != PXZ_OK) return rc;
+	if ((rc = varied_check_params(h, channels, &p)) != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, block_w, block_h, channels, mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	if ((rc = fit_check(h, n_images, n_factors, channels, criterion)) != PXZ_OK) return rc;
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
+	const uint32_t n_tiles = varied_n_tiles(images);
+	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * n_tiles;
+	if (tiles > 0xffffffffull || n_sets > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	std::vector<pxz_image_desc> dev;
+	uint64_t raw = 0;
+	if ((rc = varied_send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
+	// every rung's tiles (varied_out) and the chosen rungs' (fit_tiles); and in one block, so that one copy brings it back: the
+	// table (the rung files' offsets, the sums), the chosen files' offsets, the choices and the flags -- with the room the first
+	// writer is given behind it (none: only its offsets are wanted)
+	auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+	const uint64_t slot = (uint64_t)block_w * block_h * channels;
+	const uint64_t meta_all = up256(tiles * 12u), meta_fit = up256((uint64_t)n_tiles * 12u);
+	const size_t n_table = (size_t)n_sets + 1u + (size_t)n_sets * channels;
+	const size_t n_down = n_table + (size_t)n_images + 1u + (size_t)n_images;  // u64s (a choice and a flag: one u64 together)
+	if ((rc = ensure(h, h->varied_out, meta_all + tiles * slot)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->fit_tiles, meta_fit + (uint64_t)n_tiles * slot)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->rd, n_down * 8u + 256u)) != PXZ_OK) return rc;
+	const uint8_t *d_in = (const uint8_t *)h->varied_in.ptr;
+	uint8_t *d_all = (uint8_t *)h->varied_out.ptr, *d_fit = (uint8_t *)h->fit_tiles.ptr;
+	const TileMeta all = carve_tile_meta(d_all, (uint32_t)tiles), fit = carve_tile_meta(d_fit, n_tiles);
+	uint64_t *d_rung_offs = (uint64_t *)h->rd.ptr, *d_sse = d_rung_offs + n_sets + 1u, *d_offs = d_rung_offs + n_table;
+	uint32_t *d_choice = (uint32_t *)(d_offs + n_images + 1u), *d_flags = d_choice + n_images;
+	// 2. the ladder; 3. the writer over the rung images, for its offsets; 4. their distortion
+	if ((rc = pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, channels, &p, factors, n_factors, d_in, all.value, all.w, all.h,
+	                                                 d_all + meta_all)) != PXZ_OK)
+		return rc;
+	std::vector<pxz_image_desc> rungs;
+	rungs.reserve((size_t)n_sets);
+	for (uint32_t r = 0; r < n_factors; ++r) rungs.insert(rungs.end(), dev.begin(), dev.end());
+	if ((rc = pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &p, 0, all.value, all.w, all.h, d_all + meta_all,
+	                                          (uint8_t *)(d_rung_offs + n_down), 0, d_rung_offs)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &up, d_in, all.w, all.h, d_all + meta_all, nullptr,
+	                                              d_sse, nullptr)) != PXZ_OK)
+		return rc;
+	// 5. one rung per image; 6. its tiles as a varied batch of the images themselves
+	if ((rc = pxz_fit_varied_ladder_device(h, n_images, n_factors, channels, criterion, targets, d_rung_offs, d_sse, d_choice, d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_gather_varied_rungs_device(h, dev.data(), n_images, channels, &p, n_factors, d_choice, all.value, all.w, all.h, d_all + meta_all,
+	                                         fit.value, fit.w, fit.h, d_fit + meta_fit, nullptr)) != PXZ_OK)
+		return rc;
+	// 7. the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
+	std::vector<uint64_t> got(n_down);
+	uint64_t cap = raw + raw / 4u + 64ull * n_tiles + 4096ull * n_images;
+	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
+	for (int pass = 0; pass < 2; ++pass) {
+		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
+		if ((rc = pxz_encode_varied_frames_device(h, dev.data(), n_images, channels, &p, filter_byte, fit.value, fit.w, fit.h, d_fit + meta_fit,
+		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
+			return rc;
+		if (pass == 0) PXZ_HIP(h, hipMemcpyAsync(got.data(), d_rung_offs, n_down * 8u, hipMemcpyDeviceToHost, h->stream));
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		if (got[n_table + n_images] <= cap) break;
+		cap = got[n_table + n_images];
+	}
+	if (table_bytes)
+		for (uint64_t k = 0; k < n_sets; ++k) table_bytes[k] = got[k + 1u] - got[k];
+	if (table_sse) std::memcpy(table_sse, got.data() + n_sets + 1u, (size_t)n_sets * channels * 8u);
+	std::memcpy(file_offsets, got.data() + n_table, ((size_t)n_images + 1u) * 8u);
+	const uint32_t *picked = reinterpret_cast<const uint32_t *>(got.data() + n_table + n_images + 1u);
+	std::memcpy(choice, picked, (size_t)n_images * 4u);
+	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
+	const uint64_t total = file_offsets[n_images];
+	if (!out || out_capacity < total)
+		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
+		            (unsigned long long)out_capacity);
+	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
 	return PXZ_OK;
 }
 

@@ -579,6 +579,31 @@ struct DistortionArgs {
 	                                  //   image's valid tiles, added with atomics (zeroed before the launch)
 };
 
+// Fit to a budget (pxz_fit_varied_ladder_device, pxz_fit.hip): one rung per image out of what the writer and the distortion
+// call left for the descriptors repeated n_factors times.  The rule is fit_pick's (pxz_fit.h).
+struct FitArgs {
+	uint32_t n_images, n_factors, channels, criterion;
+	const unsigned long long *targets;       // per image (handle scratch)
+	const unsigned long long *file_offsets;  // n_factors * n_images + 1: file r * n_images + i is [k], [k + 1])
+	const unsigned long long *image_sse;     // index (r * n_images + i) * channels + c
+	uint32_t *choice, *flags;                // per image: the rung, and bit 0 when no rung met the target
+};
+
+// The chosen rungs' tiles as an ordinary varied batch (pxz_gather_varied_rungs_device, pxz_fit.hip): output tile t of image i
+// is input tile choice[i] * n_tiles + t (a choice of n_factors or more: the last rung, and bit 1 of the image's flag).
+struct GatherArgs {
+	const VariedImage *images;
+	uint32_t n_images, n_tiles, n_factors;
+	uint32_t slot_bytes;
+	const uint32_t *choice;
+	const uint32_t *value;                   // rung-major inputs (the values as their bits)
+	const uint32_t *w, *h;
+	const uint8_t *slots;
+	uint32_t *out_value, *out_w, *out_h;     // the varied layout of the n_images images
+	uint8_t *out_slots;                      // null: values and sizes only
+	uint32_t *image_flags;                   // per image 0 or 2, or null
+};
+
 // Pixel windows of files (pxz_decode_windows_device, pxz_expand_windows_device): one entry per window of the call.  A window
 // covers tile columns [c0, c0 + ccols) and tile rows [r0, r0 + crows) of its image; its covered tiles are numbered row-major
 // inside that grid from tile0 on, its covered tile rows from row0 on (pxz_window_layout).  The entry carries its image's

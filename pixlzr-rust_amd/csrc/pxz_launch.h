@@ -47,6 +47,9 @@ hipError_t launch_reshrink_ladder(const ReshrinkLadderArgs &a, uint32_t channels
 // count) for blocks of bw x bh whose staged windows take wdw dwords, from the layout function the kernels and their launches
 // use (what the host holds against kLdsPerCu before it launches); 0xffffffff: a plane of bw * bh dwords above 64 KB
 uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw);
+// fit to a budget (pxz_fit.hip): one rung per image, and the chosen rungs' tiles as a varied batch; one launch each
+hipError_t launch_fit_select(const FitArgs &a, hipStream_t stream);
+hipError_t launch_gather_rungs(const GatherArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);
