@@ -476,7 +476,7 @@ int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t c
  * pxz_transcode_varied_files gives for it at that factor.  With out == NULL or out_capacity below the last offset the call
  * returns PXZ_ERR_BUFFER_TOO_SMALL with the offsets exact and nothing written to out: that size query is the rate table -- file
  * length per file and factor, no file kept -- as pxz_rate_distortion_varied_images gives its lengths.  There is no distortion
- * column: a squared error needs the rebuilt image, and not having it is the point of this path.
+ * column here; pxz_rate_distortion_varied_files adds it, measured against what each file decodes to, still without the image.
  * Same block size: the varied reader into rung 0 of the handle's tile scratch, the re-shrink ladder in place, the varied writer
  * over the descriptors repeated n_factors times.  Another block size: reader, pxz_expand_varied_frames_device,
  * pxz_shrink_varied_ladder_frames_device, writer.  All or nothing as pxz_transcode_varied_files: a malformed file or a flagged
@@ -699,6 +699,78 @@ int pxz_encode_varied_images_fit(pxz_handle *h, const uint8_t *const *pixels, co
                                  const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity,
                                  uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes /* may be NULL */,
                                  uint64_t *table_sse /* may be NULL */);
+
+/* ---- fit a .pixlzr archive to a budget: the error of a re-shrunk tile without the image ----------------------- */
+
+/* The rule: the error of rung r of a file is measured against what the file decodes to NOW, not against an original nobody
+ * has.  For an unchanged block size tile t of the decoded image is exactly the expansion of stored tile t, so the error needs
+ * two tile-sized images in LDS and nothing of image size in device memory.
+ * For every tile of the flat tile space (pxz_varied_layout order of descs; of a descriptor only width, height and reserved are
+ * read) and every one of n_sets stored versions of it, per channel the sum over the tile's full pixels of
+ *   (expand(reference stored tile, expand_filter) - expand(set's stored tile, params->filter))^2,
+ * both being what pxz_expand_varied_frames_device writes for that stored tile with that filter: the result equals
+ * pxz_expand_varied_frames_device of the reference (expand_filter) into a packed image followed by
+ * pxz_distortion_varied_frames_device of each set against it (params->filter), bit for bit, and that image is never made.
+ * d_ref_w, d_ref_h, d_ref_slots: the archive's tiles (tiles entries, slots of block_w*block_h*channels bytes) as
+ * pxz_decode_varied_frames_device leaves them.  d_tile_w, d_tile_h, d_slots: n_sets*tiles entries, set-major -- index
+ * s*tiles + t, exactly what pxz_reshrink_varied_ladder_frames_device writes.  A ladder run IN PLACE on rung 0 has overwritten
+ * the archive's tiles: the reference must be kept, so run the ladder out of place.
+ * d_tile_sse (n_sets*tiles*channels u64, index (s*tiles + t)*channels + c; may be NULL), d_image_sse
+ * (n_sets*n_images*channels u64, index (s*n_images + i)*channels + c: what pxz_fit_varied_ladder_device reads; zeroed by the
+ * call), d_image_flags (n_images dwords, may be NULL).  Integer sums: the result does not depend on the order of the additions.
+ *   reference stored at full size: its bytes are the reference;  set tile stored at full size: sums 0, its slot is not read;
+ *   a set's stored size of zero or beyond its place: that entry all-ones (UINT64_MAX), the image's flag and
+ *   pxz_decode_status bit 0 set, the totals leave it out;  such a reference tile: every set's entry for the tile all-ones,
+ *   flagged, in no total, and nothing of the tile is read.
+ * Asynchronous on the handle's stream; the number of launches and copies does not depend on n_images or n_sets; only the varied
+ * scratch of the handle is touched (pxz_trim gives it back), none of the state of the single-geometry fast paths.
+ * Validation runs on the host before anything is launched, with pxz_distortion_varied_frames_device's rules, codes and
+ * "image i" texts (no image, so no pitch rule); PXZ_ERR_INVALID_ARG also for n_sets == 0 or a filter above 4,
+ * PXZ_ERR_UNSUPPORTED for n_sets*tiles above 2^32-1 and for a block beyond the limit below; on an error nothing is written.
+ * Limit: a wave keeps THREE planes of block_w*block_h dwords and the windows of both axes in LDS, beside the images' first
+ * tiles -- pxz_reshrink_distortion_lds_bytes says what that takes.  The largest admitted square block is 112x112 (113x113
+ * when both filters are Nearest; the re-shrink itself goes to 128x128). */
+int pxz_reshrink_distortion_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                          const pxz_params *params /* block_w, block_h; filter = filter_up */,
+                                          uint32_t expand_filter, uint32_t n_sets, const uint32_t *d_ref_w,
+                                          const uint32_t *d_ref_h, const uint8_t *d_ref_slots, const uint32_t *d_tile_w,
+                                          const uint32_t *d_tile_h, const uint8_t *d_slots, uint64_t *d_tile_sse,
+                                          uint64_t *d_image_sse, uint32_t *d_image_flags);
+
+/* Host only (no handle, no GPU), as pxz_reshrink_lds_bytes: *lds_bytes = the LDS a one-wave block of the call above takes for
+ * this block and pair of filters -- the images' first tiles (8192 bytes) and the wave's three planes and windows, from the
+ * layout function the launch uses.  A value above 163840 means the call returns PXZ_ERR_UNSUPPORTED for that block.
+ * PXZ_ERR_INVALID_ARG for a null pointer, a zero side, channels not 3|4 or a filter above 4. */
+int pxz_reshrink_distortion_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t expand_filter,
+                                      uint32_t filter_up, uint32_t *lds_bytes);
+
+/* The table of pxz_rate_distortion_varied_images for an archive: host-resident .pixlzr files in (files[i], lens[i]; all of one
+ * channel count and of params' block size), one row per (factor, file) out.  file_bytes[r*n_images + i] is the length of the
+ * file pxz_transcode_varied_ladder_files writes for file i at factors[r], sse[(r*n_images + i)*channels + c] the squared error
+ * of channel c between what file i decodes to (expand_filter) and what that new file decodes to (filter_up).  params: block_w,
+ * block_h, mode and filter (the down-scaling filter); factor is ignored.  Composition only: the headers, upload,
+ * pxz_decode_varied_frames_device into a buffer of its own, pxz_reshrink_varied_ladder_frames_device out of place,
+ * pxz_encode_varied_frames_device over the n_factors*n_images rung images with no room (for its offsets),
+ * pxz_reshrink_distortion_varied_device, one download.  Synchronous.  A malformed file or a tile that cannot be fails the
+ * whole call as in pxz_transcode_varied_files (nothing is written); files of another block size than params' are
+ * PXZ_ERR_UNSUPPORTED (there the image exists anyway: pxz_decode_varied_files + pxz_rate_distortion_varied_images serve).
+ * Other errors and limits are those of the calls it composes. */
+int pxz_rate_distortion_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                     const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                     uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse);
+
+/* "Squeeze every file of this archive under N bytes" (or "keep at least Q dB of what it decodes to now") without the images:
+ * the chain above, then pxz_fit_varied_ladder_device, pxz_gather_varied_rungs_device, pxz_encode_varied_frames_device over
+ * the n_images gathered images, one download.  targets[i] is the budget of file i under `criterion` (pxz_fit).  File i of the
+ * output is, byte for byte, pxz_transcode_varied_files of file i alone at factors[choice[i]], and the whole output equals
+ * pxz_decode_varied_files (expand_filter) followed by pxz_encode_varied_images_fit, whose pixels never exist here.  Output
+ * protocol, the PXZ_ERR_BUFFER_TOO_SMALL size query and what is always written follow pxz_encode_varied_images_fit; malformed
+ * files, flagged tiles and another block size as in pxz_rate_distortion_varied_files. */
+int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                   const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                   uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte,
+                                   uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice,
+                                   uint32_t *fit_flags, uint64_t *table_bytes /* may be NULL */, uint64_t *table_sse /* may be NULL */);
 
 /* ---- legacy image -> image filter ------------------------ */
 

@@ -13,6 +13,6 @@ from .binding import (  # noqa: F401
     PxzError, Handle, build_library, library_path, load_library, grid, encode_container, qoi_encode, axis_table,
     EXPORTED_SYMBOLS, LADDER_MAX_RUNGS, VARIED_LADDER_MAX_RUNGS, varied_layout, image_descs, file_header, psnr,
     Window, window_descs, window_layout, reshrink_lds_bytes, reshrink_ladder_lds_bytes,
-    FIT_BYTES, FIT_SSE, fit_select, sse_for_psnr,
+    FIT_BYTES, FIT_SSE, fit_select, sse_for_psnr, reshrink_distortion_lds_bytes,
 )
 from . import dist  # noqa: E402,F401  (torch.distributed plumbing: frame sharding + block-stream gather)

@@ -29,6 +29,8 @@ EXPORTED_SYMBOLS = [
     "pxz_reshrink_varied_frames_device", "pxz_reshrink_lds_bytes", "pxz_transcode_varied_files",
     "pxz_reshrink_varied_ladder_frames_device", "pxz_reshrink_ladder_lds_bytes", "pxz_transcode_varied_ladder_files",
     "pxz_fit_select", "pxz_fit_varied_ladder_device", "pxz_gather_varied_rungs_device", "pxz_encode_varied_images_fit",
+    "pxz_reshrink_distortion_varied_device", "pxz_reshrink_distortion_lds_bytes", "pxz_rate_distortion_varied_files",
+    "pxz_transcode_varied_files_fit",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -211,6 +213,15 @@ def load_library():
         L.pxz_gather_varied_rungs_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 10
         L.pxz_encode_varied_images_fit.restype = C.c_int
         L.pxz_encode_varied_images_fit.argtypes = [vp, vp, vp] + [u32] * 7 + [vp, u32, u32, vp, u32, vp, C.c_uint64] + [vp] * 5
+    if hasattr(L, "pxz_reshrink_distortion_varied_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the archive fit)
+        L.pxz_reshrink_distortion_varied_device.restype = C.c_int
+        L.pxz_reshrink_distortion_varied_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32, u32] + [vp] * 9
+        L.pxz_reshrink_distortion_lds_bytes.restype = C.c_int
+        L.pxz_reshrink_distortion_lds_bytes.argtypes = [u32] * 5 + [C.POINTER(u32)]
+        L.pxz_rate_distortion_varied_files.restype = C.c_int
+        L.pxz_rate_distortion_varied_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, vp, vp]
+        L.pxz_transcode_varied_files_fit.restype = C.c_int
+        L.pxz_transcode_varied_files_fit.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, u32, vp, u32, vp, C.c_uint64] + [vp] * 5
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -305,6 +316,16 @@ def reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter):
     unsupported)."""
     out = C.c_uint32(0)
     rc = load_library().pxz_reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter, C.byref(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out.value
+
+
+def reshrink_distortion_lds_bytes(bw, bh, channels, expand_filter, filter_up, out=None):
+    """pxz_reshrink_distortion_lds_bytes: LDS bytes of a one-wave block of reshrink_distortion_varied_device (host only; above
+    163840: unsupported).  out: a ctypes c_uint32 to write into (for the error cases)."""
+    out = C.c_uint32(0) if out is None else out
+    rc = load_library().pxz_reshrink_distortion_lds_bytes(bw, bh, channels, expand_filter, filter_up, C.byref(out))
     if rc != 0:
         raise PxzError(rc)
     return out.value
@@ -1180,6 +1201,98 @@ class Handle:
         if want_table:
             return files, choice[:n], flags[:n], table_bytes[:K, :n], table_sse[:K, :n]
         return files, choice[:n], flags[:n]
+
+    # ---- fit an archive to a budget ----
+    def reshrink_distortion_varied_device(self, sizes, channels, bw, bh, expand_filter, filter_up, ref_w, ref_h, ref_slots, ow, oh,
+                                          slots, want_tiles=True, out=None, image_flags=None, n_sets=None):
+        """pxz_reshrink_distortion_varied_device: sizes = [(width, height), ...] of the images; the archive's stored tiles
+        (ref_w[T], ref_h[T], ref_slots[T, bw*bh*C], varied layout) against n_sets stored versions of them (ow[K,T], oh[K,T],
+        slots[K,T,bw*bh*C], as reshrink_varied_ladder_frames_device leaves its rungs): per tile, set and channel the sum of
+        (expand(reference, expand_filter) - expand(set, filter_up))^2.  Returns (tile_sse int64[K,T,C] | None, image_sse
+        int64[K,n,C]); all-ones entries read as -1; image_flags (int32[n] CUDA, optional) gets 0 | 1.  out: such a pair.
+        n_sets overrides what ow's shape says; None for a tensor passes a null pointer."""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        n = len(geoms)
+        T = int(varied_layout([g[:4] for g in geoms], bw, bh)[-1]) if n and out is None else 0
+        K = n_sets if n_sets is not None else (ow.numel() // T if T else ow.shape[0])
+        if out is None:
+            dev = torch.device("cuda", self.device_id)
+            tile_sse = torch.empty((K, T, channels), dtype=torch.int64, device=dev) if want_tiles else None
+            image_sse = torch.empty((K, n, channels), dtype=torch.int64, device=dev)
+        else:
+            tile_sse, image_sse = out
+        pd = Params(bw, bh, 0, filter_up, 0.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_reshrink_distortion_varied_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, C.byref(pd), expand_filter, K, ptr(ref_w),
+            ptr(ref_h), ptr(ref_slots), ptr(ow), ptr(oh), ptr(slots), ptr(tile_sse), ptr(image_sse), ptr(image_flags)))
+        return tile_sse, image_sse
+
+    def rate_distortion_varied_files(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors):
+        """pxz_rate_distortion_varied_files: a list of .pixlzr files (bytes) of one channel count and of block size bw x bh at
+        every factor of `factors` (1..32) -> (file_bytes uint64[K,n], sse uint64[K,n,C]): the length of each re-shrunk file
+        and its squared error against what the file decodes to now."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        ch = file_header(files[0])[4] if n and len(files[0]) >= 26 else 4
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        pd = Params(bw, bh, mode, filter_down, 0.0, 0)
+        file_bytes = np.zeros((max(K, 1), max(n, 1)), np.uint64)
+        sse = np.zeros((max(K, 1), max(n, 1), ch), np.uint64)
+        self._check(self._L.pxz_rate_distortion_varied_files(
+            self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd), expand_filter, filter_up,
+            _p(fac) if K else None, K, _p(file_bytes), _p(sse)))
+        return file_bytes[:K, :n], sse[:K, :n]
+
+    def transcode_varied_files_fit(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
+                                   filter_byte=0, want_table=False, out=None):
+        """pxz_transcode_varied_files_fit: a list of .pixlzr files (bytes) -> the list of the files re-shrunk, each at the
+        factor of `factors` that fit_select picks under targets[i], the error measured against what the file decodes to now.
+        Returns (files, choice uint32[n], fit_flags uint32[n]) and, with want_table, (file_bytes uint64[K,n], sse
+        uint64[K,n,C]).  out: a numpy uint8 buffer to write into (PxzError -7 with .needed, .choice, .fit_flags and .table when
+        it is too small; size 0 is the size query), else the buffer is sized by a first call."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        ch = file_header(files[0])[4] if n and len(files[0]) >= 26 else 4
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        tg = np.array([int(t) for t in targets], np.uint64)
+        pd = Params(bw, bh, mode, filter_down, 0.0, 0)
+        offs = np.zeros(n + 1, np.uint64)
+        choice, flags = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        table_bytes = np.zeros((max(K, 1), max(n, 1)), np.uint64)
+        table_sse = np.zeros((max(K, 1), max(n, 1), ch), np.uint64)
+
+        def call(buf):
+            return self._L.pxz_transcode_varied_files_fit(
+                self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd), expand_filter, filter_up,
+                _p(fac) if K else None, K, criterion, _p(tg) if tg.size else None, filter_byte,
+                _p(buf) if buf is not None and buf.size else None, 0 if buf is None else buf.size, _p(offs), _p(choice), _p(flags),
+                _p(table_bytes), _p(table_sse))
+        if out is None:
+            out = np.empty(sum(b.size for b in bufs) + 4096 * max(n, 1), np.uint8)
+            rc = call(out)
+            if rc == -7:
+                out = np.empty(int(offs[-1]), np.uint8)
+                rc = call(out)
+        else:
+            rc = call(out)
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.needed, err.choice, err.fit_flags = int(offs[-1]), choice[:n].copy(), flags[:n].copy()
+            err.table = (table_bytes[:K, :n].copy(), table_sse[:K, :n].copy())
+            raise err
+        res = [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+        if want_table:
+            return res, choice[:n], flags[:n], table_bytes[:K, :n], table_sse[:K, :n]
+        return res, choice[:n], flags[:n]
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

@@ -119,6 +119,8 @@ struct HandleScratch {
 	DeviceBuffer fit;                 // pxz_fit_varied_ladder_device: the images' targets
 	PinnedStaging fit_targets;        //   and their pinned staging
 	DeviceBuffer fit_tiles;           // pxz_encode_varied_images_fit: the chosen rungs' tiles
+	DeviceBuffer archive_tiles;       // pxz_rate_distortion_varied_files, pxz_transcode_varied_files_fit: the archive's own tiles (the
+	                                  //   reference of the distortion call) and the flags of the reader and the re-shrink
 	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
 	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
 	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
@@ -3436,6 +3438,306 @@ int pxz_encode_varied_images_fit(pxz_handle *h, const uint8_t *const *pixels, co
 	if (table_sse) std::memcpy(table_sse, got.data() + n_sets + 1u, (size_t)n_sets * channels * 8u);
 	std::memcpy(file_offsets, got.data() + n_table, ((size_t)n_images + 1u) * 8u);
 	const uint32_t *picked = reinterpret_cast<const uint32_t *>(got.data() + n_table + n_images + 1u);
+	std::memcpy(choice, picked, (size_t)n_images * 4u);
+	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
+	const uint64_t total = file_offsets[n_images];
+	if (!out || out_capacity < total)
+		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
+		            (unsigned long long)out_capacity);
+	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
+// ---- fit an archive to a budget: the error of re-shrunk tiles against the archive's own (pxz_reshrink_distortion.hip) -------
+namespace {
+
+// LDS bytes of a one-wave block of reshrink_distortion_kernel: the wave's image of the launch's own layout function beside the
+// images' first tiles at their largest (kVxImages dwords, pxz_device.h) -- what the entry point and the size query hold against
+// kLdsPerCu, so that a block the query admits is launched whatever n_images is
+uint64_t reshrink_distortion_bytes(uint32_t bw, uint32_t bh, uint32_t wdw)
+{
+	const uint32_t dw = pxz::reshrink_distortion_tile_dw(bw, bh, wdw);
+	return dw == 0xffffffffu ? 0xffffffffull : (uint64_t)dw * 4u + 8192u;
+}
+
+// What both archive forms share, from the headers to the distortion call: the files parsed and uploaded, the reader into a
+// buffer of its own (NOT rung 0: the reference is kept), the re-shrink ladder out of place into varied_out, the flags of both
+// checked (all or nothing, as transcode_varied), the writer over the K * n rung images with no room for its offsets, and the
+// distortion call.  rd holds, in one block for one download: the rung files' offsets (n_sets + 1), the sums (n_sets * ch), and
+// `extra` more u64s for the caller, with the room the offsets-only writer is given behind them.
+struct ArchiveRungs {
+	std::vector<pxz_image_desc> descs, rungs;  // the files' images; the same once per rung
+	pxz_params p;                              // params with factor 1 (ignored by the ladder calls)
+	uint32_t ch = 0, n_tiles = 0;
+	uint64_t n_sets = 0, tiles = 0, raw = 0, slot = 0, meta_all = 0;
+	size_t n_table = 0;
+	TileMeta all{};
+	uint8_t *d_all = nullptr;
+	uint64_t *d_rung_offs = nullptr, *d_sse = nullptr;
+};
+
+int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
+                  uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, size_t extra, ArchiveRungs *s)
+{
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if (filter_up > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter_up must be 0..4, got %u", filter_up);
+	s->p = *params;
+	s->p.factor = 1.0f;
+	int rc = check_params(h, &s->p);
+	if (rc != PXZ_OK) return rc;
+	// every header first: the files must share channels and block size, and the block size must be params'
+	s->descs.resize(n_images);
+	uint32_t fbw = 0, fbh = 0, ch = 0;
+	uint64_t file_bytes = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, c, fb;
+		const char *why;
+		const int hrc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &c, &fb, &why);
+		if (hrc != PXZ_OK) return fail(h, hrc, "image %u: %s", i, why);
+		if (i == 0) {
+			fbw = bw;
+			fbh = bh;
+			ch = c;
+		} else if (bw != fbw || bh != fbh || c != ch) {
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u blocks of %u channels, image 0 holds %ux%u of %u", i, bw, bh, c, fbw, fbh, ch);
+		}
+		s->descs[i] = pxz_image_desc{w, hh, w * c, 0, 0};
+		file_bytes += lens[i];
+		s->raw += (uint64_t)w * hh * c;
+	}
+	if (fbw != s->p.block_w || fbh != s->p.block_h)
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "the files hold %ux%u blocks, params ask for %ux%u: the error without the image needs an unchanged block size (decode the files and "
+		            "use the image calls)", fbw, fbh, s->p.block_w, s->p.block_h);
+	if ((rc = reshrink_check_block(h, s->p.mode, fbw, fbh, ch, 1u)) != PXZ_OK) return rc;
+	if (reshrink_distortion_bytes(fbw, fbh, 1u) > kLdsPerCu)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "the distortion of re-shrunk tiles keeps three planes of block_w*block_h dwords in LDS (%ux%u)", fbw, fbh);
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, s->descs.data(), n_images, fbw, fbh, ch, s->p.mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	s->ch = ch;
+	s->n_tiles = varied_n_tiles(images);
+	s->n_sets = (uint64_t)n_factors * n_images;
+	s->tiles = (uint64_t)n_factors * s->n_tiles;
+	if (s->tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+
+	// the files back to back behind their offsets
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	const std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, 0);
+	if ((rc = ensure(h, h->transcode_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
+	uint8_t *d_files = (uint8_t *)h->transcode_files.ptr;
+	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
+
+	// the archive's tiles and the flags of the reader and the re-shrink (archive_tiles); every rung's tiles (varied_out)
+	auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+	s->slot = (uint64_t)fbw * fbh * ch;
+	s->meta_all = up256(s->tiles * 12u);
+	const uint64_t meta_ref = up256((uint64_t)s->n_tiles * 12u), flags_at = up256(meta_ref + (uint64_t)s->n_tiles * s->slot);
+	s->n_table = (size_t)s->n_sets + 1u + (size_t)s->n_sets * ch;
+	if ((rc = ensure(h, h->archive_tiles, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_out, s->meta_all + s->tiles * s->slot)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->rd, (s->n_table + extra) * 8u + 256u)) != PXZ_OK) return rc;
+	uint8_t *d_ref = (uint8_t *)h->archive_tiles.ptr;
+	const TileMeta ref = carve_tile_meta(d_ref, s->n_tiles);
+	uint32_t *d_flags = (uint32_t *)(d_ref + flags_at);
+	s->d_all = (uint8_t *)h->varied_out.ptr;
+	s->all = carve_tile_meta(s->d_all, (uint32_t)s->tiles);
+	s->d_rung_offs = (uint64_t *)h->rd.ptr;
+	s->d_sse = s->d_rung_offs + s->n_sets + 1u;
+
+	// reader -> the reference; ladder out of place -> the rungs
+	pxz_params pin = s->p;
+	pin.filter = expand_filter;
+	PXZ_HIP(h, hipMemsetAsync(d_ref, 0, meta_ref, h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
+	if ((rc = pxz_decode_varied_frames_device(h, s->descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, ref.value, ref.w,
+	                                          ref.h, d_ref + meta_ref, d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_reshrink_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, &s->p, expand_filter, factors, n_factors, ref.w, ref.h,
+	                                                   d_ref + meta_ref, s->all.value, s->all.w, s->all.h, s->d_all + s->meta_all,
+	                                                   d_flags + n_images)) != PXZ_OK)
+		return rc;
+	// all or nothing: a malformed file or a tile that cannot be stops the call before the writer runs
+	std::vector<uint32_t> flags(2u * (size_t)n_images);
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (flags[i] | flags[n_images + i])
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); nothing was written", i,
+			            flags[i] | flags[n_images + i]);
+
+	// the writer over the rung images, for its offsets; their distortion against the reference
+	s->rungs.reserve((size_t)s->n_sets);
+	for (uint32_t r = 0; r < n_factors; ++r) s->rungs.insert(s->rungs.end(), s->descs.begin(), s->descs.end());
+	if ((rc = pxz_encode_varied_frames_device(h, s->rungs.data(), (uint32_t)s->n_sets, ch, &s->p, 0, s->all.value, s->all.w, s->all.h,
+	                                          s->d_all + s->meta_all, (uint8_t *)(s->d_rung_offs + s->n_table + extra), 0, s->d_rung_offs)) != PXZ_OK)
+		return rc;
+	pxz_params up = s->p;
+	up.filter = filter_up;
+	return pxz_reshrink_distortion_varied_device(h, s->descs.data(), n_images, ch, &up, expand_filter, n_factors, ref.w, ref.h, d_ref + meta_ref,
+	                                             s->all.w, s->all.h, s->d_all + s->meta_all, nullptr, s->d_sse, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_reshrink_distortion_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t expand_filter, uint32_t filter_up,
+                                      uint32_t *lds_bytes)
+{
+	if (!lds_bytes || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || expand_filter > 4 || filter_up > 4)
+		return PXZ_ERR_INVALID_ARG;
+	uint64_t bytes = reshrink_distortion_bytes(block_w, block_h, 1u);
+	if (bytes <= kLdsPerCu) {  // (else: beyond the limit whatever the windows take)
+		uint32_t wdw = 0;
+		for (const uint32_t filter : {expand_filter, filter_up}) {
+			pxz::VariedExpandTableSet s;
+			if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), filter, &s)) return PXZ_ERR_INVALID_ARG;
+			wdw = std::max(wdw, varied_window_dw(s.max_window));
+		}
+		bytes = reshrink_distortion_bytes(block_w, block_h, wdw);
+	}
+	*lds_bytes = (uint32_t)std::min<uint64_t>(bytes, 0xffffffffull);
+	return PXZ_OK;
+}
+
+int pxz_reshrink_distortion_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                          const pxz_params *params, uint32_t expand_filter, uint32_t n_sets, const uint32_t *d_ref_w,
+                                          const uint32_t *d_ref_h, const uint8_t *d_ref_slots, const uint32_t *d_tile_w,
+                                          const uint32_t *d_tile_h, const uint8_t *d_slots, uint64_t *d_tile_sse, uint64_t *d_image_sse,
+                                          uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_ref_w || !d_ref_h || !d_ref_slots || !d_tile_w || !d_tile_h || !d_slots || !d_image_sse)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	if (n_sets == 0) return fail(h, PXZ_ERR_INVALID_ARG, "n_sets must be at least 1");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
+	std::vector<pxz_image_desc> sized(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
+	std::vector<pxz::VariedImage> images;
+	std::vector<uint32_t> sides;
+	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	if ((uint64_t)n_sets * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u sets", n_sets);
+	auto beyond = [&](uint32_t wdw) -> int {
+		const uint64_t bytes = reshrink_distortion_bytes(p.block_w, p.block_h, wdw);
+		if (bytes <= kLdsPerCu) return PXZ_OK;
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "a wave keeps three planes of block_w*block_h dwords and the windows of both axes in LDS: %llu bytes exceed the %u a block has (%ux%u)",
+		            (unsigned long long)bytes, kLdsPerCu, p.block_w, p.block_h);
+	};
+	if ((rc = beyond(1u)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::ReshrinkDistortionArgs a{};
+	pxz_params xp = p;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r)) != PXZ_OK) return rc;
+	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a.u)) != PXZ_OK) return rc;
+	// Both sets live in one bounded cache, and a set that is built into a full cache empties it first: the reference's set may
+	// have gone with it.  Asked for again it is found, or built into a cache that holds the sets' tables alone -- both stay.
+	if (expand_filter != p.filter && (rc = put_varied_expand_tables(h, xp, channels, sides, &a.r)) != PXZ_OK) return rc;
+	a.wdw = std::max(a.r.wdw, a.u.wdw);
+	if ((rc = beyond(a.wdw)) != PXZ_OK) return rc;
+	a.tile_dw = pxz::reshrink_distortion_tile_dw(p.block_w, p.block_h, a.wdw);
+	a.n_images = n_images;
+	a.n_tiles = varied_n_tiles(images);
+	a.n_sets = n_sets;
+	a.r.n_tiles = a.u.n_tiles = a.n_tiles;
+	a.r.tile_w = d_ref_w;
+	a.r.tile_h = d_ref_h;
+	a.r.slots = d_ref_slots;
+	a.u.tile_w = d_tile_w;
+	a.u.tile_h = d_tile_h;
+	a.u.slots = d_slots;
+	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
+	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
+	if ((rc = fresh_status(h, &a.r.status)) != PXZ_OK) return rc;
+	a.u.status = a.r.status;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.image_flags = d_image_flags;
+	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * n_images * channels * 8u, h->stream));
+	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
+	PXZ_HIP(h, pxz::launch_reshrink_distortion(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_rate_distortion_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                     const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                     uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!files || !lens || !params || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	ArchiveRungs s;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, 0, &s)) != PXZ_OK) return rc;
+	std::vector<uint64_t> got(s.n_table);
+	PXZ_HIP(h, hipMemcpyAsync(got.data(), s.d_rung_offs, s.n_table * 8u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint64_t k = 0; k < s.n_sets; ++k) file_bytes[k] = got[k + 1u] - got[k];
+	std::memcpy(sse, got.data() + s.n_sets + 1u, (size_t)s.n_sets * s.ch * 8u);
+	return PXZ_OK;
+}
+
+int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                   const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                   uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                                   uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes,
+                                   uint64_t *table_sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!files || !lens || !params || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
+		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	// behind the table, for the one download: the chosen files' offsets, the choices and the flags (a choice and a flag: one u64)
+	const size_t extra = (size_t)n_images + 1u + (size_t)n_images;
+	ArchiveRungs s;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, extra, &s)) != PXZ_OK) return rc;
+	const size_t n_down = s.n_table + extra;
+	uint64_t *d_offs = s.d_rung_offs + s.n_table;
+	uint32_t *d_choice = (uint32_t *)(d_offs + n_images + 1u), *d_flags = d_choice + n_images;
+	const uint64_t meta_fit = ((uint64_t)s.n_tiles * 12u + 255u) & ~(uint64_t)255u;
+	if ((rc = ensure(h, h->fit_tiles, meta_fit + (uint64_t)s.n_tiles * s.slot)) != PXZ_OK) return rc;
+	uint8_t *d_fit = (uint8_t *)h->fit_tiles.ptr;
+	const TileMeta fit = carve_tile_meta(d_fit, s.n_tiles);
+	// one rung per file; its tiles as a varied batch of the files' images
+	if ((rc = pxz_fit_varied_ladder_device(h, n_images, n_factors, s.ch, criterion, targets, s.d_rung_offs, s.d_sse, d_choice, d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_gather_varied_rungs_device(h, s.descs.data(), n_images, s.ch, &s.p, n_factors, d_choice, s.all.value, s.all.w, s.all.h,
+	                                         s.d_all + s.meta_all, fit.value, fit.w, fit.h, d_fit + meta_fit, nullptr)) != PXZ_OK)
+		return rc;
+	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
+	std::vector<uint64_t> got(n_down);
+	uint64_t cap = s.raw + s.raw / 4u + 64ull * s.n_tiles + 4096ull * n_images;
+	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
+	for (int pass = 0; pass < 2; ++pass) {
+		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
+		if ((rc = pxz_encode_varied_frames_device(h, s.descs.data(), n_images, s.ch, &s.p, filter_byte, fit.value, fit.w, fit.h, d_fit + meta_fit,
+		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
+			return rc;
+		if (pass == 0) PXZ_HIP(h, hipMemcpyAsync(got.data(), s.d_rung_offs, n_down * 8u, hipMemcpyDeviceToHost, h->stream));
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		if (got[s.n_table + n_images] <= cap) break;
+		cap = got[s.n_table + n_images];
+	}
+	if (table_bytes)
+		for (uint64_t k = 0; k < s.n_sets; ++k) table_bytes[k] = got[k + 1u] - got[k];
+	if (table_sse) std::memcpy(table_sse, got.data() + s.n_sets + 1u, (size_t)s.n_sets * s.ch * 8u);
+	std::memcpy(file_offsets, got.data() + s.n_table, ((size_t)n_images + 1u) * 8u);
+	const uint32_t *picked = reinterpret_cast<const uint32_t *>(got.data() + s.n_table + n_images + 1u);
 	std::memcpy(choice, picked, (size_t)n_images * 4u);
 	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
 	const uint64_t total = file_offsets[n_images];

@@ -579,6 +579,24 @@ struct DistortionArgs {
 	                                  //   image's valid tiles, added with atomics (zeroed before the launch)
 };
 
+// Squared error of re-shrunk tiles against the archive's own (pxz_reshrink_distortion_varied_device,
+// pxz_reshrink_distortion.hip): the flat tile space of `images`, one reference stored tile per tile (r: the archive, expanded
+// with expand_filter's tables; r.tile_w / r.tile_h / r.slots hold n_tiles entries) and n_sets stored versions of it, set-major (u:
+// the sets, expanded with filter_up's tables; u.tile_w / u.tile_h / u.slots hold n_sets * n_tiles entries).  r and u are what
+// put_varied_expand_tables fills; of their launch fields only r.status is read (u.status, both n_tiles, tile_dw and t0_dw are
+// unused: this struct's own count).  Outputs as DistortionArgs'.
+struct ReshrinkDistortionArgs {
+	const VariedImage *images;
+	uint32_t n_images, n_tiles, n_sets;
+	TileResizeArgs r, u;
+	uint32_t wdw;                     // dwords between the staged windows of the wave's region: the wider of r.wdw and u.wdw
+	uint32_t tile_dw;                 // dwords of one wave's image (reshrink_distortion_tile_dw, pxz_launch.h)
+	uint32_t t0_dw;                   // (set by the launch) dwords of the images' first tiles kept in LDS, 0: read from `images`
+	uint32_t *image_flags;            // per image 1 for a reference or set tile whose stored size is invalid, or null
+	unsigned long long *tile_sse;     // index (s * n_tiles + t) * channels + c, or null; all-ones for an invalid entry
+	unsigned long long *image_sse;    // index (s * n_images + i) * channels + c, added with atomics (zeroed before the launch)
+};
+
 // Fit to a budget (pxz_fit_varied_ladder_device, pxz_fit.hip): one rung per image out of what the writer and the distortion
 // call left for the descriptors repeated n_factors times.  The rule is fit_pick's (pxz_fit.h).
 struct FitArgs {

@@ -47,6 +47,15 @@ hipError_t launch_reshrink_ladder(const ReshrinkLadderArgs &a, uint32_t channels
 // count) for blocks of bw x bh whose staged windows take wdw dwords, from the layout function the kernels and their launches
 // use (what the host holds against kLdsPerCu before it launches); 0xffffffff: a plane of bw * bh dwords above 64 KB
 uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw);
+hipError_t launch_reshrink_distortion(const ReshrinkDistortionArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+// Dwords of one wave's image in reshrink_distortion_kernel for blocks of bw x bh whose staged windows take wdw dwords: three
+// planes of bw * bh dwords (the reference and varied_resize_tile's two) and the windows of both axes.  The kernel, its launch,
+// the entry point's check and the size query all take the layout from here.  0xffffffff: beyond any LDS.
+inline uint32_t reshrink_distortion_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw)
+{
+	const uint64_t dw = (3ull * bw * bh + (uint64_t)wdw * ((uint64_t)bw + bh) + 3u) & ~3ull;
+	return dw > 0x0fffffffull ? 0xffffffffu : (uint32_t)dw;
+}
 // fit to a budget (pxz_fit.hip): one rung per image, and the chosen rungs' tiles as a varied batch; one launch each
 hipError_t launch_fit_select(const FitArgs &a, hipStream_t stream);
 hipError_t launch_gather_rungs(const GatherArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
