@@ -4,8 +4,11 @@
 //
 // Who owns what: pxz_handle.h has the owners -- DeviceBuffer (a grow-only device allocation: a scratch buffer, or the one
 // allocation behind a table set) and PinnedStaging (a pinned block and the event behind the last copy out of it); each
-// frees what it holds.  HandleScratch below is everything pxz_trim gives back, pxz_handle adds what survives a trim; the
-// table caches go through cached_tables.  The kernel units' launchers are declared in pxz_launch.h.
+// frees what it holds.  HandleScratch (pxz_runtime.h) is everything pxz_trim gives back, pxz_handle adds what survives a
+// trim; the table caches go through cached_tables.  The kernel units' launchers are declared in pxz_launch.h.
+// The entry points that take host pointers and compose the device entry points of this file (the host forms) are in
+// pxz_host_forms.cpp.  pxz_runtime.h declares what they share with this file; the functions it names are defined here in
+// namespace pxz_runtime, everything else of this file stays in the anonymous namespace.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <condition_variable>
@@ -28,132 +31,18 @@
 #include "pxz_handle.h"
 #include "pxz_internal.h"
 #include "pxz_launch.h"
+#include "pxz_runtime.h"
 #include "pxz_tables.h"
 
-namespace {
-
-using pxz::AxisTab;
-using pxz::DeviceBuffer;
-using pxz::kMaxLevel;
-using pxz::PinnedStaging;
-
-// device copy of the down-scaling tables for one (tile geometry, filter): pxz::ShrinkTableSet
-struct TableSet {
-	DeviceBuffer mem;  // the one allocation behind every device pointer below
-	std::vector<AxisTab> tabs;  // host copy, passed by value in the kernel arguments
-	uint16_t *d_bounds = nullptr;
-	uint32_t *d_coeffs = nullptr;
-	int32_t *d_ksums = nullptr;
-	uint32_t *d_rows = nullptr;
-	uint32_t rows_dw = 0;
-	uint32_t *d_mf64 = nullptr;  // 64x64 fast path: matrix-core operand tables (null: not available)
-	bool opaque_stays = true;    // a constant-255 alpha comes back as 255 from every window of every table
-};
-
-// decode side: up-scaling tables of every source size to the full tile size (expand_kernel): pxz::ExpandTableSet
-struct ExpandTables {
-	DeviceBuffer mem;  // the one allocation behind every device pointer below
-	pxz::ExpandTab *d_dir = nullptr;
-	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
-	int16_t *d_coeffs = nullptr;
-	uint32_t dir_stride = 0;
-	uint32_t *d_xmf = nullptr;  // 32x32 tiles, convolutions: matrix-core operand tables (pxz_internal.h: kXmfDw)
-	uint32_t *d_xmf16 = nullptr;  // 16x16 tiles, convolutions: the same for expand16_kernel (kXmf16Dw)
-	uint32_t *d_xmf64 = nullptr;  // 64x64 tiles, convolutions: the same for expand64_kernel (kXmf64Dw)
-};
-
-// tree::process on rectangle lists: every axis table (down with the one filter, back up with the other) of every tile
-// size the recursion can reach from one (frame, block, minimum) geometry: pxz::TreeTableSet
-struct TreeTables {
-	DeviceBuffer mem;  // the one allocation behind every device pointer below
-	pxz::TreeAxisEntry *d_dir = nullptr;
-	int32_t *d_starts = nullptr, *d_sizes = nullptr;
-	int16_t *d_coeffs = nullptr;
-	uint32_t n_dir = 0;
-};
-
-// batches of differently sized images: the axis tables of every (source size, level) pair of one batch: pxz::VariedTableSet
-struct VariedTables {
-	DeviceBuffer mem;  // the one allocation behind every device pointer below
-	pxz::TreeAxisEntry *d_dir = nullptr;
-	int32_t *d_starts = nullptr, *d_sizes = nullptr;
-	int16_t *d_coeffs = nullptr;
-};
-
-// decode side of varied batches: the up-scaling table of every (full size, stored size) pair of one batch: pxz::VariedExpandTableSet
-struct VariedExpandTables {
-	DeviceBuffer mem;  // the one allocation behind every device pointer below
-	uint32_t *d_slot = nullptr;
-	pxz::ExpandTab *d_dir = nullptr;
-	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
-	int16_t *d_coeffs = nullptr;
-	uint32_t stride = 0, max_window = 0;
-};
-
-// The bounded caches hold at most this many table sets: caches, not logs -- varying geometries (tools/fuzz_tree.py, a
-// folder of many sizes) must not grow them without bound.
-constexpr size_t kTableCacheBound = 16;
-
-// Everything of a handle that pxz_trim gives back: assigning a fresh HandleScratch releases all of it, so a member
-// added here can be forgotten neither by pxz_trim nor by pxz_destroy.
-struct HandleScratch {
-	DeviceBuffer in, val, ow, oh, out, sums, chunks, work, qscratch, qmeta, status, dmeta, okscratch, rgba, slots4, pk, pkoff, tree, xlist, bigscratch;
-	uint64_t packed_len = 0;   // bytes of the stream pxz_shrink_image_packed left in `pk` (0: none)
-	static constexpr int kRing = 3;  // buffer sets of the pipelined host boundary (pxz_shrink_images*)
-	DeviceBuffer ring_in[kRing], ring_val[kRing], ring_ow[kRing], ring_oh[kRing], ring_out[kRing], ring_pk[kRing], ring_pkoff[kRing];
-	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, TreeTables> tree_tables;
-	DeviceBuffer tree_rects[2], tree_count;
-	DeviceBuffer ladder;              // factor ladder: the raw detector value of every tile, then the rungs' factors
-	PinnedStaging ladder_factors;     //   pinned staging of the factors (PXZ_LADDER_MAX_RUNGS floats)
-	DeviceBuffer varied, varied_in, varied_out, varied_files;  // varied batches: the per-image table, the host form's images,
-	                                  //   tiles and files
-	PinnedStaging varied_images;      // pinned staging of the per-image table
-	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedTables> varied_tables;  // (filter, tile sides) -> tables
-	std::map<std::pair<uint32_t, std::vector<uint32_t>>, VariedExpandTables> varied_expand_tables;  // the same for the decode side
-	DeviceBuffer varied_flags;        // per-image flags of a varied decode-side call whose caller passed none
-	DeviceBuffer rd;                  // pxz_rate_distortion_image: the files' offsets, the rungs' squared errors, the writer's room
-	DeviceBuffer windows;             // pixel windows of files: the per-window table
-	PinnedStaging window_table;       //   and its pinned staging
-	DeviceBuffer window_host;         // pxz_decode_windows_files: the files, the covered tiles, the crops and the flags
-	DeviceBuffer transcode_files, transcode_tiles;  // pxz_transcode_varied_files: the files that come in; their tiles when the block size changes
-	DeviceBuffer fit;                 // pxz_fit_varied_ladder_device: the images' targets
-	PinnedStaging fit_targets;        //   and their pinned staging
-	DeviceBuffer fit_tiles;           // pxz_encode_varied_images_fit: the chosen rungs' tiles
-	DeviceBuffer archive_tiles;       // pxz_rate_distortion_varied_files, pxz_transcode_varied_files_fit: the archive's own tiles (the
-	                                  //   reference of the distortion call) and the flags of the reader and the re-shrink
-	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
-	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
-	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
-};
-
-}  // namespace
+using namespace pxz_runtime;
+using pxz::kLdsPerCu;
 
 constexpr uint32_t kMaxImageSide = 1u << 24;  // see pxz_grid
+// a tile image of at most this many bytes is staged whole in LDS by varied_kernel (with its second image and, for shrink_by,
+// the detector's tables: 142 KB of the 160 KB)
+constexpr uint64_t kVariedMaxTileBytes = 65536;
 
-struct pxz_handle : HandleScratch {
-	int device = 0;
-	uint32_t n_cus = 256;
-	hipStream_t stream = nullptr;
-	std::string error;
-	float thresholds[pxz::kNumThresholds];
-	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, TableSet> tables;
-	// level breakpoints per (mode, factor bits, bw, bh, edge_w, edge_h)
-	struct Breaks { uint32_t b[4][pxz::kMaxLevel]; uint32_t asc[4]; };
-	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, Breaks> breaks;
-	std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, ExpandTables> expand_tables;
-	bool quiet_stats = false;         // the launch being set up writes no kernel-selection statistics (the ladder's detector)
-	uint32_t *host_stats = nullptr;  // pinned, device-visible: [0] = tiles with transparency the last finished 32x32 launch saw
-	uint32_t *dev_stats = nullptr;   //   (its device-side address); read without synchronisation, steers only the kernel choice
-	uint32_t last_alpha_kernel = 0, last_alpha_first = 0;  // what the last launch set up through this handle chose (pxz_handle_state)
-	uint32_t work_slot = 0;    // the counter the next 32x32 launch uses
-	bool timing = false;
-	uint32_t timing_stride = 1, timing_count = 0;  // every stride-th step is bracketed by events
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-	std::vector<hipEvent_t> mid_events;  // one per pair: behind the first kernel of the step
-	size_t events_used = 0;
-};
-
-namespace {
+namespace pxz_runtime {  // (varied_plan, window_plan and stage_host_image stand further down, beside what they use)
 
 int fail(pxz_handle *h, int code, const char *fmt, ...)
 {
@@ -168,16 +57,125 @@ int fail(pxz_handle *h, int code, const char *fmt, ...)
 	return code;
 }
 
-#define PXZ_HIP(h, call)                                                                      \
-	do {                                                                                      \
-		hipError_t e_ = (call);                                                               \
-		if (e_ != hipSuccess) return fail((h), PXZ_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-	} while (0)
-
 int ensure(pxz_handle *h, DeviceBuffer &b, size_t bytes)
 {
 	return b.reserve(bytes) ? PXZ_OK : fail(h, PXZ_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
 }
+
+// the decode side uses neither mode nor factor (and the reader no filter): the caller's parameters with those neutral
+pxz_params decode_side_params(const pxz_params *params, bool with_filter)
+{
+	pxz_params p = *params;
+	p.mode = 0;
+	p.factor = 0.0f;
+	if (!with_filter) p.filter = 0;
+	return p;
+}
+
+int check_params(pxz_handle *h, const pxz_params *p)
+{
+	if (p->block_w == 0 || p->block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
+	if (p->mode > 1) return fail(h, PXZ_ERR_INVALID_ARG, "mode must be 0 or 1");
+	if (p->filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter must be 0..4");
+	if (!std::isfinite(p->factor)) return fail(h, PXZ_ERR_INVALID_ARG, "factor must be finite");
+	return PXZ_OK;
+}
+
+int varied_check_params(pxz_handle *h, uint32_t channels, const pxz_params *p)
+{
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	const int rc = check_params(h, p);
+	if (rc != PXZ_OK) return rc;
+	if ((uint64_t)p->block_w * p->block_h * channels > kVariedMaxTileBytes)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "varied batches stage every tile in LDS: block_w*block_h*channels must not exceed %llu bytes",
+		            (unsigned long long)kVariedMaxTileBytes);
+	return PXZ_OK;
+}
+
+// the ladder's rules for a host array of factors
+int check_factors(pxz_handle *h, const float *factors, uint32_t n_factors, uint32_t max_rungs)
+{
+	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
+	if (n_factors == 0 || n_factors > max_rungs) return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", max_rungs, n_factors);
+	for (uint32_t r = 0; r < n_factors; ++r)
+		if (!std::isfinite(factors[r])) return fail(h, PXZ_ERR_INVALID_ARG, "factor %u must be finite", r);
+	return PXZ_OK;
+}
+
+// what pxz_fit_select and pxz_fit_varied_ladder_device check of their sizes (h may be null: the host form has no handle)
+int fit_check(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion)
+{
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (n_factors == 0 || n_factors > PXZ_VARIED_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_VARIED_LADDER_MAX_RUNGS, n_factors);
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
+		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	return PXZ_OK;
+}
+
+// The header fields of one .pixlzr file; on PXZ_ERR_INVALID_ARG *why says what is wrong with it.
+int file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h,
+                uint32_t *channels, uint32_t *filter_byte, const char **why)
+{
+	*why = "null pointer";
+	if (!file || !width || !height || !block_w || !block_h || !channels || !filter_byte) return PXZ_ERR_INVALID_ARG;
+	static const uint8_t magic[9] = {'P', 'I', 'X', 'L', 'Z', 'R', 0, 0, 2};
+	*why = "not a .pixlzr v0.0.2 file";
+	if (len < 26 || std::memcmp(file, magic, 9) != 0) return PXZ_ERR_INVALID_ARG;
+	auto be = [&](size_t o) { return ((uint32_t)file[o] << 24) | ((uint32_t)file[o + 1] << 16) | ((uint32_t)file[o + 2] << 8) | file[o + 3]; };
+	*filter_byte = file[9];
+	*width = be(10);
+	*height = be(14);
+	*block_w = be(18);
+	*block_h = be(22);
+	*why = "empty image or block in the header";
+	if (*width == 0 || *height == 0 || *block_w == 0 || *block_h == 0) return PXZ_ERR_INVALID_ARG;
+	uint32_t cols, rows;
+	pxz_grid(*width, *height, *block_w, *block_h, &cols, &rows);
+	const size_t first = 26 + (size_t)rows * 4;
+	*why = "file ends inside the first record";
+	if (len < first + 13 + 10) return PXZ_ERR_INVALID_ARG;
+	*channels = file[first + 21];  // the first record's QOI header (decode_block, mod.rs:202-242)
+	*why = "first record has neither 3 nor 4 channels";
+	if (*channels != 3 && *channels != 4) return PXZ_ERR_INVALID_ARG;
+	*why = "";
+	return PXZ_OK;
+}
+
+// the tiles of a planned batch
+uint32_t varied_n_tiles(const std::vector<pxz::VariedImage> &images)
+{
+	return images.back().tile0 + images.back().cols * images.back().rows;
+}
+
+// the covered tiles of a planned call
+uint32_t window_n_tiles(const std::vector<pxz::WindowEntry> &entries) { return entries.back().tile0 + entries.back().ccols * entries.back().crows; }
+
+// the one place that says whether the re-shrink kernels take a block: the LDS footprint (what the launch asks for) against the
+// CU's.  rung_channels: 0 for reshrink_kernel, the tiles' channel count for reshrink_ladder_kernel, whose footprint depends on it
+// (its resampled images)
+int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
+{
+	if (pxz::reshrink_lds_bytes(mode, bw, bh, rung_channels, wdw) > kLdsPerCu)
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "a re-shrink%s keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
+		            "bytes, the whole 160 KB (%ux%u)", rung_channels ? " ladder" : "", bw, bh);
+	return PXZ_OK;
+}
+
+// LDS bytes of a one-wave block of reshrink_distortion_kernel: the wave's image of the launch's own layout function beside the
+// images' first tiles at their largest (kVxImages dwords, pxz_device.h) -- what the entry point and the size query hold against
+// kLdsPerCu, so that a block the query admits is launched whatever n_images is
+uint64_t reshrink_distortion_bytes(uint32_t bw, uint32_t bh, uint32_t wdw)
+{
+	const uint32_t dw = pxz::reshrink_distortion_tile_dw(bw, bh, wdw);
+	return dw == 0xffffffffu ? 0xffffffffull : (uint64_t)dw * 4u + 8192u;
+}
+
+}  // namespace pxz_runtime
+
+namespace {
 
 // ensure() for the buffer that holds a stream kernel's binning counters: a new allocation forgets that they were left
 // zeroed (nothing in it is zero)
@@ -266,16 +264,6 @@ int download_tile_outputs(pxz_handle *h, size_t tiles, size_t slot_bytes, float 
 	return PXZ_OK;
 }
 
-// the decode side uses neither mode nor factor (and the reader no filter): the caller's parameters with those neutral
-pxz_params decode_side_params(const pxz_params *params, bool with_filter)
-{
-	pxz_params p = *params;
-	p.mode = 0;
-	p.factor = 0.0f;
-	if (!with_filter) p.filter = 0;
-	return p;
-}
-
 // these frames as tightly packed RGBA with rows of a 16-byte multiple (what the fast kernels and the block-cooperative
 // Oklab detector want)
 pxz_frames rgba16_frames(const pxz_frames *frames)
@@ -309,11 +297,11 @@ struct TablePart {
 int upload_tables(pxz_handle *h, std::initializer_list<TablePart> parts, DeviceBuffer *mem)
 {
 	size_t total = 0;
-	for (const TablePart &p : parts) total += (p.bytes + 255) & ~(size_t)255;
+	for (const TablePart &p : parts) total += up256(p.bytes);
 	mem->release();
 	hipError_t e = mem->reserve(total) ? hipSuccess : hipErrorOutOfMemory;
 	uint8_t *at = static_cast<uint8_t *>(mem->ptr);
-	for (auto p = parts.begin(); e == hipSuccess && p != parts.end(); at += (p->bytes + 255) & ~(size_t)255, ++p) {
+	for (auto p = parts.begin(); e == hipSuccess && p != parts.end(); at += up256(p->bytes), ++p) {
 		*p->dst = p->bytes ? at : nullptr;
 		if (p->bytes) e = hipMemcpy(at, p->src, p->bytes, hipMemcpyHostToDevice);
 	}
@@ -452,15 +440,6 @@ void build_breaks(pxz_handle *h, pxz::ShrinkArgs *a)
 			a->breaks[cls][j] = brk;
 		}
 	}
-}
-
-int check_params(pxz_handle *h, const pxz_params *p)
-{
-	if (p->block_w == 0 || p->block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero block size");
-	if (p->mode > 1) return fail(h, PXZ_ERR_INVALID_ARG, "mode must be 0 or 1");
-	if (p->filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter must be 0..4");
-	if (!std::isfinite(p->factor)) return fail(h, PXZ_ERR_INVALID_ARG, "factor must be finite");
-	return PXZ_OK;
 }
 
 int check_frames(pxz_handle *h, const pxz_frames *f, const pxz_params *p)
@@ -1055,7 +1034,7 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 		}
 		return PXZ_OK;
 	}
-	const size_t x_bytes = ((size_t)a.n_tiles * 4u + 255u) & ~(size_t)255u;
+	const size_t x_bytes = up256((size_t)a.n_tiles * 4u);
 	if ((rc = ensure(h, h->ladder, x_bytes + PXZ_LADDER_MAX_RUNGS * 4u)) != PXZ_OK) return rc;
 	float *d_x = (float *)h->ladder.ptr;
 	float *d_factors = (float *)((uint8_t *)h->ladder.ptr + x_bytes);
@@ -1497,35 +1476,6 @@ int pxz_decode_frames_device(pxz_handle *h, const pxz_frames *frames, const pxz_
 	return launch_on_bins(h, h->dbins_clean, a.bins, [&](bool bins_clean) { return pxz::launch_decode(a, bins_clean, h->stream); });
 }
 
-// The header fields of one .pixlzr file; on PXZ_ERR_INVALID_ARG *why says what is wrong with it.
-static int file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h,
-                       uint32_t *channels, uint32_t *filter_byte, const char **why)
-{
-	*why = "null pointer";
-	if (!file || !width || !height || !block_w || !block_h || !channels || !filter_byte) return PXZ_ERR_INVALID_ARG;
-	static const uint8_t magic[9] = {'P', 'I', 'X', 'L', 'Z', 'R', 0, 0, 2};
-	*why = "not a .pixlzr v0.0.2 file";
-	if (len < 26 || std::memcmp(file, magic, 9) != 0) return PXZ_ERR_INVALID_ARG;
-	auto be = [&](size_t o) { return ((uint32_t)file[o] << 24) | ((uint32_t)file[o + 1] << 16) | ((uint32_t)file[o + 2] << 8) | file[o + 3]; };
-	*filter_byte = file[9];
-	*width = be(10);
-	*height = be(14);
-	*block_w = be(18);
-	*block_h = be(22);
-	*why = "empty image or block in the header";
-	if (*width == 0 || *height == 0 || *block_w == 0 || *block_h == 0) return PXZ_ERR_INVALID_ARG;
-	uint32_t cols, rows;
-	pxz_grid(*width, *height, *block_w, *block_h, &cols, &rows);
-	const size_t first = 26 + (size_t)rows * 4;
-	*why = "file ends inside the first record";
-	if (len < first + 13 + 10) return PXZ_ERR_INVALID_ARG;
-	*channels = file[first + 21];  // the first record's QOI header (decode_block, mod.rs:202-242)
-	*why = "first record has neither 3 nor 4 channels";
-	if (*channels != 3 && *channels != 4) return PXZ_ERR_INVALID_ARG;
-	*why = "";
-	return PXZ_OK;
-}
-
 int pxz_file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h,
                     uint32_t *channels, uint32_t *filter_byte)
 {
@@ -1613,7 +1563,8 @@ int pxz_expand_image(pxz_handle *h, uint32_t width, uint32_t height, uint32_t ch
 
 }  // extern "C"
 
-namespace {
+namespace pxz_runtime {
+
 // The front half of the host-buffer entry points of one image (pxz_shrink_image, _ladder, _packed, pxz_rate_distortion_image)
 // after their pointer checks: the checks of the geometry, the transparency hint (*p), the tile outputs of `sets` results in
 // handle scratch (the pixels only with device_px) and the upload.  *f: the frame with its device pitch; *tiles: the tiles of
@@ -1633,6 +1584,10 @@ int stage_host_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint3
 	if ((rc = ensure_tile_outputs(h, *tiles, device_px ? *slot : 0)) != PXZ_OK) return rc;
 	return upload_image(h, pixels, width, height, channels, pitch_bytes, &f->pitch_bytes);
 }
+
+}  // namespace pxz_runtime
+
+namespace {
 
 // ... then device_call(frames with the device pitch, parameters with the hint, tiles, slot bytes), and the download of the
 // tile outputs (the pixels only with out_pixels).  The caller queues what it downloads besides and synchronises.
@@ -2152,6 +2107,10 @@ pxz::VariedImage varied_entry(uint32_t width, uint32_t height, uint32_t pitch, c
 	return im;
 }
 
+}  // namespace
+
+namespace pxz_runtime {
+
 // The per-image table of a varied batch, checked image by image before anything is launched.  channels 0: geometry only
 // (pxz_varied_layout, the writer), no pitch or tile-size rules.
 int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw, uint32_t bh, uint32_t channels, uint32_t mode,
@@ -2193,11 +2152,9 @@ int varied_plan(pxz_handle *h, const pxz_image_desc *d, uint32_t n, uint32_t bw,
 	return PXZ_OK;
 }
 
-// the tiles of a planned batch
-uint32_t varied_n_tiles(const std::vector<pxz::VariedImage> &images)
-{
-	return images.back().tile0 + images.back().cols * images.back().rows;
-}
+}  // namespace pxz_runtime
+
+namespace {
 
 // the per-image table -> handle scratch, through pinned staging that is reused once the previous copy out of it has run
 int varied_upload(pxz_handle *h, const std::vector<pxz::VariedImage> &images, const pxz::VariedImage **d_images)
@@ -2217,53 +2174,6 @@ int get_varied_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t
 		if (!pxz::build_varied_tables(sides, filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", filter);
 		return upload_tables(h, {{s.dir, &vt.d_dir}, {s.starts, &vt.d_starts}, {s.sizes, &vt.d_sizes}, {s.coeffs, &vt.d_coeffs}}, &vt.mem);
 	}, out);
-}
-
-// a tile image of at most this many bytes is staged whole in LDS by varied_kernel (with its second image and, for shrink_by,
-// the detector's tables: 142 KB of the 160 KB)
-constexpr uint64_t kVariedMaxTileBytes = 65536;
-
-int varied_check_params(pxz_handle *h, uint32_t channels, const pxz_params *p)
-{
-	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	const int rc = check_params(h, p);
-	if (rc != PXZ_OK) return rc;
-	if ((uint64_t)p->block_w * p->block_h * channels > kVariedMaxTileBytes)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "varied batches stage every tile in LDS: block_w*block_h*channels must not exceed %llu bytes",
-		            (unsigned long long)kVariedMaxTileBytes);
-	return PXZ_OK;
-}
-
-// The host forms' images (checked, none null) into handle scratch, back to back with 256-byte aligned starts: *dev are their
-// descriptors there, *raw the bytes of their pixels.
-int varied_send_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
-                       std::vector<pxz_image_desc> *dev, uint64_t *raw)
-{
-	dev->assign(descs, descs + n_images);
-	auto bytes_of = [&](uint32_t i) { return (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels; };
-	uint64_t in_bytes = 0;
-	*raw = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		(*dev)[i].offset_bytes = in_bytes;
-		in_bytes += (bytes_of(i) + 255u) & ~(uint64_t)255u;
-		*raw += (uint64_t)descs[i].width * descs[i].height * channels;
-	}
-	const int rc = ensure(h, h->varied_in, in_bytes);
-	if (rc != PXZ_OK) return rc;
-	uint8_t *d_in = (uint8_t *)h->varied_in.ptr;
-	for (uint32_t i = 0; i < n_images; ++i)
-		PXZ_HIP(h, hipMemcpyAsync(d_in + (*dev)[i].offset_bytes, pixels[i], bytes_of(i), hipMemcpyHostToDevice, h->stream));
-	return PXZ_OK;
-}
-
-// the ladder's rules for a host array of factors
-int check_factors(pxz_handle *h, const float *factors, uint32_t n_factors, uint32_t max_rungs)
-{
-	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
-	if (n_factors == 0 || n_factors > max_rungs) return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", max_rungs, n_factors);
-	for (uint32_t r = 0; r < n_factors; ++r)
-		if (!std::isfinite(factors[r])) return fail(h, PXZ_ERR_INVALID_ARG, "factor %u must be finite", r);
-	return PXZ_OK;
 }
 
 // what varied_kernel and varied_ladder_kernel are told about a planned batch (a->images is varied_upload's)
@@ -2415,56 +2325,6 @@ int pxz_encode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	                      [&](bool bins_clean) { return pxz::launch_qoi_varied(a, v, bins_clean, h->n_cus, h->stream); });
 }
 
-int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
-                             uint32_t channels, const pxz_params *params, uint32_t filter_byte, uint8_t *out,
-                             uint64_t out_capacity, uint64_t *file_offsets)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!pixels || !params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	int rc = varied_check_params(h, channels, params);
-	if (rc != PXZ_OK) return rc;
-	std::vector<pxz::VariedImage> images;
-	if ((rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, params->mode, &images, nullptr, nullptr)) != PXZ_OK)
-		return rc;
-	for (uint32_t i = 0; i < n_images; ++i)
-		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
-	PXZ_HIP(h, hipSetDevice(h->device));
-	// the images, back to back, and the tiles' outputs
-	std::vector<pxz_image_desc> dev;
-	uint64_t raw = 0;
-	if ((rc = varied_send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
-	const uint32_t n_tiles = varied_n_tiles(images);
-	const uint64_t slot = (uint64_t)params->block_w * params->block_h * channels;
-	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
-	if ((rc = ensure(h, h->varied_out, meta + (uint64_t)n_tiles * slot + 8u * ((uint64_t)n_images + 1u))) != PXZ_OK) return rc;
-	uint8_t *d_in = (uint8_t *)h->varied_in.ptr, *d_out = (uint8_t *)h->varied_out.ptr;
-	float *d_val = (float *)d_out;
-	uint32_t *d_w = (uint32_t *)(d_out + (uint64_t)n_tiles * 4u), *d_h = (uint32_t *)(d_out + (uint64_t)n_tiles * 8u);
-	uint8_t *d_slots = d_out + meta;
-	uint64_t *d_offs = (uint64_t *)(d_slots + (uint64_t)n_tiles * slot);
-	if ((rc = pxz_shrink_varied_frames_device(h, dev.data(), n_images, channels, params, d_in, d_val, d_w, d_h, d_slots)) != PXZ_OK)
-		return rc;
-	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
-	uint64_t cap = raw + raw / 4u + 64ull * n_tiles + 4096ull * n_images;
-	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
-	for (int pass = 0; pass < 2; ++pass) {
-		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
-		if ((rc = pxz_encode_varied_frames_device(h, dev.data(), n_images, channels, params, filter_byte, d_val, d_w, d_h, d_slots,
-		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
-			return rc;
-		PXZ_HIP(h, hipMemcpyAsync(file_offsets, d_offs, 8u * ((size_t)n_images + 1u), hipMemcpyDeviceToHost, h->stream));
-		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		if (file_offsets[n_images] <= cap) break;
-		cap = file_offsets[n_images];
-	}
-	const uint64_t total = file_offsets[n_images];
-	if (!out || out_capacity < total)
-		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
-		            (unsigned long long)out_capacity);
-	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
-	return PXZ_OK;
-}
-
 }  // extern "C"
 
 // ---- decode side of varied batches (varied_index_kernel in pxz_stream.hip, pxz_varied_expand.hip) -------------------------
@@ -2574,76 +2434,6 @@ int flat_decode_args(pxz_handle *h, const pxz_params &p, uint32_t channels, uint
 	return reader_scratch(h, a);
 }
 
-// ---- what the two host-files forms share (pxz_decode_varied_files, pxz_decode_windows_files)
-
-// Every header first: a file that is not the image its descriptor announces is refused before anything is written.
-// what: who expects the image ("batch", "call").  *file_bytes: the files' lengths added up.
-int check_file_headers(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
-                       uint32_t channels, const pxz_params &p, const char *what, uint64_t *file_bytes)
-{
-	*file_bytes = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
-		uint32_t w, hh, bw, bh, ch, fb;
-		const char *why;
-		const int rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why);
-		if (rc != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
-		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the %s expects %ux%u in %ux%u of %u",
-			            i, w, hh, bw, bh, ch, what, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
-		*file_bytes += lens[i];
-	}
-	return PXZ_OK;
-}
-
-// the files back to back behind their table of n_images + 1 offsets, as the reader takes them: stage holds
-// max(8 * (n_images + 1) + the files' bytes, down_bytes) -- one staging buffer for both directions, the results come back
-// only after the files have gone
-std::vector<uint8_t> stage_files(const uint8_t *const *files, const size_t *lens, uint32_t n_images, uint64_t file_bytes, uint64_t down_bytes)
-{
-	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
-	std::vector<uint8_t> stage((size_t)std::max(offs_bytes + file_bytes, down_bytes));
-	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
-	offs[0] = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
-		offs[i + 1] = offs[i] + lens[i];
-	}
-	return stage;
-}
-
-// values, widths and heights of n_tiles tiles, carved from 12 * n_tiles bytes at d
-struct TileMeta {
-	float *value;
-	uint32_t *w, *h;
-};
-TileMeta carve_tile_meta(uint8_t *d, uint32_t n_tiles)
-{
-	return {(float *)d, (uint32_t *)(d + (uint64_t)n_tiles * 4u), (uint32_t *)(d + (uint64_t)n_tiles * 8u)};
-}
-
-// The way back of n owners (pxz_image_desc or pxz_window): owner k's rows, tightly packed at packed[k].offset_bytes of stage,
-// go to the caller's place and pitch (host[k]); flags holds the decode stage's n flags, then the expand stage's, merged into
-// out_flags (or null).  Returns the first owner with a flag (n: none) and, in *first_flags, what it has.
-template <class Owner>
-uint32_t copy_out_owners(const Owner *host, const Owner *packed, uint32_t n, uint32_t channels, const uint8_t *stage, uint8_t *out_base,
-                         const uint32_t *flags, uint32_t *out_flags, uint32_t *first_flags)
-{
-	uint32_t first_bad = n;
-	for (uint32_t k = 0; k < n; ++k) {
-		const uint32_t fl = flags[k] | flags[n + k];
-		if (out_flags) out_flags[k] = fl;
-		if (fl && first_bad == n) {
-			first_bad = k;
-			*first_flags = fl;
-		}
-		const size_t row = (size_t)host[k].width * channels;
-		for (uint32_t y = 0; y < host[k].height; ++y)
-			std::memcpy(out_base + host[k].offset_bytes + (size_t)y * host[k].pitch_bytes, stage + packed[k].offset_bytes + (size_t)y * row, row);
-	}
-	return first_bad;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2712,78 +2502,10 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	return PXZ_OK;
 }
 
-int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
-                            uint32_t n_images, uint32_t channels, const pxz_params *params, uint8_t *out_base, uint32_t *image_flags)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	const pxz_params p = decode_side_params(params, true);
-	int rc = varied_check_params(h, channels, &p);
-	if (rc != PXZ_OK) return rc;
-	std::vector<pxz::VariedImage> images;
-	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
-	uint64_t file_bytes = 0;
-	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "batch", &file_bytes)) != PXZ_OK) return rc;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	// device side: the files back to back behind their offsets; the images tightly packed (256-byte aligned starts)
-	std::vector<pxz_image_desc> dev(descs, descs + n_images);
-	uint64_t img_bytes = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		dev[i].offset_bytes = img_bytes;
-		dev[i].pitch_bytes = descs[i].width * channels;
-		img_bytes += ((uint64_t)dev[i].pitch_bytes * descs[i].height + 255u) & ~(uint64_t)255u;
-	}
-	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
-	const uint32_t n_tiles = varied_n_tiles(images);
-	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
-	const uint64_t meta = ((uint64_t)n_tiles * 12u + 255u) & ~(uint64_t)255u;
-	const uint64_t flags_at = meta + (uint64_t)n_tiles * slot;
-	std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, img_bytes);
-	if ((rc = ensure(h, h->varied_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
-	uint8_t *d_files = (uint8_t *)h->varied_files.ptr, *d_out = (uint8_t *)h->varied_out.ptr, *d_img = (uint8_t *)h->varied_in.ptr;
-	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
-	PXZ_HIP(h, hipMemsetAsync(d_out + meta, 0, (size_t)n_tiles * slot, h->stream));
-	PXZ_HIP(h, hipMemsetAsync(d_img, 0, img_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
-	const TileMeta m = carve_tile_meta(d_out, n_tiles);
-	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
-	if ((rc = pxz_decode_varied_frames_device(h, dev.data(), n_images, channels, &p, d_files + offs_bytes, (const uint64_t *)d_files, m.value,
-	                                          m.w, m.h, d_out + meta, d_flags)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, channels, &p, m.w, m.h, d_out + meta, d_img, d_flags + n_images)) != PXZ_OK)
-		return rc;
-	std::vector<uint32_t> flags(2u * (size_t)n_images);
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
-	PXZ_HIP(h, hipMemcpyAsync(stage.data(), d_img, img_bytes, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	uint32_t first_flags = 0;
-	const uint32_t first_bad = copy_out_owners(descs, dev.data(), n_images, channels, stage.data(), out_base, flags.data(), image_flags, &first_flags);
-	if (first_bad != n_images)
-		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
-		            first_flags);
-	return PXZ_OK;
-}
-
 }  // extern "C"
 
 // ---- re-shrink of stored tiles (pxz_reshrink.hip): the reference CLI's pix_to_pix (src/bin/main.rs:233-265) ---------------
 namespace {
-
-using pxz::kLdsPerCu;
-
-// the one place that says whether the re-shrink kernels take a block: the LDS footprint (what the launch asks for) against the
-// CU's.  rung_channels: 0 for reshrink_kernel, the tiles' channel count for reshrink_ladder_kernel, whose footprint depends on it
-// (its resampled images)
-int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
-{
-	if (pxz::reshrink_lds_bytes(mode, bw, bh, rung_channels, wdw) > kLdsPerCu)
-		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "a re-shrink%s keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
-		            "bytes, the whole 160 KB (%ux%u)", rung_channels ? " ladder" : "", bw, bh);
-	return PXZ_OK;
-}
 
 // both size queries: the footprint with the windows of expand_filter's tables
 int reshrink_lds_query(uint32_t block_w, uint32_t block_h, uint32_t rung_channels, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes)
@@ -2897,179 +2619,6 @@ int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc
 
 }  // extern "C"
 
-namespace {
-
-// Both host forms of pix_to_pix behind one body: factors == nullptr is pxz_transcode_varied_files (one rung, the caller's
-// params->factor, the one-factor calls); otherwise pxz_transcode_varied_ladder_files (n_factors rungs, the ladder calls, the
-// outputs rung-major and the writer over the descriptors repeated n_factors times).
-int transcode_varied(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *user_params,
-                     uint32_t expand_filter, const float *factors, uint32_t n_factors, uint32_t filter_byte, uint8_t *out,
-                     uint64_t out_capacity, uint64_t *file_offsets)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!files || !lens || !user_params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	const bool ladder = factors != nullptr;
-	pxz_params ladder_params = *user_params;
-	ladder_params.factor = 1.0f;  // (ignored by the ladder calls)
-	const pxz_params *params = ladder ? &ladder_params : user_params;
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	// every header first: the files must share channels and block size
-	std::vector<pxz_image_desc> descs(n_images);
-	uint32_t fbw = 0, fbh = 0, ch = 0;
-	uint64_t file_bytes = 0, raw = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
-		uint32_t w, hh, bw, bh, c, fb;
-		const char *why;
-		const int hrc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &c, &fb, &why);
-		if (hrc != PXZ_OK) return fail(h, hrc, "image %u: %s", i, why);
-		if (i == 0) {
-			fbw = bw;
-			fbh = bh;
-			ch = c;
-		} else if (bw != fbw || bh != fbh || c != ch) {
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u blocks of %u channels, image 0 holds %ux%u of %u", i, bw, bh, c, fbw, fbh, ch);
-		}
-		descs[i] = pxz_image_desc{w, hh, w * c, 0, 0};
-		file_bytes += lens[i];
-		raw += (uint64_t)w * hh * c;
-	}
-	const bool same_block = fbw == params->block_w && fbh == params->block_h;
-	pxz_params pin = *params;  // the files' own geometry
-	pin.block_w = fbw;
-	pin.block_h = fbh;
-	pin.filter = expand_filter;
-	int rc;
-	if (same_block) {
-		if ((rc = check_params(h, params)) != PXZ_OK) return rc;
-		if ((rc = reshrink_check_block(h, params->mode, fbw, fbh, ladder ? ch : 0u, 1u)) != PXZ_OK) return rc;
-	} else {
-		const pxz_params px = decode_side_params(&pin, true);
-		if ((rc = varied_check_params(h, ch, &px)) != PXZ_OK) return rc;
-		if ((rc = varied_check_params(h, ch, params)) != PXZ_OK) return rc;
-	}
-	std::vector<pxz::VariedImage> images_in, images_out;
-	if ((rc = varied_plan(h, descs.data(), n_images, fbw, fbh, 0, 0, &images_in, nullptr, nullptr)) != PXZ_OK) return rc;
-	if ((rc = varied_plan(h, descs.data(), n_images, params->block_w, params->block_h, ch, params->mode, &images_out, nullptr, nullptr)) != PXZ_OK)
-		return rc;
-	const uint32_t n_out = varied_n_tiles(images_out), n_in = varied_n_tiles(images_in);
-	if ((uint64_t)n_factors * n_out > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
-	const uint32_t n_all = n_factors * n_out, n_files = n_factors * n_images;  // (n_files: 2^32-1 at most, a file has a tile)
-	PXZ_HIP(h, hipSetDevice(h->device));
-
-	// the files back to back behind their offsets
-	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
-	const std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, 0);
-	if ((rc = ensure(h, h->transcode_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
-	uint8_t *d_files = (uint8_t *)h->transcode_files.ptr;
-	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
-
-	// the tiles that go to the writer, rung-major: values, sizes, slots, then the new files' offsets and the flags of both stages
-	const uint64_t slot_out = (uint64_t)params->block_w * params->block_h * ch;
-	const uint64_t meta_out = ((uint64_t)n_all * 12u + 255u) & ~(uint64_t)255u;
-	const uint64_t offs_at = (meta_out + (uint64_t)n_all * slot_out + 7u) & ~(uint64_t)7u;
-	const uint64_t out_offs_bytes = 8ull * ((uint64_t)n_files + 1u);
-	const uint64_t flags_at = offs_at + out_offs_bytes;
-	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
-	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
-	const TileMeta m = carve_tile_meta(d_out, n_all);  // (the reader fills rung 0 of each array)
-	uint8_t *d_slots = d_out + meta_out;
-	uint64_t *d_offs = (uint64_t *)(d_out + offs_at);
-	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
-
-	if (same_block) {
-		// reader -> re-shrink in place (the ladder: in place on rung 0) -> writer: nothing of image size anywhere
-		PXZ_HIP(h, hipMemsetAsync(d_out, 0, meta_out, h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
-		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, m.value, m.w,
-		                                          m.h, d_slots, d_flags)) != PXZ_OK)
-			return rc;
-		rc = ladder ? pxz_reshrink_varied_ladder_frames_device(h, descs.data(), n_images, ch, params, expand_filter, factors, n_factors, m.w, m.h,
-		                                                       d_slots, m.value, m.w, m.h, d_slots, d_flags + n_images)
-		            : pxz_reshrink_varied_frames_device(h, descs.data(), n_images, ch, params, expand_filter, m.w, m.h, d_slots, m.value, m.w, m.h,
-		                                                d_slots, d_flags + n_images);
-		if (rc != PXZ_OK) return rc;
-	} else {
-		// another block size: reader at the files' geometry -> the images in handle scratch -> the varied shrink at the new one
-		const uint64_t slot_in = (uint64_t)fbw * fbh * ch;
-		const uint64_t meta_in = ((uint64_t)n_in * 12u + 255u) & ~(uint64_t)255u;
-		if ((rc = ensure(h, h->transcode_tiles, meta_in + (uint64_t)n_in * slot_in)) != PXZ_OK) return rc;
-		uint8_t *d_tin = (uint8_t *)h->transcode_tiles.ptr;
-		const TileMeta mi = carve_tile_meta(d_tin, n_in);
-		std::vector<pxz_image_desc> dev = descs;
-		uint64_t img_bytes = 0;
-		for (uint32_t i = 0; i < n_images; ++i) {
-			dev[i].offset_bytes = img_bytes;
-			img_bytes += ((uint64_t)dev[i].pitch_bytes * dev[i].height + 255u) & ~(uint64_t)255u;
-		}
-		if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
-		uint8_t *d_img = (uint8_t *)h->varied_in.ptr;
-		PXZ_HIP(h, hipMemsetAsync(d_tin, 0, meta_in, h->stream));
-		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, mi.value,
-		                                          mi.w, mi.h, d_tin + meta_in, d_flags)) != PXZ_OK)
-			return rc;
-		if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, ch, &pin, mi.w, mi.h, d_tin + meta_in, d_img, d_flags + n_images)) != PXZ_OK)
-			return rc;
-		rc = ladder ? pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, ch, params, factors, n_factors, d_img, m.value, m.w, m.h, d_slots)
-		            : pxz_shrink_varied_frames_device(h, dev.data(), n_images, ch, params, d_img, m.value, m.w, m.h, d_slots);
-		if (rc != PXZ_OK) return rc;
-	}
-	// all or nothing: a malformed file or a tile that cannot be stops the call before the writer runs
-	std::vector<uint32_t> flags(2u * (size_t)n_images);
-	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	for (uint32_t i = 0; i < n_images; ++i)
-		if (flags[i] | flags[n_images + i])
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); nothing was written", i,
-			            flags[i] | flags[n_images + i]);
-
-	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
-	std::vector<pxz_image_desc> rung_descs;  // the descriptors once per rung
-	rung_descs.reserve(n_files);
-	for (uint32_t r = 0; r < n_factors; ++r) rung_descs.insert(rung_descs.end(), descs.begin(), descs.end());
-	uint64_t cap = (raw + raw / 4u + 64ull * n_out + 4096ull * n_images) * n_factors;
-	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
-	for (int pass = 0; pass < 2; ++pass) {
-		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
-		if ((rc = pxz_encode_varied_frames_device(h, rung_descs.data(), n_files, ch, params, filter_byte, m.value, m.w, m.h, d_slots,
-		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
-			return rc;
-		PXZ_HIP(h, hipMemcpyAsync(file_offsets, d_offs, out_offs_bytes, hipMemcpyDeviceToHost, h->stream));
-		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		if (file_offsets[n_files] <= cap) break;
-		cap = file_offsets[n_files];
-	}
-	const uint64_t total = file_offsets[n_files];
-	if (!out || out_capacity < total)
-		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
-		            (unsigned long long)out_capacity);
-	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
-	return PXZ_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
-                               const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
-                               uint64_t out_capacity, uint64_t *file_offsets)
-{
-	return transcode_varied(h, files, lens, n_images, params, expand_filter, nullptr, 1u, filter_byte, out, out_capacity, file_offsets);
-}
-
-int pxz_transcode_varied_ladder_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
-                                      const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors,
-                                      uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	return transcode_varied(h, files, lens, n_images, params, expand_filter, factors, n_factors, filter_byte, out, out_capacity, file_offsets);
-}
-
-}  // extern "C"
-
 // ---- rate and distortion (pxz_distortion.hip) -----------------------------------------------------------------------------
 namespace {
 
@@ -3151,121 +2700,7 @@ int pxz_distortion_varied_frames_device(pxz_handle *h, const pxz_image_desc *des
 	return distortion_launch(h, images, sides, channels, p, 1, d_base, d_tile_w, d_tile_h, d_slots, d_tile_sse, d_image_sse, d_image_flags);
 }
 
-int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
-                              uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
-                              uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
-	if (n_factors == 0 || n_factors > PXZ_LADDER_MAX_RUNGS)
-		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_LADDER_MAX_RUNGS, n_factors);
-	if (!pixels || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
-	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
-	int rc = check_params(h, &up);
-	if (rc != PXZ_OK) return rc;
-	pxz_frames f;
-	size_t tiles = 0, slot = 0;
-	if ((rc = stage_host_image(h, pixels, width, height, channels, pitch_bytes, &p, n_factors, true, &f, &tiles, &slot)) != PXZ_OK) return rc;
-	// the files' offsets, the rungs' sums, and the room the writer is given (none: only its offsets are wanted)
-	const size_t n_out = (size_t)n_factors + 1u + (size_t)n_factors * channels;
-	if ((rc = ensure(h, h->rd, n_out * 8u + 256u)) != PXZ_OK) return rc;
-	uint64_t *d_offs = (uint64_t *)h->rd.ptr, *d_sse = d_offs + n_factors + 1u;
-	const uint8_t *d_in = (const uint8_t *)h->in.ptr;
-	float *d_val = (float *)h->val.ptr;
-	uint32_t *d_w = (uint32_t *)h->ow.ptr, *d_h = (uint32_t *)h->oh.ptr;
-	uint8_t *d_slots = (uint8_t *)h->out.ptr;
-	if ((rc = pxz_shrink_ladder_frames_device(h, &f, &p, factors, n_factors, d_in, d_val, d_w, d_h, d_slots)) != PXZ_OK) return rc;
-	pxz_frames rungs = f;  // the rung sets as a batch of n_factors frames
-	rungs.n_frames = n_factors;
-	rungs.frame_stride_bytes = (uint64_t)f.pitch_bytes * height;
-	if ((rc = pxz_encode_frames_device(h, &rungs, &p, 0, d_val, d_w, d_h, d_slots, (uint8_t *)(d_offs + n_out), 0, d_offs)) != PXZ_OK) return rc;
-	if ((rc = pxz_distortion_frames_device(h, &f, &up, n_factors, d_in, d_w, d_h, d_slots, nullptr, d_sse)) != PXZ_OK) return rc;
-	std::vector<uint64_t> got(n_out);
-	PXZ_HIP(h, hipMemcpyAsync(got.data(), d_offs, n_out * 8u, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	for (uint32_t r = 0; r < n_factors; ++r) file_bytes[r] = got[r + 1u] - got[r];
-	std::memcpy(sse, got.data() + n_factors + 1u, (size_t)n_factors * channels * 8u);
-	return PXZ_OK;
-}
-
-int pxz_rate_distortion_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
-                                      uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
-                                      uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!pixels || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
-	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
-	if ((rc = check_params(h, &up)) != PXZ_OK) return rc;
-	if ((rc = varied_check_params(h, channels, &p)) != PXZ_OK) return rc;
-	std::vector<pxz::VariedImage> images;
-	if ((rc = varied_plan(h, descs, n_images, block_w, block_h, channels, mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
-	for (uint32_t i = 0; i < n_images; ++i)
-		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
-	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * varied_n_tiles(images);
-	if (tiles > 0xffffffffull || n_sets > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
-	PXZ_HIP(h, hipSetDevice(h->device));
-	std::vector<pxz_image_desc> dev;
-	uint64_t raw = 0;
-	if ((rc = varied_send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
-	// every rung's tiles, then the files' offsets, the sums, and the room the writer is given (none: only its offsets are wanted)
-	const uint64_t slot = (uint64_t)block_w * block_h * channels;
-	const uint64_t meta = (tiles * 12u + 255u) & ~(uint64_t)255u;
-	const size_t n_out = (size_t)n_sets + 1u + (size_t)n_sets * channels;
-	if ((rc = ensure(h, h->varied_out, meta + tiles * slot)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->rd, n_out * 8u + 256u)) != PXZ_OK) return rc;
-	const uint8_t *d_in = (const uint8_t *)h->varied_in.ptr;
-	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
-	float *d_val = (float *)d_out;
-	uint32_t *d_w = (uint32_t *)(d_out + tiles * 4u), *d_h = (uint32_t *)(d_out + tiles * 8u);
-	uint8_t *d_slots = d_out + meta;
-	uint64_t *d_offs = (uint64_t *)h->rd.ptr, *d_sse = d_offs + n_sets + 1u;
-	if ((rc = pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, channels, &p, factors, n_factors, d_in, d_val, d_w, d_h,
-	                                                 d_slots)) != PXZ_OK)
-		return rc;
-	// the rung sets as a varied batch of n_factors * n_images images
-	std::vector<pxz_image_desc> rungs;
-	rungs.reserve((size_t)n_sets);
-	for (uint32_t r = 0; r < n_factors; ++r) rungs.insert(rungs.end(), dev.begin(), dev.end());
-	if ((rc = pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &p, 0, d_val, d_w, d_h, d_slots,
-	                                          (uint8_t *)(d_offs + n_out), 0, d_offs)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &up, d_in, d_w, d_h, d_slots, nullptr, d_sse,
-	                                              nullptr)) != PXZ_OK)
-		return rc;
-	std::vector<uint64_t> got(n_out);
-	PXZ_HIP(h, hipMemcpyAsync(got.data(), d_offs, n_out * 8u, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	for (uint64_t k = 0; k < n_sets; ++k) file_bytes[k] = got[k + 1u] - got[k];
-	std::memcpy(sse, got.data() + n_sets + 1u, (size_t)n_sets * channels * 8u);
-	return PXZ_OK;
-}
-
-}  // extern "C"
-
 // ---- fit to a budget: one rung per image, chosen and gathered on the device (pxz_fit.h, pxz_fit.hip) ----------------------
-namespace {
-
-// what pxz_fit_select and pxz_fit_varied_ladder_device check of their sizes (h may be null: the host form has no handle)
-int fit_check(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion)
-{
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	if (n_factors == 0 || n_factors > PXZ_VARIED_LADDER_MAX_RUNGS)
-		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_VARIED_LADDER_MAX_RUNGS, n_factors);
-	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
-		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
-	return PXZ_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int pxz_fit_select(uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion, const uint64_t *targets,
                    const uint64_t *file_bytes, const uint64_t *sse, uint32_t *choice, uint32_t *fit_flags)
 {
@@ -3356,235 +2791,7 @@ int pxz_gather_varied_rungs_device(pxz_handle *h, const pxz_image_desc *descs, u
 	return PXZ_OK;
 }
 
-int pxz_encode_varied_images_fit(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
-                                 uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
-                                 uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
-                                 const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity,
-                                 uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes, uint64_t *table_sse)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
-	if (!pixels || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
-	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
-	if ((rc = check_params(h, &up)) != PXZ_OK) return rc;
-	if ((rc = varied_check_params(h, channels, &p)) != PXZ_OK) return rc;
-	std::vector<pxz::VariedImage> images;
-	if ((rc = varied_plan(h, descs, n_images, block_w, block_h, channels, mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
-	if ((rc = fit_check(h, n_images, n_factors, channels, criterion)) != PXZ_OK) return rc;
-	for (uint32_t i = 0; i < n_images; ++i)
-		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
-	const uint32_t n_tiles = varied_n_tiles(images);
-	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * n_tiles;
-	if (tiles > 0xffffffffull || n_sets > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
-	PXZ_HIP(h, hipSetDevice(h->device));
-	std::vector<pxz_image_desc> dev;
-	uint64_t raw = 0;
-	if ((rc = varied_send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
-	// every rung's tiles (varied_out) and the chosen rungs' (fit_tiles); and in one block, so that one copy brings it back: the
-	// table (the rung files' offsets, the sums), the chosen files' offsets, the choices and the flags -- with the room the first
-	// writer is given behind it (none: only its offsets are wanted)
-	auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
-	const uint64_t slot = (uint64_t)block_w * block_h * channels;
-	const uint64_t meta_all = up256(tiles * 12u), meta_fit = up256((uint64_t)n_tiles * 12u);
-	const size_t n_table = (size_t)n_sets + 1u + (size_t)n_sets * channels;
-	const size_t n_down = n_table + (size_t)n_images + 1u + (size_t)n_images;  // u64s (a choice and a flag: one u64 together)
-	if ((rc = ensure(h, h->varied_out, meta_all + tiles * slot)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->fit_tiles, meta_fit + (uint64_t)n_tiles * slot)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->rd, n_down * 8u + 256u)) != PXZ_OK) return rc;
-	const uint8_t *d_in = (const uint8_t *)h->varied_in.ptr;
-	uint8_t *d_all = (uint8_t *)h->varied_out.ptr, *d_fit = (uint8_t *)h->fit_tiles.ptr;
-	const TileMeta all = carve_tile_meta(d_all, (uint32_t)tiles), fit = carve_tile_meta(d_fit, n_tiles);
-	uint64_t *d_rung_offs = (uint64_t *)h->rd.ptr, *d_sse = d_rung_offs + n_sets + 1u, *d_offs = d_rung_offs + n_table;
-	uint32_t *d_choice = (uint32_t *)(d_offs + n_images + 1u), *d_flags = d_choice + n_images;
-	// 2. the ladder; 3. the writer over the rung images, for its offsets; 4. their distortion
-	if ((rc = pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, channels, &p, factors, n_factors, d_in, all.value, all.w, all.h,
-	                                                 d_all + meta_all)) != PXZ_OK)
-		return rc;
-	std::vector<pxz_image_desc> rungs;
-	rungs.reserve((size_t)n_sets);
-	for (uint32_t r = 0; r < n_factors; ++r) rungs.insert(rungs.end(), dev.begin(), dev.end());
-	if ((rc = pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &p, 0, all.value, all.w, all.h, d_all + meta_all,
-	                                          (uint8_t *)(d_rung_offs + n_down), 0, d_rung_offs)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)n_sets, channels, &up, d_in, all.w, all.h, d_all + meta_all, nullptr,
-	                                              d_sse, nullptr)) != PXZ_OK)
-		return rc;
-	// 5. one rung per image; 6. its tiles as a varied batch of the images themselves
-	if ((rc = pxz_fit_varied_ladder_device(h, n_images, n_factors, channels, criterion, targets, d_rung_offs, d_sse, d_choice, d_flags)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_gather_varied_rungs_device(h, dev.data(), n_images, channels, &p, n_factors, d_choice, all.value, all.w, all.h, d_all + meta_all,
-	                                         fit.value, fit.w, fit.h, d_fit + meta_fit, nullptr)) != PXZ_OK)
-		return rc;
-	// 7. the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
-	std::vector<uint64_t> got(n_down);
-	uint64_t cap = raw + raw / 4u + 64ull * n_tiles + 4096ull * n_images;
-	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
-	for (int pass = 0; pass < 2; ++pass) {
-		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
-		if ((rc = pxz_encode_varied_frames_device(h, dev.data(), n_images, channels, &p, filter_byte, fit.value, fit.w, fit.h, d_fit + meta_fit,
-		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
-			return rc;
-		if (pass == 0) PXZ_HIP(h, hipMemcpyAsync(got.data(), d_rung_offs, n_down * 8u, hipMemcpyDeviceToHost, h->stream));
-		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		if (got[n_table + n_images] <= cap) break;
-		cap = got[n_table + n_images];
-	}
-	if (table_bytes)
-		for (uint64_t k = 0; k < n_sets; ++k) table_bytes[k] = got[k + 1u] - got[k];
-	if (table_sse) std::memcpy(table_sse, got.data() + n_sets + 1u, (size_t)n_sets * channels * 8u);
-	std::memcpy(file_offsets, got.data() + n_table, ((size_t)n_images + 1u) * 8u);
-	const uint32_t *picked = reinterpret_cast<const uint32_t *>(got.data() + n_table + n_images + 1u);
-	std::memcpy(choice, picked, (size_t)n_images * 4u);
-	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
-	const uint64_t total = file_offsets[n_images];
-	if (!out || out_capacity < total)
-		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
-		            (unsigned long long)out_capacity);
-	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
-	return PXZ_OK;
-}
-
-}  // extern "C"
-
 // ---- fit an archive to a budget: the error of re-shrunk tiles against the archive's own (pxz_reshrink_distortion.hip) -------
-namespace {
-
-// LDS bytes of a one-wave block of reshrink_distortion_kernel: the wave's image of the launch's own layout function beside the
-// images' first tiles at their largest (kVxImages dwords, pxz_device.h) -- what the entry point and the size query hold against
-// kLdsPerCu, so that a block the query admits is launched whatever n_images is
-uint64_t reshrink_distortion_bytes(uint32_t bw, uint32_t bh, uint32_t wdw)
-{
-	const uint32_t dw = pxz::reshrink_distortion_tile_dw(bw, bh, wdw);
-	return dw == 0xffffffffu ? 0xffffffffull : (uint64_t)dw * 4u + 8192u;
-}
-
-// What both archive forms share, from the headers to the distortion call: the files parsed and uploaded, the reader into a
-// buffer of its own (NOT rung 0: the reference is kept), the re-shrink ladder out of place into varied_out, the flags of both
-// checked (all or nothing, as transcode_varied), the writer over the K * n rung images with no room for its offsets, and the
-// distortion call.  rd holds, in one block for one download: the rung files' offsets (n_sets + 1), the sums (n_sets * ch), and
-// `extra` more u64s for the caller, with the room the offsets-only writer is given behind them.
-struct ArchiveRungs {
-	std::vector<pxz_image_desc> descs, rungs;  // the files' images; the same once per rung
-	pxz_params p;                              // params with factor 1 (ignored by the ladder calls)
-	uint32_t ch = 0, n_tiles = 0;
-	uint64_t n_sets = 0, tiles = 0, raw = 0, slot = 0, meta_all = 0;
-	size_t n_table = 0;
-	TileMeta all{};
-	uint8_t *d_all = nullptr;
-	uint64_t *d_rung_offs = nullptr, *d_sse = nullptr;
-};
-
-int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
-                  uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, size_t extra, ArchiveRungs *s)
-{
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	if (filter_up > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter_up must be 0..4, got %u", filter_up);
-	s->p = *params;
-	s->p.factor = 1.0f;
-	int rc = check_params(h, &s->p);
-	if (rc != PXZ_OK) return rc;
-	// every header first: the files must share channels and block size, and the block size must be params'
-	s->descs.resize(n_images);
-	uint32_t fbw = 0, fbh = 0, ch = 0;
-	uint64_t file_bytes = 0;
-	for (uint32_t i = 0; i < n_images; ++i) {
-		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
-		uint32_t w, hh, bw, bh, c, fb;
-		const char *why;
-		const int hrc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &c, &fb, &why);
-		if (hrc != PXZ_OK) return fail(h, hrc, "image %u: %s", i, why);
-		if (i == 0) {
-			fbw = bw;
-			fbh = bh;
-			ch = c;
-		} else if (bw != fbw || bh != fbh || c != ch) {
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u blocks of %u channels, image 0 holds %ux%u of %u", i, bw, bh, c, fbw, fbh, ch);
-		}
-		s->descs[i] = pxz_image_desc{w, hh, w * c, 0, 0};
-		file_bytes += lens[i];
-		s->raw += (uint64_t)w * hh * c;
-	}
-	if (fbw != s->p.block_w || fbh != s->p.block_h)
-		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "the files hold %ux%u blocks, params ask for %ux%u: the error without the image needs an unchanged block size (decode the files and "
-		            "use the image calls)", fbw, fbh, s->p.block_w, s->p.block_h);
-	if ((rc = reshrink_check_block(h, s->p.mode, fbw, fbh, ch, 1u)) != PXZ_OK) return rc;
-	if (reshrink_distortion_bytes(fbw, fbh, 1u) > kLdsPerCu)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "the distortion of re-shrunk tiles keeps three planes of block_w*block_h dwords in LDS (%ux%u)", fbw, fbh);
-	std::vector<pxz::VariedImage> images;
-	if ((rc = varied_plan(h, s->descs.data(), n_images, fbw, fbh, ch, s->p.mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
-	s->ch = ch;
-	s->n_tiles = varied_n_tiles(images);
-	s->n_sets = (uint64_t)n_factors * n_images;
-	s->tiles = (uint64_t)n_factors * s->n_tiles;
-	if (s->tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
-	PXZ_HIP(h, hipSetDevice(h->device));
-
-	// the files back to back behind their offsets
-	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
-	const std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, 0);
-	if ((rc = ensure(h, h->transcode_files, offs_bytes + file_bytes + 16u)) != PXZ_OK) return rc;
-	uint8_t *d_files = (uint8_t *)h->transcode_files.ptr;
-	PXZ_HIP(h, hipMemcpyAsync(d_files, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
-
-	// the archive's tiles and the flags of the reader and the re-shrink (archive_tiles); every rung's tiles (varied_out)
-	auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
-	s->slot = (uint64_t)fbw * fbh * ch;
-	s->meta_all = up256(s->tiles * 12u);
-	const uint64_t meta_ref = up256((uint64_t)s->n_tiles * 12u), flags_at = up256(meta_ref + (uint64_t)s->n_tiles * s->slot);
-	s->n_table = (size_t)s->n_sets + 1u + (size_t)s->n_sets * ch;
-	if ((rc = ensure(h, h->archive_tiles, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->varied_out, s->meta_all + s->tiles * s->slot)) != PXZ_OK) return rc;
-	if ((rc = ensure(h, h->rd, (s->n_table + extra) * 8u + 256u)) != PXZ_OK) return rc;
-	uint8_t *d_ref = (uint8_t *)h->archive_tiles.ptr;
-	const TileMeta ref = carve_tile_meta(d_ref, s->n_tiles);
-	uint32_t *d_flags = (uint32_t *)(d_ref + flags_at);
-	s->d_all = (uint8_t *)h->varied_out.ptr;
-	s->all = carve_tile_meta(s->d_all, (uint32_t)s->tiles);
-	s->d_rung_offs = (uint64_t *)h->rd.ptr;
-	s->d_sse = s->d_rung_offs + s->n_sets + 1u;
-
-	// reader -> the reference; ladder out of place -> the rungs
-	pxz_params pin = s->p;
-	pin.filter = expand_filter;
-	PXZ_HIP(h, hipMemsetAsync(d_ref, 0, meta_ref, h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
-	if ((rc = pxz_decode_varied_frames_device(h, s->descs.data(), n_images, ch, &pin, d_files + offs_bytes, (const uint64_t *)d_files, ref.value, ref.w,
-	                                          ref.h, d_ref + meta_ref, d_flags)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_reshrink_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, &s->p, expand_filter, factors, n_factors, ref.w, ref.h,
-	                                                   d_ref + meta_ref, s->all.value, s->all.w, s->all.h, s->d_all + s->meta_all,
-	                                                   d_flags + n_images)) != PXZ_OK)
-		return rc;
-	// all or nothing: a malformed file or a tile that cannot be stops the call before the writer runs
-	std::vector<uint32_t> flags(2u * (size_t)n_images);
-	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	for (uint32_t i = 0; i < n_images; ++i)
-		if (flags[i] | flags[n_images + i])
-			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); nothing was written", i,
-			            flags[i] | flags[n_images + i]);
-
-	// the writer over the rung images, for its offsets; their distortion against the reference
-	s->rungs.reserve((size_t)s->n_sets);
-	for (uint32_t r = 0; r < n_factors; ++r) s->rungs.insert(s->rungs.end(), s->descs.begin(), s->descs.end());
-	if ((rc = pxz_encode_varied_frames_device(h, s->rungs.data(), (uint32_t)s->n_sets, ch, &s->p, 0, s->all.value, s->all.w, s->all.h,
-	                                          s->d_all + s->meta_all, (uint8_t *)(s->d_rung_offs + s->n_table + extra), 0, s->d_rung_offs)) != PXZ_OK)
-		return rc;
-	pxz_params up = s->p;
-	up.filter = filter_up;
-	return pxz_reshrink_distortion_varied_device(h, s->descs.data(), n_images, ch, &up, expand_filter, n_factors, ref.w, ref.h, d_ref + meta_ref,
-	                                             s->all.w, s->all.h, s->d_all + s->meta_all, nullptr, s->d_sse, nullptr);
-}
-
-}  // namespace
-
-extern "C" {
-
 int pxz_reshrink_distortion_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t expand_filter, uint32_t filter_up,
                                       uint32_t *lds_bytes)
 {
@@ -3671,87 +2878,10 @@ int pxz_reshrink_distortion_varied_device(pxz_handle *h, const pxz_image_desc *d
 	return PXZ_OK;
 }
 
-int pxz_rate_distortion_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
-                                     const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
-                                     uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!files || !lens || !params || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	ArchiveRungs s;
-	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, 0, &s)) != PXZ_OK) return rc;
-	std::vector<uint64_t> got(s.n_table);
-	PXZ_HIP(h, hipMemcpyAsync(got.data(), s.d_rung_offs, s.n_table * 8u, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	for (uint64_t k = 0; k < s.n_sets; ++k) file_bytes[k] = got[k + 1u] - got[k];
-	std::memcpy(sse, got.data() + s.n_sets + 1u, (size_t)s.n_sets * s.ch * 8u);
-	return PXZ_OK;
-}
-
-int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
-                                   const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
-                                   uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
-                                   uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes,
-                                   uint64_t *table_sse)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
-	if (!files || !lens || !params || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
-		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
-	// behind the table, for the one download: the chosen files' offsets, the choices and the flags (a choice and a flag: one u64)
-	const size_t extra = (size_t)n_images + 1u + (size_t)n_images;
-	ArchiveRungs s;
-	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, extra, &s)) != PXZ_OK) return rc;
-	const size_t n_down = s.n_table + extra;
-	uint64_t *d_offs = s.d_rung_offs + s.n_table;
-	uint32_t *d_choice = (uint32_t *)(d_offs + n_images + 1u), *d_flags = d_choice + n_images;
-	const uint64_t meta_fit = ((uint64_t)s.n_tiles * 12u + 255u) & ~(uint64_t)255u;
-	if ((rc = ensure(h, h->fit_tiles, meta_fit + (uint64_t)s.n_tiles * s.slot)) != PXZ_OK) return rc;
-	uint8_t *d_fit = (uint8_t *)h->fit_tiles.ptr;
-	const TileMeta fit = carve_tile_meta(d_fit, s.n_tiles);
-	// one rung per file; its tiles as a varied batch of the files' images
-	if ((rc = pxz_fit_varied_ladder_device(h, n_images, n_factors, s.ch, criterion, targets, s.d_rung_offs, s.d_sse, d_choice, d_flags)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_gather_varied_rungs_device(h, s.descs.data(), n_images, s.ch, &s.p, n_factors, d_choice, s.all.value, s.all.w, s.all.h,
-	                                         s.d_all + s.meta_all, fit.value, fit.w, fit.h, d_fit + meta_fit, nullptr)) != PXZ_OK)
-		return rc;
-	// the files: a first guess at their room, and one more writer pass when it was short (the offsets are exact either way)
-	std::vector<uint64_t> got(n_down);
-	uint64_t cap = s.raw + s.raw / 4u + 64ull * s.n_tiles + 4096ull * n_images;
-	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
-	for (int pass = 0; pass < 2; ++pass) {
-		if ((rc = ensure(h, h->varied_files, cap)) != PXZ_OK) return rc;
-		if ((rc = pxz_encode_varied_frames_device(h, s.descs.data(), n_images, s.ch, &s.p, filter_byte, fit.value, fit.w, fit.h, d_fit + meta_fit,
-		                                          (uint8_t *)h->varied_files.ptr, cap, d_offs)) != PXZ_OK)
-			return rc;
-		if (pass == 0) PXZ_HIP(h, hipMemcpyAsync(got.data(), s.d_rung_offs, n_down * 8u, hipMemcpyDeviceToHost, h->stream));
-		PXZ_HIP(h, hipStreamSynchronize(h->stream));
-		if (got[s.n_table + n_images] <= cap) break;
-		cap = got[s.n_table + n_images];
-	}
-	if (table_bytes)
-		for (uint64_t k = 0; k < s.n_sets; ++k) table_bytes[k] = got[k + 1u] - got[k];
-	if (table_sse) std::memcpy(table_sse, got.data() + s.n_sets + 1u, (size_t)s.n_sets * s.ch * 8u);
-	std::memcpy(file_offsets, got.data() + s.n_table, ((size_t)n_images + 1u) * 8u);
-	const uint32_t *picked = reinterpret_cast<const uint32_t *>(got.data() + s.n_table + n_images + 1u);
-	std::memcpy(choice, picked, (size_t)n_images * 4u);
-	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
-	const uint64_t total = file_offsets[n_images];
-	if (!out || out_capacity < total)
-		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
-		            (unsigned long long)out_capacity);
-	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
-	return PXZ_OK;
-}
-
 }  // extern "C"
 
 // ---- pixel windows of files (window_index_kernel in pxz_stream.hip, pxz_window.hip) ---------------------------------------
-namespace {
+namespace pxz_runtime {
 
 // The per-window table of a call, checked window by window before anything is launched.  channels 0: geometry only
 // (pxz_window_layout, the decode stage), no pitch rule.  sides: the block sides and the edge sizes of the images the windows
@@ -3808,8 +2938,9 @@ int window_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, c
 	return PXZ_OK;
 }
 
-// the covered tiles of a planned call
-uint32_t window_n_tiles(const std::vector<pxz::WindowEntry> &entries) { return entries.back().tile0 + entries.back().ccols * entries.back().crows; }
+}  // namespace pxz_runtime
+
+namespace {
 
 // the per-window table -> handle scratch, as varied_upload sends the per-image table: one copy
 int window_upload(pxz_handle *h, const std::vector<pxz::WindowEntry> &entries, const pxz::WindowEntry **d_windows)
@@ -3892,65 +3023,6 @@ int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32
 	a.window_flags = d_window_flags;
 	if ((rc = window_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_window_expand(a, channels, h->n_cus, h->stream));
-	return PXZ_OK;
-}
-
-int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
-                             const pxz_window *windows, uint32_t n_windows, uint32_t channels, const pxz_params *params, uint8_t *out_base,
-                             uint64_t out_bytes, uint32_t *window_flags)
-{
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	const pxz_params p = decode_side_params(params, true);
-	int rc = varied_check_params(h, channels, &p);
-	if (rc != PXZ_OK) return rc;
-	std::vector<pxz::WindowEntry> entries;
-	if ((rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, channels, &entries, nullptr, nullptr)) != PXZ_OK) return rc;
-	for (uint32_t k = 0; k < n_windows; ++k) {
-		const pxz_window &g = windows[k];
-		if (g.offset_bytes > out_bytes || (uint64_t)(g.height - 1u) * g.pitch_bytes + (uint64_t)g.width * channels > out_bytes - g.offset_bytes)
-			return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "window %u: its output ends behind the %llu bytes of the buffer", k, (unsigned long long)out_bytes);
-	}
-	uint64_t file_bytes = 0;
-	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "call", &file_bytes)) != PXZ_OK) return rc;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	// device side, one buffer: the files back to back behind their offsets | values and sizes of the covered tiles | their
-	// slots | the crops tightly packed (256-byte aligned starts) with the two flag arrays behind them
-	auto up256 = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
-	std::vector<pxz_window> dev(windows, windows + n_windows);
-	uint64_t crop_bytes = 0;
-	for (uint32_t k = 0; k < n_windows; ++k) {
-		dev[k].offset_bytes = crop_bytes;
-		dev[k].pitch_bytes = windows[k].width * channels;
-		crop_bytes += up256((uint64_t)dev[k].pitch_bytes * windows[k].height);
-	}
-	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
-	const uint32_t n_tiles = window_n_tiles(entries);
-	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
-	const uint64_t meta_at = up256(offs_bytes + file_bytes + 16u), slots_at = meta_at + up256((uint64_t)n_tiles * 12u);
-	const uint64_t crops_at = slots_at + up256((uint64_t)n_tiles * slot), flags_at = crops_at + crop_bytes, down_bytes = crop_bytes + 8ull * n_windows;
-	std::vector<uint8_t> stage = stage_files(files, lens, n_images, file_bytes, down_bytes);
-	if ((rc = ensure(h, h->window_host, flags_at + 8ull * n_windows)) != PXZ_OK) return rc;
-	uint8_t *d = (uint8_t *)h->window_host.ptr;
-	PXZ_HIP(h, hipMemcpyAsync(d, stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
-	PXZ_HIP(h, hipMemsetAsync(d + crops_at, 0, down_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
-	const TileMeta m = carve_tile_meta(d + meta_at, n_tiles);
-	uint32_t *d_flags = (uint32_t *)(d + flags_at);
-	if ((rc = pxz_decode_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, d + offs_bytes, (const uint64_t *)d, m.value, m.w, m.h,
-	                                    d + slots_at, d_flags)) != PXZ_OK)
-		return rc;
-	if ((rc = pxz_expand_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, m.w, m.h, d + slots_at, d + crops_at,
-	                                    d_flags + n_windows)) != PXZ_OK)
-		return rc;
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
-	PXZ_HIP(h, hipMemcpyAsync(stage.data(), d + crops_at, down_bytes, hipMemcpyDeviceToHost, h->stream));
-	PXZ_HIP(h, hipStreamSynchronize(h->stream));
-	const uint32_t *flags = reinterpret_cast<const uint32_t *>(stage.data() + crop_bytes);
-	uint32_t first_flags = 0;
-	const uint32_t first_bad = copy_out_owners(windows, dev.data(), n_windows, channels, stage.data(), out_base, flags, window_flags, &first_flags);
-	if (first_bad != n_windows)
-		return fail(h, PXZ_ERR_INVALID_ARG, "window %u: malformed .pixlzr file or record in what it reads of image %u (flags %u); the other windows are complete",
-		            first_bad, windows[first_bad].image, first_flags);
 	return PXZ_OK;
 }
 

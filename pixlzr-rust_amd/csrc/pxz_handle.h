@@ -1,4 +1,4 @@
-// pxz_handle.h — owners of what a pxz_handle holds on the device and in pinned host memory (private to pxz_api.cpp).
+// pxz_handle.h — owners of what a pxz_handle holds on the device and in pinned host memory (private to the host runtime: pxz_runtime.h).
 // Each frees what it holds in its destructor and is move-only, so that a handle, a cache entry or the scratch part of
 // a handle that is destroyed, evicted or replaced gives its memory back without anyone listing it.
 #pragma once

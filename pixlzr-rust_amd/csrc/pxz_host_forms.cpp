@@ -1,0 +1,754 @@
+// pxz_host_forms.cpp — the host forms: entry points of include/pixlzr_hip.h that take host pointers and compose the device
+// entry points of pxz_api.cpp through the public C ABI -- reader, ladder, writer, distortion, fit and gather -- around
+// handle scratch.  What the forms share stands once, up front: the header scan, the files' way up, the layout of a tile set
+// and of the packed images, the flags check, the rung table, the writer's two passes and the fit tail.  From the runtime they
+// take what pxz_runtime.h declares; of the handle they touch the scratch buffers, `stream` and `device`.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/pixlzr_hip.h"
+#include "pxz_launch.h"
+#include "pxz_runtime.h"
+
+namespace {
+
+using namespace pxz_runtime;
+using pxz::kLdsPerCu;
+
+// A set of stored tiles in device memory: values, widths and heights (twelve bytes a tile, rounded up to 256), with the slots
+// behind them.
+struct TileSet {
+	float *value;
+	uint32_t *w, *h;
+	uint8_t *slots;
+	static uint64_t meta_bytes(uint64_t n_tiles) { return up256(n_tiles * 12u); }
+	static uint64_t bytes(uint64_t n_tiles, uint64_t slot_bytes) { return meta_bytes(n_tiles) + n_tiles * slot_bytes; }
+	TileSet(uint8_t *d = nullptr, uint64_t n_tiles = 0)
+	    : value((float *)d), w((uint32_t *)(d + n_tiles * 4u)), h((uint32_t *)(d + n_tiles * 8u)), slots(d + meta_bytes(n_tiles)) {}
+};
+
+// The packed layout of n owners (pxz_image_desc or pxz_window) in device memory: tight pitch, starts aligned to 256 bytes.
+// Returns the bytes of all.
+template <class Owner>
+uint64_t pack_owners(std::vector<Owner> *dev, uint32_t channels)
+{
+	uint64_t bytes = 0;
+	for (Owner &o : *dev) {
+		o.offset_bytes = bytes;
+		o.pitch_bytes = o.width * channels;
+		bytes += up256((uint64_t)o.pitch_bytes * o.height);
+	}
+	return bytes;
+}
+
+// The way back of n owners (pxz_image_desc or pxz_window): owner k's rows, tightly packed at packed[k].offset_bytes of stage,
+// go to the caller's place and pitch (host[k]); flags holds the decode stage's n flags, then the expand stage's, merged into
+// out_flags (or null).  Returns the first owner with a flag (n: none) and, in *first_flags, what it has.
+template <class Owner>
+uint32_t copy_out_owners(const Owner *host, const Owner *packed, uint32_t n, uint32_t channels, const uint8_t *stage, uint8_t *out_base,
+                         const uint32_t *flags, uint32_t *out_flags, uint32_t *first_flags)
+{
+	uint32_t first_bad = n;
+	for (uint32_t k = 0; k < n; ++k) {
+		const uint32_t fl = flags[k] | flags[n + k];
+		if (out_flags) out_flags[k] = fl;
+		if (fl && first_bad == n) {
+			first_bad = k;
+			*first_flags = fl;
+		}
+		const size_t row = (size_t)host[k].width * channels;
+		for (uint32_t y = 0; y < host[k].height; ++y)
+			std::memcpy(out_base + host[k].offset_bytes + (size_t)y * host[k].pitch_bytes, stage + packed[k].offset_bytes + (size_t)y * row, row);
+	}
+	return first_bad;
+}
+
+// The host forms' images (checked, none null) into handle scratch, back to back with 256-byte aligned starts: *dev are their
+// descriptors there, *raw the bytes of their pixels.
+int send_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                std::vector<pxz_image_desc> *dev, uint64_t *raw)
+{
+	dev->assign(descs, descs + n_images);
+	auto bytes_of = [&](uint32_t i) { return (uint64_t)descs[i].pitch_bytes * (descs[i].height - 1) + (uint64_t)descs[i].width * channels; };
+	uint64_t in_bytes = 0;
+	*raw = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		(*dev)[i].offset_bytes = in_bytes;
+		in_bytes += up256(bytes_of(i));
+		*raw += (uint64_t)descs[i].width * descs[i].height * channels;
+	}
+	const int rc = ensure(h, h->varied_in, in_bytes);
+	if (rc != PXZ_OK) return rc;
+	uint8_t *d_in = (uint8_t *)h->varied_in.ptr;
+	for (uint32_t i = 0; i < n_images; ++i)
+		PXZ_HIP(h, hipMemcpyAsync(d_in + (*dev)[i].offset_bytes, pixels[i], bytes_of(i), hipMemcpyHostToDevice, h->stream));
+	return PXZ_OK;
+}
+
+// Every header first: a file that is not the image its descriptor announces is refused before anything is written.
+// what: who expects the image ("batch", "call").  *file_bytes: the files' lengths added up.
+int check_file_headers(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
+                       uint32_t channels, const pxz_params &p, const char *what, uint64_t *file_bytes)
+{
+	*file_bytes = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, ch, fb;
+		const char *why;
+		const int rc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &ch, &fb, &why);
+		if (rc != PXZ_OK) return fail(h, rc, "image %u: %s", i, why);
+		if (w != descs[i].width || hh != descs[i].height || bw != p.block_w || bh != p.block_h || ch != channels)
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u px in %ux%u blocks of %u channels, the %s expects %ux%u in %ux%u of %u",
+			            i, w, hh, bw, bh, ch, what, descs[i].width, descs[i].height, p.block_w, p.block_h, channels);
+		*file_bytes += lens[i];
+	}
+	return PXZ_OK;
+}
+
+// Every header first, for the forms that take their geometry from the files: they must share channels and block size.
+// descs: the files' images, tightly pitched; raw: the bytes of their pixels.
+struct FileScan {
+	std::vector<pxz_image_desc> descs;
+	uint32_t block_w = 0, block_h = 0, channels = 0;
+	uint64_t file_bytes = 0, raw = 0;
+};
+int scan_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, FileScan *s)
+{
+	s->descs.resize(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if (!files[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null file", i);
+		uint32_t w, hh, bw, bh, c, fb;
+		const char *why;
+		const int hrc = file_header(files[i], lens[i], &w, &hh, &bw, &bh, &c, &fb, &why);
+		if (hrc != PXZ_OK) return fail(h, hrc, "image %u: %s", i, why);
+		if (i == 0) {
+			s->block_w = bw;
+			s->block_h = bh;
+			s->channels = c;
+		} else if (bw != s->block_w || bh != s->block_h || c != s->channels) {
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: the file holds %ux%u blocks of %u channels, image 0 holds %ux%u of %u", i, bw, bh, c,
+			            s->block_w, s->block_h, s->channels);
+		}
+		s->descs[i] = pxz_image_desc{w, hh, w * c, 0, 0};
+		s->file_bytes += lens[i];
+		s->raw += (uint64_t)w * hh * c;
+	}
+	return PXZ_OK;
+}
+
+// The files as the reader takes them, back to back behind their table of n_images + 1 offsets: the first sent_bytes() of
+// `buffer`, which is grown to `room` bytes (the windows form keeps more in it).  stage: the host side of the one copy up, of
+// max(what goes up, down_bytes) bytes -- one staging buffer for both directions, the results come back after the files have gone.
+struct SentFiles {
+	const uint64_t *d_offsets = nullptr;
+	const uint8_t *d_files = nullptr;
+	std::vector<uint8_t> stage;
+};
+uint64_t sent_bytes(uint32_t n_images, uint64_t file_bytes) { return 8ull * ((uint64_t)n_images + 1u) + file_bytes + 16u; }
+int send_files(pxz_handle *h, DeviceBuffer &buffer, uint64_t room, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+               uint64_t file_bytes, uint64_t down_bytes, SentFiles *s)
+{
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	s->stage.resize((size_t)std::max(offs_bytes + file_bytes, down_bytes));
+	uint64_t *offs = reinterpret_cast<uint64_t *>(s->stage.data());
+	offs[0] = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		std::memcpy(s->stage.data() + offs_bytes + offs[i], files[i], lens[i]);
+		offs[i + 1] = offs[i] + lens[i];
+	}
+	const int rc = ensure(h, buffer, room);
+	if (rc != PXZ_OK) return rc;
+	PXZ_HIP(h, hipMemcpyAsync(buffer.ptr, s->stage.data(), offs_bytes + file_bytes, hipMemcpyHostToDevice, h->stream));
+	s->d_offsets = (const uint64_t *)buffer.ptr;
+	s->d_files = (const uint8_t *)buffer.ptr + offs_bytes;
+	return PXZ_OK;
+}
+
+// All or nothing: the flags of the reader (n_images) and of the stage behind it (n_images more) are fetched, and a malformed
+// file or a tile that cannot be stops the call before the writer runs.
+int check_stage_flags(pxz_handle *h, const uint32_t *d_flags, uint32_t n_images)
+{
+	std::vector<uint32_t> flags(2u * (size_t)n_images);
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (flags[i] | flags[n_images + i])
+			return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); nothing was written", i,
+			            flags[i] | flags[n_images + i]);
+	return PXZ_OK;
+}
+
+// the descriptors once per rung: the rung sets as one varied batch of n_factors * n images
+std::vector<pxz_image_desc> repeat_descs(const std::vector<pxz_image_desc> &descs, uint32_t n_factors)
+{
+	std::vector<pxz_image_desc> rungs;
+	rungs.reserve((size_t)n_factors * descs.size());
+	for (uint32_t r = 0; r < n_factors; ++r) rungs.insert(rungs.end(), descs.begin(), descs.end());
+	return rungs;
+}
+
+// One block of handle scratch (rd) that one copy brings back (n_down u64s): the rung files' offsets (n_sets + 1), the sums (n_sets *
+// ch) and, for a fit form of n_fit images (0: no fit), the chosen files' offsets (n_fit + 1), the choices and the flags (a choice and
+// a flag: one u64 together) -- and behind it the room the offsets-only writer is given (none).
+struct RungTable {
+	size_t n_sets = 0, n_table = 0, n_down = 0;
+	uint64_t *d_offs = nullptr, *d_sse = nullptr, *d_fit_offs = nullptr;
+	uint8_t *d_room = nullptr;
+};
+int carve_rung_table(pxz_handle *h, size_t n_sets, uint32_t ch, size_t n_fit, RungTable *t)
+{
+	t->n_sets = n_sets;
+	t->n_table = n_sets + 1u + n_sets * ch;
+	t->n_down = t->n_table + (n_fit ? 2u * n_fit + 1u : 0u);
+	const int rc = ensure(h, h->rd, t->n_down * 8u + 256u);
+	if (rc != PXZ_OK) return rc;
+	t->d_offs = (uint64_t *)h->rd.ptr;
+	t->d_sse = t->d_offs + n_sets + 1u;
+	t->d_fit_offs = t->d_offs + t->n_table;
+	t->d_room = (uint8_t *)(t->d_offs + t->n_down);
+	return PXZ_OK;
+}
+
+// the table as the callers want it: the files' lengths and the sums (either may be null)
+void unpack_rung_table(const uint64_t *got, size_t n_sets, uint32_t ch, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (file_bytes)
+		for (size_t k = 0; k < n_sets; ++k) file_bytes[k] = got[k + 1u] - got[k];
+	if (sse) std::memcpy(sse, got + n_sets + 1u, n_sets * ch * 8u);
+}
+
+// where the rate-distortion forms end: the table comes down, the stream drains, and the caller gets it unpacked
+int download_rung_table(pxz_handle *h, const RungTable &t, uint32_t ch, uint64_t *file_bytes, uint64_t *sse)
+{
+	std::vector<uint64_t> got(t.n_table);
+	PXZ_HIP(h, hipMemcpyAsync(got.data(), t.d_offs, t.n_table * 8u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	unpack_rung_table(got.data(), t.n_sets, ch, file_bytes, sse);
+	return PXZ_OK;
+}
+
+// Fills the table of the rungs `all` (rung-major, n_factors sets of the images descs): the writer over the descriptors once per
+// rung, for its offsets alone, then the rungs' distortion -- against the images at d_images (ref null: descs say where), or
+// against the archive's own tiles *ref, which expand_filter expands.
+int rung_table(pxz_handle *h, const std::vector<pxz_image_desc> &descs, uint32_t n_factors, uint32_t ch, const pxz_params &p, const pxz_params &up,
+               const TileSet &all, const RungTable &t, const uint8_t *d_images, const TileSet *ref, uint32_t expand_filter)
+{
+	const std::vector<pxz_image_desc> rungs = repeat_descs(descs, n_factors);
+	const int rc = pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &p, 0, all.value, all.w, all.h, all.slots, t.d_room, 0,
+	                                               t.d_offs);
+	if (rc != PXZ_OK) return rc;
+	if (!ref)
+		return pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &up, d_images, all.w, all.h, all.slots, nullptr, t.d_sse,
+		                                           nullptr);
+	return pxz_reshrink_distortion_varied_device(h, descs.data(), (uint32_t)descs.size(), ch, &up, expand_filter, n_factors, ref->w, ref->h, ref->slots,
+	                                             all.w, all.h, all.slots, nullptr, t.d_sse, nullptr);
+}
+
+// The files of `tiles` (n_factors sets of the images descs, rung-major) into varied_files and out to the caller: a first guess
+// at their room (raw: the bytes of the images' pixels; n_tiles: the tiles of one set), and one more writer pass when it was
+// short -- the offsets are exact whichever pass wrote them, so they come down once, behind the first: the n_block u64s at
+// d_block into *got, the offsets among them at offs_at.  file_offsets is filled also when out is too small; nothing goes out then.
+int write_files(pxz_handle *h, const std::vector<pxz_image_desc> &descs, uint32_t n_factors, uint32_t ch, const pxz_params &p, uint32_t filter_byte,
+                const TileSet &tiles, uint64_t raw, uint32_t n_tiles, uint64_t *d_block, size_t n_block, size_t offs_at, std::vector<uint64_t> *got,
+                uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets)
+{
+	const std::vector<pxz_image_desc> rungs = repeat_descs(descs, n_factors);
+	const uint32_t n_files = (uint32_t)rungs.size();
+	got->resize(n_block);
+	uint64_t cap = (raw + raw / 4u + 64ull * n_tiles + 4096ull * descs.size()) * n_factors;
+	if (cap < h->varied_files.cap) cap = h->varied_files.cap;
+	for (int pass = 0; pass < 2; ++pass) {
+		int rc = ensure(h, h->varied_files, cap);
+		if (rc != PXZ_OK) return rc;
+		if ((rc = pxz_encode_varied_frames_device(h, rungs.data(), n_files, ch, &p, filter_byte, tiles.value, tiles.w, tiles.h, tiles.slots,
+		                                          (uint8_t *)h->varied_files.ptr, cap, d_block + offs_at)) != PXZ_OK)
+			return rc;
+		if (pass == 0) PXZ_HIP(h, hipMemcpyAsync(got->data(), d_block, n_block * 8u, hipMemcpyDeviceToHost, h->stream));
+		PXZ_HIP(h, hipStreamSynchronize(h->stream));
+		if ((*got)[offs_at + n_files] <= cap) break;
+		cap = (*got)[offs_at + n_files];
+	}
+	std::memcpy(file_offsets, got->data() + offs_at, ((size_t)n_files + 1u) * 8u);
+	const uint64_t total = file_offsets[n_files];
+	if (!out || out_capacity < total)
+		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the files need %llu bytes, out holds %llu", (unsigned long long)total,
+		            (unsigned long long)out_capacity);
+	PXZ_HIP(h, hipMemcpy(out, h->varied_files.ptr, total, hipMemcpyDeviceToHost));
+	return PXZ_OK;
+}
+
+// The images as the device calls take them (of the image forms: where send_images put them), every rung's tiles in varied_out
+// and their table in rd.
+struct Rungs {
+	std::vector<pxz_image_desc> descs;
+	pxz_params p;   // the ladder's and the writer's: factor 1 (ignored by the ladder calls)
+	uint32_t ch = 0, n_tiles = 0;  // (the tiles of one rung)
+	uint64_t raw = 0;
+	TileSet all;
+	RungTable t;
+};
+
+// The image forms from their parameter checks to the filled table: the ladder over the images, then rung_table against the
+// images themselves.  criterion: the fit form's, checked in its place among the others (null: no fit).
+int image_rungs(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, uint32_t block_w,
+                uint32_t block_h, uint32_t mode, uint32_t filter_down, uint32_t filter_up, const float *factors, uint32_t n_factors,
+                const uint32_t *criterion, Rungs *s)
+{
+	s->p = pxz_params{block_w, block_h, mode, filter_down, 1.0f, 0};
+	const pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
+	int rc = check_params(h, &up);
+	if (rc != PXZ_OK) return rc;
+	if ((rc = varied_check_params(h, channels, &s->p)) != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, block_w, block_h, channels, mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	if (criterion && (rc = fit_check(h, n_images, n_factors, channels, *criterion)) != PXZ_OK) return rc;
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
+	s->ch = channels;
+	s->n_tiles = varied_n_tiles(images);
+	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * s->n_tiles;
+	if (tiles > 0xffffffffull || n_sets > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	if ((rc = send_images(h, pixels, descs, n_images, channels, &s->descs, &s->raw)) != PXZ_OK) return rc;
+	const uint64_t slot = (uint64_t)block_w * block_h * channels;
+	if ((rc = ensure(h, h->varied_out, TileSet::bytes(tiles, slot))) != PXZ_OK) return rc;
+	if ((rc = carve_rung_table(h, (size_t)n_sets, channels, criterion ? n_images : 0u, &s->t)) != PXZ_OK) return rc;
+	const uint8_t *d_in = (const uint8_t *)h->varied_in.ptr;
+	s->all = TileSet((uint8_t *)h->varied_out.ptr, tiles);
+	if ((rc = pxz_shrink_varied_ladder_frames_device(h, s->descs.data(), n_images, channels, &s->p, factors, n_factors, d_in, s->all.value, s->all.w,
+	                                                 s->all.h, s->all.slots)) != PXZ_OK)
+		return rc;
+	return rung_table(h, s->descs, n_factors, channels, s->p, up, s->all, s->t, d_in, nullptr, 0);
+}
+
+// The archive forms from their parameter checks to the filled table: the files parsed and uploaded, the reader into a buffer
+// of its own (NOT rung 0: the reference is kept), the re-shrink ladder out of place into varied_out, the flags of both checked,
+// then rung_table against the reference.
+int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
+                  uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, bool fit, Rungs *s)
+{
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if (filter_up > 4) return fail(h, PXZ_ERR_INVALID_ARG, "filter_up must be 0..4, got %u", filter_up);
+	s->p = *params;
+	s->p.factor = 1.0f;
+	int rc = check_params(h, &s->p);
+	if (rc != PXZ_OK) return rc;
+	FileScan scan;  // (the block size must be params' besides)
+	if ((rc = scan_files(h, files, lens, n_images, &scan)) != PXZ_OK) return rc;
+	const uint32_t fbw = scan.block_w, fbh = scan.block_h, ch = scan.channels;
+	if (fbw != s->p.block_w || fbh != s->p.block_h)
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "the files hold %ux%u blocks, params ask for %ux%u: the error without the image needs an unchanged block size (decode the files and "
+		            "use the image calls)", fbw, fbh, s->p.block_w, s->p.block_h);
+	if ((rc = reshrink_check_block(h, s->p.mode, fbw, fbh, ch, 1u)) != PXZ_OK) return rc;
+	if (reshrink_distortion_bytes(fbw, fbh, 1u) > kLdsPerCu)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "the distortion of re-shrunk tiles keeps three planes of block_w*block_h dwords in LDS (%ux%u)", fbw, fbh);
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, scan.descs.data(), n_images, fbw, fbh, ch, s->p.mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	s->descs = std::move(scan.descs);
+	s->raw = scan.raw;
+	s->ch = ch;
+	s->n_tiles = varied_n_tiles(images);
+	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * s->n_tiles;
+	if (tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	SentFiles sent;
+	if ((rc = send_files(h, h->transcode_files, sent_bytes(n_images, scan.file_bytes), files, lens, n_images, scan.file_bytes, 0, &sent)) != PXZ_OK)
+		return rc;
+
+	// the archive's tiles and the flags of the reader and the re-shrink (archive_tiles); every rung's tiles (varied_out)
+	const uint64_t slot = (uint64_t)fbw * fbh * ch;
+	const uint64_t flags_at = up256(TileSet::bytes(s->n_tiles, slot));
+	if ((rc = ensure(h, h->archive_tiles, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_out, TileSet::bytes(tiles, slot))) != PXZ_OK) return rc;
+	if ((rc = carve_rung_table(h, (size_t)n_sets, ch, fit ? n_images : 0u, &s->t)) != PXZ_OK) return rc;
+	uint8_t *d_ref = (uint8_t *)h->archive_tiles.ptr;
+	const TileSet ref(d_ref, s->n_tiles);
+	uint32_t *d_flags = (uint32_t *)(d_ref + flags_at);
+	s->all = TileSet((uint8_t *)h->varied_out.ptr, tiles);
+
+	// reader -> the reference; ladder out of place -> the rungs
+	pxz_params pin = s->p;
+	pin.filter = expand_filter;
+	PXZ_HIP(h, hipMemsetAsync(d_ref, 0, TileSet::meta_bytes(s->n_tiles), h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
+	if ((rc = pxz_decode_varied_frames_device(h, s->descs.data(), n_images, ch, &pin, sent.d_files, sent.d_offsets, ref.value, ref.w, ref.h, ref.slots,
+	                                          d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_reshrink_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, &s->p, expand_filter, factors, n_factors, ref.w, ref.h, ref.slots,
+	                                                   s->all.value, s->all.w, s->all.h, s->all.slots, d_flags + n_images)) != PXZ_OK)
+		return rc;
+	if ((rc = check_stage_flags(h, d_flags, n_images)) != PXZ_OK) return rc;
+	pxz_params up = s->p;
+	up.filter = filter_up;
+	return rung_table(h, s->descs, n_factors, ch, s->p, up, s->all, s->t, nullptr, &ref, expand_filter);
+}
+
+// Where both fit forms end, behind the filled table: one rung per image chosen on the device, its tiles gathered as a varied
+// batch of the images themselves (fit_tiles), the files written, and the one download unpacked -- the table (optional), the
+// files' offsets, the choices and the flags.
+int fit_and_write(pxz_handle *h, const Rungs &s, uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                  uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes, uint64_t *table_sse)
+{
+	const uint32_t n_images = (uint32_t)s.descs.size();
+	const uint64_t slot = (uint64_t)s.p.block_w * s.p.block_h * s.ch;
+	int rc = ensure(h, h->fit_tiles, TileSet::bytes(s.n_tiles, slot));
+	if (rc != PXZ_OK) return rc;
+	const TileSet fit((uint8_t *)h->fit_tiles.ptr, s.n_tiles);
+	uint64_t *d_offs = s.t.d_fit_offs;
+	uint32_t *d_choice = (uint32_t *)(d_offs + n_images + 1u), *d_flags = d_choice + n_images;
+	if ((rc = pxz_fit_varied_ladder_device(h, n_images, n_factors, s.ch, criterion, targets, s.t.d_offs, s.t.d_sse, d_choice, d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_gather_varied_rungs_device(h, s.descs.data(), n_images, s.ch, &s.p, n_factors, d_choice, s.all.value, s.all.w, s.all.h, s.all.slots,
+	                                         fit.value, fit.w, fit.h, fit.slots, nullptr)) != PXZ_OK)
+		return rc;
+	std::vector<uint64_t> got;
+	rc = write_files(h, s.descs, 1u, s.ch, s.p, filter_byte, fit, s.raw, s.n_tiles, s.t.d_offs, s.t.n_down, s.t.n_table, &got, out, out_capacity,
+	                 file_offsets);
+	if (rc != PXZ_OK && rc != PXZ_ERR_BUFFER_TOO_SMALL) return rc;
+	unpack_rung_table(got.data(), s.t.n_sets, s.ch, table_bytes, table_sse);
+	const uint32_t *picked = reinterpret_cast<const uint32_t *>(got.data() + s.t.n_table + n_images + 1u);
+	std::memcpy(choice, picked, (size_t)n_images * 4u);
+	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
+	return rc;
+}
+
+// Both host forms of pix_to_pix behind one body: factors == nullptr is pxz_transcode_varied_files (one rung, the caller's
+// params->factor, the one-factor calls); otherwise pxz_transcode_varied_ladder_files (n_factors rungs, the ladder calls, the
+// outputs rung-major and the writer over the descriptors repeated n_factors times).
+int transcode_varied(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *user_params,
+                     uint32_t expand_filter, const float *factors, uint32_t n_factors, uint32_t filter_byte, uint8_t *out,
+                     uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !user_params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const bool ladder = factors != nullptr;
+	pxz_params ladder_params = *user_params;
+	ladder_params.factor = 1.0f;  // (ignored by the ladder calls)
+	const pxz_params *params = ladder ? &ladder_params : user_params;
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	FileScan scan;
+	int rc = scan_files(h, files, lens, n_images, &scan);
+	if (rc != PXZ_OK) return rc;
+	const std::vector<pxz_image_desc> &descs = scan.descs;
+	const uint32_t fbw = scan.block_w, fbh = scan.block_h, ch = scan.channels;
+	const bool same_block = fbw == params->block_w && fbh == params->block_h;
+	pxz_params pin = *params;  // the files' own geometry
+	pin.block_w = fbw;
+	pin.block_h = fbh;
+	pin.filter = expand_filter;
+	if (same_block) {
+		if ((rc = check_params(h, params)) != PXZ_OK) return rc;
+		if ((rc = reshrink_check_block(h, params->mode, fbw, fbh, ladder ? ch : 0u, 1u)) != PXZ_OK) return rc;
+	} else {
+		const pxz_params px = decode_side_params(&pin, true);
+		if ((rc = varied_check_params(h, ch, &px)) != PXZ_OK) return rc;
+		if ((rc = varied_check_params(h, ch, params)) != PXZ_OK) return rc;
+	}
+	std::vector<pxz::VariedImage> images_in, images_out;
+	if ((rc = varied_plan(h, descs.data(), n_images, fbw, fbh, 0, 0, &images_in, nullptr, nullptr)) != PXZ_OK) return rc;
+	if ((rc = varied_plan(h, descs.data(), n_images, params->block_w, params->block_h, ch, params->mode, &images_out, nullptr, nullptr)) != PXZ_OK)
+		return rc;
+	const uint32_t n_out = varied_n_tiles(images_out), n_in = varied_n_tiles(images_in);
+	if ((uint64_t)n_factors * n_out > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	const uint32_t n_all = n_factors * n_out, n_files = n_factors * n_images;  // (n_files: 2^32-1 at most, a file has a tile)
+	PXZ_HIP(h, hipSetDevice(h->device));
+	SentFiles sent;
+	if ((rc = send_files(h, h->transcode_files, sent_bytes(n_images, scan.file_bytes), files, lens, n_images, scan.file_bytes, 0, &sent)) != PXZ_OK)
+		return rc;
+
+	// the tiles that go to the writer, rung-major: values, sizes, slots, then the new files' offsets and the flags of both stages
+	const uint64_t slot_out = (uint64_t)params->block_w * params->block_h * ch;
+	const uint64_t offs_at = (TileSet::bytes(n_all, slot_out) + 7u) & ~(uint64_t)7u;
+	const uint64_t flags_at = offs_at + 8ull * ((uint64_t)n_files + 1u);
+	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
+	const TileSet m(d_out, n_all);  // (the reader fills rung 0 of each array)
+	uint64_t *d_offs = (uint64_t *)(d_out + offs_at);
+	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
+
+	if (same_block) {
+		// reader -> re-shrink in place (the ladder: in place on rung 0) -> writer: nothing of image size anywhere
+		PXZ_HIP(h, hipMemsetAsync(d_out, 0, TileSet::meta_bytes(n_all), h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
+		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, sent.d_files, sent.d_offsets, m.value, m.w, m.h, m.slots,
+		                                          d_flags)) != PXZ_OK)
+			return rc;
+		rc = ladder ? pxz_reshrink_varied_ladder_frames_device(h, descs.data(), n_images, ch, params, expand_filter, factors, n_factors, m.w, m.h,
+		                                                       m.slots, m.value, m.w, m.h, m.slots, d_flags + n_images)
+		            : pxz_reshrink_varied_frames_device(h, descs.data(), n_images, ch, params, expand_filter, m.w, m.h, m.slots, m.value, m.w, m.h,
+		                                                m.slots, d_flags + n_images);
+		if (rc != PXZ_OK) return rc;
+	} else {
+		// another block size: reader at the files' geometry -> the images in handle scratch -> the varied shrink at the new one
+		const uint64_t slot_in = (uint64_t)fbw * fbh * ch;
+		if ((rc = ensure(h, h->transcode_tiles, TileSet::bytes(n_in, slot_in))) != PXZ_OK) return rc;
+		const TileSet mi((uint8_t *)h->transcode_tiles.ptr, n_in);
+		std::vector<pxz_image_desc> dev = descs;
+		const uint64_t img_bytes = pack_owners(&dev, ch);
+		if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
+		uint8_t *d_img = (uint8_t *)h->varied_in.ptr;
+		PXZ_HIP(h, hipMemsetAsync(mi.value, 0, TileSet::meta_bytes(n_in), h->stream));
+		if ((rc = pxz_decode_varied_frames_device(h, descs.data(), n_images, ch, &pin, sent.d_files, sent.d_offsets, mi.value, mi.w, mi.h, mi.slots,
+		                                          d_flags)) != PXZ_OK)
+			return rc;
+		if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, ch, &pin, mi.w, mi.h, mi.slots, d_img, d_flags + n_images)) != PXZ_OK)
+			return rc;
+		rc = ladder ? pxz_shrink_varied_ladder_frames_device(h, dev.data(), n_images, ch, params, factors, n_factors, d_img, m.value, m.w, m.h, m.slots)
+		            : pxz_shrink_varied_frames_device(h, dev.data(), n_images, ch, params, d_img, m.value, m.w, m.h, m.slots);
+		if (rc != PXZ_OK) return rc;
+	}
+	if ((rc = check_stage_flags(h, d_flags, n_images)) != PXZ_OK) return rc;
+	std::vector<uint64_t> got;
+	return write_files(h, descs, n_factors, ch, *params, filter_byte, m, scan.raw, n_out, d_offs, (size_t)n_files + 1u, 0, &got, out, out_capacity,
+	                   file_offsets);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_encode_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                             uint32_t channels, const pxz_params *params, uint32_t filter_byte, uint8_t *out,
+                             uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!pixels || !params || !file_offsets) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	int rc = varied_check_params(h, channels, params);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, params->mode, &images, nullptr, nullptr)) != PXZ_OK)
+		return rc;
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (!pixels[i]) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: null pixels", i);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// the images, back to back, and the tiles' outputs with the files' offsets behind them
+	std::vector<pxz_image_desc> dev;
+	uint64_t raw = 0;
+	if ((rc = send_images(h, pixels, descs, n_images, channels, &dev, &raw)) != PXZ_OK) return rc;
+	const uint32_t n_tiles = varied_n_tiles(images);
+	const uint64_t offs_at = TileSet::bytes(n_tiles, (uint64_t)params->block_w * params->block_h * channels);
+	if ((rc = ensure(h, h->varied_out, offs_at + 8u * ((uint64_t)n_images + 1u))) != PXZ_OK) return rc;
+	uint8_t *d_out = (uint8_t *)h->varied_out.ptr;
+	const TileSet m(d_out, n_tiles);
+	if ((rc = pxz_shrink_varied_frames_device(h, dev.data(), n_images, channels, params, (const uint8_t *)h->varied_in.ptr, m.value, m.w, m.h,
+	                                          m.slots)) != PXZ_OK)
+		return rc;
+	std::vector<uint64_t> got;
+	return write_files(h, dev, 1u, channels, *params, filter_byte, m, raw, n_tiles, (uint64_t *)(d_out + offs_at), (size_t)n_images + 1u, 0, &got, out,
+	                   out_capacity, file_offsets);
+}
+
+int pxz_decode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
+                            uint32_t n_images, uint32_t channels, const pxz_params *params, uint8_t *out_base, uint32_t *image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, channels, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	uint64_t file_bytes = 0;
+	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "batch", &file_bytes)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// device side: the files back to back behind their offsets; the images tightly packed
+	std::vector<pxz_image_desc> dev(descs, descs + n_images);
+	const uint64_t img_bytes = pack_owners(&dev, channels);
+	const uint32_t n_tiles = varied_n_tiles(images);
+	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
+	const uint64_t flags_at = TileSet::bytes(n_tiles, slot);
+	SentFiles sent;
+	if ((rc = send_files(h, h->varied_files, sent_bytes(n_images, file_bytes), files, lens, n_images, file_bytes, img_bytes, &sent)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
+	uint8_t *d_out = (uint8_t *)h->varied_out.ptr, *d_img = (uint8_t *)h->varied_in.ptr;
+	const TileSet m(d_out, n_tiles);
+	PXZ_HIP(h, hipMemsetAsync(m.slots, 0, (size_t)n_tiles * slot, h->stream));
+	PXZ_HIP(h, hipMemsetAsync(d_img, 0, img_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
+	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
+	if ((rc = pxz_decode_varied_frames_device(h, dev.data(), n_images, channels, &p, sent.d_files, sent.d_offsets, m.value, m.w, m.h, m.slots,
+	                                          d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, channels, &p, m.w, m.h, m.slots, d_img, d_flags + n_images)) != PXZ_OK)
+		return rc;
+	std::vector<uint32_t> flags(2u * (size_t)n_images);
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
+	PXZ_HIP(h, hipMemcpyAsync(sent.stage.data(), d_img, img_bytes, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	uint32_t first_flags = 0;
+	const uint32_t first_bad = copy_out_owners(descs, dev.data(), n_images, channels, sent.stage.data(), out_base, flags.data(), image_flags, &first_flags);
+	if (first_bad != n_images)
+		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
+		            first_flags);
+	return PXZ_OK;
+}
+
+int pxz_transcode_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                               const pxz_params *params, uint32_t expand_filter, uint32_t filter_byte, uint8_t *out,
+                               uint64_t out_capacity, uint64_t *file_offsets)
+{
+	return transcode_varied(h, files, lens, n_images, params, expand_filter, nullptr, 1u, filter_byte, out, out_capacity, file_offsets);
+}
+
+int pxz_transcode_varied_ladder_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                      const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors,
+                                      uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	return transcode_varied(h, files, lens, n_images, params, expand_filter, factors, n_factors, filter_byte, out, out_capacity, file_offsets);
+}
+
+int pxz_rate_distortion_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                              uint32_t pitch_bytes, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                              uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!factors) return fail(h, PXZ_ERR_INVALID_ARG, "null factors");
+	if (n_factors == 0 || n_factors > PXZ_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_LADDER_MAX_RUNGS, n_factors);
+	if (!pixels || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	pxz_params p{block_w, block_h, mode, filter_down, 1.0f, 0};
+	pxz_params up{block_w, block_h, 0, filter_up, 0.0f, 0};
+	int rc = check_params(h, &up);
+	if (rc != PXZ_OK) return rc;
+	pxz_frames f;
+	size_t tiles = 0, slot = 0;
+	if ((rc = stage_host_image(h, pixels, width, height, channels, pitch_bytes, &p, n_factors, true, &f, &tiles, &slot)) != PXZ_OK) return rc;
+	RungTable t;
+	if ((rc = carve_rung_table(h, n_factors, channels, 0, &t)) != PXZ_OK) return rc;
+	const uint8_t *d_in = (const uint8_t *)h->in.ptr;
+	float *d_val = (float *)h->val.ptr;
+	uint32_t *d_w = (uint32_t *)h->ow.ptr, *d_h = (uint32_t *)h->oh.ptr;
+	uint8_t *d_slots = (uint8_t *)h->out.ptr;
+	if ((rc = pxz_shrink_ladder_frames_device(h, &f, &p, factors, n_factors, d_in, d_val, d_w, d_h, d_slots)) != PXZ_OK) return rc;
+	pxz_frames rungs = f;  // the rung sets as a batch of n_factors frames
+	rungs.n_frames = n_factors;
+	rungs.frame_stride_bytes = (uint64_t)f.pitch_bytes * height;
+	if ((rc = pxz_encode_frames_device(h, &rungs, &p, 0, d_val, d_w, d_h, d_slots, t.d_room, 0, t.d_offs)) != PXZ_OK) return rc;
+	if ((rc = pxz_distortion_frames_device(h, &f, &up, n_factors, d_in, d_w, d_h, d_slots, nullptr, t.d_sse)) != PXZ_OK) return rc;
+	return download_rung_table(h, t, channels, file_bytes, sse);
+}
+
+int pxz_rate_distortion_varied_images(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                      uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                      uint32_t filter_up, const float *factors, uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!pixels || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	Rungs s;
+	if ((rc = image_rungs(h, pixels, descs, n_images, channels, block_w, block_h, mode, filter_down, filter_up, factors, n_factors, nullptr, &s)) != PXZ_OK)
+		return rc;
+	return download_rung_table(h, s.t, channels, file_bytes, sse);
+}
+
+int pxz_encode_varied_images_fit(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                 uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                 uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                 const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity,
+                                 uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes, uint64_t *table_sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!pixels || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	Rungs s;
+	if ((rc = image_rungs(h, pixels, descs, n_images, channels, block_w, block_h, mode, filter_down, filter_up, factors, n_factors, &criterion, &s)) !=
+	    PXZ_OK)
+		return rc;
+	return fit_and_write(h, s, n_factors, criterion, targets, filter_byte, out, out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
+}
+
+int pxz_rate_distortion_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                     const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                     uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!files || !lens || !params || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	Rungs s;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, false, &s)) != PXZ_OK) return rc;
+	return download_rung_table(h, s.t, s.ch, file_bytes, sse);
+}
+
+int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                   const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                   uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                                   uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes,
+                                   uint64_t *table_sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!files || !lens || !params || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
+		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	Rungs s;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, &s)) != PXZ_OK) return rc;
+	return fit_and_write(h, s, n_factors, criterion, targets, filter_byte, out, out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
+}
+
+int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
+                             const pxz_window *windows, uint32_t n_windows, uint32_t channels, const pxz_params *params, uint8_t *out_base,
+                             uint64_t out_bytes, uint32_t *window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !out_base) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::WindowEntry> entries;
+	if ((rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, channels, &entries, nullptr, nullptr)) != PXZ_OK) return rc;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const pxz_window &g = windows[k];
+		if (g.offset_bytes > out_bytes || (uint64_t)(g.height - 1u) * g.pitch_bytes + (uint64_t)g.width * channels > out_bytes - g.offset_bytes)
+			return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "window %u: its output ends behind the %llu bytes of the buffer", k, (unsigned long long)out_bytes);
+	}
+	uint64_t file_bytes = 0;
+	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "call", &file_bytes)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// device side, one buffer: the files back to back behind their offsets | the covered tiles | the crops tightly packed with
+	// the two flag arrays behind them
+	std::vector<pxz_window> dev(windows, windows + n_windows);
+	const uint64_t crop_bytes = pack_owners(&dev, channels);
+	const uint32_t n_tiles = window_n_tiles(entries);
+	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
+	const uint64_t tiles_at = up256(sent_bytes(n_images, file_bytes)), crops_at = tiles_at + up256(TileSet::bytes(n_tiles, slot));
+	const uint64_t flags_at = crops_at + crop_bytes, down_bytes = crop_bytes + 8ull * n_windows;
+	SentFiles sent;
+	if ((rc = send_files(h, h->window_host, flags_at + 8ull * n_windows, files, lens, n_images, file_bytes, down_bytes, &sent)) != PXZ_OK) return rc;
+	uint8_t *d = (uint8_t *)h->window_host.ptr;
+	PXZ_HIP(h, hipMemsetAsync(d + crops_at, 0, down_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
+	const TileSet m(d + tiles_at, n_tiles);
+	uint32_t *d_flags = (uint32_t *)(d + flags_at);
+	if ((rc = pxz_decode_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, sent.d_files, sent.d_offsets, m.value, m.w, m.h, m.slots,
+	                                    d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_expand_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, m.w, m.h, m.slots, d + crops_at, d_flags + n_windows)) !=
+	    PXZ_OK)
+		return rc;
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
+	PXZ_HIP(h, hipMemcpyAsync(sent.stage.data(), d + crops_at, down_bytes, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	const uint32_t *flags = reinterpret_cast<const uint32_t *>(sent.stage.data() + crop_bytes);
+	uint32_t first_flags = 0;
+	const uint32_t first_bad = copy_out_owners(windows, dev.data(), n_windows, channels, sent.stage.data(), out_base, flags, window_flags, &first_flags);
+	if (first_bad != n_windows)
+		return fail(h, PXZ_ERR_INVALID_ARG, "window %u: malformed .pixlzr file or record in what it reads of image %u (flags %u); the other windows are complete",
+		            first_bad, windows[first_bad].image, first_flags);
+	return PXZ_OK;
+}
+
+}  // extern "C"
