@@ -772,6 +772,118 @@ int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, c
                                    uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice,
                                    uint32_t *fit_flags, uint64_t *table_bytes /* may be NULL */, uint64_t *table_sse /* may be NULL */);
 
+/* ---- fit to a budget per tile: each tile at the rung its group's target picks ---------------------------------- */
+
+/* A .pixlzr file knows no factors: every record carries its own stored size and value, so a file whose tiles come from
+ * different rungs of a ladder is an ordinary file.  One factor per image spends bytes evenly where the error is not even; the
+ * calls below choose a rung per TILE, under one target per GROUP -- a run of consecutive images (one image, or a whole folder).
+ * Candidate (t, r), rung r of flat tile t, has b = the bytes of its record (u32) and s = the sum over its channels of its
+ * squared error.  It is usable when no channel sum is UINT64_MAX, s < 2^32 and b < 2^24 (the library's own calls stay inside
+ * both for every block they admit: 65536 * 255^2 < 2^32); unusable candidates are skipped.  A tile with no usable candidate
+ * gets choice 0, counts in no total and sets bit 1 of its group's flags.
+ *   pick(t, lambda) = the usable r with the smallest (s + lambda*b, b, r), lambda an integer in [0, PXZ_TILEFIT_LAMBDA_MAX];
+ *   B(lambda) = the group's fixed bytes + the sum of b(pick) over its tiles, S(lambda) = the sum of s(pick).
+ * B never increases with lambda and S never decreases.  All arithmetic is u64 (a cost stays below 2^57).
+ *   PXZ_FIT_BYTES  lambda* = the smallest lambda with B(lambda) <= target.  B(2^32) > target: lambda* = 2^32 and bit 0 (missed)
+ *                  is set -- every tile has taken its fewest bytes, so no assignment of rungs fits.
+ *   PXZ_FIT_SSE    lambda* = the largest lambda with S(lambda) <= target.  S(0) > target: lambda* = 0 and bit 0 is set.
+ * Never worse than one factor for the group: when the target was not missed, the totals (B_u(r), S_u(r)) of each rung that is
+ * usable for every tile of the group go through pxz_fit_select's rule, and the group takes that one rung for all its tiles
+ * (bit 2) when it is eligible and its (minimised, constrained) pair is strictly smaller than that of the pick at lambda*.
+ * Flags per group: bit 0 missed, bit 1 a tile without a usable candidate, bit 2 one rung for all. */
+#define PXZ_TILEFIT_LAMBDA_MAX 4294967296ull   /* 2^32 */
+
+/* The rule on the host (no handle, no GPU, like pxz_fit_select).  Group g owns the flat tiles [group_tile_offsets[g],
+ * group_tile_offsets[g+1]) (n_groups + 1 entries from 0 on, strictly ascending: a group has a tile), tiles =
+ * group_tile_offsets[n_groups]; group_fixed_bytes[g] are the headers and line tables of its files, targets[g] its budget under
+ * `criterion` (pxz_fit).  tile_bytes[r*tiles + t] (u32) and tile_sse[(r*tiles + t)*channels + c] (u64) are the candidates,
+ * 1 <= n_factors <= PXZ_VARIED_LADDER_MAX_RUNGS.  Outputs: tile_choice[t], and per group lambda (lambda*), bytes and sse (the
+ * totals of the final choice, fixed bytes included) and flags.  PXZ_ERR_INVALID_ARG for a null pointer, n_groups 0, n_factors 0
+ * or above the maximum, channels not 3|4, an unknown criterion, or offsets that do not start at 0 or do not ascend;
+ * PXZ_ERR_UNSUPPORTED for n_factors * tiles above 2^32-1; on an error nothing is written.  The device call below runs the same
+ * text of the rule. */
+int pxz_fit_tiles_select(uint32_t n_groups, const uint64_t *group_tile_offsets, const uint64_t *group_fixed_bytes, uint32_t n_factors,
+                         uint32_t channels, uint32_t criterion, const uint64_t *targets, const uint32_t *tile_bytes,
+                         const uint64_t *tile_sse, uint32_t *tile_choice, uint64_t *group_lambda, uint64_t *group_bytes,
+                         uint64_t *group_sse, uint32_t *group_flags);
+
+/* The record lengths of the writer: the inputs of pxz_encode_varied_frames_device (for a ladder's result: the descriptors
+ * repeated n_factors times, as there) in, d_record_bytes out -- one u32 per tile in flat tile order, the bytes record t
+ * occupies in its file: "block" + value + length field + QOI without its magic = 13 + the record's length field.
+ * d_file_offsets (n_images + 1 u64, may be NULL) is exactly what pxz_encode_varied_frames_device gives with out_capacity 0.
+ * For every image: 26 + 4*rows + the sum of its tiles' record bytes == the length of its file.  No file is written.
+ * Asynchronous on the handle's stream; the number of launches does not depend on n_images.  Validation is
+ * pxz_encode_varied_frames_device's; on an error nothing is written. */
+int pxz_record_bytes_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                   const pxz_params *params, const float *d_block_value, const uint32_t *d_tile_w,
+                                   const uint32_t *d_tile_h, const uint8_t *d_slots, uint32_t *d_record_bytes,
+                                   uint64_t *d_file_offsets /* may be NULL */);
+
+/* The rule on the device, over a varied ladder's result: d_record_bytes (the call above over the descriptors repeated
+ * n_factors times: index r*tiles + t) and d_tile_sse (pxz_distortion_varied_frames_device or
+ * pxz_reshrink_distortion_varied_device over the same: index (r*tiles + t)*channels + c).  descs are the n_images images
+ * themselves; of params only block_w and block_h are read.  group_first is a HOST array of n_groups + 1 image indices,
+ * strictly ascending from 0 to n_images: group g is the images [group_first[g], group_first[g+1]); NULL means every image is
+ * its own group (n_groups must be n_images then).  targets is a HOST array of n_groups entries; both travel through handle
+ * buffers that pxz_trim gives back.  The fixed bytes of a group are the sum of 26 + 4*rows over its images.
+ * d_tile_choice (tiles dwords), d_group_lambda, d_group_bytes, d_group_sse (n_groups u64 each) and d_group_flags (n_groups
+ * dwords) equal pxz_fit_tiles_select on the downloaded tables.  A fixed chain of one memset and 37 launches (one per halving of
+ * [0, 2^32], 33 of them, the kernel boundary being the only synchronisation), whatever n_images, n_groups, the tiles and n_factors are;
+ * nothing is read back in between; integer atomics only, so the result does not depend on the order of arrival.
+ * Asynchronous on the handle's stream; none of the state the single-geometry fast paths keep in the handle is touched.
+ * Validation runs on the host before anything is launched, as pxz_gather_varied_rungs_device and pxz_fit_select, plus
+ * PXZ_ERR_UNSUPPORTED for block_w*block_h*channels > 65536 (the bound on s rests on it) and PXZ_ERR_INVALID_ARG for a bad
+ * group_first or n_groups; on an error nothing is written. */
+int pxz_fit_varied_tiles_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                const pxz_params *params, const uint32_t *group_first /* may be NULL */, uint32_t n_groups,
+                                uint32_t n_factors, uint32_t criterion, const uint64_t *targets, const uint32_t *d_record_bytes,
+                                const uint64_t *d_tile_sse, uint32_t *d_tile_choice, uint64_t *d_group_lambda,
+                                uint64_t *d_group_bytes, uint64_t *d_group_sse, uint32_t *d_group_flags);
+
+/* pxz_gather_varied_rungs_device with a choice per tile: output tile t is input tile d_tile_choice[t]*tiles + t -- the value's
+ * bits, both sizes and exactly the valid bytes of the slot; d_tile_choice has tiles entries in flat tile order.  A choice of
+ * n_factors or more is read as n_factors-1 and sets bit 1 of the owning image's entry of d_image_flags (n_images dwords, may
+ * be NULL; zeroed by the call).  One kernel launch, no LDS, 64-bit offsets; everything else -- the outputs, d_out_pixels NULL,
+ * validation, codes and limits -- is pxz_gather_varied_rungs_device's. */
+int pxz_gather_varied_tile_rungs_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                        const pxz_params *params, uint32_t n_factors, const uint32_t *d_tile_choice,
+                                        const float *d_block_value, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                        const uint8_t *d_slots, float *d_out_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                        uint8_t *d_out_pixels, uint32_t *d_image_flags);
+
+/* pxz_encode_varied_images_fit with a rung per tile: host images in, one .pixlzr file per image out, its tiles taken from the
+ * rungs the rule above picks under targets[g] (n_groups entries) for the groups group_first describes (as in
+ * pxz_fit_varied_tiles_device; NULL: every image its own group, n_groups == n_images; one group over all images is "one
+ * budget for the whole folder").  Composition only: upload, pxz_shrink_varied_ladder_frames_device,
+ * pxz_record_bytes_varied_device and pxz_distortion_varied_frames_device (with its per-tile sums) over the n_factors*n_images
+ * rung images, pxz_fit_varied_tiles_device, pxz_gather_varied_tile_rungs_device, pxz_encode_varied_frames_device over the
+ * n_images gathered images, one download.  File i is what pxz_encode_container makes of image i's gathered tiles; with one
+ * factor it is pxz_encode_varied_images' file.  group_bytes[g] is the summed length of the group's files, group_sse[g] the
+ * squared error between its images and what pxz_decode_varied_files (filter_up) makes of those files.
+ * Always written: file_offsets (n_images + 1), tile_choice (tiles entries in flat tile order, may be NULL) and the groups'
+ * lambda, bytes, sse and flags (n_groups each); the files go to out when out_capacity >= file_offsets[n_images], else the call
+ * returns PXZ_ERR_BUFFER_TOO_SMALL and writes nothing to out (out may be NULL for that size query).  A tile without a usable
+ * candidate or a choice beyond the ladder cannot come from the library's own ladder: PXZ_ERR_INTERNAL.  Errors and limits are
+ * those of the calls it composes; on any other error nothing is written. */
+int pxz_encode_varied_images_fit_tiles(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                       uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                       uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                       const uint32_t *group_first /* may be NULL */, uint32_t n_groups, const uint64_t *targets,
+                                       uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets,
+                                       uint32_t *tile_choice /* may be NULL */, uint64_t *group_lambda, uint64_t *group_bytes,
+                                       uint64_t *group_sse, uint32_t *group_flags);
+
+/* The same for an archive, as pxz_transcode_varied_files_fit: the error of a candidate is measured against what its file
+ * decodes to NOW (pxz_reshrink_distortion_varied_device with its per-tile sums), nothing of image size exists on the device,
+ * and a malformed file or a tile that cannot be fails the whole call before anything is written.  group_sse[g] is the squared
+ * error between what the group's input files decode to (expand_filter) and what its output files decode to (filter_up). */
+int pxz_transcode_varied_files_fit_tiles(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                         const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                         uint32_t n_factors, uint32_t criterion, const uint32_t *group_first /* may be NULL */,
+                                         uint32_t n_groups, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                                         uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice /* may be NULL */,
+                                         uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags);
+
 /* ---- legacy image -> image filter ------------------------ */
 
 /* process_custom (src/process/mod.rs:71-102) with the closures of process() (:107-121: |x - avg| and the

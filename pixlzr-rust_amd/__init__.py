@@ -14,5 +14,6 @@ from .binding import (  # noqa: F401
     EXPORTED_SYMBOLS, LADDER_MAX_RUNGS, VARIED_LADDER_MAX_RUNGS, varied_layout, image_descs, file_header, psnr,
     Window, window_descs, window_layout, reshrink_lds_bytes, reshrink_ladder_lds_bytes,
     FIT_BYTES, FIT_SSE, fit_select, sse_for_psnr, reshrink_distortion_lds_bytes,
+    TILEFIT_LAMBDA_MAX, TILEFIT_MISSED, TILEFIT_NO_CANDIDATE, TILEFIT_UNIFORM, fit_tiles_select,
 )
 from . import dist  # noqa: E402,F401  (torch.distributed plumbing: frame sharding + block-stream gather)

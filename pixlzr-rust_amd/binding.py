@@ -31,11 +31,15 @@ EXPORTED_SYMBOLS = [
     "pxz_fit_select", "pxz_fit_varied_ladder_device", "pxz_gather_varied_rungs_device", "pxz_encode_varied_images_fit",
     "pxz_reshrink_distortion_varied_device", "pxz_reshrink_distortion_lds_bytes", "pxz_rate_distortion_varied_files",
     "pxz_transcode_varied_files_fit",
+    "pxz_fit_tiles_select", "pxz_record_bytes_varied_device", "pxz_fit_varied_tiles_device", "pxz_gather_varied_tile_rungs_device",
+    "pxz_encode_varied_images_fit_tiles", "pxz_transcode_varied_files_fit_tiles",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
 VARIED_LADDER_MAX_RUNGS = 32  # PXZ_VARIED_LADDER_MAX_RUNGS
 FIT_BYTES, FIT_SSE = 0, 1  # pxz_fit
+TILEFIT_LAMBDA_MAX = 2 ** 32  # PXZ_TILEFIT_LAMBDA_MAX
+TILEFIT_MISSED, TILEFIT_NO_CANDIDATE, TILEFIT_UNIFORM = 1, 2, 4  # bits of a group's flags (pxz_fit_tiles_select)
 
 STATUS = {0: "PXZ_OK", -1: "PXZ_ERR_INVALID_ARG", -2: "PXZ_ERR_NO_DEVICE", -3: "PXZ_ERR_HIP",
           -4: "PXZ_ERR_TILE_TOO_SMALL", -5: "PXZ_ERR_UNSUPPORTED", -6: "PXZ_ERR_NOMEM",
@@ -222,6 +226,21 @@ def load_library():
         L.pxz_rate_distortion_varied_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, vp, vp]
         L.pxz_transcode_varied_files_fit.restype = C.c_int
         L.pxz_transcode_varied_files_fit.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, u32, vp, u32, vp, C.c_uint64] + [vp] * 5
+    if hasattr(L, "pxz_fit_tiles_select"):  # (a build of an earlier commit named by PXZ_LIB lacks the per-tile fit)
+        L.pxz_fit_tiles_select.restype = C.c_int
+        L.pxz_fit_tiles_select.argtypes = [u32, vp, vp, u32, u32, u32] + [vp] * 8
+        L.pxz_record_bytes_varied_device.restype = C.c_int
+        L.pxz_record_bytes_varied_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 6
+        L.pxz_fit_varied_tiles_device.restype = C.c_int
+        L.pxz_fit_varied_tiles_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), vp, u32, u32, u32] + [vp] * 8
+        L.pxz_gather_varied_tile_rungs_device.restype = C.c_int
+        L.pxz_gather_varied_tile_rungs_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 10
+        L.pxz_encode_varied_images_fit_tiles.restype = C.c_int
+        L.pxz_encode_varied_images_fit_tiles.argtypes = ([vp, vp, vp] + [u32] * 7 + [vp, u32, u32, vp, u32, vp, u32, vp, C.c_uint64]
+                                                         + [vp] * 6)
+        L.pxz_transcode_varied_files_fit_tiles.restype = C.c_int
+        L.pxz_transcode_varied_files_fit_tiles.argtypes = ([vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, u32, vp, u32, vp, u32, vp,
+                                                            C.c_uint64] + [vp] * 6)
     L.pxz_lod_frames_device.restype = C.c_int
     L.pxz_lod_frames_device.argtypes = [vp, C.POINTER(Frames), C.POINTER(Params)] + [vp] * 3
     L.pxz_oklab_pixels_device.restype = C.c_int
@@ -414,6 +433,32 @@ def fit_select(file_bytes, sse, criterion, targets, n_images=None, n_factors=Non
     if rc != 0:
         raise PxzError(rc)
     return choice[:n], flags[:n]
+
+
+def fit_tiles_select(group_tile_offsets, group_fixed_bytes, tile_bytes, tile_sse, criterion, targets, n_groups=None, n_factors=None,
+                     channels=None, out=None):
+    """pxz_fit_tiles_select: the rung of every tile under its group's target, on the host.  group_tile_offsets (G + 1 integers
+    from 0 on), group_fixed_bytes and targets (G integers), tile_bytes uint32[K, T] and tile_sse uint64[K, T, C] -> (tile_choice
+    uint32[T], lambda uint64[G], bytes uint64[G], sse uint64[G], flags uint32[G]; TILEFIT_MISSED | TILEFIT_NO_CANDIDATE |
+    TILEFIT_UNIFORM).  No GPU.  n_groups, n_factors and channels override what the shapes say, None among the arrays passes a
+    null pointer, and out = such a 5-tuple is written in place (all for the error cases)."""
+    u64 = lambda a: None if a is None else np.array([int(x) for x in a], np.uint64)  # noqa: E731
+    off, fixed, tg = u64(group_tile_offsets), u64(group_fixed_bytes), u64(targets)
+    tb = None if tile_bytes is None else np.ascontiguousarray(tile_bytes, np.uint32)
+    ts = None if tile_sse is None else np.ascontiguousarray(tile_sse, np.uint64)
+    G = n_groups if n_groups is not None else len(off) - 1
+    K = n_factors if n_factors is not None else tb.shape[0]
+    ch = channels if channels is not None else ts.shape[2]
+    T = int(off[-1]) if off is not None and len(off) else 0
+    if out is None:
+        out = (np.zeros(max(T, 1), np.uint32), np.zeros(max(G, 1), np.uint64), np.zeros(max(G, 1), np.uint64), np.zeros(max(G, 1), np.uint64),
+               np.zeros(max(G, 1), np.uint32))
+    choice, lam, gb, gs, fl = out
+    rc = load_library().pxz_fit_tiles_select(G, _p(off), _p(fixed), K, ch, criterion, _p(tg), _p(tb), _p(ts), _p(choice), _p(lam), _p(gb),
+                                             _p(gs), _p(fl))
+    if rc != 0:
+        raise PxzError(rc)
+    return choice[:T], lam[:G], gb[:G], gs[:G], fl[:G]
 
 
 def axis_table(in_size, out_size, filt):
@@ -1293,6 +1338,159 @@ class Handle:
         if want_table:
             return res, choice[:n], flags[:n], table_bytes[:K, :n], table_sse[:K, :n]
         return res, choice[:n], flags[:n]
+
+    # ---- fit to a budget per tile ----
+    def record_bytes_varied_device(self, sizes, channels, bw, bh, vals, ow, oh, slots, want_offsets=True, out=None):
+        """pxz_record_bytes_varied_device: sizes = [(width, height), ...] of the images whose tiles (varied layout; for a ladder's
+        result the sizes repeated K times and the tensors flattened) are given -> (record_bytes int32[T], file_offsets
+        int64[n+1] | None): the bytes of every tile's record in its file, and what encode_varied_frames_device gives for its
+        offsets.  out: such a pair (the offsets may be None); None for a tensor passes a null pointer."""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        n = len(geoms)
+        if out is None:
+            T = int(varied_layout(geoms, bw, bh)[-1])
+            out = (torch.empty(T, dtype=torch.int32, device=vals.device),
+                   torch.empty(n + 1, dtype=torch.int64, device=vals.device) if want_offsets else None)
+        rec, offs = out
+        pd = Params(bw, bh, 0, 0, 1.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_record_bytes_varied_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, C.byref(pd), ptr(vals), ptr(ow), ptr(oh), ptr(slots),
+            ptr(rec), ptr(offs)))
+        return rec, offs
+
+    def fit_varied_tiles_device(self, sizes, channels, bw, bh, record_bytes, tile_sse, criterion, targets, group_first=None, n_groups=None,
+                                n_factors=None, out=None):
+        """pxz_fit_varied_tiles_device: fit_tiles_select on the device.  sizes = [(width, height), ...] of the images,
+        record_bytes int32[K, T] (record_bytes_varied_device over the images repeated K times) and tile_sse int64[K, T, C] (the
+        distortion calls' per-tile sums over the same) are CUDA tensors; group_first (G + 1 host image indices, None: every
+        image its own group) and targets (G host integers) -> (tile_choice int32[T], lambda int64[G], bytes int64[G], sse
+        int64[G], flags int32[G]) CUDA tensors, or out = such a 5-tuple.  n_groups and n_factors override what the arguments
+        say; None for targets or a tensor passes a null pointer."""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        n = len(geoms)
+        gf = None if group_first is None else np.array([int(x) for x in group_first], np.uint32)
+        G = n_groups if n_groups is not None else (n if gf is None else len(gf) - 1)
+        K = n_factors if n_factors is not None else record_bytes.shape[0]
+        tg = None if targets is None else np.array([int(t) for t in targets], np.uint64)
+        if out is None:
+            T = int(varied_layout(geoms, bw, bh)[-1])
+            dev = torch.device("cuda", self.device_id)
+            out = (torch.empty(T, dtype=torch.int32, device=dev),) + tuple(torch.empty(G, dtype=torch.int64, device=dev) for _ in range(3)) + (
+                torch.empty(G, dtype=torch.int32, device=dev),)
+        pd = Params(bw, bh, 0, 0, 0.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_fit_varied_tiles_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, C.byref(pd), _p(gf), G, K, criterion, _p(tg),
+            ptr(record_bytes), ptr(tile_sse), *[ptr(t) for t in out]))
+        return out
+
+    def gather_varied_tile_rungs_device(self, sizes, channels, bw, bh, n_factors, tile_choice, vals, ow, oh, slots, out=None,
+                                        image_flags=None, want_pixels=True):
+        """pxz_gather_varied_tile_rungs_device: gather_varied_rungs_device with a choice per tile -- tile_choice int32[T] CUDA in
+        flat tile order; output tile t comes from rung tile_choice[t].  image_flags (int32[n] CUDA, optional) gets 2 for an
+        image that holds a tile whose choice was n_factors or more, else 0."""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        if out is None:
+            T = int(varied_layout(geoms, bw, bh)[-1])
+            dev = vals.device
+            out = (torch.empty(T, dtype=torch.float32, device=dev), torch.empty(T, dtype=torch.int32, device=dev),
+                   torch.empty(T, dtype=torch.int32, device=dev),
+                   torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None)
+        o_vals, o_w, o_h, o_slots = out
+        pd = Params(bw, bh, 0, 0, 0.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_gather_varied_tile_rungs_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), n_factors, ptr(tile_choice), ptr(vals),
+            ptr(ow), ptr(oh), ptr(slots), ptr(o_vals), ptr(o_w), ptr(o_h), ptr(o_slots), ptr(image_flags)))
+        return o_vals, o_w, o_h, o_slots
+
+    def _fit_tiles_outputs(self, n, G, T):
+        return (np.zeros(n + 1, np.uint64), np.zeros(max(T, 1), np.uint32), np.zeros(max(G, 1), np.uint64), np.zeros(max(G, 1), np.uint64),
+                np.zeros(max(G, 1), np.uint64), np.zeros(max(G, 1), np.uint32))
+
+    def _fit_tiles_result(self, call, first_size, n, G, T, res, out):
+        """the two-call protocol of the tile-fit forms: out None -> a first guess, then the exact size"""
+        offs, choice, lam, gb, gs, fl = res
+        if out is None:
+            out = np.empty(first_size, np.uint8)
+            rc = call(out)
+            if rc == -7:
+                out = np.empty(int(offs[-1]), np.uint8)
+                rc = call(out)
+        else:
+            rc = call(out)
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.needed, err.tile_choice, err.groups = int(offs[-1]), choice[:T].copy(), (lam[:G].copy(), gb[:G].copy(), gs[:G].copy(), fl[:G].copy())
+            raise err
+        files = [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+        return files, choice[:T], lam[:G], gb[:G], gs[:G], fl[:G]
+
+    def encode_varied_images_fit_tiles(self, imgs, bw, bh, mode, filter_down, filter_up, factors, criterion, targets, group_first=None,
+                                       filter_byte=0, out=None):
+        """pxz_encode_varied_images_fit_tiles: host images (numpy uint8 [H, W, C], one channel count) -> one .pixlzr file per
+        image whose tiles come from the rungs of `factors` (1..32) that fit_tiles_select picks under targets[g] for the groups
+        of group_first (G + 1 image indices; None: every image its own group).  Returns (files: a list of bytes, tile_choice
+        uint32[T] in flat tile order, lambda uint64[G], bytes uint64[G], sse uint64[G], flags uint32[G]).  out: a numpy uint8
+        buffer to write into (PxzError -7 with .needed, .tile_choice and .groups when it is too small; size 0 is the size
+        query), else the buffer is sized by a first call."""
+        imgs = [np.ascontiguousarray(i) if i.strides[1] != i.shape[2] or i.strides[2] != 1 else i for i in imgs]
+        n = len(imgs)
+        ch = imgs[0].shape[2] if n else 4
+        geoms = [(i.shape[1], i.shape[0], i.strides[0], 0) for i in imgs]
+        ptrs = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in imgs])
+        descs = image_descs(geoms)
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        gf = None if group_first is None else np.array([int(x) for x in group_first], np.uint32)
+        G = n if gf is None else len(gf) - 1
+        tg = np.array([int(t) for t in targets], np.uint64)
+        T = int(varied_layout(geoms, bw, bh)[-1]) if n else 0
+        res = self._fit_tiles_outputs(n, G, T)
+
+        def call(buf):
+            return self._L.pxz_encode_varied_images_fit_tiles(
+                self._h, C.cast(ptrs, C.c_void_p), C.cast(descs, C.c_void_p), n, ch, bw, bh, mode, filter_down, filter_up,
+                _p(fac) if K else None, K, criterion, _p(gf), G, _p(tg) if tg.size else None, filter_byte,
+                _p(buf) if buf is not None and buf.size else None, 0 if buf is None else buf.size, *[_p(a) for a in res])
+        return self._fit_tiles_result(call, sum(i.size for i in imgs) * 5 // 4 + 4096 * max(n, 1), n, G, T, res, out)
+
+    def transcode_varied_files_fit_tiles(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
+                                         group_first=None, filter_byte=0, out=None):
+        """pxz_transcode_varied_files_fit_tiles: the same for a list of .pixlzr files (bytes) of one channel count and of block
+        size bw x bh, the error measured against what each file decodes to now (expand_filter).  Returns and out as
+        encode_varied_images_fit_tiles."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        fac = np.ascontiguousarray(factors, np.float32)
+        K = fac.size
+        gf = None if group_first is None else np.array([int(x) for x in group_first], np.uint32)
+        G = n if gf is None else len(gf) - 1
+        tg = np.array([int(t) for t in targets], np.uint64)
+        pd = Params(bw, bh, mode, filter_down, 0.0, 0)
+        try:
+            geoms = [file_header(f)[:2] for f in files]
+            T = int(varied_layout([(w, h, 0, 0) for (w, h) in geoms], bw, bh)[-1])
+        except PxzError:  # (a malformed file: the call itself says which)
+            T = 0
+        res = self._fit_tiles_outputs(n, G, T)
+
+        def call(buf):
+            return self._L.pxz_transcode_varied_files_fit_tiles(
+                self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd), expand_filter, filter_up,
+                _p(fac) if K else None, K, criterion, _p(gf), G, _p(tg) if tg.size else None, filter_byte,
+                _p(buf) if buf is not None and buf.size else None, 0 if buf is None else buf.size, res[0].ctypes.data,
+                _p(res[1]) if T else None, *[_p(a) for a in res[2:]])
+        return self._fit_tiles_result(call, sum(b.size for b in bufs) + 4096 * max(n, 1), n, G, T, res, out)
 
     # ---- decode side: Pixlzr::expand + to_image ----
     def expand_image(self, width, height, channels, bw, bh, filt, tile_w, tile_h, slots):

@@ -33,6 +33,7 @@
 #include "pxz_launch.h"
 #include "pxz_runtime.h"
 #include "pxz_tables.h"
+#include "pxz_tilefit.h"
 
 using namespace pxz_runtime;
 using pxz::kLdsPerCu;
@@ -111,6 +112,24 @@ int fit_check(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t cha
 	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
 	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
 		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	return PXZ_OK;
+}
+
+// the groups of the per-tile fit: runs of consecutive images, given by their first images (null: every image its own group)
+int tile_groups_check(pxz_handle *h, const uint32_t *group_first, uint32_t n_groups, uint32_t n_images)
+{
+	if (!group_first) {
+		if (n_groups != n_images)
+			return fail(h, PXZ_ERR_INVALID_ARG, "group_first is null (every image its own group): n_groups must be n_images = %u, got %u", n_images,
+			            n_groups);
+		return PXZ_OK;
+	}
+	if (n_groups == 0 || n_groups > n_images) return fail(h, PXZ_ERR_INVALID_ARG, "n_groups must be 1..n_images = %u, got %u", n_images, n_groups);
+	if (group_first[0] != 0 || group_first[n_groups] != n_images)
+		return fail(h, PXZ_ERR_INVALID_ARG, "group_first must run from 0 to n_images = %u", n_images);
+	for (uint32_t g = 0; g < n_groups; ++g)
+		if (group_first[g + 1u] <= group_first[g] || group_first[g + 1u] > n_images)
+			return fail(h, PXZ_ERR_INVALID_ARG, "group %u: group_first must ascend (a group has an image)", g);
 	return PXZ_OK;
 }
 
@@ -2202,6 +2221,71 @@ void varied_fill_args(pxz_handle *h, const std::vector<pxz::VariedImage> &images
 	std::memcpy(a->thresholds, h->thresholds, sizeof a->thresholds);
 }
 
+// The varied writer behind both of its entry points, past their null checks.  pxz_encode_varied_frames_device: d_out and
+// d_file_offsets given, d_record_bytes null.  pxz_record_bytes_varied_device: d_out null and no capacity -- the same launches,
+// which then write the offsets alone -- and the record lengths out of the writer's scratch behind them.
+int encode_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, const pxz_params *params,
+                  uint32_t filter_byte, const float *d_block_value, const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots,
+                  uint8_t *d_out, uint64_t out_capacity, uint64_t *d_file_offsets, uint32_t *d_record_bytes)
+{
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4");
+	std::vector<pxz::VariedImage> images;
+	uint32_t n_rows = 0;
+	int rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, 0, 0, &images, nullptr, &n_rows);
+	if (rc != PXZ_OK) return rc;
+	const uint32_t n_tiles = varied_n_tiles(images), c = channels;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::QoiArgs a{};
+	if ((rc = writer_scratch(h, n_tiles, params->block_w, params->block_h, c, &a)) != PXZ_OK) return rc;
+	pxz::VariedWriterArgs v{};
+	if ((rc = varied_upload(h, images, &v.images)) != PXZ_OK) return rc;
+	a.slots = d_slots;
+	a.w = d_tile_w;
+	a.h = d_tile_h;
+	a.value = d_block_value;
+	a.out = d_out;
+	a.file_offsets = (unsigned long long *)d_file_offsets;
+	a.capacity = out_capacity;
+	// one "frame" of n_tiles tiles and no tile rows of its own: the splice puts record t at hdr_bytes + scan(t), and the
+	// per-image headers come from varied_headers_kernel
+	a.tiles_per_frame = n_tiles;
+	a.cols = 0;
+	a.rows = 0;
+	a.channels = c;
+	a.hdr_bytes = images[0].hdr_bytes;
+	a.bw = params->block_w;
+	a.bh = params->block_h;
+	a.filter_byte = filter_byte;
+	v.n_images = n_images;
+	v.n_tiles = n_tiles;
+	v.n_rows = n_rows;
+	v.bw = params->block_w;
+	v.bh = params->block_h;
+	v.filter_byte = filter_byte;
+	v.rec_len = a.rec_len;
+	v.offsets = a.offsets;
+	v.chunk_totals = a.chunk_totals;
+	v.out = d_out;
+	v.file_offsets = a.file_offsets;
+	v.capacity = out_capacity;
+	if (!d_out) {
+		// pxz_record_bytes_varied_device: no room, so no byte of a file is written -- the pointer only has to be one
+		a.out = v.out = a.scratch;
+		if (!d_file_offsets) {
+			if ((rc = ensure(h, h->record_offsets, ((size_t)n_images + 1u) * 8u)) != PXZ_OK) return rc;
+			a.file_offsets = v.file_offsets = (unsigned long long *)h->record_offsets.ptr;
+		}
+	}
+	if ((rc = launch_on_bins(h, h->qbins_clean, a.bins,
+	                         [&](bool bins_clean) { return pxz::launch_qoi_varied(a, v, bins_clean, h->n_cus, h->stream); })) != PXZ_OK)
+		return rc;
+	if (!d_record_bytes) return PXZ_OK;
+	// (the per-image table is still where varied_upload put it: nothing has been uploaded over it since)
+	const pxz::RecordBytesArgs rb{v.images, n_images, n_tiles, a.rec_len, d_record_bytes};
+	PXZ_HIP(h, pxz::launch_record_bytes(rb, h->stream));
+	return PXZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2281,48 +2365,17 @@ int pxz_encode_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params || !d_block_value || !d_tile_w || !d_tile_h || !d_slots || !d_out || !d_file_offsets)
 		return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4");
-	std::vector<pxz::VariedImage> images;
-	uint32_t n_rows = 0;
-	int rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, 0, 0, &images, nullptr, &n_rows);
-	if (rc != PXZ_OK) return rc;
-	const uint32_t n_tiles = varied_n_tiles(images), c = channels;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	pxz::QoiArgs a{};
-	if ((rc = writer_scratch(h, n_tiles, params->block_w, params->block_h, c, &a)) != PXZ_OK) return rc;
-	pxz::VariedWriterArgs v{};
-	if ((rc = varied_upload(h, images, &v.images)) != PXZ_OK) return rc;
-	a.slots = d_slots;
-	a.w = d_tile_w;
-	a.h = d_tile_h;
-	a.value = d_block_value;
-	a.out = d_out;
-	a.file_offsets = (unsigned long long *)d_file_offsets;
-	a.capacity = out_capacity;
-	// one "frame" of n_tiles tiles and no tile rows of its own: the splice puts record t at hdr_bytes + scan(t), and the
-	// per-image headers come from varied_headers_kernel
-	a.tiles_per_frame = n_tiles;
-	a.cols = 0;
-	a.rows = 0;
-	a.channels = c;
-	a.hdr_bytes = images[0].hdr_bytes;
-	a.bw = params->block_w;
-	a.bh = params->block_h;
-	a.filter_byte = filter_byte;
-	v.n_images = n_images;
-	v.n_tiles = n_tiles;
-	v.n_rows = n_rows;
-	v.bw = params->block_w;
-	v.bh = params->block_h;
-	v.filter_byte = filter_byte;
-	v.rec_len = a.rec_len;
-	v.offsets = a.offsets;
-	v.chunk_totals = a.chunk_totals;
-	v.out = d_out;
-	v.file_offsets = a.file_offsets;
-	v.capacity = out_capacity;
-	return launch_on_bins(h, h->qbins_clean, a.bins,
-	                      [&](bool bins_clean) { return pxz::launch_qoi_varied(a, v, bins_clean, h->n_cus, h->stream); });
+	return encode_varied(h, descs, n_images, channels, params, filter_byte, d_block_value, d_tile_w, d_tile_h, d_slots, d_out, out_capacity,
+	                     d_file_offsets, nullptr);
+}
+
+int pxz_record_bytes_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                   const pxz_params *params, const float *d_block_value, const uint32_t *d_tile_w,
+                                   const uint32_t *d_tile_h, const uint8_t *d_slots, uint32_t *d_record_bytes, uint64_t *d_file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params || !d_block_value || !d_tile_w || !d_tile_h || !d_slots || !d_record_bytes) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	return encode_varied(h, descs, n_images, channels, params, 0, d_block_value, d_tile_w, d_tile_h, d_slots, nullptr, 0, d_file_offsets, d_record_bytes);
 }
 
 }  // extern "C"
@@ -2788,6 +2841,151 @@ int pxz_gather_varied_rungs_device(pxz_handle *h, const pxz_image_desc *descs, u
 	a.out_slots = d_out_pixels;
 	a.image_flags = d_image_flags;
 	PXZ_HIP(h, pxz::launch_gather_rungs(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+// ---- fit to a budget per tile: one rung per tile under a target per group of images (pxz_tilefit.h, pxz_tilefit.hip) -------
+int pxz_fit_tiles_select(uint32_t n_groups, const uint64_t *group_tile_offsets, const uint64_t *group_fixed_bytes, uint32_t n_factors,
+                         uint32_t channels, uint32_t criterion, const uint64_t *targets, const uint32_t *tile_bytes, const uint64_t *tile_sse,
+                         uint32_t *tile_choice, uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags)
+{
+	if (!group_tile_offsets || !group_fixed_bytes || !targets || !tile_bytes || !tile_sse || !tile_choice || !group_lambda || !group_bytes ||
+	    !group_sse || !group_flags)
+		return PXZ_ERR_INVALID_ARG;
+	const int rc = fit_check(nullptr, n_groups, n_factors, channels, criterion);  // (n_groups 0: "empty", as no images there)
+	if (rc != PXZ_OK) return rc;
+	if (group_tile_offsets[0] != 0) return PXZ_ERR_INVALID_ARG;
+	for (uint32_t g = 0; g < n_groups; ++g)
+		if (group_tile_offsets[g + 1u] <= group_tile_offsets[g]) return PXZ_ERR_INVALID_ARG;  // (a group has a tile)
+	const uint64_t tiles = group_tile_offsets[n_groups];
+	if (tiles * n_factors > 0xffffffffull) return PXZ_ERR_UNSUPPORTED;
+	std::vector<uint64_t> cand(tiles * n_factors);
+	for (uint64_t k = 0; k < cand.size(); ++k) cand[k] = pxz::tilefit_pack(tile_bytes[k], tile_sse + k * channels, channels);
+	for (uint32_t g = 0; g < n_groups; ++g) {
+		const uint64_t t0 = group_tile_offsets[g];
+		const pxz::TileFitGroup r = pxz::tilefit_group(
+			n_factors, criterion, targets[g], group_fixed_bytes[g], group_tile_offsets[g + 1u] - t0,
+			[&](uint32_t rung, uint64_t t) { return cand[rung * tiles + t0 + t]; }, tile_choice + t0);
+		group_lambda[g] = r.lambda;
+		group_bytes[g] = r.bytes;
+		group_sse[g] = r.sse;
+		group_flags[g] = r.flags;
+	}
+	return PXZ_OK;
+}
+
+int pxz_fit_varied_tiles_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, const pxz_params *params,
+                                const uint32_t *group_first, uint32_t n_groups, uint32_t n_factors, uint32_t criterion, const uint64_t *targets,
+                                const uint32_t *d_record_bytes, const uint64_t *d_tile_sse, uint32_t *d_tile_choice, uint64_t *d_group_lambda,
+                                uint64_t *d_group_bytes, uint64_t *d_group_sse, uint32_t *d_group_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!d_record_bytes || !d_tile_sse || !d_tile_choice || !d_group_lambda || !d_group_bytes || !d_group_sse || !d_group_flags)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	int rc = fit_check(h, n_images, n_factors, channels, criterion);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	// a tile's error stays below 2^32 (tilefit_pack) while it has at most 65536 samples: 65536 * 255^2 < 2^32
+	if ((uint64_t)params->block_w * params->block_h * channels > 65536u)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "the per-tile fit keeps a tile's squared error in 32 bits: block_w*block_h*channels must not exceed 65536");
+	const uint32_t n_tiles = varied_n_tiles(images);
+	if ((uint64_t)n_factors * n_tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	if ((rc = tile_groups_check(h, group_first, n_groups, n_images)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// the groups' table as the kernels read it: targets | fixed bytes | first tiles (n_groups + 1)
+	const size_t G = n_groups, K = n_factors;
+	const size_t table_bytes = up256(16u * G + 4u * (G + 1u));
+	std::vector<uint8_t> table(table_bytes);
+	uint64_t *t_targets = reinterpret_cast<uint64_t *>(table.data()), *t_fixed = t_targets + G;
+	uint32_t *t_tile0 = reinterpret_cast<uint32_t *>(t_fixed + G);
+	for (uint32_t g = 0; g < n_groups; ++g) {
+		const uint32_t i0 = group_first ? group_first[g] : g, i1 = group_first ? group_first[g + 1u] : g + 1u;
+		t_targets[g] = targets[g];
+		t_fixed[g] = 0;
+		for (uint32_t i = i0; i < i1; ++i) t_fixed[g] += images[i].hdr_bytes;
+		t_tile0[g] = images[i0].tile0;
+	}
+	t_tile0[n_groups] = n_tiles;
+	// behind it, zeroed: the steps' totals, the totals at lambda*, the uniform totals, the groups' bits; then what the kernels
+	// write before they read it: the intervals, the uniform rungs, the tiles' groups, the packed candidates
+	const size_t zero_u64 = (size_t)pxz::kTileFitSteps * G + 2u * G + 3u * K * G;
+	const size_t zero_bytes = zero_u64 * 8u + up256(4u * G);
+	const size_t interval_at = table_bytes + zero_bytes, uni_rung_at = interval_at + 32u * G;
+	const size_t tile_group_at = uni_rung_at + up256(4u * G), cand_at = tile_group_at + up256(4u * (size_t)n_tiles);
+	if ((rc = ensure(h, h->tilefit, cand_at + 8u * K * n_tiles)) != PXZ_OK) return rc;
+	uint8_t *d = (uint8_t *)h->tilefit.ptr;
+	PXZ_HIP(h, h->tilefit_table.send(table.data(), table_bytes, d, h->stream));
+	PXZ_HIP(h, hipMemsetAsync(d + table_bytes, 0, zero_bytes, h->stream));
+	pxz::TileFitArgs a{};
+	a.n_tiles = n_tiles;
+	a.n_groups = n_groups;
+	a.n_factors = n_factors;
+	a.channels = channels;
+	a.criterion = criterion;
+	a.targets = (const unsigned long long *)d;
+	a.fixed = a.targets + G;
+	a.group_tile0 = (const uint32_t *)(a.fixed + G);
+	a.acc = (unsigned long long *)(d + table_bytes);
+	a.tot = a.acc + (size_t)pxz::kTileFitSteps * G;
+	a.uni = a.tot + 2u * G;
+	a.group_bits = (uint32_t *)(a.uni + 3u * K * G);
+	a.interval = (unsigned long long *)(d + interval_at);
+	a.uni_rung = (uint32_t *)(d + uni_rung_at);
+	a.tile_group = (uint32_t *)(d + tile_group_at);
+	a.cand = (unsigned long long *)(d + cand_at);
+	a.record_bytes = d_record_bytes;
+	a.tile_sse = (const unsigned long long *)d_tile_sse;
+	a.tile_choice = d_tile_choice;
+	a.group_lambda = (unsigned long long *)d_group_lambda;
+	a.group_bytes = (unsigned long long *)d_group_bytes;
+	a.group_sse = (unsigned long long *)d_group_sse;
+	a.group_flags = d_group_flags;
+	PXZ_HIP(h, pxz::launch_tilefit(a, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_gather_varied_tile_rungs_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                        const pxz_params *params, uint32_t n_factors, const uint32_t *d_tile_choice,
+                                        const float *d_block_value, const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots,
+                                        float *d_out_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (n_factors == 0 || n_factors > PXZ_VARIED_LADDER_MAX_RUNGS)
+		return fail(h, PXZ_ERR_INVALID_ARG, "n_factors must be 1..%u, got %u", PXZ_VARIED_LADDER_MAX_RUNGS, n_factors);
+	if (!d_tile_choice || !d_block_value || !d_tile_w || !d_tile_h || !d_out_value || !d_out_w || !d_out_h || (d_out_pixels && !d_slots))
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	std::vector<pxz::VariedImage> images;
+	int rc = varied_plan(h, descs, n_images, params->block_w, params->block_h, channels, 0, &images, nullptr, nullptr);
+	if (rc != PXZ_OK) return rc;
+	const uint64_t slot = (uint64_t)params->block_w * params->block_h * channels;
+	if (slot > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a slot of %ux%u px takes more than 2^32-1 bytes", params->block_w, params->block_h);
+	if ((uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::GatherArgs a{};
+	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.n_images = n_images;
+	a.n_tiles = varied_n_tiles(images);
+	a.n_factors = n_factors;
+	a.slot_bytes = (uint32_t)slot;
+	a.choice = d_tile_choice;
+	a.value = (const uint32_t *)d_block_value;
+	a.w = d_tile_w;
+	a.h = d_tile_h;
+	a.slots = d_slots;
+	a.out_value = (uint32_t *)d_out_value;
+	a.out_w = d_out_w;
+	a.out_h = d_out_h;
+	a.out_slots = d_out_pixels;
+	a.image_flags = d_image_flags;
+	PXZ_HIP(h, pxz::launch_gather_tile_rungs(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
 }
 

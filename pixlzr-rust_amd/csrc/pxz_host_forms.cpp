@@ -232,19 +232,24 @@ int download_rung_table(pxz_handle *h, const RungTable &t, uint32_t ch, uint64_t
 
 // Fills the table of the rungs `all` (rung-major, n_factors sets of the images descs): the writer over the descriptors once per
 // rung, for its offsets alone, then the rungs' distortion -- against the images at d_images (ref null: descs say where), or
-// against the archive's own tiles *ref, which expand_filter expands.
+// against the archive's own tiles *ref, which expand_filter expands.  The tile-fit forms want the same per tile: with
+// d_record_bytes the writer's pass is pxz_record_bytes_varied_device (the offsets come with it), and d_tile_sse takes the
+// distortion call's per-tile sums (both null: the per-image forms, as before).
 int rung_table(pxz_handle *h, const std::vector<pxz_image_desc> &descs, uint32_t n_factors, uint32_t ch, const pxz_params &p, const pxz_params &up,
-               const TileSet &all, const RungTable &t, const uint8_t *d_images, const TileSet *ref, uint32_t expand_filter)
+               const TileSet &all, const RungTable &t, const uint8_t *d_images, const TileSet *ref, uint32_t expand_filter,
+               uint32_t *d_record_bytes = nullptr, uint64_t *d_tile_sse = nullptr)
 {
 	const std::vector<pxz_image_desc> rungs = repeat_descs(descs, n_factors);
-	const int rc = pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &p, 0, all.value, all.w, all.h, all.slots, t.d_room, 0,
-	                                               t.d_offs);
+	const int rc = d_record_bytes ? pxz_record_bytes_varied_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &p, all.value, all.w, all.h, all.slots,
+	                                                               d_record_bytes, t.d_offs)
+	                              : pxz_encode_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &p, 0, all.value, all.w, all.h, all.slots,
+	                                                                t.d_room, 0, t.d_offs);
 	if (rc != PXZ_OK) return rc;
 	if (!ref)
-		return pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &up, d_images, all.w, all.h, all.slots, nullptr, t.d_sse,
+		return pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &up, d_images, all.w, all.h, all.slots, d_tile_sse, t.d_sse,
 		                                           nullptr);
 	return pxz_reshrink_distortion_varied_device(h, descs.data(), (uint32_t)descs.size(), ch, &up, expand_filter, n_factors, ref->w, ref->h, ref->slots,
-	                                             all.w, all.h, all.slots, nullptr, t.d_sse, nullptr);
+	                                             all.w, all.h, all.slots, d_tile_sse, t.d_sse, nullptr);
 }
 
 // The files of `tiles` (n_factors sets of the images descs, rung-major) into varied_files and out to the caller: a first guess
@@ -289,7 +294,22 @@ struct Rungs {
 	uint64_t raw = 0;
 	TileSet all;
 	RungTable t;
+	bool per_tile = false;             // the tile-fit forms (set by the caller): the two tables below are wanted
+	uint32_t *d_record_bytes = nullptr;  // every rung's record bytes (n_factors * n_tiles) ...
+	uint64_t *d_tile_sse = nullptr;      // ... and squared errors per channel, in tilefit_tables
 };
+
+// the per-tile tables of the tile-fit forms, over `tiles` = n_factors * n_tiles rung tiles (nothing unless s->per_tile)
+int carve_tile_tables(pxz_handle *h, uint64_t tiles, uint32_t ch, Rungs *s)
+{
+	if (!s->per_tile) return PXZ_OK;
+	const uint64_t sse_at = up256(tiles * 4u);
+	const int rc = ensure(h, h->tilefit_tables, sse_at + tiles * ch * 8u);
+	if (rc != PXZ_OK) return rc;
+	s->d_record_bytes = (uint32_t *)h->tilefit_tables.ptr;
+	s->d_tile_sse = (uint64_t *)((uint8_t *)h->tilefit_tables.ptr + sse_at);
+	return PXZ_OK;
+}
 
 // The image forms from their parameter checks to the filled table: the ladder over the images, then rung_table against the
 // images themselves.  criterion: the fit form's, checked in its place among the others (null: no fit).
@@ -317,12 +337,13 @@ int image_rungs(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_des
 	const uint64_t slot = (uint64_t)block_w * block_h * channels;
 	if ((rc = ensure(h, h->varied_out, TileSet::bytes(tiles, slot))) != PXZ_OK) return rc;
 	if ((rc = carve_rung_table(h, (size_t)n_sets, channels, criterion ? n_images : 0u, &s->t)) != PXZ_OK) return rc;
+	if ((rc = carve_tile_tables(h, tiles, channels, s)) != PXZ_OK) return rc;
 	const uint8_t *d_in = (const uint8_t *)h->varied_in.ptr;
 	s->all = TileSet((uint8_t *)h->varied_out.ptr, tiles);
 	if ((rc = pxz_shrink_varied_ladder_frames_device(h, s->descs.data(), n_images, channels, &s->p, factors, n_factors, d_in, s->all.value, s->all.w,
 	                                                 s->all.h, s->all.slots)) != PXZ_OK)
 		return rc;
-	return rung_table(h, s->descs, n_factors, channels, s->p, up, s->all, s->t, d_in, nullptr, 0);
+	return rung_table(h, s->descs, n_factors, channels, s->p, up, s->all, s->t, d_in, nullptr, 0, s->d_record_bytes, s->d_tile_sse);
 }
 
 // The archive forms from their parameter checks to the filled table: the files parsed and uploaded, the reader into a buffer
@@ -367,6 +388,7 @@ int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens
 	if ((rc = ensure(h, h->archive_tiles, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->varied_out, TileSet::bytes(tiles, slot))) != PXZ_OK) return rc;
 	if ((rc = carve_rung_table(h, (size_t)n_sets, ch, fit ? n_images : 0u, &s->t)) != PXZ_OK) return rc;
+	if ((rc = carve_tile_tables(h, tiles, ch, s)) != PXZ_OK) return rc;
 	uint8_t *d_ref = (uint8_t *)h->archive_tiles.ptr;
 	const TileSet ref(d_ref, s->n_tiles);
 	uint32_t *d_flags = (uint32_t *)(d_ref + flags_at);
@@ -385,7 +407,7 @@ int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens
 	if ((rc = check_stage_flags(h, d_flags, n_images)) != PXZ_OK) return rc;
 	pxz_params up = s->p;
 	up.filter = filter_up;
-	return rung_table(h, s->descs, n_factors, ch, s->p, up, s->all, s->t, nullptr, &ref, expand_filter);
+	return rung_table(h, s->descs, n_factors, ch, s->p, up, s->all, s->t, nullptr, &ref, expand_filter, s->d_record_bytes, s->d_tile_sse);
 }
 
 // Where both fit forms end, behind the filled table: one rung per image chosen on the device, its tiles gathered as a varied
@@ -415,6 +437,61 @@ int fit_and_write(pxz_handle *h, const Rungs &s, uint32_t n_factors, uint32_t cr
 	std::memcpy(choice, picked, (size_t)n_images * 4u);
 	std::memcpy(fit_flags, picked + n_images, (size_t)n_images * 4u);
 	return rc;
+}
+
+// Where both tile-fit forms end, behind the filled tables: one rung per tile chosen on the device under the groups' targets,
+// the chosen tiles gathered as a varied batch of the images themselves (fit_tiles), the files written, and the one download
+// unpacked -- the files' offsets, the groups' results and the tiles' choices (optional).
+int fit_tiles_and_write(pxz_handle *h, const Rungs &s, uint32_t n_factors, uint32_t criterion, const uint32_t *group_first, uint32_t n_groups,
+                        const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice,
+                        uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags)
+{
+	const uint32_t n_images = (uint32_t)s.descs.size();
+	const uint64_t slot = (uint64_t)s.p.block_w * s.p.block_h * s.ch;
+	int rc = ensure(h, h->fit_tiles, TileSet::bytes(s.n_tiles, slot));
+	if (rc != PXZ_OK) return rc;
+	const TileSet fit((uint8_t *)h->fit_tiles.ptr, s.n_tiles);
+	// what comes down in one copy: the files' offsets (n_images + 1) | lambda | bytes | sse (n_groups u64 each) | as dwords the
+	// groups' flags, the gather's image flags and the tiles' choices
+	const size_t G = n_groups, n_dwords = G + n_images + (size_t)s.n_tiles;
+	const size_t n_block = (size_t)n_images + 1u + 3u * G + (n_dwords + 1u) / 2u;
+	if ((rc = ensure(h, h->tilefit_down, n_block * 8u)) != PXZ_OK) return rc;
+	uint64_t *d_block = (uint64_t *)h->tilefit_down.ptr;
+	uint64_t *d_lambda = d_block + n_images + 1u, *d_bytes = d_lambda + G, *d_sse = d_bytes + G;
+	uint32_t *d_gflags = (uint32_t *)(d_sse + G), *d_iflags = d_gflags + G, *d_choice = d_iflags + n_images;
+	if ((rc = pxz_fit_varied_tiles_device(h, s.descs.data(), n_images, s.ch, &s.p, group_first, n_groups, n_factors, criterion, targets, s.d_record_bytes,
+	                                      s.d_tile_sse, d_choice, d_lambda, d_bytes, d_sse, d_gflags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_gather_varied_tile_rungs_device(h, s.descs.data(), n_images, s.ch, &s.p, n_factors, d_choice, s.all.value, s.all.w, s.all.h,
+	                                              s.all.slots, fit.value, fit.w, fit.h, fit.slots, d_iflags)) != PXZ_OK)
+		return rc;
+	std::vector<uint64_t> got;
+	rc = write_files(h, s.descs, 1u, s.ch, s.p, filter_byte, fit, s.raw, s.n_tiles, d_block, n_block, 0, &got, out, out_capacity, file_offsets);
+	if (rc != PXZ_OK && rc != PXZ_ERR_BUFFER_TOO_SMALL) return rc;
+	const uint64_t *g64 = got.data() + n_images + 1u;
+	std::memcpy(group_lambda, g64, G * 8u);
+	std::memcpy(group_bytes, g64 + G, G * 8u);
+	std::memcpy(group_sse, g64 + 2u * G, G * 8u);
+	const uint32_t *g32 = reinterpret_cast<const uint32_t *>(g64 + 3u * G);
+	std::memcpy(group_flags, g32, G * 4u);
+	if (tile_choice) std::memcpy(tile_choice, g32 + G + n_images, (size_t)s.n_tiles * 4u);
+	// the library's own ladder gives every tile a usable candidate at every rung, and the select no rung beyond the ladder
+	for (uint32_t g = 0; g < n_groups; ++g)
+		if (g32[g] & 2u) return fail(h, PXZ_ERR_INTERNAL, "group %u: a tile of the library's own ladder has no usable candidate", g);
+	for (uint32_t i = 0; i < n_images; ++i)
+		if (g32[G + i]) return fail(h, PXZ_ERR_INTERNAL, "image %u: the select chose a rung beyond the ladder (flags %u)", i, g32[G + i]);
+	return rc;
+}
+
+// what the tile-fit forms check of their own arguments before anything is uploaded
+int fit_tiles_check(pxz_handle *h, uint32_t n_images, uint32_t criterion, const uint32_t *group_first, uint32_t n_groups, const uint64_t *targets,
+                    const void *file_offsets, const void *group_lambda, const void *group_bytes, const void *group_sse, const void *group_flags)
+{
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!file_offsets || !group_lambda || !group_bytes || !group_sse || !group_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
+		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	return tile_groups_check(h, group_first, n_groups, n_images);
 }
 
 // Both host forms of pix_to_pix behind one body: factors == nullptr is pxz_transcode_varied_files (one rung, the caller's
@@ -698,6 +775,51 @@ int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, c
 	Rungs s;
 	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, &s)) != PXZ_OK) return rc;
 	return fit_and_write(h, s, n_factors, criterion, targets, filter_byte, out, out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
+}
+
+int pxz_encode_varied_images_fit_tiles(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
+                                       uint32_t channels, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t filter_down,
+                                       uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                       const uint32_t *group_first, uint32_t n_groups, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                                       uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice, uint64_t *group_lambda,
+                                       uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!pixels) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if ((rc = fit_tiles_check(h, n_images, criterion, group_first, n_groups, targets, file_offsets, group_lambda, group_bytes, group_sse, group_flags)) !=
+	    PXZ_OK)
+		return rc;
+	Rungs s;
+	s.per_tile = true;
+	if ((rc = image_rungs(h, pixels, descs, n_images, channels, block_w, block_h, mode, filter_down, filter_up, factors, n_factors, &criterion, &s)) !=
+	    PXZ_OK)
+		return rc;
+	return fit_tiles_and_write(h, s, n_factors, criterion, group_first, n_groups, targets, filter_byte, out, out_capacity, file_offsets, tile_choice,
+	                           group_lambda, group_bytes, group_sse, group_flags);
+}
+
+int pxz_transcode_varied_files_fit_tiles(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                         const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                         uint32_t n_factors, uint32_t criterion, const uint32_t *group_first, uint32_t n_groups,
+                                         const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets,
+                                         uint32_t *tile_choice, uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse,
+                                         uint32_t *group_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!files || !lens || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if ((rc = fit_tiles_check(h, n_images, criterion, group_first, n_groups, targets, file_offsets, group_lambda, group_bytes, group_sse, group_flags)) !=
+	    PXZ_OK)
+		return rc;
+	Rungs s;
+	s.per_tile = true;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, &s)) != PXZ_OK) return rc;
+	return fit_tiles_and_write(h, s, n_factors, criterion, group_first, n_groups, targets, filter_byte, out, out_capacity, file_offsets, tile_choice,
+	                           group_lambda, group_bytes, group_sse, group_flags);
 }
 
 int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,

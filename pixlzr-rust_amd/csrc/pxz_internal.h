@@ -621,6 +621,40 @@ struct GatherArgs {
 	uint8_t *out_slots;                      // null: values and sizes only
 	uint32_t *image_flags;                   // per image 0 or 2, or null
 };
+// (pxz_gather_varied_tile_rungs_device, pxz_tilefit.hip, fills the same struct: choice then has an entry per output tile, and
+// image_flags is zeroed before the launch -- the kernel only sets bit 1)
+
+// The writer's record lengths out of its scratch (pxz_record_bytes_varied_device, pxz_tilefit.hip): rec_len as
+// launch_qoi_varied leaves it, the next image's header on every image's last record but the last's.
+struct RecordBytesArgs {
+	const VariedImage *images;
+	uint32_t n_images, n_tiles;
+	const uint32_t *rec_len;
+	uint32_t *record_bytes;                  // per tile: 13 + the record's length field
+};
+
+// Fit to a budget per tile (pxz_fit_varied_tiles_device, pxz_tilefit.hip): one rung per tile under one target per group of
+// images.  The rule is pxz_tilefit.h's; everything but the inputs and the outputs is handle scratch.
+struct TileFitArgs {
+	uint32_t n_tiles, n_groups, n_factors, channels, criterion;
+	uint32_t step;                           // (set by the launch) the halving a tilefit_step_kernel runs
+	const uint32_t *group_tile0;             // n_groups + 1: group g owns the flat tiles [g], [g + 1])
+	const unsigned long long *fixed;         // per group: the headers and line tables of its files
+	const unsigned long long *targets;       // per group
+	const uint32_t *record_bytes;            // index r * n_tiles + t
+	const unsigned long long *tile_sse;      // index (r * n_tiles + t) * channels + c
+	unsigned long long *cand;                // index r * n_tiles + t: tilefit_pack of the candidate
+	uint32_t *tile_group;                    // per tile
+	unsigned long long *interval;            // [2][n_groups][2]: lo, hi; step k reads buffer (k + 1) & 1 and writes k & 1
+	unsigned long long *acc;                 // [kTileFitSteps][n_groups]: the group's total at step k's lambda (zeroed)
+	unsigned long long *tot;                 // [n_groups][2]: bytes and error at lambda* (zeroed)
+	unsigned long long *uni;                 // [n_groups][n_factors][3]: a rung's bytes, error, tiles without it (zeroed)
+	uint32_t *group_bits;                    // per group: kTileFitNoCandidate (zeroed)
+	uint32_t *uni_rung;                      // per group: the rung all its tiles take, or 0xffffffff
+	uint32_t *tile_choice;                   // outputs: per tile
+	unsigned long long *group_lambda, *group_bytes, *group_sse;  // per group
+	uint32_t *group_flags;
+};
 
 // Pixel windows of files (pxz_decode_windows_device, pxz_expand_windows_device): one entry per window of the call.  A window
 // covers tile columns [c0, c0 + ccols) and tile rows [r0, r0 + crows) of its image; its covered tiles are numbered row-major

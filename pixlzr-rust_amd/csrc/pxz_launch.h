@@ -59,6 +59,11 @@ inline uint32_t reshrink_distortion_tile_dw(uint32_t bw, uint32_t bh, uint32_t w
 // fit to a budget (pxz_fit.hip): one rung per image, and the chosen rungs' tiles as a varied batch; one launch each
 hipError_t launch_fit_select(const FitArgs &a, hipStream_t stream);
 hipError_t launch_gather_rungs(const GatherArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+// fit to a budget per tile (pxz_tilefit.hip): the record lengths out of the writer's scratch (one launch); the select, a chain
+// of 3 + kTileFitSteps + 1 launches whatever the sizes; the gather with a choice per tile (one launch)
+hipError_t launch_record_bytes(const RecordBytesArgs &a, hipStream_t stream);
+hipError_t launch_tilefit(const TileFitArgs &a, hipStream_t stream);
+hipError_t launch_gather_tile_rungs(const GatherArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 size_t qoi_scratch_bytes(uint32_t n_tiles, uint32_t slot_px, uint32_t channels);
 uint32_t qoi_bins_dwords();
 uint32_t waves_per_tile(uint32_t bw, uint32_t bh);

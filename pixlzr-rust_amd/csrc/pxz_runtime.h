@@ -105,6 +105,11 @@ struct HandleScratch {
 	DeviceBuffer fit_tiles;           // the fit forms: the chosen rungs' tiles
 	DeviceBuffer archive_tiles;       // the archive forms: the archive's own tiles (the reference of the distortion call) and the flags of
 	                                  //   the reader and the re-shrink
+	DeviceBuffer record_offsets;      // pxz_record_bytes_varied_device: the files' offsets of a caller that passed none
+	DeviceBuffer tilefit;             // pxz_fit_varied_tiles_device: the groups' table, the packed candidates, intervals and totals
+	PinnedStaging tilefit_table;      //   pinned staging of the groups' table (targets, fixed bytes, first tiles)
+	DeviceBuffer tilefit_tables;      // the tile-fit forms: every rung's record bytes and per-tile errors
+	DeviceBuffer tilefit_down;        //   and what comes down with the files' offsets: the choices and the groups' results
 	bool work_ready = false;   // both worklist counters are zero / consistent with work_slot
 	const uint32_t *qbins_clean = nullptr;  // the writer's binning counters at this address were left zeroed by the last launch_qoi
 	const uint32_t *dbins_clean = nullptr;  // the same for the reader's (launch_decode)
@@ -154,6 +159,7 @@ int check_params(pxz_handle *h, const pxz_params *p);
 int varied_check_params(pxz_handle *h, uint32_t channels, const pxz_params *p);
 int check_factors(pxz_handle *h, const float *factors, uint32_t n_factors, uint32_t max_rungs);
 int fit_check(pxz_handle *h, uint32_t n_images, uint32_t n_factors, uint32_t channels, uint32_t criterion);
+int tile_groups_check(pxz_handle *h, const uint32_t *group_first, uint32_t n_groups, uint32_t n_images);
 
 pxz_params decode_side_params(const pxz_params *params, bool with_filter);
 int file_header(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint32_t *block_w, uint32_t *block_h, uint32_t *channels,
