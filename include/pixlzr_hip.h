@@ -420,13 +420,60 @@ int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs
  * side, a mode above 1 or a filter above 4. */
 int pxz_reshrink_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes);
 
+/* Re-tile: pix_to_pix with -b, a block size that CHANGES, on the stored tiles of a varied batch.  A tile of the rebuilt
+ * image's new grid is put together, in LDS, from the parts of the stored tiles that cover it -- each part expanded with the
+ * arithmetic of pxz_expand_varied_frames_device, or copied when its tile is stored at full size -- then measured and
+ * resampled into its new slot by the same kernel: nothing of image size is read, written or allocated.  Inputs d_tile_w,
+ * d_tile_h, d_slots are in the pxz_varied_layout order for src_block_w x src_block_h with slots of
+ * src_block_w*src_block_h*channels bytes (what pxz_decode_varied_frames_device or a varied shrink at that block leaves);
+ * outputs d_block_value, d_out_w, d_out_h, d_out_pixels are in the pxz_varied_layout order for params->block_w x block_h
+ * with slots of block_w*block_h*channels bytes.  Of descs[i] only width and height are read.  expand_filter is what
+ * to_image(filter) takes; params carries what the shrink takes (the NEW block size, mode, filter, factor).
+ * For every image without a flagged tile the results equal, bit for bit (value bits, sizes, the valid bytes of every slot),
+ * pxz_expand_varied_frames_device at the source block with expand_filter into a tightly packed image followed by
+ * pxz_shrink_varied_frames_device with params on that image.  When both blocks are equal, the results equal
+ * pxz_reshrink_varied_frames_device.
+ * A SOURCE tile whose stored size is zero or exceeds its place in the source grid is flagged as by
+ * pxz_expand_varied_frames_device -- d_image_flags (n_images dwords, may be NULL) receives 0 or 1 per image,
+ * pxz_decode_status reports bit 0 -- and every destination tile that it covers gets d_out_w = d_out_h = 0 and value bits 0;
+ * their slots are left as they were.  d_out_pixels may be NULL (values and sizes only).
+ * The two layouts differ, so there is no in-place form: inputs and outputs must not overlap.
+ * Asynchronous on the handle's stream; the number of launches does not depend on n_images.  Validation runs on the host
+ * before anything is launched, with the rules, codes and "image i" texts of pxz_shrink_varied_frames_device for the
+ * destination geometry (PXZ_ERR_TILE_TOO_SMALL included), and PXZ_ERR_INVALID_ARG for a zero source block or an
+ * expand_filter above 4; on an error nothing is written.
+ * Limit of this path: a block keeps the destination tile image (D = block_w*block_h*4 bytes: a dword per pixel, for RGB as
+ * for RGBA) and one more region in LDS: while the tile is assembled, the stored pixels that one part's windows read (at most
+ * about min(src, dst block) plus a window on each axis), the horizontal pass's intermediate and the windows of both source
+ * axes; afterwards the image's other plane (D) and in shrink_by mode the detector's planes (16 KB), beside shrink_by's tables
+ * (14 KB).  D and src_block_w*src_block_h*4 must not exceed 65536 bytes each and the sum not 160 KB; a pair beyond that gives
+ * PXZ_ERR_UNSUPPORTED (pxz_retile_lds_bytes says which).  With Lanczos3 every pair of square blocks up to 109x109 fits, and
+ * 128x128 on one side with up to 99x99 on the other; 128x128 <-> 128x127 does not.
+ * The call touches only the varied scratch and none of the state the single-geometry fast paths keep in the handle;
+ * pxz_trim gives back what it grew. */
+int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params,
+                                    uint32_t expand_filter, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                    const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                    uint8_t *d_out_pixels, uint32_t *d_image_flags);
+
+/* LDS bytes of one block of the call above (host only: no handle, no GPU), from the layout function the kernel and its launch
+ * use; conventions of pxz_reshrink_lds_bytes: a value above 163840 (0xffffffff when a plane of either block exceeds 65536
+ * bytes) means PXZ_ERR_UNSUPPORTED.  PXZ_ERR_INVALID_ARG for a null pointer, a zero side, a mode above 1 or a filter above 4. */
+int pxz_retile_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t mode,
+                         uint32_t expand_filter, uint32_t *lds_bytes);
+
 /* pix_to_pix for a folder, host files in, host files out, synchronously.  Every header is parsed on the host first
  * (pxz_file_header); the files must share channels and block size (PXZ_ERR_INVALID_ARG, "image i" otherwise), and the
  * descriptors come from the headers.  When the files' block size equals params->block_w / block_h the files go through the
  * varied reader, the re-shrink above in place and the varied writer: no allocation of image size anywhere.  With another
- * block size (the CLI's -b on a .pix input) they go through the varied reader at their own geometry,
- * pxz_expand_varied_frames_device into a scratch image batch of the handle, pxz_shrink_varied_frames_device at the new
- * geometry and the writer.  filter_byte goes into the new headers.  file_offsets (n_images + 1) are always written; the
+ * block size (the CLI's -b on a .pix input) they go through the varied reader at their own geometry, the re-tile above and
+ * the writer whenever the new block divides the files' block on both axes (64x64 files to 32x32 tiles: every new tile lies
+ * inside one tile of the files) and pxz_retile_lds_bytes says the pair fits: again nothing of image size is allocated.  Any
+ * other pair goes through the reader, pxz_expand_varied_frames_device into a scratch image batch of the handle,
+ * pxz_shrink_varied_frames_device at the new geometry and the writer -- new tiles that merge or straddle tiles of the files
+ * measured slower through the re-tile, files to files; the files are byte for byte the same either way.
+ * filter_byte goes into the new headers.  file_offsets (n_images + 1) are always written; the
  * files go to out when out_capacity >= file_offsets[n_images], else the call returns PXZ_ERR_BUFFER_TOO_SMALL and writes
  * nothing to out (out may be NULL for that size query), as pxz_encode_varied_images.  All or nothing: a malformed file or a
  * flagged tile gives PXZ_ERR_INVALID_ARG naming the first such image, and nothing is written to out or file_offsets.

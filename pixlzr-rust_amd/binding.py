@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "pxz_transcode_varied_files_fit",
     "pxz_fit_tiles_select", "pxz_record_bytes_varied_device", "pxz_fit_varied_tiles_device", "pxz_gather_varied_tile_rungs_device",
     "pxz_encode_varied_images_fit_tiles", "pxz_transcode_varied_files_fit_tiles",
+    "pxz_retile_varied_frames_device", "pxz_retile_lds_bytes",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -208,6 +209,11 @@ def load_library():
         L.pxz_reshrink_ladder_lds_bytes.argtypes = [u32] * 5 + [C.POINTER(u32)]
         L.pxz_transcode_varied_ladder_files.restype = C.c_int
         L.pxz_transcode_varied_ladder_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, vp, u32, u32, vp, C.c_uint64, vp]
+    if hasattr(L, "pxz_retile_varied_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the re-tile)
+        L.pxz_retile_varied_frames_device.restype = C.c_int
+        L.pxz_retile_varied_frames_device.argtypes = [vp, vp, u32, u32, u32, u32, C.POINTER(Params), u32] + [vp] * 8
+        L.pxz_retile_lds_bytes.restype = C.c_int
+        L.pxz_retile_lds_bytes.argtypes = [u32] * 6 + [C.POINTER(u32)]
     if hasattr(L, "pxz_fit_select"):  # (a build of an earlier commit named by PXZ_LIB lacks the fit)
         L.pxz_fit_select.restype = C.c_int
         L.pxz_fit_select.argtypes = [u32] * 4 + [vp] * 5
@@ -325,6 +331,16 @@ def reshrink_lds_bytes(bw, bh, mode, expand_filter):
     """pxz_reshrink_lds_bytes: LDS bytes of one block of the re-shrink kernel (host only; above 163840: unsupported)."""
     out = C.c_uint32(0)
     rc = load_library().pxz_reshrink_lds_bytes(bw, bh, mode, expand_filter, C.byref(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out.value
+
+
+def retile_lds_bytes(src_bw, src_bh, bw, bh, mode, expand_filter):
+    """pxz_retile_lds_bytes: LDS bytes of one block of the re-tile kernel for source blocks of src_bw x src_bh and destination
+    blocks of bw x bh (host only; above 163840: unsupported)."""
+    out = C.c_uint32(0)
+    rc = load_library().pxz_retile_lds_bytes(src_bw, src_bh, bw, bh, mode, expand_filter, C.byref(out))
     if rc != 0:
         raise PxzError(rc)
     return out.value
@@ -934,6 +950,38 @@ class Handle:
             err.needed = int(offs[-1])
             raise err
         return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+    # ---- re-tile: stored tiles at one block size to stored tiles at another ----
+    def retile_varied_frames_device(self, sizes, channels, src_bw, src_bh, bw, bh, mode, filt, factor, expand_filter, ow, oh, slots,
+                                    want_pixels=True, out=None, image_flags=None):
+        """pxz_retile_varied_frames_device: the stored tiles (w[S], h[S], slots[S, src_bw*src_bh*C], varied layout at
+        src_bw x src_bh) of the images sizes = [(width, height), ...] expanded with expand_filter and shrunk again with (mode,
+        filt, factor) at the block bw x bh, without the images.  Returns (tile_offsets uint64[n+1], values[T], w[T], h[T],
+        slots[T, bw*bh*C] | None) in the varied layout at bw x bh.  out: a 4-tuple of such tensors (slots may be None), none of
+        them an input.  image_flags (int32[n] CUDA, optional) gets 0 | 1."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            dev = ow.device
+            vals = torch.empty(T, dtype=torch.float32, device=dev)
+            nw = torch.empty(T, dtype=torch.int32, device=dev)
+            nh = torch.empty(T, dtype=torch.int32, device=dev)
+            nslots = torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, nw, nh, nslots = out
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_retile_varied_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, src_bw, src_bh, C.byref(pd), expand_filter,
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, nw, nh, nslots
 
     # ---- re-shrink ladder: stored tiles to stored tiles at several factors ----
     def reshrink_varied_ladder_frames_device(self, sizes, channels, bw, bh, mode, filt, factors, expand_filter, ow, oh, slots,

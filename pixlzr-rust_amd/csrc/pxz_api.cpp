@@ -2672,6 +2672,84 @@ int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc
 
 }  // extern "C"
 
+// ---- re-tile of stored tiles (pxz_retile.hip): pix_to_pix with -b, a block size that changes ------------------------------
+extern "C" {
+
+int pxz_retile_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter,
+                         uint32_t *lds_bytes)
+{
+	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4)
+		return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::retile_lds_bytes(mode, src_block_w, src_block_h, block_w, block_h, 1u);
+	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
+	pxz::VariedExpandTableSet s;
+	if (!pxz::build_varied_expand_tables(unique_sides({src_block_w, src_block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::retile_lds_bytes(mode, src_block_w, src_block_h, block_w, block_h, varied_window_dw(s.max_window));
+	return PXZ_OK;
+}
+
+int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params, uint32_t expand_filter,
+                                    const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value,
+                                    uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const pxz_params p = *params;
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	if (src_block_w == 0 || src_block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	// the one place that says whether retile_kernel takes a pair of blocks: its LDS footprint against the CU's
+	auto check_pair = [&](uint32_t wdw) {
+		if (pxz::retile_lds_bytes(p.mode, src_block_w, src_block_h, p.block_w, p.block_h, wdw) > kLdsPerCu)
+			return fail(h, PXZ_ERR_UNSUPPORTED,
+			            "a re-tile keeps a %ux%u tile image (a dword per pixel), the staged parts of %ux%u source tiles and the source windows in LDS: "
+			            "they exceed a block's 160 KB (pxz_retile_lds_bytes)", p.block_w, p.block_h, src_block_w, src_block_h);
+		return (int)PXZ_OK;
+	};
+	if ((rc = check_pair(1u)) != PXZ_OK) return rc;
+	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
+	std::vector<pxz_image_desc> sized(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
+	std::vector<pxz::VariedImage> images, src_images;
+	std::vector<uint32_t> sides, src_sides;
+	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	if ((rc = varied_plan(h, sized.data(), n_images, src_block_w, src_block_h, 0, 0, &src_images, &src_sides, nullptr)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::RetileArgs a{};
+	pxz_params xp = p;  // the expand side: the source geometry
+	xp.block_w = src_block_w;
+	xp.block_h = src_block_h;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, src_sides, &a.x)) != PXZ_OK) return rc;
+	if ((rc = check_pair(a.x.wdw)) != PXZ_OK) return rc;
+	if ((rc = fresh_status(h, &a.x.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.image_flags = d_image_flags;
+	// both per-image tables in one upload: the destination layout's, then the source layout's
+	const uint32_t n_src_tiles = varied_n_tiles(src_images);
+	std::vector<pxz::VariedImage> both = images;
+	both.insert(both.end(), src_images.begin(), src_images.end());
+	if ((rc = varied_upload(h, both, &a.v.images)) != PXZ_OK) return rc;
+	a.src_images = a.v.images + n_images;
+	varied_fill_args(h, images, channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.v);
+	a.v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is assembled
+	a.x.n_tiles = n_src_tiles;
+	a.x.tile_w = d_tile_w;
+	a.x.tile_h = d_tile_h;
+	a.x.slots = d_slots;
+	PXZ_HIP(h, pxz::launch_retile(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+}  // extern "C"
+
 // ---- rate and distortion (pxz_distortion.hip) -----------------------------------------------------------------------------
 namespace {
 

@@ -541,6 +541,19 @@ struct ReshrinkLadderArgs {
 	float factors[kVariedLadderMaxRungs];
 };
 
+// Re-tile of stored tiles (pxz_retile_varied_frames_device, pxz_retile.hip): the stored tiles of one layout of a batch brought to
+// the tiles of another layout of the same images, one DESTINATION tile per block.  v is the shrink side as varied_kernel takes
+// it, for the destination block (v.base is unused, v.tile_bytes is one LDS plane of v.bw * v.bh dwords, rounded up to 16 bytes;
+// v.images is the destination layout's table); x is the expand side for the SOURCE block (x.bw, x.bh, x.slot_bytes; the tables of
+// put_varied_expand_tables for the source geometry; the stored sizes and slots that are read; the status word; x.tile_dw and
+// x.t0_dw are unused: the block's LDS is retile_lds', pxz_varied_tile.h).  Inputs and outputs never alias: the layouts differ.
+struct RetileArgs {
+	VariedArgs v;
+	TileResizeArgs x;
+	const VariedImage *src_images;    // the same images in the source layout (entry i: image i), of which tile0, cols, rows and edges are read
+	uint32_t *image_flags;            // per image 1 for a source tile whose stored size is invalid, or null
+};
+
 // Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
 // back to their places in the images.
 struct VariedExpandArgs : TileResizeArgs {

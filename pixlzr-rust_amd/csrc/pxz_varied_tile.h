@@ -4,6 +4,8 @@
 //   all four:          the detector's LDS constants, varied_pixel, varied_pass (one resample pass along one axis), varied_store;
 //   the two ladders:   the detectors up to their raw results (varied_oklab_raw, varied_sobel_sums) and varied_unpremultiply;
 //   the re-shrinks:    the block's LDS layout (reshrink_lds: both kernels' launches and the host's limit check);
+//   retile_kernel (pxz_retile.hip): its LDS layout (retile_lds), and of the above varied_pixel, varied_pass, varied_store and
+//                      varied_unpremultiply; its partial tile expand and its detectors are copies of reshrink_kernel's;
 //   reshrink_ladder_kernel: the tile image of a stored tile (reshrink_tile_image: clone-in, or varied_resize_tile of pxz_device.h
 //                      by the whole block, and the RGB pack);
 //   varied_ladder_kernel: everything behind the detector (varied_ladder_tail: the rungs' decisions, clones, resamples and
@@ -229,6 +231,61 @@ __host__ __device__ inline ReshrinkLds reshrink_lds(uint32_t mode, uint32_t bw, 
 	l.own = a_bytes > plane ? after : 0u;
 	l.f = i_bytes;
 	l.total = a_bytes > plane ? after + a_bytes : after;
+	return l;
+}
+
+// ---- the re-tile: a destination tile's image assembled from parts of source tiles (retile_kernel, pxz_retile.hip)
+//
+// Where a block of retile_kernel keeps its images: byte offsets into its dynamic LDS, and their sum (0xffffffff: a plane beyond
+// the limit below).  The kernel, its launch and the host's limit check (pxz_retile_lds_bytes, the entry point, the host form)
+// all take the layout from here.
+//   [oklab tables, shrink_by only: 14 336 B] [X: D = dbw * dbh * 4, rounded up to 16] [U]
+// X is the destination tile image: one dword per pixel while it is assembled, then C bytes per pixel (RGB is packed in place).
+// U is one region with two lives.  During the assembly it holds, for one covering source tile at a time,
+//   [the staged stored pixels: pw x ph dwords] [the horizontal pass's intermediate: cwmax x ph dwords]
+//   [the windows of both SOURCE axes: (sbw + sbh) * wdw dwords]
+// Only the stored pixels that the wanted part's windows read are staged -- a rectangle of the stored tile -- so the staging is
+// bounded by the part, not by the source block: a part is at most cwmax = min(sbw, dbw) by chmax = min(sbh, dbh) samples, the
+// windows of n consecutive samples of an up-scaling table span at most n + (widest window) stored samples (a window starts at
+// most one sample after its neighbour's), and the widest window has at most 2 (wdw - 1) taps; with two samples to spare
+//   pw = min(sbw, cwmax + 2 (wdw - 1) + 2),  ph = min(sbh, chmax + 2 (wdw - 1) + 2).
+// After the assembly U is X's other plane (D bytes: what the shrink's passes alternate with) and, in shrink_by mode, the
+// detector's planes (16 KB), one over the other as in reshrink_kernel with large planes: the detector is done before the first
+// pass writes.  So U = max(assembly, D, 16 KB in shrink_by mode).  The shrink's windows are not staged: varied_pass reads them
+// from the tables, as in the re-shrink.
+// Limit: D <= 65536 and sbw * sbh * 4 <= 65536 (either beyond: 0xffffffff), and the sum within the CU's 160 KB.  With Lanczos3
+// (wdw = 5) that admits equal square blocks up to 109x109 on both sides in shrink_by mode, and a 128x128 block on one side with
+// a square block of up to 99x99 on the other; 128x128 <-> 128x127 does not fit (a part can then be nearly the whole source
+// tile: 64 KB staged, 64 KB of intermediate), nor does a one-row block of 16384 (its windows alone).  Destination blocks of
+// 32x32 and 48x20 take 34-35 KB in shrink_by mode whatever the source block up to 64x64: four blocks per CU, as varied_kernel.
+constexpr uint32_t kRetileMaxPlaneBytes = 65536;
+struct RetileLds {
+	uint32_t x, u;       // the destination tile image; the region of the assembly / of the other plane and the detector's planes
+	uint32_t pw, ph;     // the staged rectangle's bounds (samples)
+	uint32_t inter;      // the intermediate, from the start of the dynamic LDS
+	uint32_t wx;         // the staged windows: x's sbw entries, then y's sbh entries, wdw dwords each
+	uint32_t total;
+};
+
+__host__ __device__ inline RetileLds retile_lds(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t wdw)
+{
+	auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+	auto lesser = [](uint32_t a, uint32_t b) { return a < b ? a : b; };
+	RetileLds l{0, 0, 0, 0, 0, 0, 0xffffffffu};
+	const uint64_t d64 = ((uint64_t)dbw * dbh * 4u + 15u) & ~(uint64_t)15u, s64 = (uint64_t)sbw * sbh * 4u;
+	if (sbw == 0u || sbh == 0u || dbw == 0u || dbh == 0u || wdw == 0u || wdw > 64u || d64 > kRetileMaxPlaneBytes || s64 > kRetileMaxPlaneBytes) return l;
+	const uint32_t d = (uint32_t)d64;
+	const uint32_t cwmax = lesser(sbw, dbw), chmax = lesser(sbh, dbh);
+	l.pw = lesser(sbw, cwmax + 2u * (wdw - 1u) + 2u);
+	l.ph = lesser(sbh, chmax + 2u * (wdw - 1u) + 2u);
+	l.x = mode == 0u ? kVariedTables * 4u : 0u;
+	l.u = l.x + d;
+	l.inter = l.u + up16(l.pw * l.ph * 4u);
+	l.wx = l.inter + up16(cwmax * l.ph * 4u);
+	uint32_t u_bytes = l.wx + (((sbw + sbh) * wdw + 3u) & ~3u) * 4u - l.u;  // (sides of at most 16384, wdw of at most 64)
+	if (u_bytes < d) u_bytes = d;
+	if (mode == 0u && u_bytes < kVariedPlaneBytes) u_bytes = kVariedPlaneBytes;
+	l.total = l.u + u_bytes;
 	return l;
 }
 
