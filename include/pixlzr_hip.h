@@ -517,6 +517,53 @@ int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc
 int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode, uint32_t expand_filter,
                                   uint32_t *lds_bytes);
 
+/* Re-tile ladder: pxz_retile_varied_frames_device at several factors in ONE launch, whatever n_images and n_factors are -- an
+ * archive written at one block size, no source images, and the question how far it can be squeezed at another.  Every tile of
+ * the new grid is assembled once from the parts of the stored tiles that cover it and measured once (neither depends on the
+ * factor); each rung only decides its levels, and a tile is resampled once per distinct pair of levels among its rungs.
+ * Inputs (d_tile_w, d_tile_h, d_slots in the pxz_varied_layout order for src_block_w x src_block_h, descs, channels,
+ * expand_filter, params with the NEW block size, mode and filter) are those of pxz_retile_varied_frames_device;
+ * params->factor is ignored.  factors is a HOST array as in pxz_reshrink_varied_ladder_frames_device (1 <= n_factors <=
+ * PXZ_VARIED_LADDER_MAX_RUNGS, each finite; any order, repeats allowed).
+ * Outputs are rung-major in the DESTINATION layout, exactly as pxz_shrink_varied_ladder_frames_device lays them out for
+ * params->block_w x block_h: rung r of tile t of image i is index r*tiles + tile_offsets[i] + t of d_block_value, d_out_w,
+ * d_out_h and of the slots (block_w*block_h*channels bytes, 64-bit offsets) of d_out_pixels, which may be NULL (values and
+ * sizes only); the writer takes them with descs repeated n_factors times.
+ * Rung r equals pxz_retile_varied_frames_device with factor = factors[r] bit for bit (value bits, sizes, the valid bytes of
+ * every slot), and therefore rung r of pxz_expand_varied_frames_device at the source block followed by
+ * pxz_shrink_varied_ladder_frames_device at the new one.  When both blocks are equal the results equal
+ * pxz_reshrink_varied_ladder_frames_device out of place.
+ * A SOURCE tile whose stored size is zero or exceeds its place in the source grid sets d_image_flags (n_images dwords, may be
+ * NULL) and status bit 0 as in the re-tile, and every destination tile that it covers gets d_out_w = d_out_h = 0 and value
+ * bits 0 at EVERY rung; every rung's slot of such a tile is left as it was.
+ * The two layouts differ, so there is no in-place form: inputs and outputs must not overlap.
+ * Asynchronous on the handle's stream; one launch.  Validation runs on the host before anything is launched; on an error
+ * nothing is written.  Rules, codes and "image i" texts are pxz_retile_varied_frames_device's for the destination geometry
+ * (PXZ_ERR_TILE_TOO_SMALL included; PXZ_ERR_INVALID_ARG for a zero source block or an expand_filter above 4);
+ * PXZ_ERR_INVALID_ARG for factors null, n_factors 0 or above the maximum, or a non-finite factor; PXZ_ERR_UNSUPPORTED beyond
+ * the LDS limit (pxz_retile_ladder_lds_bytes says which pairs) or when n_factors * tiles exceeds 2^32-1.
+ * Limit of this path: a block keeps the destination tile image (D = block_w*block_h*4 bytes) and one more region: the
+ * re-tile's staging while the tile is assembled, afterwards the detector's planes (16 KB, shrink_by) and the resampled
+ * images of one pair of levels (about 3/4 of block_w*block_h*channels bytes: a half and a quarter) -- the larger of the two,
+ * beside shrink_by's tables (14 KB).  D and src_block_w*src_block_h*4 must not exceed 65536 bytes each and the sum not 160
+ * KB.  The image's other plane, which the one-factor call keeps, is not needed, so every pair pxz_retile_lds_bytes admits is
+ * admitted here (blocks of a few pixels take some bytes more: 3x5 RGBA 80 against 64).
+ * The call touches only the varied scratch and none of the state the single-geometry fast paths keep in the handle;
+ * pxz_trim gives back what it grew. */
+int pxz_retile_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                           uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params,
+                                           uint32_t expand_filter, const float *factors, uint32_t n_factors,
+                                           const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots,
+                                           float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels,
+                                           uint32_t *d_image_flags);
+
+/* LDS bytes of one block of the call above (host only: no handle, no GPU), from the layout function the kernel and its launch
+ * use; conventions of pxz_retile_lds_bytes: a value above 163840 (0xffffffff when a plane of either block exceeds 65536
+ * bytes) means PXZ_ERR_UNSUPPORTED.  The footprint depends on the channel count (the resampled images).
+ * PXZ_ERR_INVALID_ARG for a null pointer, a zero side, channels other than 3 or 4, a mode above 1 or a filter above 4. */
+int pxz_retile_ladder_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h,
+                                uint32_t channels, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes);
+
 /* pxz_transcode_varied_files at several factors: host files in, host files out, synchronously.  params->factor is ignored;
  * factors as above.  The new files are rung-major: file_offsets has n_factors*n_images + 1 entries, and the file of image i at
  * factors[r] is out[file_offsets[r*n_images + i] .. file_offsets[r*n_images + i + 1]), byte for byte what
@@ -525,8 +572,14 @@ int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t c
  * length per file and factor, no file kept -- as pxz_rate_distortion_varied_images gives its lengths.  There is no distortion
  * column here; pxz_rate_distortion_varied_files adds it, measured against what each file decodes to, still without the image.
  * Same block size: the varied reader into rung 0 of the handle's tile scratch, the re-shrink ladder in place, the varied writer
- * over the descriptors repeated n_factors times.  Another block size: reader, pxz_expand_varied_frames_device,
- * pxz_shrink_varied_ladder_frames_device, writer.  All or nothing as pxz_transcode_varied_files: a malformed file or a flagged
+ * over the descriptors repeated n_factors times.  Another block size: reader at the files' geometry, the re-tile ladder
+ * above and the writer whenever the new block divides the files' block on both axes and pxz_retile_ladder_lds_bytes says the
+ * pair fits -- nothing of image size is allocated; any other pair goes through reader, pxz_expand_varied_frames_device into
+ * a scratch image batch of the handle, pxz_shrink_varied_ladder_frames_device and the writer.  That is the rule of
+ * pxz_transcode_varied_files, and the measurement of DESIGN.md 8p supports it: from the same tiles the re-tile ladder is
+ * 1.06-1.68x faster than expand + varied ladder where new tiles split tiles of the files (files to files level to 1.04x
+ * on strongly shrunk files), but 0.91-1.27x where they merge and 0.72-1.06x where they straddle them, behind on strongly
+ * shrunk files in two runs.  The files are byte for byte the same either way.  All or nothing as pxz_transcode_varied_files: a malformed file or a flagged
  * tile gives PXZ_ERR_INVALID_ARG naming the first such image, and nothing is written to out or file_offsets.  Errors and limits
  * otherwise as the calls it is made of. */
 int pxz_transcode_varied_ladder_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "pxz_fit_tiles_select", "pxz_record_bytes_varied_device", "pxz_fit_varied_tiles_device", "pxz_gather_varied_tile_rungs_device",
     "pxz_encode_varied_images_fit_tiles", "pxz_transcode_varied_files_fit_tiles",
     "pxz_retile_varied_frames_device", "pxz_retile_lds_bytes",
+    "pxz_retile_varied_ladder_frames_device", "pxz_retile_ladder_lds_bytes",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -214,6 +215,11 @@ def load_library():
         L.pxz_retile_varied_frames_device.argtypes = [vp, vp, u32, u32, u32, u32, C.POINTER(Params), u32] + [vp] * 8
         L.pxz_retile_lds_bytes.restype = C.c_int
         L.pxz_retile_lds_bytes.argtypes = [u32] * 6 + [C.POINTER(u32)]
+    if hasattr(L, "pxz_retile_varied_ladder_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the re-tile ladder)
+        L.pxz_retile_varied_ladder_frames_device.restype = C.c_int
+        L.pxz_retile_varied_ladder_frames_device.argtypes = [vp, vp, u32, u32, u32, u32, C.POINTER(Params), u32, vp, u32] + [vp] * 8
+        L.pxz_retile_ladder_lds_bytes.restype = C.c_int
+        L.pxz_retile_ladder_lds_bytes.argtypes = [u32] * 7 + [C.POINTER(u32)]
     if hasattr(L, "pxz_fit_select"):  # (a build of an earlier commit named by PXZ_LIB lacks the fit)
         L.pxz_fit_select.restype = C.c_int
         L.pxz_fit_select.argtypes = [u32] * 4 + [vp] * 5
@@ -341,6 +347,16 @@ def retile_lds_bytes(src_bw, src_bh, bw, bh, mode, expand_filter):
     blocks of bw x bh (host only; above 163840: unsupported)."""
     out = C.c_uint32(0)
     rc = load_library().pxz_retile_lds_bytes(src_bw, src_bh, bw, bh, mode, expand_filter, C.byref(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out.value
+
+
+def retile_ladder_lds_bytes(src_bw, src_bh, bw, bh, channels, mode, expand_filter):
+    """pxz_retile_ladder_lds_bytes: LDS bytes of one block of the re-tile ladder kernel for source blocks of src_bw x src_bh and
+    destination blocks of bw x bh (host only; above 163840: unsupported)."""
+    out = C.c_uint32(0)
+    rc = load_library().pxz_retile_ladder_lds_bytes(src_bw, src_bh, bw, bh, channels, mode, expand_filter, C.byref(out))
     if rc != 0:
         raise PxzError(rc)
     return out.value
@@ -976,6 +992,40 @@ class Handle:
         self.use_torch_stream()
         self._check(self._L.pxz_retile_varied_frames_device(
             self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, src_bw, src_bh, C.byref(pd), expand_filter,
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, nw, nh, nslots
+
+    # ---- re-tile ladder: stored tiles at one block size to stored tiles at another, at several factors ----
+    def retile_varied_ladder_frames_device(self, sizes, channels, src_bw, src_bh, bw, bh, mode, filt, factors, expand_filter, ow, oh, slots,
+                                           want_pixels=True, out=None, image_flags=None, n_factors=None):
+        """pxz_retile_varied_ladder_frames_device: retile_varied_frames_device at every factor of `factors` (a host sequence,
+        1..32 of them) in one launch.  Returns (tile_offsets uint64[n+1], values[K,T], w[K,T], h[K,T], slots[K,T,bw*bh*C] |
+        None) in the varied layout at bw x bh; rung r equals retile_varied_frames_device(..., factors[r], ...).  out: a 4-tuple
+        of such tensors (slots may be None), none of them an input.  factors None with n_factors passes a null pointer."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        fac = None if factors is None else np.ascontiguousarray(factors, np.float32)
+        K = n_factors if n_factors is not None else (0 if fac is None else fac.size)
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            T = int(offs[-1])
+            dev = ow.device
+            vals = torch.empty((K, T), dtype=torch.float32, device=dev)
+            nw = torch.empty((K, T), dtype=torch.int32, device=dev)
+            nh = torch.empty((K, T), dtype=torch.int32, device=dev)
+            nslots = torch.empty((K, T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, nw, nh, nslots = out
+        pd = Params(bw, bh, mode, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_retile_varied_ladder_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, src_bw, src_bh, C.byref(pd), expand_filter,
+            _p(fac) if fac is not None and fac.size else None, K,
             C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
             C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
             C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))

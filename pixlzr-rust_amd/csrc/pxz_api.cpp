@@ -2672,41 +2672,56 @@ int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc
 
 }  // extern "C"
 
-// ---- re-tile of stored tiles (pxz_retile.hip): pix_to_pix with -b, a block size that changes ------------------------------
-extern "C" {
+// ---- re-tile of stored tiles (pxz_retile.hip, pxz_retile_ladder.hip): pix_to_pix with -b, a block size that changes -------
+namespace {
 
-int pxz_retile_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter,
-                         uint32_t *lds_bytes)
+// the footprint of one block for a pair of blocks whose staged windows take wdw dwords: retile_kernel's (rung_channels == 0) or
+// retile_ladder_kernel's for that channel count
+uint32_t retile_footprint(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t rung_channels, uint32_t wdw)
+{
+	return rung_channels == 0u ? pxz::retile_lds_bytes(mode, sbw, sbh, dbw, dbh, wdw)
+	                           : pxz::retile_ladder_lds_bytes(mode, sbw, sbh, dbw, dbh, rung_channels, wdw);
+}
+
+// both size queries: the footprint with the windows of expand_filter's tables
+int retile_lds_query(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t rung_channels, uint32_t mode,
+                     uint32_t expand_filter, uint32_t *lds_bytes)
 {
 	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4)
 		return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::retile_lds_bytes(mode, src_block_w, src_block_h, block_w, block_h, 1u);
+	*lds_bytes = retile_footprint(mode, src_block_w, src_block_h, block_w, block_h, rung_channels, 1u);
 	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
 	pxz::VariedExpandTableSet s;
 	if (!pxz::build_varied_expand_tables(unique_sides({src_block_w, src_block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::retile_lds_bytes(mode, src_block_w, src_block_h, block_w, block_h, varied_window_dw(s.max_window));
+	*lds_bytes = retile_footprint(mode, src_block_w, src_block_h, block_w, block_h, rung_channels, varied_window_dw(s.max_window));
 	return PXZ_OK;
 }
 
-int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
-                                    uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params, uint32_t expand_filter,
-                                    const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value,
-                                    uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+// Both device forms of the re-tile behind one body, from the check of the device pointers on (h, params and the ladder's factors
+// are checked by the entry points): factors == nullptr is pxz_retile_varied_frames_device (params->factor, retile_kernel;
+// n_factors is not read); otherwise pxz_retile_varied_ladder_frames_device (n_factors rungs, retile_ladder_kernel, outputs
+// rung-major in the destination layout).
+int retile_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, uint32_t src_block_w, uint32_t src_block_h,
+                  const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors, const uint32_t *d_tile_w,
+                  const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                  uint8_t *d_out_pixels, uint32_t *d_image_flags)
 {
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
 	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	const pxz_params p = *params;
+	const bool ladder = factors != nullptr;
+	pxz_params p = *params;
+	if (ladder) p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
+	const uint32_t rung_channels = ladder ? channels : 0u;
 	int rc = varied_check_params(h, channels, &p);
 	if (rc != PXZ_OK) return rc;
 	if (src_block_w == 0 || src_block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
 	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	// the one place that says whether retile_kernel takes a pair of blocks: its LDS footprint against the CU's
+	// the one place that says whether the kernel takes a pair of blocks: its LDS footprint against the CU's
 	auto check_pair = [&](uint32_t wdw) {
-		if (pxz::retile_lds_bytes(p.mode, src_block_w, src_block_h, p.block_w, p.block_h, wdw) > kLdsPerCu)
+		if (retile_footprint(p.mode, src_block_w, src_block_h, p.block_w, p.block_h, rung_channels, wdw) > kLdsPerCu)
 			return fail(h, PXZ_ERR_UNSUPPORTED,
 			            "a re-tile keeps a %ux%u tile image (a dword per pixel), the staged parts of %ux%u source tiles and the source windows in LDS: "
-			            "they exceed a block's 160 KB (pxz_retile_lds_bytes)", p.block_w, p.block_h, src_block_w, src_block_h);
+			            "they exceed a block's 160 KB (%s)", p.block_w, p.block_h, src_block_w, src_block_h,
+			            ladder ? "pxz_retile_ladder_lds_bytes" : "pxz_retile_lds_bytes");
 		return (int)PXZ_OK;
 	};
 	if ((rc = check_pair(1u)) != PXZ_OK) return rc;
@@ -2719,10 +2734,13 @@ int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	std::vector<uint32_t> sides, src_sides;
 	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
 	if ((rc = varied_plan(h, sized.data(), n_images, src_block_w, src_block_h, 0, 0, &src_images, &src_sides, nullptr)) != PXZ_OK) return rc;
+	if (ladder && (uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
 	PXZ_HIP(h, hipSetDevice(h->device));
 	const VariedTables *vt = nullptr;
 	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
-	pxz::RetileArgs a{};
+	pxz::RetileLadderArgs la{};  // (the one-factor call launches its la.r)
+	pxz::RetileArgs &a = la.r;
 	pxz_params xp = p;  // the expand side: the source geometry
 	xp.block_w = src_block_w;
 	xp.block_h = src_block_h;
@@ -2744,8 +2762,56 @@ int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	a.x.tile_w = d_tile_w;
 	a.x.tile_h = d_tile_h;
 	a.x.slots = d_slots;
-	PXZ_HIP(h, pxz::launch_retile(a, channels, h->n_cus, h->stream));
+	if (!ladder) {
+		PXZ_HIP(h, pxz::launch_retile(a, channels, h->n_cus, h->stream));
+		return PXZ_OK;
+	}
+	la.n_factors = n_factors;
+	std::memcpy(la.factors, factors, n_factors * sizeof(float));
+	PXZ_HIP(h, pxz::launch_retile_ladder(la, channels, h->n_cus, h->stream));
 	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_retile_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter,
+                         uint32_t *lds_bytes)
+{
+	return retile_lds_query(src_block_w, src_block_h, block_w, block_h, 0u, mode, expand_filter, lds_bytes);
+}
+
+int pxz_retile_ladder_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode,
+                                uint32_t expand_filter, uint32_t *lds_bytes)
+{
+	if (channels != 3 && channels != 4) return PXZ_ERR_INVALID_ARG;
+	return retile_lds_query(src_block_w, src_block_h, block_w, block_h, channels, mode, expand_filter, lds_bytes);
+}
+
+int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                    uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params, uint32_t expand_filter,
+                                    const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value,
+                                    uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	return retile_varied(h, descs, n_images, channels, src_block_w, src_block_h, params, expand_filter, nullptr, 0u, d_tile_w, d_tile_h, d_slots,
+	                     d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags);
+}
+
+int pxz_retile_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                           uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params, uint32_t expand_filter,
+                                           const float *factors, uint32_t n_factors, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
+                                           const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                                           uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	return retile_varied(h, descs, n_images, channels, src_block_w, src_block_h, params, expand_filter, factors, n_factors, d_tile_w, d_tile_h,
+	                     d_slots, d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags);
 }
 
 }  // extern "C"

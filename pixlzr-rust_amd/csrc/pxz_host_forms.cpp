@@ -562,17 +562,20 @@ int transcode_varied(pxz_handle *h, const uint8_t *const *files, const size_t *l
 		if (rc != PXZ_OK) return rc;
 	} else {
 		// another block size: reader at the files' geometry, then
-		//   a pair of blocks that retile_kernel takes (one factor) and whose new tiles each lie inside one tile of the files -- the new
-		//   block divides the files' on both axes: the re-tile at the new geometry, nothing of image size anywhere;
-		//   any other pair, and the ladder: the images in handle scratch -> the varied shrink at the new geometry.  (New tiles that
-		//   merge or straddle tiles of the files measured slower through the re-tile than through these four calls, files to files, by
-		//   more than the spread of two runs: 0.76-0.93x on strongly shrunk files, DESIGN.md 8o.  The device call takes every pair.)
+		//   a pair of blocks that retile_kernel (one factor) or retile_ladder_kernel (the ladder) takes and whose new tiles each lie
+		//   inside one tile of the files -- the new block divides the files' on both axes: the re-tile, or the re-tile ladder, at the
+		//   new geometry, nothing of image size anywhere;
+		//   any other pair: the images in handle scratch -> the varied shrink, or the varied ladder, at the new geometry.  (New tiles
+		//   that merge or straddle tiles of the files measured slower through the re-tile than through these four calls, files to
+		//   files, by more than the spread of two runs: 0.76-0.93x on strongly shrunk files; for the ladder see 8p.  The
+		//   device calls take every pair.)
 		const uint64_t slot_in = (uint64_t)fbw * fbh * ch;
 		if ((rc = ensure(h, h->transcode_tiles, TileSet::bytes(n_in, slot_in))) != PXZ_OK) return rc;
 		const TileSet mi((uint8_t *)h->transcode_tiles.ptr, n_in);
 		uint32_t retile_bytes = 0;
-		const bool retile = !ladder && fbw % params->block_w == 0 && fbh % params->block_h == 0 &&
-		                    pxz_retile_lds_bytes(fbw, fbh, params->block_w, params->block_h, params->mode, expand_filter, &retile_bytes) == PXZ_OK &&
+		const bool retile = fbw % params->block_w == 0 && fbh % params->block_h == 0 &&
+		                    (ladder ? pxz_retile_ladder_lds_bytes(fbw, fbh, params->block_w, params->block_h, ch, params->mode, expand_filter, &retile_bytes)
+		                            : pxz_retile_lds_bytes(fbw, fbh, params->block_w, params->block_h, params->mode, expand_filter, &retile_bytes)) == PXZ_OK &&
 		                    retile_bytes <= kLdsPerCu;
 		std::vector<pxz_image_desc> dev = descs;
 		uint8_t *d_img = nullptr;
@@ -586,8 +589,10 @@ int transcode_varied(pxz_handle *h, const uint8_t *const *files, const size_t *l
 		                                          d_flags)) != PXZ_OK)
 			return rc;
 		if (retile) {
-			rc = pxz_retile_varied_frames_device(h, descs.data(), n_images, ch, fbw, fbh, params, expand_filter, mi.w, mi.h, mi.slots, m.value, m.w, m.h,
-			                                     m.slots, d_flags + n_images);
+			rc = ladder ? pxz_retile_varied_ladder_frames_device(h, descs.data(), n_images, ch, fbw, fbh, params, expand_filter, factors, n_factors, mi.w,
+			                                                     mi.h, mi.slots, m.value, m.w, m.h, m.slots, d_flags + n_images)
+			            : pxz_retile_varied_frames_device(h, descs.data(), n_images, ch, fbw, fbh, params, expand_filter, mi.w, mi.h, mi.slots, m.value,
+			                                              m.w, m.h, m.slots, d_flags + n_images);
 		} else {
 			if ((rc = pxz_expand_varied_frames_device(h, dev.data(), n_images, ch, &pin, mi.w, mi.h, mi.slots, d_img, d_flags + n_images)) != PXZ_OK)
 				return rc;

@@ -554,6 +554,15 @@ struct RetileArgs {
 	uint32_t *image_flags;            // per image 1 for a source tile whose stored size is invalid, or null
 };
 
+// Re-tile ladder (pxz_retile_varied_ladder_frames_device, pxz_retile_ladder.hip): the re-tile's arguments (r.v.factor is not
+// read; r.v.value, out_w, out_h, out_px hold n_factors rungs of r.v.n_tiles entries each, rung-major in the destination layout)
+// and the rungs' factors, by value.  The block's LDS is retile_ladder_lds' (pxz_varied_tile.h).
+struct RetileLadderArgs {
+	RetileArgs r;
+	uint32_t n_factors;
+	float factors[kVariedLadderMaxRungs];
+};
+
 // Expand of a varied batch (pxz_expand_varied_frames_device, pxz_varied_expand.hip): the stored tiles of the flat tile space
 // back to their places in the images.
 struct VariedExpandArgs : TileResizeArgs {

@@ -52,6 +52,10 @@ uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t ru
 // its launch use (what the host holds against kLdsPerCu before it launches); 0xffffffff: a plane of either block above 64 KB
 hipError_t launch_retile(const RetileArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 uint32_t retile_lds_bytes(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t wdw);
+// re-tile ladder (pxz_retile_ladder.hip): one launch whatever the rungs; and the LDS bytes of one block of retile_ladder_kernel,
+// from retile_ladder_lds (pxz_varied_tile.h) with the rungs' channel count, under the conventions of retile_lds_bytes
+hipError_t launch_retile_ladder(const RetileLadderArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+uint32_t retile_ladder_lds_bytes(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t channels, uint32_t wdw);
 hipError_t launch_reshrink_distortion(const ReshrinkDistortionArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 // Dwords of one wave's image in reshrink_distortion_kernel for blocks of bw x bh whose staged windows take wdw dwords: three
 // planes of bw * bh dwords (the reference and varied_resize_tile's two) and the windows of both axes.  The kernel, its launch,

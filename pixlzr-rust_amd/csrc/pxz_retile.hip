@@ -34,6 +34,9 @@
 //                runs them, unchanged in arithmetic (copied from there, not called, for the reason given there: DESIGN.md 8k;
 //                the pass and the store are pxz_varied_tile.h's).
 // Source and destination layouts differ, so there is no in-place form.
+// Steps 1 to 3 stand a second time as retile_assemble (pxz_varied_tile.h), which retile_ladder_kernel (pxz_retile_ladder.hip)
+// calls; THIS KERNEL KEEPS ITS INLINE TEXT -- its timing is pinned in DESIGN.md 8o, and folding it onto the function is a change
+// with its own A/B.  A FIX TO STEPS 1 TO 3 HERE BELONGS THERE TOO, and the other way round.
 //
 // LDS of one block: retile_lds (pxz_varied_tile.h), where the layout and its limit are described; the kernel, this launch and
 // the host take it from there.

@@ -6,6 +6,9 @@
 //   the re-shrinks:    the block's LDS layout (reshrink_lds: both kernels' launches and the host's limit check);
 //   retile_kernel (pxz_retile.hip): its LDS layout (retile_lds), and of the above varied_pixel, varied_pass, varied_store and
 //                      varied_unpremultiply; its partial tile expand and its detectors are copies of reshrink_kernel's;
+//   retile_ladder_kernel (pxz_retile_ladder.hip): its LDS layout (retile_ladder_lds), the assembly of a destination tile
+//                      (retile_assemble: retile_kernel's steps 1 to 3, which that kernel keeps inline), the two ladders' detectors
+//                      and varied_ladder_tail;
 //   reshrink_ladder_kernel: the tile image of a stored tile (reshrink_tile_image: clone-in, or varied_resize_tile of pxz_device.h
 //                      by the whole block, and the RGB pack);
 //   varied_ladder_kernel: everything behind the detector (varied_ladder_tail: the rungs' decisions, clones, resamples and
@@ -287,6 +290,243 @@ __host__ __device__ inline RetileLds retile_lds(uint32_t mode, uint32_t sbw, uin
 	if (mode == 0u && u_bytes < kVariedPlaneBytes) u_bytes = kVariedPlaneBytes;
 	l.total = l.u + u_bytes;
 	return l;
+}
+
+// ---- the re-tile ladder: the same assembly, then the ladder's tail (retile_ladder_kernel, pxz_retile_ladder.hip)
+//
+// Where a block of retile_ladder_kernel keeps its images: byte offsets into its dynamic LDS, and their sum (0xffffffff beyond
+// retile_lds' own limits: D or sbw * sbh * 4 above 65536).  The kernel, its launch and the host's limit check
+// (pxz_retile_ladder_lds_bytes, the entry point, the host form) all take the layout from here.
+//   [oklab tables, shrink_by only: 14 336 B] [X: D = dbw * dbh * 4, rounded up to 16] [U]
+// X is the destination tile image as in retile_lds.  During the assembly U is what retile_lds lays out (staged pixels,
+// intermediate, windows of both source axes, at the same offsets).  Afterwards U is the ladder's A: the detector's planes
+// [4][kVariedChunk] (16 KB, shrink_by only), then the passes' I at its start and F behind I -- reshrink_lds' sizes for the
+// destination block and the channel count.  varied_ladder_tail goes X -> I -> F and never writes X after the premultiply, so
+// X's other plane is not needed: U = max(assembly, A).  Wherever A <= D that is at most the one-factor re-tile's footprint;
+// only tiny blocks have A > D (a 3x5 RGBA block: I + F = 48 + 32 bytes beside D = 64).
+struct RetileLadderLds {
+	uint32_t x, u;       // the destination tile image; the region of the assembly, then A
+	uint32_t pw, ph;     // the staged rectangle's bounds (samples)
+	uint32_t inter;      // the intermediate, from the start of the dynamic LDS
+	uint32_t wx;         // the staged windows: x's sbw entries, then y's sbh entries, wdw dwords each
+	uint32_t f;          // F, from the start of U (= the room of I)
+	uint32_t total;
+};
+
+__host__ __device__ inline RetileLadderLds retile_ladder_lds(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t channels,
+                                                             uint32_t wdw)
+{
+	auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+	const RetileLds r = retile_lds(mode, sbw, sbh, dbw, dbh, wdw);
+	RetileLadderLds l{r.x, r.u, r.pw, r.ph, r.inter, r.wx, 0, 0xffffffffu};
+	if (r.total == 0xffffffffu) return l;
+	// A: the widest horizontal result I and the result F behind it, or a vertical-only result (reshrink_lds, varied_ladder_lds)
+	const uint32_t hw = dbw > 1u ? (dbw + 1u) / 2u : 0u, hh = dbh > 1u ? (dbh + 1u) / 2u : 0u;
+	const uint32_t i_bytes = up16(hw * dbh * channels);
+	const uint32_t hv = i_bytes + up16(hw * hh * channels), v_only = up16(dbw * hh * channels);
+	uint32_t a_bytes = hv > v_only ? hv : v_only;
+	if (mode == 0u && a_bytes < kVariedPlaneBytes) a_bytes = kVariedPlaneBytes;  // the detector's planes
+	uint32_t u_bytes = r.wx + (((sbw + sbh) * wdw + 3u) & ~3u) * 4u - r.u;  // the assembly (retile_lds)
+	if (u_bytes < a_bytes) u_bytes = a_bytes;
+	l.f = i_bytes;
+	l.total = l.u + u_bytes;
+	return l;
+}
+
+// retile_kernel's steps 1 to 3 (pxz_retile.hip, where they are described) for the destination tile whose rectangle is
+// [X0, X0 + w) x [Y0, Y0 + h) of an image whose SOURCE grid is sm: the covering source tiles, the assembly in s_img (one dword per
+// pixel, rows w apart; s_src, s_tmp, s_wx, s_wy: the staging of retile_lds), and the pack to C bytes per pixel in place.  Returns
+// true ("bad") when a covering tile's stored size cannot be: the assembly stops there and s_img holds nothing of use.  Ends in a
+// barrier either way.  retile_kernel KEEPS ITS OWN INLINE TEXT of these steps (its timing is pinned in DESIGN.md 8o; 8k showed
+// what a call can cost): A FIX HERE BELONGS THERE TOO, and the other way round -- and to the expand arithmetic of
+// varied_resize_tile (pxz_device.h) and reshrink_kernel step 4, from which both are copied.
+template <int C>
+__device__ __forceinline__ bool retile_assemble(const TileResizeArgs &x, const VariedImage &sm, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                                                uint32_t *s_img, uint32_t *s_src, uint32_t *s_tmp, uint32_t *s_wx, uint32_t *s_wy, uint32_t tid)
+{
+	const bool conv = x.filter != 0u;
+	const uint32_t n = w * h;
+	// ---- 1. the source tiles that cover the rectangle
+	const uint32_t X1 = X0 + w, Y1 = Y0 + h;
+	const uint32_t sc0 = X0 / x.bw, sr0 = Y0 / x.bh;
+	const uint32_t ncx = (X1 - 1u) / x.bw - sc0 + 1u, ncy = (Y1 - 1u) / x.bh - sr0 + 1u;
+
+	// ---- 2. the tile image, covering tile by covering tile (every value that steers the loop is the same in all threads)
+	bool bad = false;
+	for (uint32_t k = 0; k < ncx * ncy; ++k) {
+		const uint32_t ky = k / ncx;
+		const uint32_t sty = sr0 + ky, stx = sc0 + (k - ky * ncx);
+		const uint32_t fw = stx + 1u == sm.cols ? sm.edge_w : x.bw, fh = sty + 1u == sm.rows ? sm.edge_h : x.bh;
+		const uint32_t st = sm.tile0 + sty * sm.cols + stx;
+		const uint32_t tw = x.tile_w[st], th = x.tile_h[st];
+		if (tw == 0u || th == 0u || tw > fw || th > fh) {  // (bad_stored_size, pxz_device.h)
+			bad = true;
+			break;
+		}
+		const uint8_t *src = x.slots + (size_t)st * x.slot_bytes;
+		// the wanted part in the source tile's coordinates, and its place in X
+		const uint32_t ox = stx * x.bw, oy = sty * x.bh;
+		const uint32_t cx0 = X0 > ox ? X0 - ox : 0u, cy0 = Y0 > oy ? Y0 - oy : 0u;
+		const uint32_t cx1 = (X1 < ox + fw ? X1 : ox + fw) - ox, cy1 = (Y1 < oy + fh ? Y1 : oy + fh) - oy;
+		const uint32_t cw = cx1 - cx0, chh = cy1 - cy0;
+		uint32_t *dst = s_img + (oy + cy0 - Y0) * w + (ox + cx0 - X0);
+
+		if (tw == fw && th == fh) {
+			// clone in: the part's pixels from the slot (no LDS but X is touched: no barrier between two clones)
+			RowWalker rw(tid, kVariedThreads, cw);
+			for (uint32_t i = tid; i < cw * chh; i += kVariedThreads, rw.next()) {
+				const uint32_t at = (cy0 + rw.row) * fw + cx0 + rw.col;
+				uint32_t px;
+				if constexpr (C == 4) px = reinterpret_cast<const uint32_t *>(src)[at];
+				else px = (uint32_t)src[3u * at] | ((uint32_t)src[3u * at + 1u] << 8) | ((uint32_t)src[3u * at + 2u] << 16) | 0xff000000u;
+				dst[rw.row * w + rw.col] = px;
+			}
+			continue;
+		}
+		ExpandTab tab_x{0, 0, 0, 0}, tab_y{0, 0, 0, 0};
+		auto stage_windows = [&](uint32_t *wd, const ExpandTab &tab, uint32_t lo, uint32_t hi) {
+			for (uint32_t o = lo + tid; o < hi; o += kVariedThreads) {
+				uint32_t *d = wd + x.wdw * o;
+				const uint32_t first = x.starts[tab.start_off + o];
+				const uint32_t cnt = conv ? x.sizes[tab.start_off + o] : 1u;
+				d[0] = first | (cnt << 16);
+				if (conv) {
+					const int16_t *kk = x.coeffs + tab.coeff_off + o * tab.window;
+					for (uint32_t j = 0; j < cnt; j += 2u)
+						d[1u + (j >> 1)] = (uint32_t)(uint16_t)kk[j] | (j + 1u < cnt ? (uint32_t)(uint16_t)kk[j + 1u] << 16 : 0u);
+				}
+			}
+		};
+		// expand (reshrink_kernel step 4, restricted to the part).  The windows of the wanted samples at their own indices:
+		// first | count << 16, then the weights as i16 pairs
+		const bool need_h = tw != fw, need_v = th != fh;
+		// the stored samples the part's windows read: [rx0, rx1) x [ry0, ry1) -- window starts ascend with the sample, so the first
+		// wanted sample's start and the last one's end bound them (an axis that keeps its size: the part itself)
+		uint32_t rx0 = cx0, rx1 = cx1, ry0 = cy0, ry1 = cy1;
+		if (need_h) {
+			tab_x = x.dir[(size_t)x.slot[fw] * x.stride + tw];
+			stage_windows(s_wx, tab_x, cx0, cx1);
+			rx0 = x.starts[tab_x.start_off + cx0];
+			rx1 = x.starts[tab_x.start_off + cx1 - 1u] + (conv ? x.sizes[tab_x.start_off + cx1 - 1u] : 1u);
+		}
+		if (need_v) {
+			tab_y = x.dir[(size_t)x.slot[fh] * x.stride + th];
+			stage_windows(s_wy, tab_y, cy0, cy1);
+			ry0 = x.starts[tab_y.start_off + cy0];
+			ry1 = x.starts[tab_y.start_off + cy1 - 1u] + (conv ? x.sizes[tab_y.start_off + cy1 - 1u] : 1u);
+		}
+		const uint32_t pw = rx1 - rx0, ph = ry1 - ry0;  // (within the layout's pw x ph: retile_lds)
+		// those stored pixels -> one dword per pixel in s_src, rows pw apart (RGBA under a convolution alpha-premultiplied as fir does)
+		{
+			RowWalker rw(tid, kVariedThreads, pw);
+			for (uint32_t i = tid; i < pw * ph; i += kVariedThreads, rw.next()) {
+				const uint32_t at = (ry0 + rw.row) * tw + rx0 + rw.col;
+				uint32_t px;
+				if constexpr (C == 4) {
+					px = reinterpret_cast<const uint32_t *>(src)[at];
+					if (conv) px = premultiply(px);  // fir: U8x4 is alpha-premultiplied before a convolution
+				} else {
+					px = (uint32_t)src[3u * at] | ((uint32_t)src[3u * at + 1u] << 8) | ((uint32_t)src[3u * at + 2u] << 16) | 0xff000000u;
+				}
+				s_src[i] = px;
+			}
+		}
+		__syncthreads();
+
+		if (!conv) {  // ResizeAlg::Nearest
+			RowWalker rw(tid, kVariedThreads, cw);
+			for (uint32_t i = tid; i < cw * chh; i += kVariedThreads, rw.next()) {
+				const uint32_t ux = cx0 + rw.col, uy = cy0 + rw.row;
+				const uint32_t sx = need_h ? (s_wx[x.wdw * ux] & 0xffffu) : ux, sy = need_v ? (s_wy[x.wdw * uy] & 0xffffu) : uy;
+				dst[rw.row * w + rw.col] = s_src[(sy - ry0) * pw + (sx - rx0)];
+			}
+		} else {
+			if (need_h) {
+				// horizontal pass: item = (wanted column, row) -- of the ph staged rows (into the intermediate, cw wide, when the
+				// vertical pass follows; th == fh otherwise: the staged rows are the wanted rows, into X)
+				const int prec = tab_x.precision;
+				const int32_t init = 1 << (prec - 1);
+				RowWalker rw(tid, kVariedThreads, cw);
+				for (uint32_t i = tid; i < cw * ph; i += kVariedThreads, rw.next()) {
+					const uint32_t *wd = s_wx + x.wdw * (cx0 + rw.col);
+					const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
+					const uint32_t *row = s_src + rw.row * pw + (first - rx0);
+					int32_t acc[4] = {init, init, init, init};
+					// two taps per v_dot2_i32_i16 (an odd count has a zero weight for the pixel read past the window: at the end of
+					// the staged rectangle's last row that is the first dword of the intermediate, inside the block's LDS)
+					for (uint32_t j = 0; j < cnt; j += 2u) {
+						const uint32_t w2 = wd[1u + (j >> 1)], p0 = row[j], p1 = row[j + 1u];
+#pragma unroll
+						for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
+					}
+					uint32_t px = clip8_med3(acc[0], prec) | (clip8_med3(acc[1], prec) << 8) | (clip8_med3(acc[2], prec) << 16);
+					px |= C == 4 ? clip8_med3(acc[3], prec) << 24 : 0xff000000u;
+					if (need_v) {
+						s_tmp[i] = px;
+					} else {
+						if constexpr (C == 4) px = unpremultiply(px);
+						dst[rw.row * w + rw.col] = px;
+					}
+				}
+				if (need_v) __syncthreads();
+			}
+			if (need_v) {
+				// vertical pass: item = (wanted column, wanted row); the rows it reads are cw wide behind a horizontal pass, the
+				// staged rows otherwise (pw == cw then).  The row an odd count reads past the window lies behind the rectangle:
+				// in the intermediate or in the staged windows, inside the block's LDS, and has a zero weight
+				const uint32_t *cur = need_h ? s_tmp : s_src;
+				const uint32_t pitch = need_h ? cw : pw;
+				const int prec = tab_y.precision;
+				const int32_t init = 1 << (prec - 1);
+				RowWalker rw(tid, kVariedThreads, cw);
+				for (uint32_t i = tid; i < cw * chh; i += kVariedThreads, rw.next()) {
+					const uint32_t *wd = s_wy + x.wdw * (cy0 + rw.row);
+					const uint32_t hdr = wd[0], first = hdr & 0xffffu, cnt = hdr >> 16;
+					const uint32_t *col = cur + (first - ry0) * pitch + rw.col;
+					int32_t acc[4] = {init, init, init, init};
+					for (uint32_t j = 0; j < cnt; j += 2u) {
+						const uint32_t w2 = wd[1u + (j >> 1)], p0 = col[j * pitch], p1 = col[(j + 1u) * pitch];
+#pragma unroll
+						for (uint32_t c = 0; c < (uint32_t)C; ++c) acc[c] = dot2(__builtin_amdgcn_perm(p1, p0, c | 0x0c000c00u | ((4u + c) << 16)), w2, acc[c]);
+					}
+					uint32_t px = clip8_med3(acc[0], prec) | (clip8_med3(acc[1], prec) << 8) | (clip8_med3(acc[2], prec) << 16);
+					px |= C == 4 ? clip8_med3(acc[3], prec) << 24 : 0xff000000u;
+					if constexpr (C == 4) px = unpremultiply(px);
+					dst[rw.row * w + rw.col] = px;
+				}
+			}
+		}
+		__syncthreads();  // the next covering tile reuses the staging
+	}
+	__syncthreads();  // X is whole -- or, bad: threads still behind may be cloning into X, which the next tile writes
+	if (bad) return true;
+
+	// ---- 3. the tile image as varied_kernel stages it: C bytes per pixel, tightly packed, in X
+	if constexpr (C == 3) {
+		// RGB: the dwords packed to 3 bytes in place, 1024 pixels a round (four per thread as three dwords, bytes at the tail): a
+		// round writes below what later rounds read, and the barrier keeps its own reads ahead of its writes
+		uint8_t *s_x = reinterpret_cast<uint8_t *>(s_img);
+		for (uint32_t base = 0; base < n; base += 4u * kVariedThreads) {
+			const uint32_t q = (base >> 2) + tid, i0 = 4u * q;
+			uint32_t p[4];
+#pragma unroll
+			for (uint32_t j = 0; j < 4u; ++j) p[j] = i0 + j < n ? s_img[i0 + j] : 0u;
+			__syncthreads();
+			if (i0 + 4u <= n) {
+				s_img[3u * q] = (p[0] & 0xffffffu) | (p[1] << 24);
+				s_img[3u * q + 1u] = ((p[1] >> 8) & 0xffffu) | (p[2] << 16);
+				s_img[3u * q + 2u] = ((p[2] >> 16) & 0xffu) | (p[3] << 8);
+			} else {
+				for (uint32_t j = 0; i0 + j < n; ++j) {
+					s_x[3u * (i0 + j)] = (uint8_t)p[j];
+					s_x[3u * (i0 + j) + 1u] = (uint8_t)(p[j] >> 8);
+					s_x[3u * (i0 + j) + 2u] = (uint8_t)(p[j] >> 16);
+				}
+			}
+			__syncthreads();
+		}
+	}
+	return false;
 }
 
 // The tile image of stored tile (tw x th at src, tightly packed) of full size w x h, in the planes p0 / p1 of the block's LDS:
