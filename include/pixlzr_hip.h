@@ -853,7 +853,7 @@ int pxz_reshrink_distortion_lds_bytes(uint32_t block_w, uint32_t block_h, uint32
  * pxz_encode_varied_frames_device over the n_factors*n_images rung images with no room (for its offsets),
  * pxz_reshrink_distortion_varied_device, one download.  Synchronous.  A malformed file or a tile that cannot be fails the
  * whole call as in pxz_transcode_varied_files (nothing is written); files of another block size than params' are
- * PXZ_ERR_UNSUPPORTED (there the image exists anyway: pxz_decode_varied_files + pxz_rate_distortion_varied_images serve).
+ * PXZ_ERR_UNSUPPORTED (pxz_rate_distortion_retile_files and the two fit forms beside it, below, take another block size).
  * Other errors and limits are those of the calls it composes. */
 int pxz_rate_distortion_varied_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
                                      const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
@@ -983,6 +983,101 @@ int pxz_transcode_varied_files_fit_tiles(pxz_handle *h, const uint8_t *const *fi
                                          uint32_t n_groups, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
                                          uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice /* may be NULL */,
                                          uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags);
+
+/* ---- fit a .pixlzr archive to a budget at a NEW block size: the error of a re-tiled tile without the image ------ */
+
+/* pxz_reshrink_distortion_varied_device for a block size that changes: the sets are tiles of the grid of params->block_w x
+ * block_h, the archive's tiles those of src_block_w x src_block_h, both over the same images (pxz_varied_layout order of descs
+ * at the respective block; of a descriptor only width, height and reserved are read).  For every tile of the DESTINATION grid,
+ * every one of n_sets stored versions of it and every channel, the sum over the tile's full pixels of
+ *   (decoded(archive)[pixel] - expand(set's stored tile, params->filter)[pixel])^2,
+ * decoded(archive) being what pxz_expand_varied_frames_device writes from the archive's tiles at the source block with
+ * expand_filter: the result equals that call into a tightly packed image followed by pxz_distortion_varied_frames_device at the
+ * new block for each set (params->filter), bit for bit, and that image is never made -- a destination tile of it is put together
+ * in LDS from the parts of the source tiles that cover it, as pxz_retile_varied_frames_device does.  When both blocks are
+ * equal the result equals pxz_reshrink_distortion_varied_device.
+ * d_ref_w, d_ref_h, d_ref_slots: the archive's tiles in the SOURCE layout (slots of src_block_w*src_block_h*channels bytes) as
+ * pxz_decode_varied_frames_device leaves them.  d_tile_w, d_tile_h, d_slots: n_sets*tiles entries of the DESTINATION layout,
+ * set-major -- index s*tiles + t, slots of block_w*block_h*channels bytes, exactly what
+ * pxz_retile_varied_ladder_frames_device writes.  d_tile_sse (may be NULL), d_image_sse (zeroed by the call) and d_image_flags
+ * (may be NULL) have the sizes and index orders of pxz_reshrink_distortion_varied_device, tiles being the destination grid's,
+ * so pxz_fit_varied_ladder_device and pxz_fit_varied_tiles_device take them as they are.  Integer sums, 64-bit integer
+ * atomics: the result does not depend on the order of arrival.
+ *   set tile stored at full size: sums 0, its slot is not read;
+ *   a set's stored size of zero or beyond its place: that entry all-ones (UINT64_MAX), the image's flag and
+ *   pxz_decode_status bit 0 set, the totals leave it out;
+ *   a SOURCE tile whose stored size is zero or beyond its place in the source grid: every set's entry of EVERY destination tile
+ *   it covers all-ones, flagged, in no total, and nothing of those tiles is compared.
+ * Asynchronous on the handle's stream; one launch, whatever n_images and n_sets are; only the varied scratch of the handle is
+ * touched (pxz_trim gives it back), none of the state of the single-geometry fast paths.
+ * Validation runs on the host before anything is launched; on an error nothing is written.  Rules, codes and "image i" texts
+ * are pxz_retile_varied_ladder_frames_device's for the two geometries (PXZ_ERR_INVALID_ARG for a zero source block or an
+ * expand_filter above 4) and pxz_reshrink_distortion_varied_device's for n_sets and the filters; PXZ_ERR_UNSUPPORTED beyond the
+ * LDS limit (pxz_retile_distortion_lds_bytes says which pairs) or when n_sets*tiles exceeds 2^32-1.
+ * Limit: a block keeps TWO destination tile images (D = block_w*block_h*4 bytes each: the reference and one set's tile) and
+ * the re-tile's staging -- for the source side, or for a whole stored tile of the destination block (up to D staged, up to D of
+ * intermediate, the windows of both axes), whichever is larger.  D and src_block_w*src_block_h*4 must not exceed 65536 bytes
+ * each and the sum not 160 KB.  With Lanczos3 on both sides the largest admitted equal square pair is 99x99 <-> 99x99
+ * (160 832 bytes; 100x100 takes 164 000); 64x64 destination blocks take 66.5 KB at most, 32x32 ones at most 22.6 KB from
+ * source blocks up to 64x64. */
+int pxz_retile_distortion_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                        uint32_t src_block_w, uint32_t src_block_h,
+                                        const pxz_params *params /* the NEW block_w, block_h; filter = filter_up */,
+                                        uint32_t expand_filter, uint32_t n_sets, const uint32_t *d_ref_w,
+                                        const uint32_t *d_ref_h, const uint8_t *d_ref_slots, const uint32_t *d_tile_w,
+                                        const uint32_t *d_tile_h, const uint8_t *d_slots, uint64_t *d_tile_sse,
+                                        uint64_t *d_image_sse, uint32_t *d_image_flags);
+
+/* LDS bytes of one block of the call above (host only: no handle, no GPU), from the layout function the kernel and its launch
+ * use; conventions of pxz_retile_ladder_lds_bytes: a value above 163840 (0xffffffff when a plane of either block exceeds 65536
+ * bytes) means PXZ_ERR_UNSUPPORTED.  The footprint depends on both filters (the staged windows) and not on the channel count.
+ * PXZ_ERR_INVALID_ARG for a null pointer, a zero side, channels other than 3 or 4 or a filter above 4. */
+int pxz_retile_distortion_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h,
+                                    uint32_t channels, uint32_t expand_filter, uint32_t filter_up, uint32_t *lds_bytes);
+
+/* pxz_rate_distortion_varied_files at a NEW block size: params->block_w x block_h is the block of the files that would be
+ * written, the files' own block comes from their headers (all of one block and channel count).  file_bytes[r*n_images + i] is
+ * the length of the file pxz_transcode_varied_ladder_files writes for file i at factors[r] with these params (its size query),
+ * sse[(r*n_images + i)*channels + c] the squared error of channel c between what file i decodes to (expand_filter) and what
+ * that new file decodes to (filter_up).  Composition only: the headers, upload, pxz_decode_varied_frames_device at the files'
+ * geometry into a buffer of its own, then the rungs --
+ *   another block: pxz_expand_varied_frames_device into a scratch image batch of the handle (on the device: no pixel crosses
+ *   the bus), pxz_shrink_varied_ladder_frames_device, the writer for its offsets, pxz_distortion_varied_frames_device against
+ *   that image;
+ *   equal blocks: the chain of pxz_rate_distortion_varied_files --
+ * and one download.  The rule of pxz_transcode_varied_ladder_files would send a pair whose new block divides the files' block
+ * through pxz_retile_varied_ladder_frames_device and pxz_retile_distortion_varied_device, with nothing of image size allocated.
+ * Files to files that route measured 7-9 % SLOWER than the image batch on strongly shrunk files, in two runs whose samples
+ * spread by 1 %, and level on files stored mostly full, so, as for the merging and straddling pairs of
+ * pxz_transcode_varied_files, this call takes the images for every other block; a caller to whom the 4 bytes per pixel of
+ * scratch matter more than the time composes the device calls.  The numbers are the same on every path.  Synchronous.  A malformed file or a tile that cannot be fails the
+ * whole call as in pxz_transcode_varied_files (PXZ_ERR_INVALID_ARG naming the first such image; nothing is written).  Other
+ * errors and limits are those of the calls it composes. */
+int pxz_rate_distortion_retile_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                     const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                     uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse);
+
+/* pxz_transcode_varied_files_fit at a NEW block size: "squeeze this 64x64 archive under N bytes per file at 32x32 tiles".  The
+ * chain above, then pxz_fit_varied_ladder_device, pxz_gather_varied_rungs_device, the writer over the gathered images, one
+ * download.  Arguments and output protocol are pxz_transcode_varied_files_fit's; params->block_w x block_h is the NEW block.
+ * File i of the output is, byte for byte, pxz_transcode_varied_files of file i alone at factors[choice[i]] with the new block,
+ * and the whole output equals pxz_decode_varied_files (expand_filter) followed by pxz_encode_varied_images_fit at the new
+ * block.  With equal blocks it is pxz_transcode_varied_files_fit. */
+int pxz_retile_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte,
+                                uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice,
+                                uint32_t *fit_flags, uint64_t *table_bytes /* may be NULL */, uint64_t *table_sse /* may be NULL */);
+
+/* pxz_transcode_varied_files_fit_tiles at a NEW block size: a rung per tile of the NEW grid under the groups' targets.
+ * Arguments and output protocol are pxz_transcode_varied_files_fit_tiles's (tile_choice: the new grid's tiles); the whole
+ * output equals pxz_decode_varied_files (expand_filter) followed by pxz_encode_varied_images_fit_tiles at the new block. */
+int pxz_retile_varied_files_fit_tiles(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                      const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                      uint32_t n_factors, uint32_t criterion, const uint32_t *group_first /* may be NULL */,
+                                      uint32_t n_groups, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                                      uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice /* may be NULL */,
+                                      uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags);
 
 /* ---- legacy image -> image filter ------------------------ */
 

@@ -12,7 +12,7 @@ from .binding import (  # noqa: F401
     DIST_OPAQUE, DIST_ALPHA, DIST_FLAT, DIST_NOISE,
     PxzError, Handle, build_library, library_path, load_library, grid, encode_container, qoi_encode, axis_table,
     EXPORTED_SYMBOLS, LADDER_MAX_RUNGS, VARIED_LADDER_MAX_RUNGS, varied_layout, image_descs, file_header, psnr,
-    Window, window_descs, window_layout, reshrink_lds_bytes, reshrink_ladder_lds_bytes, retile_lds_bytes, retile_ladder_lds_bytes,
+    Window, window_descs, window_layout, reshrink_lds_bytes, reshrink_ladder_lds_bytes, retile_lds_bytes, retile_ladder_lds_bytes, retile_distortion_lds_bytes,
     FIT_BYTES, FIT_SSE, fit_select, sse_for_psnr, reshrink_distortion_lds_bytes,
     TILEFIT_LAMBDA_MAX, TILEFIT_MISSED, TILEFIT_NO_CANDIDATE, TILEFIT_UNIFORM, fit_tiles_select,
 )

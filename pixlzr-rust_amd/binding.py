@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "pxz_encode_varied_images_fit_tiles", "pxz_transcode_varied_files_fit_tiles",
     "pxz_retile_varied_frames_device", "pxz_retile_lds_bytes",
     "pxz_retile_varied_ladder_frames_device", "pxz_retile_ladder_lds_bytes",
+    "pxz_retile_distortion_varied_device", "pxz_retile_distortion_lds_bytes", "pxz_rate_distortion_retile_files",
+    "pxz_retile_varied_files_fit", "pxz_retile_varied_files_fit_tiles",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -229,6 +231,18 @@ def load_library():
         L.pxz_gather_varied_rungs_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 10
         L.pxz_encode_varied_images_fit.restype = C.c_int
         L.pxz_encode_varied_images_fit.argtypes = [vp, vp, vp] + [u32] * 7 + [vp, u32, u32, vp, u32, vp, C.c_uint64] + [vp] * 5
+    if hasattr(L, "pxz_retile_distortion_varied_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the archive fit at a new block)
+        L.pxz_retile_distortion_varied_device.restype = C.c_int
+        L.pxz_retile_distortion_varied_device.argtypes = [vp, vp, u32, u32, u32, u32, C.POINTER(Params), u32, u32] + [vp] * 9
+        L.pxz_retile_distortion_lds_bytes.restype = C.c_int
+        L.pxz_retile_distortion_lds_bytes.argtypes = [u32] * 7 + [C.POINTER(u32)]
+        L.pxz_rate_distortion_retile_files.restype = C.c_int
+        L.pxz_rate_distortion_retile_files.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, vp, vp]
+        L.pxz_retile_varied_files_fit.restype = C.c_int
+        L.pxz_retile_varied_files_fit.argtypes = [vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, u32, vp, u32, vp, C.c_uint64] + [vp] * 5
+        L.pxz_retile_varied_files_fit_tiles.restype = C.c_int
+        L.pxz_retile_varied_files_fit_tiles.argtypes = ([vp, vp, vp, u32, C.POINTER(Params), u32, u32, vp, u32, u32, vp, u32, vp, u32, vp,
+                                                         C.c_uint64] + [vp] * 6)
     if hasattr(L, "pxz_reshrink_distortion_varied_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the archive fit)
         L.pxz_reshrink_distortion_varied_device.restype = C.c_int
         L.pxz_reshrink_distortion_varied_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), u32, u32] + [vp] * 9
@@ -367,6 +381,17 @@ def reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter):
     unsupported)."""
     out = C.c_uint32(0)
     rc = load_library().pxz_reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter, C.byref(out))
+    if rc != 0:
+        raise PxzError(rc)
+    return out.value
+
+
+def retile_distortion_lds_bytes(src_bw, src_bh, bw, bh, channels, expand_filter, filter_up, out=None):
+    """pxz_retile_distortion_lds_bytes: LDS bytes of one block of retile_distortion_varied_device for source blocks of
+    src_bw x src_bh and destination blocks of bw x bh (host only; above 163840: unsupported).  out: a ctypes c_uint32 to write
+    into (for the error cases)."""
+    out = C.c_uint32(0) if out is None else out
+    rc = load_library().pxz_retile_distortion_lds_bytes(src_bw, src_bh, bw, bh, channels, expand_filter, filter_up, C.byref(out))
     if rc != 0:
         raise PxzError(rc)
     return out.value
@@ -1373,10 +1398,59 @@ class Handle:
             ptr(ref_h), ptr(ref_slots), ptr(ow), ptr(oh), ptr(slots), ptr(tile_sse), ptr(image_sse), ptr(image_flags)))
         return tile_sse, image_sse
 
-    def rate_distortion_varied_files(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors):
+    def retile_distortion_varied_device(self, sizes, channels, src_bw, src_bh, bw, bh, expand_filter, filter_up, ref_w, ref_h,
+                                        ref_slots, ow, oh, slots, want_tiles=True, out=None, image_flags=None, n_sets=None):
+        """pxz_retile_distortion_varied_device: reshrink_distortion_varied_device for a block size that changes: the archive's
+        stored tiles in the layout of src_bw x src_bh blocks (ref_w[Ts], ref_h[Ts], ref_slots[Ts, src_bw*src_bh*C]) against n_sets
+        stored versions of the tiles of the bw x bh grid (ow[K,T], oh[K,T], slots[K,T,bw*bh*C], as
+        retile_varied_ladder_frames_device leaves its rungs).  Returns, out, image_flags and n_sets as there, T being the tiles
+        of the bw x bh grid."""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        n = len(geoms)
+        T = int(varied_layout([g[:4] for g in geoms], bw, bh)[-1]) if n and out is None else 0
+        K = n_sets if n_sets is not None else (ow.numel() // T if T else ow.shape[0])
+        if out is None:
+            dev = torch.device("cuda", self.device_id)
+            tile_sse = torch.empty((K, T, channels), dtype=torch.int64, device=dev) if want_tiles else None
+            image_sse = torch.empty((K, n, channels), dtype=torch.int64, device=dev)
+        else:
+            tile_sse, image_sse = out
+        pd = Params(bw, bh, 0, filter_up, 0.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(self._L.pxz_retile_distortion_varied_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, src_bw, src_bh, C.byref(pd), expand_filter, K,
+            ptr(ref_w), ptr(ref_h), ptr(ref_slots), ptr(ow), ptr(oh), ptr(slots), ptr(tile_sse), ptr(image_sse), ptr(image_flags)))
+        return tile_sse, image_sse
+
+    def rate_distortion_retile_files(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors):
+        """pxz_rate_distortion_retile_files: rate_distortion_varied_files with bw x bh the NEW block size (the files' own comes
+        from their headers): the length of each file re-tiled at every factor and its squared error against what the file
+        decodes to now."""
+        return self.rate_distortion_varied_files(files, bw, bh, mode, filter_down, expand_filter, filter_up, factors,
+                                                 _entry="pxz_rate_distortion_retile_files")
+
+    def retile_varied_files_fit(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
+                                filter_byte=0, want_table=False, out=None):
+        """pxz_retile_varied_files_fit: transcode_varied_files_fit with bw x bh the NEW block size; returns and out as there."""
+        return self.transcode_varied_files_fit(files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
+                                               filter_byte=filter_byte, want_table=want_table, out=out, _entry="pxz_retile_varied_files_fit")
+
+    def retile_varied_files_fit_tiles(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
+                                      group_first=None, filter_byte=0, out=None):
+        """pxz_retile_varied_files_fit_tiles: transcode_varied_files_fit_tiles with bw x bh the NEW block size (tile_choice: the
+        tiles of the new grid); returns and out as there."""
+        return self.transcode_varied_files_fit_tiles(files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
+                                                     group_first=group_first, filter_byte=filter_byte, out=out,
+                                                     _entry="pxz_retile_varied_files_fit_tiles")
+
+    def rate_distortion_varied_files(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors,
+                                     _entry="pxz_rate_distortion_varied_files"):
         """pxz_rate_distortion_varied_files: a list of .pixlzr files (bytes) of one channel count and of block size bw x bh at
         every factor of `factors` (1..32) -> (file_bytes uint64[K,n], sse uint64[K,n,C]): the length of each re-shrunk file
-        and its squared error against what the file decodes to now."""
+        and its squared error against what the file decodes to now.  (_entry: the entry point that is called -- the forms that
+        take another block size share this marshalling.)"""
         n = len(files)
         bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
         ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
@@ -1387,13 +1461,13 @@ class Handle:
         pd = Params(bw, bh, mode, filter_down, 0.0, 0)
         file_bytes = np.zeros((max(K, 1), max(n, 1)), np.uint64)
         sse = np.zeros((max(K, 1), max(n, 1), ch), np.uint64)
-        self._check(self._L.pxz_rate_distortion_varied_files(
+        self._check(getattr(self._L, _entry)(
             self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd), expand_filter, filter_up,
             _p(fac) if K else None, K, _p(file_bytes), _p(sse)))
         return file_bytes[:K, :n], sse[:K, :n]
 
     def transcode_varied_files_fit(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
-                                   filter_byte=0, want_table=False, out=None):
+                                   filter_byte=0, want_table=False, out=None, _entry="pxz_transcode_varied_files_fit"):
         """pxz_transcode_varied_files_fit: a list of .pixlzr files (bytes) -> the list of the files re-shrunk, each at the
         factor of `factors` that fit_select picks under targets[i], the error measured against what the file decodes to now.
         Returns (files, choice uint32[n], fit_flags uint32[n]) and, with want_table, (file_bytes uint64[K,n], sse
@@ -1414,7 +1488,7 @@ class Handle:
         table_sse = np.zeros((max(K, 1), max(n, 1), ch), np.uint64)
 
         def call(buf):
-            return self._L.pxz_transcode_varied_files_fit(
+            return getattr(self._L, _entry)(
                 self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd), expand_filter, filter_up,
                 _p(fac) if K else None, K, criterion, _p(tg) if tg.size else None, filter_byte,
                 _p(buf) if buf is not None and buf.size else None, 0 if buf is None else buf.size, _p(offs), _p(choice), _p(flags),
@@ -1561,7 +1635,7 @@ class Handle:
         return self._fit_tiles_result(call, sum(i.size for i in imgs) * 5 // 4 + 4096 * max(n, 1), n, G, T, res, out)
 
     def transcode_varied_files_fit_tiles(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors, criterion, targets,
-                                         group_first=None, filter_byte=0, out=None):
+                                         group_first=None, filter_byte=0, out=None, _entry="pxz_transcode_varied_files_fit_tiles"):
         """pxz_transcode_varied_files_fit_tiles: the same for a list of .pixlzr files (bytes) of one channel count and of block
         size bw x bh, the error measured against what each file decodes to now (expand_filter).  Returns and out as
         encode_varied_images_fit_tiles."""
@@ -1583,7 +1657,7 @@ class Handle:
         res = self._fit_tiles_outputs(n, G, T)
 
         def call(buf):
-            return self._L.pxz_transcode_varied_files_fit_tiles(
+            return getattr(self._L, _entry)(
                 self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, C.byref(pd), expand_filter, filter_up,
                 _p(fac) if K else None, K, criterion, _p(gf), G, _p(tg) if tg.size else None, filter_byte,
                 _p(buf) if buf is not None and buf.size else None, 0 if buf is None else buf.size, res[0].ctypes.data,

@@ -3220,6 +3220,99 @@ int pxz_reshrink_distortion_varied_device(pxz_handle *h, const pxz_image_desc *d
 	return PXZ_OK;
 }
 
+// ---- fit an archive to a budget at a new block size: the error of re-tiled tiles against the archive (pxz_retile_distortion.hip)
+int pxz_retile_distortion_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t channels,
+                                    uint32_t expand_filter, uint32_t filter_up, uint32_t *lds_bytes)
+{
+	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || expand_filter > 4 ||
+	    filter_up > 4)
+		return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::retile_distortion_lds_bytes(src_block_w, src_block_h, block_w, block_h, 1u, 1u);
+	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
+	pxz::VariedExpandTableSet rs, us;
+	if (!pxz::build_varied_expand_tables(unique_sides({src_block_w, src_block_h}), expand_filter, &rs)) return PXZ_ERR_INVALID_ARG;
+	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), filter_up, &us)) return PXZ_ERR_INVALID_ARG;
+	*lds_bytes = pxz::retile_distortion_lds_bytes(src_block_w, src_block_h, block_w, block_h, varied_window_dw(rs.max_window),
+	                                              varied_window_dw(us.max_window));
+	return PXZ_OK;
+}
+
+int pxz_retile_distortion_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                        uint32_t src_block_w, uint32_t src_block_h, const pxz_params *params, uint32_t expand_filter,
+                                        uint32_t n_sets, const uint32_t *d_ref_w, const uint32_t *d_ref_h, const uint8_t *d_ref_slots,
+                                        const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, uint64_t *d_tile_sse,
+                                        uint64_t *d_image_sse, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_ref_w || !d_ref_h || !d_ref_slots || !d_tile_w || !d_tile_h || !d_slots || !d_image_sse)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	if (src_block_w == 0 || src_block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
+	if (n_sets == 0) return fail(h, PXZ_ERR_INVALID_ARG, "n_sets must be at least 1");
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	// the one place that says whether the kernel takes a pair of blocks: its LDS footprint against the CU's
+	auto check_pair = [&](uint32_t wdw_src, uint32_t wdw_set) {
+		if (pxz::retile_distortion_lds_bytes(src_block_w, src_block_h, p.block_w, p.block_h, wdw_src, wdw_set) > kLdsPerCu)
+			return fail(h, PXZ_ERR_UNSUPPORTED,
+			            "the distortion of re-tiled tiles keeps two %ux%u tile images (a dword per pixel) and the staged parts and windows of %ux%u source "
+			            "tiles, or of a whole stored %ux%u tile, in LDS: they exceed a block's 160 KB (pxz_retile_distortion_lds_bytes)",
+			            p.block_w, p.block_h, src_block_w, src_block_h, p.block_w, p.block_h);
+		return (int)PXZ_OK;
+	};
+	if ((rc = check_pair(1u, 1u)) != PXZ_OK) return rc;
+	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
+	std::vector<pxz_image_desc> sized(n_images);
+	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
+	std::vector<pxz::VariedImage> images, src_images;
+	std::vector<uint32_t> sides, src_sides;
+	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
+	if ((rc = varied_plan(h, sized.data(), n_images, src_block_w, src_block_h, 0, 0, &src_images, &src_sides, nullptr)) != PXZ_OK) return rc;
+	if ((uint64_t)n_sets * varied_n_tiles(images) > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u sets", n_sets);
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::RetileDistortionArgs a{};
+	pxz_params xp = p;  // the reference's side: the source geometry
+	xp.block_w = src_block_w;
+	xp.block_h = src_block_h;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, src_sides, &a.r)) != PXZ_OK) return rc;
+	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a.u)) != PXZ_OK) return rc;
+	// Both sets live in one bounded cache, and a set that is built into a full cache empties it first: the reference's set may
+	// have gone with it.  Asked for again it is found, or built into a cache that holds the sets' tables alone -- both stay.
+	if ((expand_filter != p.filter || src_sides != sides) && (rc = put_varied_expand_tables(h, xp, channels, src_sides, &a.r)) != PXZ_OK) return rc;
+	if ((rc = check_pair(a.r.wdw, a.u.wdw)) != PXZ_OK) return rc;
+	a.n_images = n_images;
+	a.n_tiles = varied_n_tiles(images);
+	a.n_sets = n_sets;
+	a.r.n_tiles = varied_n_tiles(src_images);
+	a.u.n_tiles = a.n_tiles;
+	a.r.tile_w = d_ref_w;
+	a.r.tile_h = d_ref_h;
+	a.r.slots = d_ref_slots;
+	a.u.tile_w = d_tile_w;
+	a.u.tile_h = d_tile_h;
+	a.u.slots = d_slots;
+	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
+	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
+	if ((rc = fresh_status(h, &a.r.status)) != PXZ_OK) return rc;
+	a.u.status = a.r.status;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.image_flags = d_image_flags;
+	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * n_images * channels * 8u, h->stream));
+	// both per-image tables in one upload: the destination layout's, then the source layout's
+	std::vector<pxz::VariedImage> both = images;
+	both.insert(both.end(), src_images.begin(), src_images.end());
+	if ((rc = varied_upload(h, both, &a.images)) != PXZ_OK) return rc;
+	a.src_images = a.images + n_images;
+	PXZ_HIP(h, pxz::launch_retile_distortion(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
 }  // extern "C"
 
 // ---- pixel windows of files (window_index_kernel in pxz_stream.hip, pxz_window.hip) ---------------------------------------

@@ -232,12 +232,13 @@ int download_rung_table(pxz_handle *h, const RungTable &t, uint32_t ch, uint64_t
 
 // Fills the table of the rungs `all` (rung-major, n_factors sets of the images descs): the writer over the descriptors once per
 // rung, for its offsets alone, then the rungs' distortion -- against the images at d_images (ref null: descs say where), or
-// against the archive's own tiles *ref, which expand_filter expands.  The tile-fit forms want the same per tile: with
+// against the archive's own tiles *ref, which expand_filter expands and which lie in the layout of src_bw x src_bh blocks: the
+// block of p (the re-shrink's distortion) or another (the re-tile's).  The tile-fit forms want the same per tile: with
 // d_record_bytes the writer's pass is pxz_record_bytes_varied_device (the offsets come with it), and d_tile_sse takes the
 // distortion call's per-tile sums (both null: the per-image forms, as before).
 int rung_table(pxz_handle *h, const std::vector<pxz_image_desc> &descs, uint32_t n_factors, uint32_t ch, const pxz_params &p, const pxz_params &up,
-               const TileSet &all, const RungTable &t, const uint8_t *d_images, const TileSet *ref, uint32_t expand_filter,
-               uint32_t *d_record_bytes = nullptr, uint64_t *d_tile_sse = nullptr)
+               const TileSet &all, const RungTable &t, const uint8_t *d_images, const TileSet *ref, uint32_t src_bw, uint32_t src_bh,
+               uint32_t expand_filter, uint32_t *d_record_bytes = nullptr, uint64_t *d_tile_sse = nullptr)
 {
 	const std::vector<pxz_image_desc> rungs = repeat_descs(descs, n_factors);
 	const int rc = d_record_bytes ? pxz_record_bytes_varied_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &p, all.value, all.w, all.h, all.slots,
@@ -248,6 +249,9 @@ int rung_table(pxz_handle *h, const std::vector<pxz_image_desc> &descs, uint32_t
 	if (!ref)
 		return pxz_distortion_varied_frames_device(h, rungs.data(), (uint32_t)rungs.size(), ch, &up, d_images, all.w, all.h, all.slots, d_tile_sse, t.d_sse,
 		                                           nullptr);
+	if (src_bw != p.block_w || src_bh != p.block_h)
+		return pxz_retile_distortion_varied_device(h, descs.data(), (uint32_t)descs.size(), ch, src_bw, src_bh, &up, expand_filter, n_factors, ref->w, ref->h,
+		                                           ref->slots, all.w, all.h, all.slots, d_tile_sse, t.d_sse, nullptr);
 	return pxz_reshrink_distortion_varied_device(h, descs.data(), (uint32_t)descs.size(), ch, &up, expand_filter, n_factors, ref->w, ref->h, ref->slots,
 	                                             all.w, all.h, all.slots, d_tile_sse, t.d_sse, nullptr);
 }
@@ -343,14 +347,22 @@ int image_rungs(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_des
 	if ((rc = pxz_shrink_varied_ladder_frames_device(h, s->descs.data(), n_images, channels, &s->p, factors, n_factors, d_in, s->all.value, s->all.w,
 	                                                 s->all.h, s->all.slots)) != PXZ_OK)
 		return rc;
-	return rung_table(h, s->descs, n_factors, channels, s->p, up, s->all, s->t, d_in, nullptr, 0, s->d_record_bytes, s->d_tile_sse);
+	return rung_table(h, s->descs, n_factors, channels, s->p, up, s->all, s->t, d_in, nullptr, 0, 0, 0, s->d_record_bytes, s->d_tile_sse);
 }
 
-// The archive forms from their parameter checks to the filled table: the files parsed and uploaded, the reader into a buffer
-// of its own (NOT rung 0: the reference is kept), the re-shrink ladder out of place into varied_out, the flags of both checked,
-// then rung_table against the reference.
+// The archive forms from their parameter checks to the filled table: the files parsed and uploaded, the reader at the files'
+// geometry into a buffer of its own (NOT rung 0: the reference is kept), the rungs into varied_out, the flags of both stages
+// checked, then rung_table.  params' block is the rungs'; the files' comes from their headers.
+//   equal blocks:   the re-shrink ladder out of place; rung_table against the reference (the re-shrink's distortion).
+//   another block (new_block: the forms that take one; the others refuse it): the images in handle scratch (varied_in) -> the
+//     varied ladder; rung_table against those images.  The rule of transcode_varied would send a pair whose new block divides the
+//     files' on both axes through the re-tile ladder and rung_table against the reference in the files' layout (the re-tile's
+//     distortion), with nothing of image size anywhere.  That route measured SLOWER files to files than the images, by 7-9 % on
+//     strongly shrunk files in two runs whose samples spread by 1 %, and level elsewhere, so by 8o's precedent
+//     every other block takes the images; the route is kept for the measurement build alone.  The device calls take every pair.
+// The tables are the same on every path.
 int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
-                  uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, bool fit, Rungs *s)
+                  uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, bool fit, bool new_block, Rungs *s)
 {
 	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
 	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
@@ -359,55 +371,96 @@ int archive_rungs(pxz_handle *h, const uint8_t *const *files, const size_t *lens
 	s->p.factor = 1.0f;
 	int rc = check_params(h, &s->p);
 	if (rc != PXZ_OK) return rc;
-	FileScan scan;  // (the block size must be params' besides)
+	FileScan scan;
 	if ((rc = scan_files(h, files, lens, n_images, &scan)) != PXZ_OK) return rc;
 	const uint32_t fbw = scan.block_w, fbh = scan.block_h, ch = scan.channels;
-	if (fbw != s->p.block_w || fbh != s->p.block_h)
+	const bool same_block = fbw == s->p.block_w && fbh == s->p.block_h;
+	if (!same_block && !new_block)
 		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "the files hold %ux%u blocks, params ask for %ux%u: the error without the image needs an unchanged block size (decode the files and "
-		            "use the image calls)", fbw, fbh, s->p.block_w, s->p.block_h);
-	if ((rc = reshrink_check_block(h, s->p.mode, fbw, fbh, ch, 1u)) != PXZ_OK) return rc;
-	if (reshrink_distortion_bytes(fbw, fbh, 1u) > kLdsPerCu)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "the distortion of re-shrunk tiles keeps three planes of block_w*block_h dwords in LDS (%ux%u)", fbw, fbh);
-	std::vector<pxz::VariedImage> images;
-	if ((rc = varied_plan(h, scan.descs.data(), n_images, fbw, fbh, ch, s->p.mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+		            "the files hold %ux%u blocks, params ask for %ux%u: this call needs an unchanged block size (pxz_rate_distortion_retile_files, "
+		            "pxz_retile_varied_files_fit and pxz_retile_varied_files_fit_tiles take another)", fbw, fbh, s->p.block_w, s->p.block_h);
+	pxz_params pin = s->p;  // the files' own geometry
+	pin.block_w = fbw;
+	pin.block_h = fbh;
+	pin.filter = expand_filter;
+	if (same_block) {
+		if ((rc = reshrink_check_block(h, s->p.mode, fbw, fbh, ch, 1u)) != PXZ_OK) return rc;
+		if (reshrink_distortion_bytes(fbw, fbh, 1u) > kLdsPerCu)
+			return fail(h, PXZ_ERR_UNSUPPORTED, "the distortion of re-shrunk tiles keeps three planes of block_w*block_h dwords in LDS (%ux%u)", fbw, fbh);
+	} else {
+		const pxz_params px = decode_side_params(&pin, true);
+		if ((rc = varied_check_params(h, ch, &px)) != PXZ_OK) return rc;
+		if ((rc = varied_check_params(h, ch, &s->p)) != PXZ_OK) return rc;
+	}
+	std::vector<pxz::VariedImage> images_in, images;
+	if (!same_block && (rc = varied_plan(h, scan.descs.data(), n_images, fbw, fbh, 0, 0, &images_in, nullptr, nullptr)) != PXZ_OK) return rc;
+	if ((rc = varied_plan(h, scan.descs.data(), n_images, s->p.block_w, s->p.block_h, ch, s->p.mode, &images, nullptr, nullptr)) != PXZ_OK) return rc;
 	s->descs = std::move(scan.descs);
 	s->raw = scan.raw;
 	s->ch = ch;
 	s->n_tiles = varied_n_tiles(images);
+	const uint32_t n_in = same_block ? s->n_tiles : varied_n_tiles(images_in);
 	const uint64_t n_sets = (uint64_t)n_factors * n_images, tiles = (uint64_t)n_factors * s->n_tiles;
 	if (tiles > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	// another block: the images (the rule above).  The re-tile route stays behind a measurement build (make exp EXP=41):
+	// there a pair whose new tiles split tiles of the files, and that both kernels take, goes through the re-tile ladder
+#if defined(PXZ_EXP) && PXZ_EXP == 41
+	uint32_t ladder_bytes = 0, distortion_bytes = 0;
+	const bool retile = !same_block && fbw % s->p.block_w == 0 && fbh % s->p.block_h == 0 &&
+	                    pxz_retile_ladder_lds_bytes(fbw, fbh, s->p.block_w, s->p.block_h, ch, s->p.mode, expand_filter, &ladder_bytes) == PXZ_OK &&
+	                    ladder_bytes <= kLdsPerCu &&
+	                    pxz_retile_distortion_lds_bytes(fbw, fbh, s->p.block_w, s->p.block_h, ch, expand_filter, filter_up, &distortion_bytes) == PXZ_OK &&
+	                    distortion_bytes <= kLdsPerCu;
+#else
+	const bool retile = false;
+#endif
+	const bool by_images = !same_block && !retile;
 	PXZ_HIP(h, hipSetDevice(h->device));
 	SentFiles sent;
 	if ((rc = send_files(h, h->transcode_files, sent_bytes(n_images, scan.file_bytes), files, lens, n_images, scan.file_bytes, 0, &sent)) != PXZ_OK)
 		return rc;
 
-	// the archive's tiles and the flags of the reader and the re-shrink (archive_tiles); every rung's tiles (varied_out)
-	const uint64_t slot = (uint64_t)fbw * fbh * ch;
-	const uint64_t flags_at = up256(TileSet::bytes(s->n_tiles, slot));
+	// the archive's tiles and the flags of the reader and the stage behind it (archive_tiles); every rung's tiles (varied_out)
+	const uint64_t slot_in = (uint64_t)fbw * fbh * ch, slot = (uint64_t)s->p.block_w * s->p.block_h * ch;
+	const uint64_t flags_at = up256(TileSet::bytes(n_in, slot_in));
 	if ((rc = ensure(h, h->archive_tiles, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
 	if ((rc = ensure(h, h->varied_out, TileSet::bytes(tiles, slot))) != PXZ_OK) return rc;
 	if ((rc = carve_rung_table(h, (size_t)n_sets, ch, fit ? n_images : 0u, &s->t)) != PXZ_OK) return rc;
 	if ((rc = carve_tile_tables(h, tiles, ch, s)) != PXZ_OK) return rc;
+	uint8_t *d_img = nullptr;
+	if (by_images) {
+		const uint64_t img_bytes = pack_owners(&s->descs, ch);
+		if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
+		d_img = (uint8_t *)h->varied_in.ptr;
+	}
 	uint8_t *d_ref = (uint8_t *)h->archive_tiles.ptr;
-	const TileSet ref(d_ref, s->n_tiles);
+	const TileSet ref(d_ref, n_in);
 	uint32_t *d_flags = (uint32_t *)(d_ref + flags_at);
 	s->all = TileSet((uint8_t *)h->varied_out.ptr, tiles);
 
 	// reader -> the reference; ladder out of place -> the rungs
-	pxz_params pin = s->p;
-	pin.filter = expand_filter;
-	PXZ_HIP(h, hipMemsetAsync(d_ref, 0, TileSet::meta_bytes(s->n_tiles), h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
+	PXZ_HIP(h, hipMemsetAsync(d_ref, 0, TileSet::meta_bytes(n_in), h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
 	if ((rc = pxz_decode_varied_frames_device(h, s->descs.data(), n_images, ch, &pin, sent.d_files, sent.d_offsets, ref.value, ref.w, ref.h, ref.slots,
 	                                          d_flags)) != PXZ_OK)
 		return rc;
-	if ((rc = pxz_reshrink_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, &s->p, expand_filter, factors, n_factors, ref.w, ref.h, ref.slots,
-	                                                   s->all.value, s->all.w, s->all.h, s->all.slots, d_flags + n_images)) != PXZ_OK)
-		return rc;
+	if (same_block) {
+		rc = pxz_reshrink_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, &s->p, expand_filter, factors, n_factors, ref.w, ref.h, ref.slots,
+		                                              s->all.value, s->all.w, s->all.h, s->all.slots, d_flags + n_images);
+	} else if (retile) {
+		rc = pxz_retile_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, fbw, fbh, &s->p, expand_filter, factors, n_factors, ref.w, ref.h,
+		                                            ref.slots, s->all.value, s->all.w, s->all.h, s->all.slots, d_flags + n_images);
+	} else {
+		if ((rc = pxz_expand_varied_frames_device(h, s->descs.data(), n_images, ch, &pin, ref.w, ref.h, ref.slots, d_img, d_flags + n_images)) != PXZ_OK)
+			return rc;
+		rc = pxz_shrink_varied_ladder_frames_device(h, s->descs.data(), n_images, ch, &s->p, factors, n_factors, d_img, s->all.value, s->all.w, s->all.h,
+		                                            s->all.slots);
+	}
+	if (rc != PXZ_OK) return rc;
 	if ((rc = check_stage_flags(h, d_flags, n_images)) != PXZ_OK) return rc;
 	pxz_params up = s->p;
 	up.filter = filter_up;
-	return rung_table(h, s->descs, n_factors, ch, s->p, up, s->all, s->t, nullptr, &ref, expand_filter, s->d_record_bytes, s->d_tile_sse);
+	return rung_table(h, s->descs, n_factors, ch, s->p, up, s->all, s->t, d_img, by_images ? nullptr : &ref, fbw, fbh, expand_filter, s->d_record_bytes,
+	                  s->d_tile_sse);
 }
 
 // Where both fit forms end, behind the filled table: one rung per image chosen on the device, its tiles gathered as a varied
@@ -492,6 +545,59 @@ int fit_tiles_check(pxz_handle *h, uint32_t n_images, uint32_t criterion, const 
 	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
 		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
 	return tile_groups_check(h, group_first, n_groups, n_images);
+}
+
+// The three archive forms behind their entry points, each twice: new_block false are the forms that need the files' block to be
+// params' (pxz_rate_distortion_varied_files, pxz_transcode_varied_files_fit, pxz_transcode_varied_files_fit_tiles), true the
+// forms that take another (pxz_rate_distortion_retile_files, pxz_retile_varied_files_fit, pxz_retile_varied_files_fit_tiles).
+int archive_table(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params, uint32_t expand_filter,
+                  uint32_t filter_up, const float *factors, uint32_t n_factors, bool new_block, uint64_t *file_bytes, uint64_t *sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!files || !lens || !params || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	Rungs s;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, false, new_block, &s)) != PXZ_OK) return rc;
+	return download_rung_table(h, s.t, s.ch, file_bytes, sse);
+}
+
+int archive_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params, uint32_t expand_filter,
+                uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion, const uint64_t *targets, uint32_t filter_byte,
+                bool new_block, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes,
+                uint64_t *table_sse)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
+	if (!files || !lens || !params || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
+		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
+	Rungs s;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, new_block, &s)) != PXZ_OK) return rc;
+	return fit_and_write(h, s, n_factors, criterion, targets, filter_byte, out, out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
+}
+
+int archive_fit_tiles(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
+                      uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                      const uint32_t *group_first, uint32_t n_groups, const uint64_t *targets, uint32_t filter_byte, bool new_block, uint8_t *out,
+                      uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice, uint64_t *group_lambda, uint64_t *group_bytes,
+                      uint64_t *group_sse, uint32_t *group_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
+	if (rc != PXZ_OK) return rc;
+	if (!files || !lens || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if ((rc = fit_tiles_check(h, n_images, criterion, group_first, n_groups, targets, file_offsets, group_lambda, group_bytes, group_sse, group_flags)) !=
+	    PXZ_OK)
+		return rc;
+	Rungs s;
+	s.per_tile = true;
+	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, new_block, &s)) != PXZ_OK) return rc;
+	return fit_tiles_and_write(h, s, n_factors, criterion, group_first, n_groups, targets, filter_byte, out, out_capacity, file_offsets, tile_choice,
+	                           group_lambda, group_bytes, group_sse, group_flags);
 }
 
 // Both host forms of pix_to_pix behind one body: factors == nullptr is pxz_transcode_varied_files (one rung, the caller's
@@ -772,13 +878,14 @@ int pxz_rate_distortion_varied_files(pxz_handle *h, const uint8_t *const *files,
                                      const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
                                      uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
 {
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!files || !lens || !params || !file_bytes || !sse) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	Rungs s;
-	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, false, &s)) != PXZ_OK) return rc;
-	return download_rung_table(h, s.t, s.ch, file_bytes, sse);
+	return archive_table(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, false, file_bytes, sse);
+}
+
+int pxz_rate_distortion_retile_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                                     const pxz_params *params, uint32_t expand_filter, uint32_t filter_up, const float *factors,
+                                     uint32_t n_factors, uint64_t *file_bytes, uint64_t *sse)
+{
+	return archive_table(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, file_bytes, sse);
 }
 
 int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
@@ -787,16 +894,17 @@ int pxz_transcode_varied_files_fit(pxz_handle *h, const uint8_t *const *files, c
                                    uint64_t out_capacity, uint64_t *file_offsets, uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes,
                                    uint64_t *table_sse)
 {
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!targets) return fail(h, PXZ_ERR_INVALID_ARG, "null targets");
-	if (!files || !lens || !params || !file_offsets || !choice || !fit_flags) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	if (criterion != PXZ_FIT_BYTES && criterion != PXZ_FIT_SSE)
-		return fail(h, PXZ_ERR_INVALID_ARG, "criterion must be PXZ_FIT_BYTES (0) or PXZ_FIT_SSE (1), got %u", criterion);
-	Rungs s;
-	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, &s)) != PXZ_OK) return rc;
-	return fit_and_write(h, s, n_factors, criterion, targets, filter_byte, out, out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
+	return archive_fit(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, criterion, targets, filter_byte, false, out,
+	                   out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
+}
+
+int pxz_retile_varied_files_fit(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
+                                uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                const uint64_t *targets, uint32_t filter_byte, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets,
+                                uint32_t *choice, uint32_t *fit_flags, uint64_t *table_bytes, uint64_t *table_sse)
+{
+	return archive_fit(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, criterion, targets, filter_byte, true, out,
+	                   out_capacity, file_offsets, choice, fit_flags, table_bytes, table_sse);
 }
 
 int pxz_encode_varied_images_fit_tiles(pxz_handle *h, const uint8_t *const *pixels, const pxz_image_desc *descs, uint32_t n_images,
@@ -829,19 +937,18 @@ int pxz_transcode_varied_files_fit_tiles(pxz_handle *h, const uint8_t *const *fi
                                          uint32_t *tile_choice, uint64_t *group_lambda, uint64_t *group_bytes, uint64_t *group_sse,
                                          uint32_t *group_flags)
 {
-	if (!h) return PXZ_ERR_INVALID_ARG;
-	int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
-	if (rc != PXZ_OK) return rc;
-	if (!files || !lens || !params) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	if ((rc = fit_tiles_check(h, n_images, criterion, group_first, n_groups, targets, file_offsets, group_lambda, group_bytes, group_sse, group_flags)) !=
-	    PXZ_OK)
-		return rc;
-	Rungs s;
-	s.per_tile = true;
-	if ((rc = archive_rungs(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, true, &s)) != PXZ_OK) return rc;
-	return fit_tiles_and_write(h, s, n_factors, criterion, group_first, n_groups, targets, filter_byte, out, out_capacity, file_offsets, tile_choice,
-	                           group_lambda, group_bytes, group_sse, group_flags);
+	return archive_fit_tiles(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, criterion, group_first, n_groups, targets,
+	                         filter_byte, false, out, out_capacity, file_offsets, tile_choice, group_lambda, group_bytes, group_sse, group_flags);
+}
+
+int pxz_retile_varied_files_fit_tiles(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_params *params,
+                                      uint32_t expand_filter, uint32_t filter_up, const float *factors, uint32_t n_factors, uint32_t criterion,
+                                      const uint32_t *group_first, uint32_t n_groups, const uint64_t *targets, uint32_t filter_byte, uint8_t *out,
+                                      uint64_t out_capacity, uint64_t *file_offsets, uint32_t *tile_choice, uint64_t *group_lambda,
+                                      uint64_t *group_bytes, uint64_t *group_sse, uint32_t *group_flags)
+{
+	return archive_fit_tiles(h, files, lens, n_images, params, expand_filter, filter_up, factors, n_factors, criterion, group_first, n_groups, targets,
+	                         filter_byte, true, out, out_capacity, file_offsets, tile_choice, group_lambda, group_bytes, group_sse, group_flags);
 }
 
 int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,

@@ -619,6 +619,22 @@ struct ReshrinkDistortionArgs {
 	unsigned long long *image_sse;    // index (s * n_images + i) * channels + c, added with atomics (zeroed before the launch)
 };
 
+// Squared error of re-tiled tiles against the archive they came from (pxz_retile_distortion_varied_device,
+// pxz_retile_distortion.hip): the flat tile space of `images`, the DESTINATION layout, one destination tile per block.  r is the
+// archive: the SOURCE block (r.bw, r.bh, r.slot_bytes), expand_filter's tables for the source geometry, and the stored sizes and
+// slots of the source layout `src_images` (entry i: image i).  u are the n_sets stored versions of every destination tile,
+// set-major: the destination block, filter_up's tables, n_sets * n_tiles entries.  r and u are what put_varied_expand_tables
+// fills; of their launch fields only r.status is read (the block's LDS is retile_distortion_lds', pxz_varied_tile.h).
+// Outputs as DistortionArgs'.
+struct RetileDistortionArgs {
+	const VariedImage *images, *src_images;
+	uint32_t n_images, n_tiles, n_sets;
+	TileResizeArgs r, u;
+	uint32_t *image_flags;            // per image 1 for a source or set tile whose stored size is invalid, or null
+	unsigned long long *tile_sse;     // index (s * n_tiles + t) * channels + c, or null; all-ones for an invalid entry
+	unsigned long long *image_sse;    // index (s * n_images + i) * channels + c, added with atomics (zeroed before the launch)
+};
+
 // Fit to a budget (pxz_fit_varied_ladder_device, pxz_fit.hip): one rung per image out of what the writer and the distortion
 // call left for the descriptors repeated n_factors times.  The rule is fit_pick's (pxz_fit.h).
 struct FitArgs {

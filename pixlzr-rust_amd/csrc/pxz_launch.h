@@ -65,6 +65,11 @@ inline uint32_t reshrink_distortion_tile_dw(uint32_t bw, uint32_t bh, uint32_t w
 	const uint64_t dw = (3ull * bw * bh + (uint64_t)wdw * ((uint64_t)bw + bh) + 3u) & ~3ull;
 	return dw > 0x0fffffffull ? 0xffffffffu : (uint32_t)dw;
 }
+// re-tile distortion (pxz_retile_distortion.hip): one launch whatever the sets; and the LDS bytes of one block of
+// retile_distortion_kernel, from retile_distortion_lds (pxz_varied_tile.h), for source windows of wdw_src dwords and set windows of
+// wdw_set, under the conventions of retile_lds_bytes
+hipError_t launch_retile_distortion(const RetileDistortionArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+uint32_t retile_distortion_lds_bytes(uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t wdw_src, uint32_t wdw_set);
 // fit to a budget (pxz_fit.hip): one rung per image, and the chosen rungs' tiles as a varied batch; one launch each
 hipError_t launch_fit_select(const FitArgs &a, hipStream_t stream);
 hipError_t launch_gather_rungs(const GatherArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);

@@ -9,6 +9,7 @@
 //   retile_ladder_kernel (pxz_retile_ladder.hip): its LDS layout (retile_ladder_lds), the assembly of a destination tile
 //                      (retile_assemble: retile_kernel's steps 1 to 3, which that kernel keeps inline), the two ladders' detectors
 //                      and varied_ladder_tail;
+//   retile_distortion_kernel (pxz_retile_distortion.hip): its LDS layout (retile_distortion_lds) and retile_assemble, twice;
 //   reshrink_ladder_kernel: the tile image of a stored tile (reshrink_tile_image: clone-in, or varied_resize_tile of pxz_device.h
 //                      by the whole block, and the RGB pack);
 //   varied_ladder_kernel: everything behind the detector (varied_ladder_tail: the rungs' decisions, clones, resamples and
@@ -330,6 +331,51 @@ __host__ __device__ inline RetileLadderLds retile_ladder_lds(uint32_t mode, uint
 	if (u_bytes < a_bytes) u_bytes = a_bytes;
 	l.f = i_bytes;
 	l.total = l.u + u_bytes;
+	return l;
+}
+
+// ---- the re-tile distortion: two assemblies of one destination tile, compared (retile_distortion_kernel, pxz_retile_distortion.hip)
+//
+// Where a block of retile_distortion_kernel keeps its images: byte offsets into its dynamic LDS, and their sum (0xffffffff beyond
+// retile_lds' own limits: D or sbw * sbh * 4 above 65536).  The kernel, its launch and the host's limit check
+// (pxz_retile_distortion_lds_bytes, the entry point, the host forms) all take the layout from here.
+//   [R: D = dbw * dbh * 4, rounded up to 16] [E: D] [S]
+// R is the reference -- the destination tile of what the archive decodes to, assembled from the SOURCE tiles that cover it -- and E
+// one set's stored tile of the destination layout at its full size; each is a dword per pixel while it is assembled and C bytes
+// per pixel, tightly packed, when it is compared.  S is the staging of retile_assemble, one region for both sides, laid out as
+// retile_lds lays out the assembly (staged pixels, intermediate, windows of both axes) for
+//   the source side: source blocks sbw x sbh -> parts of a dbw x dbh tile, windows of wdw_src dwords (expand_filter's tables);
+//   the set side:    "source" blocks dbw x dbh -> the whole dbw x dbh tile, windows of wdw_set dwords (filter_up's tables);
+// each side at its own offsets and its own window stride, S as large as the larger of the two needs.
+// Limit: the sum within the CU's 160 KB.  The set side stages a whole stored tile (up to D), its intermediate (up to D) and the
+// windows of both axes, so equal square blocks of side n with Lanczos3 on both sides (both strides 5) take 16 n^2 + 40 n bytes
+// and what rounds each region up to 16: up to 99x99 (160 832 bytes); 100x100 is beyond (164 000), and fits only with Nearest on
+// both sides (161 600).  Destination blocks of 32x32 take 16.5-22.6 KB whatever the source block up to 64x64 (seven blocks a CU
+// and more), 64x64 ones 65-66.5 KB (two).
+struct RetileDistortionLds {
+	uint32_t r, e, s;                      // the two planes and the staging
+	uint32_t src_inter, src_wx;            // the source side's intermediate and windows, from the start of the dynamic LDS
+	uint32_t set_inter, set_wx;            // the set side's
+	uint32_t total;
+};
+
+__host__ __device__ inline RetileDistortionLds retile_distortion_lds(uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t wdw_src,
+                                                                     uint32_t wdw_set)
+{
+	RetileDistortionLds l{0, 0, 0, 0, 0, 0, 0, 0xffffffffu};
+	const RetileLds a = retile_lds(1u, sbw, sbh, dbw, dbh, wdw_src), b = retile_lds(1u, dbw, dbh, dbw, dbh, wdw_set);
+	if (a.total == 0xffffffffu || b.total == 0xffffffffu) return l;
+	const uint32_t d = a.u;  // (mode 1: X stands at 0 and U behind it, D bytes on)
+	const uint32_t need_a = a.wx + (((sbw + sbh) * wdw_src + 3u) & ~3u) * 4u - a.u;
+	const uint32_t need_b = b.wx + (((dbw + dbh) * wdw_set + 3u) & ~3u) * 4u - b.u;
+	l.r = 0u;
+	l.e = d;
+	l.s = 2u * d;
+	l.src_inter = l.s + (a.inter - a.u);
+	l.src_wx = l.s + (a.wx - a.u);
+	l.set_inter = l.s + (b.inter - b.u);
+	l.set_wx = l.s + (b.wx - b.u);
+	l.total = l.s + (need_a > need_b ? need_a : need_b);
 	return l;
 }
 
