@@ -12,7 +12,11 @@ or double size and nothing else notices.  Here the tiles sit on the breakpoints:
 
 Every comparison is bit for bit against the oracle on the same pixels (sizes, value bits, the valid slot bytes); there is no
 tolerance anywhere.  The breakpoints come from the oracle alone, by bisection over reduce_dims -- never from the product.
-All tile construction is CPU work, cached per module."""
+All tile construction is CPU work, cached per module.
+
+The kernels that keep a text of the compare of their own -- varied_ladder_kernel, reshrink_kernel, reshrink_ladder_kernel,
+retile_kernel, retile_ladder_kernel -- meet the same tiles in tests/test_gpu_archive_breakpoints.py, through the builders of
+this module (which imports without a GPU) and the archives of tests/test_archive_breakpoints_host.py."""
 import numpy as np
 import pytest
 
