@@ -640,6 +640,8 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 		// the Oklab detector also takes a ragged last row of whole bands (256 pixels = 256/bw rows) of the square sizes
 		a.ok_rows = square_fast && a.edge_h % ok_row_quantum == 0 ? a.rows : a.full_rows;
 	}
+	// (a pitch whose lane offsets leave 32 bits: no fast path, as for an unaligned batch)
+	if (!pxz::fast32_lane_offset_fits(a.pitch)) a.full_cols = a.full_rows = a.ok_rows = 0;
 	const pxz::FinishArgs fin{a.sums, value, lod0, lod1, a.n_tiles, a.tiles_per_frame, a.cols, a.rows,
 	                          a.bw, a.bh, a.edge_w, a.edge_h, a.mode, a.factor};
 	hipEvent_t e0 = nullptr, e1 = nullptr, emid = nullptr;

@@ -279,6 +279,19 @@ __device__ __forceinline__ uint32_t wave_sum_sgpr(uint32_t v)
 	return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
 	       (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
+// the same with the four row sums joined on the vector unit: row_bcast15 hands lane 15 of a row to the next row (rows 1 and 3
+// take it), row_bcast31 lane 31 to rows 2 and 3; lane 63 then holds the sum -- 2 DPP adds and 1 readlane for 4 readlanes and 3
+// scalar adds
+__device__ __forceinline__ uint32_t wave_sum_sgpr_bcast(uint32_t v)
+{
+	v += dpp_mov<0xB1>(v);
+	v += dpp_mov<0x4E>(v);
+	v += dpp_mov<0x124>(v);
+	v += dpp_mov<0x128>(v);
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+	return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
 __device__ __forceinline__ uint32_t wave_and_sgpr(uint32_t v)
 {
 	v &= dpp_mov<0xB1>(v);
@@ -958,6 +971,36 @@ __device__ __forceinline__ uint3 stream_load3(const uint8_t *p)
 	const u32t v = __builtin_nontemporal_load(reinterpret_cast<const u32t *>(p));
 	return make_uint3(v.x, v.y, v.z);
 }
+// The same from a wave-uniform pointer and a 32-bit lane offset: the scalar-base form of global_load (pointer in two scalar
+// registers, offset in one vector register, no address arithmetic on the vector unit).  The pointer passes through an empty
+// asm as a scalar: left to add pointer and offset up as it likes, the compiler forms the first address per lane and steps
+// from load to load with 64-bit vector adds.  Behind the asm the pointer is named as global memory again, or the loads
+// come out as flat ones.
+// The offset has to come out of such an asm too (lane_offset_here), in the basic block of the loads: widened to 64 bits
+// once, outside the loop that uses it, it reaches the load as a 64-bit register pair and the form is not chosen.
+typedef const __attribute__((address_space(1))) uint8_t *global_bytes;
+__device__ __forceinline__ uint32_t lane_offset_here(uint32_t off)
+{
+	asm volatile("" : "+v"(off));
+	return off;
+}
+__device__ __forceinline__ global_bytes uniform_global_at(const uint8_t *&base, uint32_t off)
+{
+	asm volatile("" : "+s"(base));
+	return (global_bytes)base + off;
+}
+__device__ __forceinline__ uint4 stream_load4_at(const uint8_t *&base, uint32_t off)
+{
+	typedef uint32_t u32q __attribute__((ext_vector_type(4)));
+	const u32q v = __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) u32q *>(uniform_global_at(base, off)));
+	return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ uint3 stream_load3_at(const uint8_t *&base, uint32_t off)
+{
+	typedef uint32_t u32t __attribute__((ext_vector_type(3)));
+	const u32t v = __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) u32t *>(uniform_global_at(base, off)));
+	return make_uint3(v.x, v.y, v.z);
+}
 
 // Fast-path eligibility of a tile (full 32x32 RGBA, 16-byte aligned rows) and its first byte.
 template <int C = 4, class Args>
@@ -972,21 +1015,28 @@ __device__ __forceinline__ bool fast32_tile_src(const Args &a, uint32_t tile_g, 
 }
 // Issues the four loads of a lane's share of a fast tile: rows l/8 + 8k, pixel quad l%8 -- 16 bytes of an RGBA row, 12
 // of an RGB one (pre[k].w unused).
+// The address is split where the hardware splits it: the tile's first byte and the three steps of eight rows are the same
+// for the whole wave and stay on the scalar unit (a 64-bit pointer in two scalar registers), the lane's own part
+// (lane/8 rows + its pixel quad) is ONE 32-bit offset that does not change from tile to tile -- the scalar-base form of
+// global_load.  Added up per lane it was five 64-bit vector adds per tile.  The offset fits 32 bits for every batch the
+// host lets onto the fast path (fast32_lane_offset_fits, pxz_internal.h).
 template <int C = 4, class Args>
 __device__ __forceinline__ void fast32_prefetch(const Args &a, uint32_t tile_g, uint32_t lane, uint4 (&pre)[4], bool &valid, bool skip_loads = false)
 {
 	const uint8_t *src;
 	valid = fast32_tile_src<C>(a, tile_g, src);
 	if (valid && !skip_loads) {  // (skip_loads: the caller knows it will not look at the pixels -- a tile the detector already copied)
-		const uint8_t *p = src + (size_t)(lane >> 3) * a.pitch + (lane & 7u) * (4u * (uint32_t)C);
+		const uint32_t off = lane_offset_here((lane >> 3) * a.pitch + (lane & 7u) * (4u * (uint32_t)C));
+		const uint8_t *rows = src;  // wave-uniform
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
 			if constexpr (C == 4) {
-				pre[k] = stream_load4(p + (size_t)(8 * k) * a.pitch);
+				pre[k] = stream_load4_at(rows, off);
 			} else {
-				const uint3 v = stream_load3(p + (size_t)(8 * k) * a.pitch);  // rows are 4-byte aligned
+				const uint3 v = stream_load3_at(rows, off);  // rows are 4-byte aligned
 				pre[k] = make_uint4(v.x, v.y, v.z, 0u);
 			}
+			rows += (size_t)8 * a.pitch;
 		}
 	}
 }

@@ -170,6 +170,15 @@ struct LadderArgs {
 	uint32_t breaks_asc[4];
 };
 
+// shrink32_kernel and shrink32a_kernel address a lane's share of a tile as (wave-uniform 64-bit pointer) + (32-bit lane
+// offset): lane/8 rows (at most 7) + the lane's pixel quad (at most 7 * 16 bytes).  A pitch beyond this (613 MB per row) is
+// the host's to catch: such a batch gets no fast path at all (full_cols = full_rows = 0, the generic kernel takes every tile).
+constexpr uint32_t kFast32LaneRows = 7, kFast32LaneBytes = 7 * 16;
+constexpr bool fast32_lane_offset_fits(uint32_t pitch)
+{
+	return (uint64_t)kFast32LaneRows * pitch + kFast32LaneBytes <= 0xffffffffull;
+}
+
 // Arguments of shrink32_kernel (full 32x32 RGBA tiles only): the subset of ShrinkArgs it needs
 struct Fast32Args {
 	const uint8_t *src;

@@ -100,8 +100,13 @@ __global__ void __launch_bounds__(1024) shrink32_kernel(const Fast32Args a)
 			if constexpr (C == 4) {
 				uint32_t *d = reinterpret_cast<uint32_t *>(pend_dst);
 				if (pend_px >= 4u) {  // whole 16-byte groups (pixel counts are powers of two)
-					for (uint32_t i = tid; i < (pend_px >> 2); i += 64u)
-						reinterpret_cast<uint4 *>(d)[i] = reinterpret_cast<const uint4 *>(pend_src)[i];
+					// the slot's pointer is wave-uniform and a slot is 4 KB: a 32-bit byte offset per lane, no 64-bit vector adds
+					// (taken afresh in every pass: as the loop's induction variable it is widened to a 64-bit per-lane pointer)
+					for (uint32_t off = tid * 16u; off < pend_px * 4u; off += 1024u) {
+						uint32_t o = off;
+						asm volatile("" : "+v"(o));
+						*reinterpret_cast<uint4 *>(pend_dst + o) = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(pend_src) + off);
+					}
 				} else if (tid < pend_px) {
 					d[tid] = pend_src[tid];
 				}
@@ -208,6 +213,8 @@ __global__ void __launch_bounds__(1024) shrink32_kernel(const Fast32Args a)
 			const uint4 v = pre[k];
 			uint32_t *d = s_pl + row * kRS32 + col * 2u;
 			if constexpr (C == 4) {
+				// (R and B through px & 0x00ff00ff and half-word stores -- 16 plain ANDs for 16 of these permutes, 32 ds_write_b16 for 8
+				// ds_write_b64 -- was measured and lost 7 %: DESIGN §6d)
 #pragma unroll
 				for (uint32_t c = 0; c < 3; ++c) {
 					const uint32_t sel = c | 0x0c000c00u | ((4u + c) << 16);
@@ -311,8 +318,8 @@ __global__ void __launch_bounds__(1024) shrink32_kernel(const Fast32Args a)
 				asm volatile("" : "+v"(qq));  // (a fresh compare, not a hoisted and spilled lane mask)
 				if (qq == 15u) sum_hz = sum_vr = 0;  // pair 15 starts no window (x = 30, 31)
 			}
-			sum_hz = wave_sum_sgpr(sum_hz);
-			sum_vr = wave_sum_sgpr(sum_vr);
+			sum_hz = wave_sum_sgpr_bcast(sum_hz);
+			sum_vr = wave_sum_sgpr_bcast(sum_vr);
 			m0 = level_of(sum_hz);
 			m1 = level_of(sum_vr);
 			key0 = sum_hz;
