@@ -816,6 +816,7 @@ int pxz_create(int device_id, pxz_handle **out)
 	if (!h) return PXZ_ERR_NOMEM;
 	h->device = device_id;
 	h->n_cus = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
+	if (const int v = pxz::knobs().cus; v >= 1 && (uint32_t)v < h->n_cus) h->n_cus = (uint32_t)v;  // test knob: every launcher sizes its grid by this
 	if (!pxz::build_level_thresholds(h->thresholds, pxz::kNumThresholds)) {
 		delete h;
 		return PXZ_ERR_UNSUPPORTED;  // platform log2f is not a clean step around 2^(k+1/2)

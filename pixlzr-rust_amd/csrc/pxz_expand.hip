@@ -1423,6 +1423,7 @@ hipError_t launch_expand(const ExpandArgs &a, uint32_t n_cus, hipStream_t stream
 		const uint32_t wave_bytes = (a.channels == 4 ? kX64Wave : kX64Wave3) * 4u;
 		uint32_t wpb = (160u * 1024u - 16u - xmf_bytes) / wave_bytes;
 		if (wpb > 16u) wpb = 16u;
+		if (const uint32_t v = (uint32_t)knobs().wpb; v >= 1 && v < wpb) wpb = v;
 		const uint32_t lds_bytes = xmf_bytes + wpb * wave_bytes + 16u;
 		const uint32_t need = (a.n_tiles + wpb - 1u) / wpb;
 		void (*k64)(const ExpandArgs) = a.channels == 4 ? expand64_kernel<4> : expand64_kernel<3>;
@@ -1437,7 +1438,9 @@ hipError_t launch_expand(const ExpandArgs &a, uint32_t n_cus, hipStream_t stream
 	if (a.list != nullptr) {
 		// 16x16 RGBA tiles: the 2x2 groups first, then what they left (partial groups, one-pass and odd sizes) through the list
 		const uint32_t xmf_bytes = a.xmf16 ? kXmf16Levels * kXmf16Dw * 4u : 0u;
-		const uint32_t wpb = 16u, lds_bytes = xmf_bytes + wpb * kX16Wave * 4u + 16u;
+		uint32_t wpb = 16u;
+		if (const uint32_t v = (uint32_t)knobs().wpb; v >= 1 && v < wpb) wpb = v;
+		const uint32_t lds_bytes = xmf_bytes + wpb * kX16Wave * 4u + 16u;
 		const uint32_t gcols = (a.cols + 1u) >> 1, grows = (a.rows + 1u) >> 1, n_groups = (a.n_tiles / a.tiles_per_frame) * gcols * grows;
 		const uint32_t need = (n_groups + wpb - 1u) / wpb, resident = 2u * n_cus;
 		hipLaunchKernelGGL(expand16_kernel, dim3(need < resident ? need : resident), dim3(64u * wpb), lds_bytes, stream, a);
@@ -1468,6 +1471,7 @@ hipError_t launch_expand_general(const ExpandArgs &a, uint32_t n_cus, hipStream_
 	uint32_t wpb = (kLds - 16u - xmf_bytes) / tile_bytes;
 	const uint32_t wpb_max = f32 ? 16u : 4u;
 	if (wpb > wpb_max) wpb = wpb_max;
+	if (const uint32_t v = (uint32_t)knobs().wpb; v >= 1 && v < wpb) wpb = v;
 	if (wpb < 1u) return hipErrorInvalidValue;
 	const uint32_t lds_bytes = xmf_bytes + wpb * tile_bytes + 16u;
 	uint32_t per_cu = kLds / lds_bytes;

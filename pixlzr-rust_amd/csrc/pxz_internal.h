@@ -262,6 +262,7 @@ struct Knobs {
 	bool tree_rects;        // PXZ_TREE_RECTS: tree::process always goes over rectangle lists (pxz_tree.hip), also where the per-level grids apply
 	int wpb;                // PXZ_WPB: waves per block of the persistent kernels (0: default)
 	int chunk_lg;           // PXZ_CHUNK_LG: log2 of the ticket run length of shrink32_kernel (-1: default)
+	int cus;                // PXZ_CUS: every grid is sized as for a chip of at most this many CUs (0: the device's count); never raises it
 };
 const Knobs &knobs();
 

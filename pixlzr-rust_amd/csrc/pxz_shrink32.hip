@@ -1211,6 +1211,7 @@ hipError_t launch_fast32_16(const ShrinkArgs &a, ShrinkArgs &ga, uint32_t channe
 		fa.tile_dw = (4u * kPD32 + 2u * kRS32 + 3u) & ~3u;
 		uint32_t wa = (kLds - fa.tab_dw * 4u - kTail) / (fa.tile_dw * 4u);
 		if (wa > 16u) wa = 16u;
+		if (const uint32_t v = (uint32_t)knobs().wpb; v >= 1 && v < wa) wa = v;
 		const uint32_t lds_a = fa.tab_dw * 4u + wa * fa.tile_dw * 4u + kTail;
 		if (a.mode == 1) {
 			auto k = shrink32a_kernel<1>;

@@ -648,6 +648,8 @@ const Knobs &knobs()
 		v.wpb = e ? atoi(e) : 0;
 		e = getenv("PXZ_CHUNK_LG");
 		v.chunk_lg = e ? (atoi(e) & 15) : -1;
+		e = getenv("PXZ_CUS");
+		v.cus = e ? atoi(e) : 0;
 		return v;
 	}();
 	return k;
