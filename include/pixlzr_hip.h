@@ -663,6 +663,77 @@ int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const s
                              uint32_t n_images, const pxz_window *windows, uint32_t n_windows, uint32_t channels,
                              const pxz_params *params, uint8_t *out_base, uint64_t out_bytes, uint32_t *window_flags);
 
+/* ---- decode at reduced scale: images and windows at 1/2^k from the stored tiles ---------------- */
+
+/* A .pixlzr file is a level-of-detail format; the calls above rebuild every tile at its full size, and both callers named
+ * above want fewer pixels than the file holds: the viewer a zoomed-out viewport, the data loader a thumbnail or a small crop.
+ * The reference has the semantics already: Pixlzr::expand (pixlzr.rs:77-122) resizes each block to whatever the struct's public
+ * width, height, block_width and block_height say, through PixlzrBlock::resize (block.rs:273-334), which takes any source and
+ * target size.  With s = 2^scale_log2: set block_width /= s, block_height /= s, width = ceil(width/s), height = ceil(height/s)
+ * on an opened file, and expand(filter).to_image() is the image these calls return.
+ *   - s must divide block_w and block_h (PXZ_ERR_INVALID_ARG otherwise);
+ *   - a tile whose full place is fw x fh at (x0, y0) is resized to ceil(fw/s) x ceil(fh/s) and written at (x0/s, y0/s); the
+ *     scaled image is ceil(W/s) x ceil(H/s); the tile grid, and so pxz_varied_layout and pxz_window_layout, are unchanged;
+ *   - the resize is PixlzrBlock::resize for ANY size pair: a clone when both sizes agree (bytes as they are), the Nearest pick,
+ *     or the horizontal then the vertical convolution pass with a u8 intermediate, RGBA premultiplied around them.  One flag,
+ *     target wider than stored || target higher than stored, picks the kernel of Triangle for BOTH axes (block.rs:301-304,
+ *     mod.rs:65-107): Hamming when nothing grows, Bilinear when any axis grows -- then also on the axis that shrinks;
+ *   - a stored size is impossible only when it is zero or exceeds the FULL place fw x fh; above the target it is ordinary.
+ *
+ * pxz_scaled_size: the scaled image's size (host only, like pxz_grid).  PXZ_ERR_INVALID_ARG for a null pointer, a zero size or
+ * block, scale_log2 > 31, or a scale that does not divide both block sides; PXZ_ERR_UNSUPPORTED as pxz_grid. */
+int pxz_scaled_size(uint32_t width, uint32_t height, uint32_t block_w, uint32_t block_h, uint32_t scale_log2, uint32_t *out_w,
+                    uint32_t *out_h);
+
+/* The axis table the scaled kernels use for in_size stored samples -> out_size (host only, beside pxz_axis_table, same
+ * outputs).  other_axis_grows: the tile's other axis grows, which sets PixlzrBlock::resize's flag for this one too; it matters
+ * only for Triangle on an axis that shrinks.  With other_axis_grows == 0 this is pxz_axis_table. */
+int pxz_scaled_axis_table(uint32_t in_size, uint32_t out_size, uint32_t filter, uint32_t other_axis_grows, int32_t *starts,
+                          int32_t *sizes, int16_t *coeffs, int32_t *window, int32_t *precision);
+
+/* LDS bytes of one wave's image in the scaled kernels for blocks of block_w x block_h decoded at scales up to
+ * 2^max_scale_log2 with `filter` (host only): two planes of a dword per block pixel, the staged windows of both axes -- sized
+ * by the taps the largest scale needs -- and a row of padding.  *lds_bytes is written whenever the arguments are valid;
+ * PXZ_ERR_UNSUPPORTED when the image, with the 8 KB of owners' first tiles beside it, exceeds the 160 KB of a block (the two
+ * calls below answer the same), or when block_w*block_h*channels exceeds 65536 bytes; PXZ_ERR_INVALID_ARG for a scale that
+ * does not divide the block.  Blocks up to 128x128 fit; there is no HBM form. */
+int pxz_expand_scaled_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t filter, uint32_t max_scale_log2,
+                                uint32_t *lds_bytes);
+
+/* pxz_expand_varied_frames_device at reduced scale: image i of the batch is written at 1/2^scale_log2[i] (a HOST array of
+ * n_images entries).  descs[i].width and .height are the FILE's, so the tiles are pxz_varied_layout's; pitch_bytes and
+ * offset_bytes describe the SCALED output, pitch_bytes >= ceil(width/s)*channels.  Otherwise the call behaves as
+ * pxz_expand_varied_frames_device: validation on the host before any launch with its codes and texts ("image i"), bytes that
+ * belong to no image are not written, flags as there, one launch whatever n_images.  With every scale 0 the output equals that
+ * call's byte for byte.  A wave's image beyond LDS (pxz_expand_scaled_lds_bytes) is PXZ_ERR_UNSUPPORTED. */
+int pxz_expand_varied_scaled_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                           const pxz_params *params, const uint32_t *scale_log2, const uint32_t *d_tile_w,
+                                           const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_image_flags);
+
+/* pxz_expand_windows_device at reduced scale: window k is written at 1/2^scale_log2[k] (a HOST array of n_windows entries).
+ * The windows are the SAME structs, in full-resolution pixels, that pxz_window_layout and pxz_decode_windows_device took, so
+ * the reader is used unchanged.  With s = 2^scale_log2[k]: x and y must be multiples of s, x+width a multiple of s or the
+ * image's width, y+height a multiple of s or the image's height (PXZ_ERR_INVALID_ARG, "window k").  The output is
+ * ceil((x+width)/s) - x/s pixels wide and ceil((y+height)/s) - y/s high -- pitch_bytes is checked against that -- and equals
+ * that rectangle, from (x/s, y/s) on, of the scaled whole image; no byte outside it is written.  Flags, errors and limits as
+ * pxz_expand_windows_device and pxz_expand_scaled_lds_bytes. */
+int pxz_expand_windows_scaled_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows,
+                                     uint32_t n_windows, uint32_t channels, const pxz_params *params, const uint32_t *scale_log2,
+                                     const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_base,
+                                     uint32_t *d_window_flags);
+
+/* The host forms: pxz_decode_varied_files and pxz_decode_windows_files with a scale per image / per window (host arrays).
+ * descs[i] carries the FILE's width and height and the pitch and offset of the SCALED image in out_base; a window its
+ * full-resolution rectangle and the pitch and offset of its scaled crop.  Composition through the calls above and the
+ * unchanged readers; only the scaled bytes come down.  Errors, flags and the all-or-nothing rules are those of the twins. */
+int pxz_decode_varied_files_scaled(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
+                                   uint32_t n_images, uint32_t channels, const pxz_params *params, const uint32_t *scale_log2,
+                                   uint8_t *out_base, uint32_t *image_flags);
+int pxz_decode_windows_files_scaled(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs,
+                                    uint32_t n_images, const pxz_window *windows, uint32_t n_windows, uint32_t channels,
+                                    const pxz_params *params, const uint32_t *scale_log2, uint8_t *out_base, uint64_t out_bytes,
+                                    uint32_t *window_flags);
+
 /* ---- rate and distortion: what a factor costs and what it loses ---------------- */
 
 /* The squared error of stored tiles against the frames they were shrunk from.  Nothing in the reference computes it:

@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "pxz_retile_varied_ladder_frames_device", "pxz_retile_ladder_lds_bytes",
     "pxz_retile_distortion_varied_device", "pxz_retile_distortion_lds_bytes", "pxz_rate_distortion_retile_files",
     "pxz_retile_varied_files_fit", "pxz_retile_varied_files_fit_tiles",
+    "pxz_scaled_size", "pxz_scaled_axis_table", "pxz_expand_scaled_lds_bytes", "pxz_expand_varied_scaled_frames_device",
+    "pxz_expand_windows_scaled_device", "pxz_decode_varied_files_scaled", "pxz_decode_windows_files_scaled",
 ]
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
@@ -299,6 +301,21 @@ def load_library():
     L.pxz_synth_frames_device.argtypes = [vp, C.POINTER(Frames), vp, u32, u32]
     L.pxz_axis_table.restype = C.c_int
     L.pxz_axis_table.argtypes = [u32] * 3 + [vp] * 3 + [C.POINTER(C.c_int32)] * 2
+    if hasattr(L, "pxz_scaled_size"):  # (a build of an earlier commit named by PXZ_LIB lacks the scaled decode)
+        L.pxz_scaled_size.restype = C.c_int
+        L.pxz_scaled_size.argtypes = [u32] * 5 + [C.POINTER(u32)] * 2
+        L.pxz_scaled_axis_table.restype = C.c_int
+        L.pxz_scaled_axis_table.argtypes = [u32] * 4 + [vp] * 3 + [C.POINTER(C.c_int32)] * 2
+        L.pxz_expand_scaled_lds_bytes.restype = C.c_int
+        L.pxz_expand_scaled_lds_bytes.argtypes = [u32] * 5 + [C.POINTER(u32)]
+        L.pxz_expand_varied_scaled_frames_device.restype = C.c_int
+        L.pxz_expand_varied_scaled_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params)] + [vp] * 6
+        L.pxz_expand_windows_scaled_device.restype = C.c_int
+        L.pxz_expand_windows_scaled_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params)] + [vp] * 6
+        L.pxz_decode_varied_files_scaled.restype = C.c_int
+        L.pxz_decode_varied_files_scaled.argtypes = [vp, vp, vp, vp, u32, u32, C.POINTER(Params), vp, vp, vp]
+        L.pxz_decode_windows_files_scaled.restype = C.c_int
+        L.pxz_decode_windows_files_scaled.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp, C.c_uint64, vp]
     L.pxz_enable_timing.restype = C.c_int
     L.pxz_enable_timing.argtypes = [vp, C.c_int]
     L.pxz_last_first_kernel_ms.restype = C.c_int
@@ -345,6 +362,53 @@ def window_layout(sizes, windows, bw, bh):
     if rc != 0:
         raise PxzError(rc)
     return out
+
+
+def scaled_size(width, height, bw, bh, scale_log2):
+    """pxz_scaled_size: the size (width, height) of an image decoded at 1/2^scale_log2; the scale must divide the block."""
+    w, h = C.c_uint32(), C.c_uint32()
+    rc = load_library().pxz_scaled_size(width, height, bw, bh, scale_log2, C.byref(w), C.byref(h))
+    if rc != 0:
+        raise PxzError(rc)
+    return w.value, h.value
+
+
+def scaled_window_size(window, scale_log2):
+    """the output size (width, height) of the full-resolution window (image, x, y, width, height, ...) at 1/2^scale_log2"""
+    _, x, y, w, h = window[:5]
+    s = 1 << scale_log2
+    return -(-(x + w) // s) - x // s, -(-(y + h) // s) - y // s
+
+
+def scaled_axis_table(in_size, out_size, filt, other_axis_grows=False):
+    """pxz_scaled_axis_table: (starts, sizes, coeffs[out, window], precision) of the table the scaled kernels use for an axis
+    of in_size stored samples resized to out_size; other_axis_grows sets PixlzrBlock::resize's flag for this axis too."""
+    L = load_library()
+    window, prec = C.c_int32(), C.c_int32()
+    rc = L.pxz_scaled_axis_table(in_size, out_size, filt, int(other_axis_grows), None, None, None, C.byref(window), C.byref(prec))
+    if rc != 0:
+        raise PxzError(rc)
+    starts = np.zeros(out_size, np.int32)
+    sizes = np.zeros(out_size, np.int32)
+    k = np.zeros((out_size, window.value), np.int16)
+    L.pxz_scaled_axis_table(in_size, out_size, filt, int(other_axis_grows), _p(starts), _p(sizes), _p(k), C.byref(window), C.byref(prec))
+    return starts, sizes, k, prec.value
+
+
+def expand_scaled_lds_bytes(bw, bh, channels, filt, max_scale_log2):
+    """pxz_expand_scaled_lds_bytes: LDS bytes of one wave's image of the scaled kernels (host only).  Raises PxzError (with
+    .lds_bytes) when it does not fit."""
+    out = C.c_uint32(0)
+    rc = load_library().pxz_expand_scaled_lds_bytes(bw, bh, channels, filt, max_scale_log2, C.byref(out))
+    if rc != 0:
+        err = PxzError(rc)
+        err.lds_bytes = out.value
+        raise err
+    return out.value
+
+
+def _u32s(values):
+    return (C.c_uint32 * max(len(values), 1))(*[int(v) for v in values])
 
 
 def reshrink_lds_bytes(bw, bh, mode, expand_filter):
@@ -1198,6 +1262,103 @@ class Handle:
                                               channels, C.byref(pd), _p(out), out.size, _p(flags))
         if own:
             result = [out[w[6]:w[6] + w[3] * w[4] * channels].reshape(w[4], w[3], channels) for w in windows]
+        else:
+            result = out
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.flags, err.crops = flags[:k], result
+            raise err
+        return result, flags[:k]
+
+    # ---- decode at reduced scale ----
+    def expand_varied_scaled_frames_device(self, descs, channels, bw, bh, filt, scales, ow, oh, slots, out, image_flags=None):
+        """pxz_expand_varied_scaled_frames_device: expand_varied_frames_device with image i written at 1/2^scales[i].  descs =
+        [(file width, file height, pitch_bytes, offset_bytes), ...]: pitch and offset describe the SCALED image.  Returns out."""
+        geoms = [tuple(d) for d in descs]
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_expand_varied_scaled_frames_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), C.cast(_u32s(scales), C.c_void_p),
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(out.data_ptr()),
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        return out
+
+    def expand_windows_scaled_device(self, sizes, windows, channels, bw, bh, filt, scales, ow, oh, slots, out, window_flags=None):
+        """pxz_expand_windows_scaled_device: expand_windows_device with window k written at 1/2^scales[k].  The windows are the
+        full-resolution rectangles of window_layout; pitch and offset describe the SCALED crop.  Returns out."""
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_expand_windows_scaled_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), C.cast(window_descs(windows), C.c_void_p), len(windows),
+            channels, C.byref(pd), C.cast(_u32s(scales), C.c_void_p), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()), C.c_void_p(out.data_ptr()),
+            C.c_void_p(window_flags.data_ptr()) if window_flags is not None else None))
+        return out
+
+    def decode_varied_files_scaled(self, files, channels, bw, bh, filt, scales, sizes=None, out=None, descs=None):
+        """pxz_decode_varied_files_scaled: decode_varied_files with image i decoded at 1/2^scales[i] -> a list of (ceil(height/s),
+        ceil(width/s), channels) images.  sizes (the FILES') defaults to what the headers say; with out and descs = [(file width,
+        file height, pitch_bytes, offset_bytes), ...] the scaled images are written there instead.  Returns (images | out, flags);
+        raises PxzError (with .flags) when a file is refused or malformed."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        if sizes is None and descs is None:
+            sizes = [file_header(f)[:2] for f in files]
+        own = descs is None
+        if own:
+            descs, shapes, at = [], [], 0
+            for (w, h), k in zip(sizes, scales):
+                sw, sh = -(-w // (1 << k)), -(-h // (1 << k))
+                descs.append((w, h, sw * channels, at))
+                shapes.append((sw, sh))
+                at += sw * sh * channels
+            out = np.zeros(max(at, 1), np.uint8)
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        flags = np.zeros(max(n, 1), np.uint32)
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        rc = self._L.pxz_decode_varied_files_scaled(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p),
+                                                    C.cast(image_descs(descs), C.c_void_p), n, channels, C.byref(pd),
+                                                    C.cast(_u32s(scales), C.c_void_p), _p(out), _p(flags))
+        if own:
+            result = [out[d[3]:d[3] + sw * sh * channels].reshape(sh, sw, channels) for d, (sw, sh) in zip(descs, shapes)]
+        else:
+            result = out
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.flags, err.images = flags[:n], result
+            raise err
+        return result, flags[:n]
+
+    def decode_windows_files_scaled(self, files, windows, channels, bw, bh, filt, scales, sizes=None, out=None):
+        """pxz_decode_windows_files_scaled: decode_windows_files with window k decoded at 1/2^scales[k]; windows = [(image, x, y,
+        width, height), ...] in full-resolution pixels -> a list of scaled crops.  With out (a numpy uint8 buffer) the windows
+        carry the pitch_bytes and offset_bytes of their scaled crops too.  Returns (crops | out, flags uint32[k]); raises PxzError
+        (with .flags, .crops) when a file is refused or a window comes back flagged."""
+        n, k = len(files), len(windows)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        if sizes is None:
+            sizes = [file_header(f)[:2] for f in files]
+        own = out is None
+        shapes = [scaled_window_size(w, s) for w, s in zip(windows, scales)]
+        if own:
+            full, at = [], 0
+            for (i, x, y, w, h), (sw, sh) in zip(windows, shapes):
+                full.append((i, x, y, w, h, sw * channels, at))
+                at += sw * sh * channels
+            windows = full
+            out = np.zeros(max(at, 1), np.uint8)
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        flags = np.zeros(max(k, 1), np.uint32)
+        pd = Params(bw, bh, 0, filt, 0.0, 0)
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        rc = self._L.pxz_decode_windows_files_scaled(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p),
+                                                     C.cast(image_descs(geoms), C.c_void_p), n, C.cast(window_descs(windows), C.c_void_p), k,
+                                                     channels, C.byref(pd), C.cast(_u32s(scales), C.c_void_p), _p(out), out.size, _p(flags))
+        if own:
+            result = [out[w[6]:w[6] + sw * sh * channels].reshape(sh, sw, channels) for w, (sw, sh) in zip(windows, shapes)]
         else:
             result = out
         if rc != 0:

@@ -3465,3 +3465,233 @@ int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32
 }
 
 }  // extern "C"
+
+// ---- decode at reduced scale (pxz_scaled_expand.hip) --------------------------------------------------------------------
+namespace pxz_runtime {
+
+// one owner's scale: 2^shift must divide both block sides (who: "image" or "window")
+int scaled_check_shift(pxz_handle *h, const char *who, uint32_t index, uint32_t shift, uint32_t bw, uint32_t bh)
+{
+	if (shift > 31u || (bw & ((1u << shift) - 1u)) != 0u || (bh & ((1u << shift) - 1u)) != 0u)
+		return fail(h, PXZ_ERR_INVALID_ARG, "%s %u: the scale 2^%u does not divide the %ux%u block", who, index, shift, bw, bh);
+	return PXZ_OK;
+}
+
+// a window's corners lie on multiples of its scale, or on the image's right and lower edge
+int scaled_check_window(pxz_handle *h, uint32_t index, const pxz_window &w, uint32_t img_w, uint32_t img_h, uint32_t shift)
+{
+	const uint32_t low = (1u << shift) - 1u;
+	const uint32_t x1 = w.x + w.width, y1 = w.y + w.height;
+	if ((w.x & low) != 0u || (w.y & low) != 0u || ((x1 & low) != 0u && x1 != img_w) || ((y1 & low) != 0u && y1 != img_h))
+		return fail(h, PXZ_ERR_INVALID_ARG, "window %u: the rectangle %ux%u at (%u, %u) does not lie on multiples of the scale 2^%u (or on the image's edge)",
+		            index, w.width, w.height, w.x, w.y, shift);
+	return PXZ_OK;
+}
+
+}  // namespace pxz_runtime
+
+namespace {
+
+// the (target size, largest stored size) pairs of one owner's tiles: the block sides and the image's edges at the owner's scale
+void scaled_add_targets(std::map<uint32_t, uint32_t> *most, uint32_t bw, uint32_t bh, uint32_t edge_w, uint32_t edge_h, uint32_t shift)
+{
+	for (uint32_t full : {bw, bh, edge_w, edge_h}) {
+		uint32_t &m = (*most)[scaled_extent(full, shift)];
+		if (full > m) m = full;
+	}
+}
+
+// dwords of the staged windows of one axis for a call (scaled_window_dw over the block's longer side)
+uint32_t scaled_call_window_dw(uint32_t bw, uint32_t bh, uint32_t filter, uint32_t max_shift)
+{
+	return pxz::scaled_window_dw(bw > bh ? bw : bh, pxz::filter_support(filter), max_shift);
+}
+
+// The tables of a scaled call, cached on the handle under (filter, pairs), and with them everything of ScaledExpandArgs that
+// does not depend on the owners.  A wave's image beyond LDS is refused here.
+int put_scaled_tables(pxz_handle *h, const pxz_params &p, uint32_t channels, const std::map<uint32_t, uint32_t> &most, uint32_t max_shift,
+                      pxz::ScaledExpandArgs *a)
+{
+	a->bw = p.block_w;
+	a->bh = p.block_h;
+	a->slot_bytes = p.block_w * p.block_h * channels;
+	a->filter = p.filter;
+	a->win_dw = scaled_call_window_dw(p.block_w, p.block_h, p.filter, max_shift);
+	a->tile_dw = pxz::scaled_tile_dw(a->bw, a->bh, a->win_dw);
+	if (varied_image_beyond_lds(a->tile_dw))
+		return fail(h, PXZ_ERR_UNSUPPORTED, "a wave keeps a %ux%u tile of %u channels and its windows in LDS: %llu bytes exceed what a block has", a->bw,
+		            a->bh, channels, (unsigned long long)a->tile_dw * 4u);
+	std::vector<uint32_t> flat;
+	for (const auto &tm : most) {
+		flat.push_back(tm.first);
+		flat.push_back(tm.second);
+	}
+	const ScaledExpandTables *st = nullptr;
+	const int rc = cached_tables(h, h->scaled_tables, std::make_pair(p.filter, flat), kTableCacheBound, [&](ScaledExpandTables &t) {
+		std::vector<uint32_t> targets, stored;
+		for (const auto &tm : most) {
+			targets.push_back(tm.first);
+			stored.push_back(tm.second);
+		}
+		pxz::ScaledExpandTableSet s;
+		if (!pxz::build_scaled_expand_tables(targets, stored, p.filter, &s)) return fail(h, PXZ_ERR_INVALID_ARG, "unknown filter %u", p.filter);
+		t.stride = s.stride;
+		t.max_win_dw = s.max_win_dw;
+		return upload_tables(h, {{s.slot, &t.d_slot}, {s.dir, &t.d_dir}, {s.mixed, &t.d_mixed}, {s.starts, &t.d_starts}, {s.sizes, &t.d_sizes},
+		                         {s.coeffs, &t.d_coeffs}}, &t.mem);
+	}, &st);
+	if (rc != PXZ_OK) return rc;
+	// (the bound of scaled_window_dw holds for every pair a tile of the call can have; a set beyond it would overrun the staging)
+	if (st->max_win_dw > a->win_dw)
+		return fail(h, PXZ_ERR_INTERNAL, "staged windows of %u dwords exceed the %u the layout has", st->max_win_dw, a->win_dw);
+	a->slot = st->d_slot;
+	a->dir = st->d_dir;
+	a->mixed = st->d_mixed;
+	a->stride = st->stride;
+	a->starts = st->d_starts;
+	a->sizes = st->d_sizes;
+	a->coeffs = st->d_coeffs;
+	return PXZ_OK;
+}
+
+// the per-owner table -> handle scratch, as varied_upload sends the per-image table: one copy
+template <class Entry>
+int scaled_upload(pxz_handle *h, const std::vector<Entry> &entries, const Entry **d_entries)
+{
+	const size_t bytes = entries.size() * sizeof(Entry);
+	int rc = ensure(h, h->scaled, bytes);
+	if (rc != PXZ_OK) return rc;
+	PXZ_HIP(h, h->scaled_table.send(entries.data(), bytes, h->scaled.ptr, h->stream));
+	*d_entries = (const Entry *)h->scaled.ptr;
+	return PXZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pxz_scaled_size(uint32_t width, uint32_t height, uint32_t block_w, uint32_t block_h, uint32_t scale_log2, uint32_t *out_w, uint32_t *out_h)
+{
+	if (!out_w || !out_h || width == 0 || height == 0 || block_w == 0 || block_h == 0) return PXZ_ERR_INVALID_ARG;
+	if (width > kMaxImageSide || height > kMaxImageSide) return PXZ_ERR_UNSUPPORTED;
+	const int rc = scaled_check_shift(nullptr, "image", 0, scale_log2, block_w, block_h);
+	if (rc != PXZ_OK) return rc;
+	*out_w = scaled_extent(width, scale_log2);
+	*out_h = scaled_extent(height, scale_log2);
+	return PXZ_OK;
+}
+
+int pxz_scaled_axis_table(uint32_t in_size, uint32_t out_size, uint32_t filter, uint32_t other_axis_grows, int32_t *starts, int32_t *sizes,
+                          int16_t *coeffs, int32_t *window, int32_t *precision)
+{
+	if (in_size == 0 || out_size == 0 || filter > 4) return PXZ_ERR_INVALID_ARG;
+	pxz::AxisWindows w;
+	if (!pxz::build_axis(in_size, out_size, filter, &w, out_size > in_size || other_axis_grows != 0u)) return PXZ_ERR_INVALID_ARG;
+	if (window) *window = w.window;
+	if (precision) *precision = w.precision;
+	if (starts) std::memcpy(starts, w.starts.data(), sizeof(int32_t) * out_size);
+	if (sizes) std::memcpy(sizes, w.sizes.data(), sizeof(int32_t) * out_size);
+	if (coeffs && !w.coeffs.empty()) std::memcpy(coeffs, w.coeffs.data(), sizeof(int16_t) * w.coeffs.size());
+	return PXZ_OK;
+}
+
+int pxz_expand_scaled_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t filter, uint32_t max_scale_log2, uint32_t *lds_bytes)
+{
+	if (!lds_bytes || block_w == 0 || block_h == 0 || filter > 4 || (channels != 3 && channels != 4)) return PXZ_ERR_INVALID_ARG;
+	const int rc = scaled_check_shift(nullptr, "image", 0, max_scale_log2, block_w, block_h);
+	if (rc != PXZ_OK) return rc;
+	const uint32_t tile_dw = pxz::scaled_tile_dw(block_w, block_h, scaled_call_window_dw(block_w, block_h, filter, max_scale_log2));
+	*lds_bytes = tile_dw > 0x3fffffffu ? 0xffffffffu : tile_dw * 4u;
+	if ((uint64_t)block_w * block_h * channels > kVariedMaxTileBytes || varied_image_beyond_lds(tile_dw)) return PXZ_ERR_UNSUPPORTED;
+	return PXZ_OK;
+}
+
+int pxz_expand_varied_scaled_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
+                                           const pxz_params *params, const uint32_t *scale_log2, const uint32_t *d_tile_w,
+                                           const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_base) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (!scale_log2) return fail(h, PXZ_ERR_INVALID_ARG, "null scales");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	// (the geometry is the files'; the pitch rule is held against the scaled rows below)
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, 0, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	std::vector<pxz::ScaledImage> entries(n_images);
+	std::map<uint32_t, uint32_t> most;
+	uint32_t max_shift = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		const uint32_t k = scale_log2[i];
+		if ((rc = scaled_check_shift(h, "image", i, k, p.block_w, p.block_h)) != PXZ_OK) return rc;
+		const pxz::VariedImage &im = images[i];
+		if ((uint64_t)im.pitch < (uint64_t)scaled_extent(im.width, k) * channels) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: pitch smaller than a row", i);
+		entries[i] = pxz::ScaledImage{im.offset, im.tile0, im.pitch, im.cols, im.rows, im.edge_w, im.edge_h, k, 0u};
+		scaled_add_targets(&most, p.block_w, p.block_h, im.edge_w, im.edge_h, k);
+		if (k > max_shift) max_shift = k;
+	}
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::ScaledExpandArgs a{};
+	if ((rc = put_scaled_tables(h, p, channels, most, max_shift, &a)) != PXZ_OK) return rc;
+	a.n_owners = n_images;
+	a.n_tiles = varied_n_tiles(images);
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.base = d_base;
+	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
+	a.flags = d_image_flags;
+	if ((rc = scaled_upload(h, entries, &a.images)) != PXZ_OK) return rc;
+	PXZ_HIP(h, pxz::launch_scaled_expand(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_expand_windows_scaled_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows,
+                                     uint32_t channels, const pxz_params *params, const uint32_t *scale_log2, const uint32_t *d_tile_w,
+                                     const uint32_t *d_tile_h, const uint8_t *d_slots, uint8_t *d_base, uint32_t *d_window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_tile_w || !d_tile_h || !d_slots || !d_base) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (!scale_log2) return fail(h, PXZ_ERR_INVALID_ARG, "null scales");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	// (the rectangles are full-resolution ones; the pitch rule is held against the scaled rows below)
+	std::vector<pxz::WindowEntry> plan;
+	if ((rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, 0, &plan, nullptr, nullptr)) != PXZ_OK) return rc;
+	std::vector<pxz::ScaledWindow> entries(n_windows);
+	std::map<uint32_t, uint32_t> most;
+	uint32_t max_shift = 0;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const uint32_t sh = scale_log2[k];
+		const pxz::WindowEntry &e = plan[k];
+		if ((rc = scaled_check_shift(h, "window", k, sh, p.block_w, p.block_h)) != PXZ_OK) return rc;
+		if ((rc = scaled_check_window(h, k, windows[k], e.img_w, e.img_h, sh)) != PXZ_OK) return rc;
+		const uint32_t x0 = e.x >> sh, y0 = e.y >> sh, x1 = scaled_extent(e.x + e.w, sh), y1 = scaled_extent(e.y + e.h, sh);
+		if ((uint64_t)e.pitch < (uint64_t)(x1 - x0) * channels) return fail(h, PXZ_ERR_INVALID_ARG, "window %u: pitch smaller than a row", k);
+		entries[k] = pxz::ScaledWindow{e.offset, e.tile0, e.pitch, x0, y0, x1, y1, e.c0, e.r0, e.ccols, e.cols, e.rows, e.edge_w, e.edge_h, sh};
+		scaled_add_targets(&most, p.block_w, p.block_h, e.edge_w, e.edge_h, sh);
+		if (sh > max_shift) max_shift = sh;
+	}
+	PXZ_HIP(h, hipSetDevice(h->device));
+	pxz::ScaledExpandArgs a{};
+	if ((rc = put_scaled_tables(h, p, channels, most, max_shift, &a)) != PXZ_OK) return rc;
+	a.n_owners = n_windows;
+	a.n_tiles = window_n_tiles(plan);
+	a.tile_w = d_tile_w;
+	a.tile_h = d_tile_h;
+	a.slots = d_slots;
+	a.base = d_base;
+	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_window_flags, n_windows)) != PXZ_OK) return rc;
+	a.flags = d_window_flags;
+	if ((rc = scaled_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
+	PXZ_HIP(h, pxz::launch_scaled_expand(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+}  // extern "C"

@@ -1002,4 +1002,132 @@ int pxz_decode_windows_files(pxz_handle *h, const uint8_t *const *files, const s
 	return PXZ_OK;
 }
 
+// ---- decode at reduced scale: the two forms above with a scale per owner.  The descriptors (windows) the caller passed keep
+// the FILE's geometry; `out` are the same owners with their SCALED width and height at the caller's pitch and offset, which is
+// what pack_owners and copy_out_owners lay out and copy.
+
+int pxz_decode_varied_files_scaled(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
+                                   uint32_t channels, const pxz_params *params, const uint32_t *scale_log2, uint8_t *out_base, uint32_t *image_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !out_base || !scale_log2) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::VariedImage> images;
+	if ((rc = varied_plan(h, descs, n_images, p.block_w, p.block_h, 0, 0, &images, nullptr, nullptr)) != PXZ_OK) return rc;
+	std::vector<pxz_image_desc> out(descs, descs + n_images);
+	for (uint32_t i = 0; i < n_images; ++i) {
+		if ((rc = scaled_check_shift(h, "image", i, scale_log2[i], p.block_w, p.block_h)) != PXZ_OK) return rc;
+		out[i].width = scaled_extent(descs[i].width, scale_log2[i]);
+		out[i].height = scaled_extent(descs[i].height, scale_log2[i]);
+		if ((uint64_t)out[i].pitch_bytes < (uint64_t)out[i].width * channels) return fail(h, PXZ_ERR_INVALID_ARG, "image %u: pitch smaller than a row", i);
+	}
+	uint64_t file_bytes = 0;
+	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "batch", &file_bytes)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// device side: the files back to back behind their offsets; the scaled images tightly packed
+	std::vector<pxz_image_desc> packed(out);
+	const uint64_t img_bytes = pack_owners(&packed, channels);
+	std::vector<pxz_image_desc> dev(descs, descs + n_images);  // the files' geometry, the packed images' places
+	for (uint32_t i = 0; i < n_images; ++i) {
+		dev[i].pitch_bytes = packed[i].pitch_bytes;
+		dev[i].offset_bytes = packed[i].offset_bytes;
+	}
+	const uint32_t n_tiles = varied_n_tiles(images);
+	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
+	const uint64_t flags_at = TileSet::bytes(n_tiles, slot);
+	SentFiles sent;
+	if ((rc = send_files(h, h->varied_files, sent_bytes(n_images, file_bytes), files, lens, n_images, file_bytes, img_bytes, &sent)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_out, flags_at + 8ull * n_images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->varied_in, img_bytes)) != PXZ_OK) return rc;
+	uint8_t *d_out = (uint8_t *)h->varied_out.ptr, *d_img = (uint8_t *)h->varied_in.ptr;
+	const TileSet m(d_out, n_tiles);
+	PXZ_HIP(h, hipMemsetAsync(m.slots, 0, (size_t)n_tiles * slot, h->stream));
+	PXZ_HIP(h, hipMemsetAsync(d_img, 0, img_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
+	uint32_t *d_flags = (uint32_t *)(d_out + flags_at);
+	if ((rc = pxz_decode_varied_frames_device(h, dev.data(), n_images, channels, &p, sent.d_files, sent.d_offsets, m.value, m.w, m.h, m.slots,
+	                                          d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_expand_varied_scaled_frames_device(h, dev.data(), n_images, channels, &p, scale_log2, m.w, m.h, m.slots, d_img,
+	                                                 d_flags + n_images)) != PXZ_OK)
+		return rc;
+	std::vector<uint32_t> flags(2u * (size_t)n_images);
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
+	PXZ_HIP(h, hipMemcpyAsync(sent.stage.data(), d_img, img_bytes, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	uint32_t first_flags = 0;
+	const uint32_t first_bad = copy_out_owners(out.data(), packed.data(), n_images, channels, sent.stage.data(), out_base, flags.data(), image_flags,
+	                                           &first_flags);
+	if (first_bad != n_images)
+		return fail(h, PXZ_ERR_INVALID_ARG, "image %u: malformed .pixlzr file or record (flags %u); the other images are complete", first_bad,
+		            first_flags);
+	return PXZ_OK;
+}
+
+int pxz_decode_windows_files_scaled(pxz_handle *h, const uint8_t *const *files, const size_t *lens, const pxz_image_desc *descs, uint32_t n_images,
+                                    const pxz_window *windows, uint32_t n_windows, uint32_t channels, const pxz_params *params,
+                                    const uint32_t *scale_log2, uint8_t *out_base, uint64_t out_bytes, uint32_t *window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !out_base || !scale_log2) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	const pxz_params p = decode_side_params(params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	std::vector<pxz::WindowEntry> entries;
+	if ((rc = window_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, 0, &entries, nullptr, nullptr)) != PXZ_OK) return rc;
+	std::vector<pxz_window> out(windows, windows + n_windows);  // the scaled crops at the caller's places
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const pxz_window &g = windows[k];
+		const uint32_t sh = scale_log2[k];
+		if ((rc = scaled_check_shift(h, "window", k, sh, p.block_w, p.block_h)) != PXZ_OK) return rc;
+		if ((rc = scaled_check_window(h, k, g, entries[k].img_w, entries[k].img_h, sh)) != PXZ_OK) return rc;
+		out[k].width = scaled_extent(g.x + g.width, sh) - (g.x >> sh);
+		out[k].height = scaled_extent(g.y + g.height, sh) - (g.y >> sh);
+		if ((uint64_t)g.pitch_bytes < (uint64_t)out[k].width * channels) return fail(h, PXZ_ERR_INVALID_ARG, "window %u: pitch smaller than a row", k);
+		if (g.offset_bytes > out_bytes ||
+		    (uint64_t)(out[k].height - 1u) * g.pitch_bytes + (uint64_t)out[k].width * channels > out_bytes - g.offset_bytes)
+			return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "window %u: its output ends behind the %llu bytes of the buffer", k, (unsigned long long)out_bytes);
+	}
+	uint64_t file_bytes = 0;
+	if ((rc = check_file_headers(h, files, lens, descs, n_images, channels, p, "call", &file_bytes)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// device side, one buffer, as pxz_decode_windows_files: files | covered tiles | the scaled crops tightly packed, the flags
+	std::vector<pxz_window> packed(out);
+	const uint64_t crop_bytes = pack_owners(&packed, channels);
+	std::vector<pxz_window> dev(windows, windows + n_windows);  // the full-resolution rectangles, the packed crops' places
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		dev[k].pitch_bytes = packed[k].pitch_bytes;
+		dev[k].offset_bytes = packed[k].offset_bytes;
+	}
+	const uint32_t n_tiles = window_n_tiles(entries);
+	const uint64_t slot = (uint64_t)p.block_w * p.block_h * channels;
+	const uint64_t tiles_at = up256(sent_bytes(n_images, file_bytes)), crops_at = tiles_at + up256(TileSet::bytes(n_tiles, slot));
+	const uint64_t flags_at = crops_at + crop_bytes, down_bytes = crop_bytes + 8ull * n_windows;
+	SentFiles sent;
+	if ((rc = send_files(h, h->window_host, flags_at + 8ull * n_windows, files, lens, n_images, file_bytes, down_bytes, &sent)) != PXZ_OK) return rc;
+	uint8_t *d = (uint8_t *)h->window_host.ptr;
+	PXZ_HIP(h, hipMemsetAsync(d + crops_at, 0, down_bytes, h->stream));  // (the place of a tile that cannot be expanded stays zero)
+	const TileSet m(d + tiles_at, n_tiles);
+	uint32_t *d_flags = (uint32_t *)(d + flags_at);
+	if ((rc = pxz_decode_windows_device(h, descs, n_images, dev.data(), n_windows, channels, &p, sent.d_files, sent.d_offsets, m.value, m.w, m.h, m.slots,
+	                                    d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_expand_windows_scaled_device(h, descs, n_images, dev.data(), n_windows, channels, &p, scale_log2, m.w, m.h, m.slots, d + crops_at,
+	                                           d_flags + n_windows)) != PXZ_OK)
+		return rc;
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));  // the files have left the staging buffer
+	PXZ_HIP(h, hipMemcpyAsync(sent.stage.data(), d + crops_at, down_bytes, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	const uint32_t *flags = reinterpret_cast<const uint32_t *>(sent.stage.data() + crop_bytes);
+	uint32_t first_flags = 0;
+	const uint32_t first_bad = copy_out_owners(out.data(), packed.data(), n_windows, channels, sent.stage.data(), out_base, flags, window_flags,
+	                                           &first_flags);
+	if (first_bad != n_windows)
+		return fail(h, PXZ_ERR_INVALID_ARG, "window %u: malformed .pixlzr file or record in what it reads of image %u (flags %u); the other windows are complete",
+		            first_bad, windows[first_bad].image, first_flags);
+	return PXZ_OK;
+}
+
 }  // extern "C"

@@ -726,6 +726,57 @@ struct WindowExpandArgs : TileResizeArgs {
 	uint32_t *window_flags;           // per window 1 for a covered tile whose stored size is invalid, or null
 };
 
+// Decode at reduced scale (pxz_expand_varied_scaled_frames_device, pxz_expand_windows_scaled_device; pxz_scaled_expand.hip):
+// the stored tiles of a flat tile space resized to ceil(full / 2^shift) on each axis and written at (x0, y0) >> shift, the
+// shift being the owner's (an image's, or a window's).
+// One axis table per (target size, stored size) pair the call can meet: dir[slot[target] * stride + stored], indexed as
+// VariedExpandTableSet's with the target in the place of the full size; `mixed` is the same directory for the axis that
+// SHRINKS while the other one grows (the upscale flag set on a down-scaling axis: another kernel for Triangle, the same
+// entry as dir's for the other filters).  Entries of stored == target (that axis is not resampled) are zero.
+struct ScaledTab {
+	uint32_t start_off;      // into starts[] / sizes[] (nearest: starts[] is the source index)
+	uint32_t coeff_off;      // into coeffs[]: target * window weights
+	uint16_t window;         // weights per output sample in coeffs[]
+	uint16_t precision;
+	uint16_t taps;           // the widest window of the table as built (clipped to the stored size)
+	uint16_t wdw;            // dwords of one staged window: 1 + ceil(taps / 2); Nearest: 1
+};
+// one image of a scaled varied call: its grid is the FILE's, offset and pitch describe the scaled output
+struct ScaledImage {
+	uint64_t offset;
+	uint32_t tile0, pitch;
+	uint32_t cols, rows, edge_w, edge_h;
+	uint32_t shift, pad;
+};
+// one window of a scaled windows call: the covered grid is the full-resolution rectangle's (pxz_window_layout), the rectangle
+// itself is kept in scaled pixels, [x0, x1) x [y0, y1) of the scaled image
+struct ScaledWindow {
+	uint64_t offset;
+	uint32_t tile0, pitch;
+	uint32_t x0, y0, x1, y1;
+	uint32_t c0, r0, ccols, cols, rows, edge_w, edge_h;
+	uint32_t shift;
+};
+struct ScaledExpandArgs {
+	uint32_t bw, bh, slot_bytes, filter;
+	const uint32_t *slot;
+	const ScaledTab *dir, *mixed;
+	uint32_t stride;
+	const uint16_t *starts, *sizes;
+	const int16_t *coeffs;
+	uint32_t win_dw;                  // dwords of the staged windows of one axis (scaled_window_dw, pxz_scaled_tile.h)
+	uint32_t tile_dw;                 // dwords of one wave's image (scaled_tile_dw)
+	uint32_t t0_dw;                   // (set by the launch) dwords of the owners' first tiles kept in LDS, 0: read from the table
+	uint32_t *status;                 // bit 0: a tile's stored size is 0 or exceeds its FULL place
+	uint32_t n_tiles, n_owners;
+	const uint32_t *tile_w, *tile_h;  // per tile: stored size
+	const uint8_t *slots;             // per tile slot_bytes, tile_w * tile_h * channels valid, tightly packed
+	const ScaledImage *images;        // scaled_expand_kernel's owners
+	const ScaledWindow *windows;      // scaled_window_expand_kernel's
+	uint8_t *base;                    // owner k at base + offset, pitch between rows
+	uint32_t *flags;                  // per owner 1 for a tile whose stored size is invalid, or null
+};
+
 struct SynthArgs {
 	uint8_t *dst;
 	uint64_t frame_stride;

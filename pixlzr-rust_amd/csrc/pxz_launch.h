@@ -30,6 +30,32 @@ uint32_t varied_expand_tile_dw(uint32_t bw, uint32_t bh, uint32_t wdw);
 // the LDS form's grid for n_tiles tiles of n_images images, one wave per tile: *t0_dw = dwords of the images' first tiles a
 // block keeps in LDS (0: more images than it holds); threads == 0: one wave's image does not fit
 LaunchGeom varied_expand_geom(uint32_t n_images, uint32_t n_tiles, uint32_t tile_dw, uint32_t n_cus, uint32_t *t0_dw);
+// decode at reduced scale (pxz_scaled_expand.hip): one launch over a.images, or over a.windows when that is set; the wave's
+// image (a.tile_dw: scaled_tile_dw, pxz_scaled_tile.h) is always in LDS, on varied_expand_geom's grid
+hipError_t launch_scaled_expand(const ScaledExpandArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+// Dwords of the staged windows of one axis for blocks whose longer side is `side`, tables whose kernel has the given support
+// (0: Nearest) and scales 2^0 .. 2^max_shift: at scale 2^k an axis has at most ceil(side / 2^k) output samples of at most
+// min(side, 2 * ceil(support * 2^k) + 1) taps each (an up-scaling window: 2 * ceil(support) + 1), a header dword before
+// the i16 pairs.
+inline uint32_t scaled_window_dw(uint32_t side, uint32_t support, uint32_t max_shift)
+{
+	uint32_t most = 0;
+	for (uint32_t k = 0; k <= max_shift && k < 32u; ++k) {
+		const uint32_t outs = (uint32_t)(((uint64_t)side + (1ull << k) - 1u) >> k);
+		uint64_t taps = support ? 2ull * ((uint64_t)support << k) + 1u : 1u;
+		if (taps > side) taps = side;
+		const uint32_t dw = outs * (1u + (support ? ((uint32_t)taps + 1u) / 2u : 0u));
+		if (dw > most) most = dw;
+	}
+	return most;
+}
+
+// dwords of one wave's image of scaled_resize_tile (its layout: pxz_scaled_tile.h); 0xffffffff: beyond any LDS
+inline uint32_t scaled_tile_dw(uint32_t bw, uint32_t bh, uint32_t win_dw)
+{
+	const uint64_t dw = (2ull * bw * bh + 2ull * win_dw + bw + 3u) & ~3ull;
+	return dw > 0x0fffffffull ? 0xffffffffu : (uint32_t)dw;
+}
 hipError_t launch_distortion(const DistortionArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_widen(const WidenArgs &a, hipStream_t stream);
 hipError_t launch_narrow(const NarrowArgs &a, hipStream_t stream);

@@ -74,6 +74,16 @@ struct VariedExpandTables {
 	uint32_t stride = 0, max_window = 0;
 };
 
+// decode at reduced scale: the axis table of every (target size, stored size) pair of one call: pxz::ScaledExpandTableSet
+struct ScaledExpandTables {
+	DeviceBuffer mem;  // the one allocation behind every device pointer below
+	uint32_t *d_slot = nullptr;
+	pxz::ScaledTab *d_dir = nullptr, *d_mixed = nullptr;
+	uint16_t *d_starts = nullptr, *d_sizes = nullptr;
+	int16_t *d_coeffs = nullptr;
+	uint32_t stride = 0, max_win_dw = 0;
+};
+
 // The bounded caches hold at most this many table sets: caches, not logs -- varying geometries (tools/fuzz_tree.py, a
 // folder of many sizes) must not grow them without bound.
 constexpr size_t kTableCacheBound = 16;
@@ -99,6 +109,9 @@ struct HandleScratch {
 	DeviceBuffer windows;             // pixel windows of files: the per-window table
 	PinnedStaging window_table;       //   and its pinned staging
 	DeviceBuffer window_host;         // the windows form: the files, the covered tiles, the crops and the flags
+	std::map<std::pair<uint32_t, std::vector<uint32_t>>, ScaledExpandTables> scaled_tables;  // (filter, target / largest stored size pairs)
+	DeviceBuffer scaled;              // decode at reduced scale: the per-owner table
+	PinnedStaging scaled_table;       //   and its pinned staging
 	DeviceBuffer transcode_files, transcode_tiles;  // the transcode and archive forms: the files that come in; their tiles when the block size changes
 	DeviceBuffer fit;                 // pxz_fit_varied_ladder_device: the images' targets
 	PinnedStaging fit_targets;        //   and their pinned staging
@@ -170,6 +183,11 @@ uint32_t varied_n_tiles(const std::vector<pxz::VariedImage> &images);
 int window_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *w, uint32_t n_windows, uint32_t bw,
                 uint32_t bh, uint32_t channels, std::vector<pxz::WindowEntry> *entries, std::vector<uint32_t> *sides, uint32_t *n_rows);
 uint32_t window_n_tiles(const std::vector<pxz::WindowEntry> &entries);
+// decode at reduced scale: the rules of one owner's scale (s | block, "image i" / "window k") and a window's alignment, and
+// the scaled size of a full-resolution extent
+int scaled_check_shift(pxz_handle *h, const char *who, uint32_t index, uint32_t shift, uint32_t bw, uint32_t bh);
+int scaled_check_window(pxz_handle *h, uint32_t index, const pxz_window &w, uint32_t img_w, uint32_t img_h, uint32_t shift);
+inline uint32_t scaled_extent(uint32_t v, uint32_t shift) { return (uint32_t)(((uint64_t)v + (1ull << shift) - 1u) >> shift); }
 int stage_host_image(pxz_handle *h, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t pitch_bytes,
                      pxz_params *p, uint32_t sets, bool device_px, pxz_frames *f, size_t *tiles, size_t *slot);
 int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw);

@@ -624,6 +624,72 @@ bool build_varied_expand_tables(const std::vector<uint32_t> &sizes, uint32_t fil
 	return true;
 }
 
+uint32_t filter_support(uint32_t filter)
+{
+	Kernel1D k;
+	return filter != 0u && kernel_for(filter, false, &k) ? (uint32_t)k.support : 0u;
+}
+
+bool build_scaled_expand_tables(const std::vector<uint32_t> &targets, const std::vector<uint32_t> &max_stored, uint32_t filter,
+                                ScaledExpandTableSet *out)
+{
+	ScaledExpandTableSet &s = *out;
+	s = ScaledExpandTableSet{};
+	if (targets.size() != max_stored.size() || filter > 4u) return false;
+	std::map<uint32_t, uint32_t> most;  // target -> its largest stored size
+	uint32_t top = 0, top_stored = 0;
+	for (size_t i = 0; i < targets.size(); ++i) {
+		if (targets[i] == 0u) continue;
+		uint32_t &m = most[targets[i]];
+		if (max_stored[i] > m) m = max_stored[i];
+		if (targets[i] > top) top = targets[i];
+		if (max_stored[i] > top_stored) top_stored = max_stored[i];
+	}
+	s.stride = top_stored + 1u;
+	s.slot.assign(top + 1u, 0xffffffffu);
+	uint32_t n = 0;
+	for (const auto &tm : most) s.slot[tm.first] = n++;
+	s.dir.assign((size_t)(n ? n : 1u) * s.stride, ScaledTab{0, 0, 0, 0, 0, 0});
+	s.mixed = s.dir;
+	auto append = [&](uint32_t in, uint32_t outsz, bool upscale, ScaledTab *t) {
+		AxisWindows win;
+		if (!build_axis(in, outsz, filter, &win, upscale)) return false;
+		t->start_off = (uint32_t)s.starts.size();
+		t->coeff_off = (uint32_t)s.coeffs.size();
+		t->window = (uint16_t)win.window;
+		t->precision = (uint16_t)win.precision;
+		uint32_t taps = 0;
+		for (uint32_t o = 0; o < outsz; ++o) {
+			s.starts.push_back((uint16_t)win.starts[o]);
+			s.sizes.push_back((uint16_t)win.sizes[o]);
+			if ((uint32_t)win.sizes[o] > taps) taps = (uint32_t)win.sizes[o];
+		}
+		s.coeffs.insert(s.coeffs.end(), win.coeffs.begin(), win.coeffs.end());
+		t->taps = (uint16_t)taps;
+		t->wdw = (uint16_t)(filter == 0u ? 1u : 1u + (taps + 1u) / 2u);
+		if (taps > s.max_taps) s.max_taps = taps;
+		if (outsz * t->wdw > s.max_win_dw) s.max_win_dw = outsz * t->wdw;
+		return true;
+	};
+	for (const auto &tm : most) {
+		const uint32_t target = tm.first;
+		for (uint32_t in = 1; in <= tm.second; ++in) {
+			if (in == target) continue;
+			const size_t at = (size_t)s.slot[target] * s.stride + in;
+			if (!append(in, target, target > in, &s.dir[at])) return false;
+			s.mixed[at] = s.dir[at];
+			// (only Triangle's kernel depends on the flag: mod.rs:65-107)
+			if (in > target && filter == 1u && !append(in, target, true, &s.mixed[at])) return false;
+		}
+	}
+	if (s.starts.empty()) {
+		s.starts.push_back(0);
+		s.sizes.push_back(0);
+	}
+	if (s.coeffs.empty()) s.coeffs.push_back(0);
+	return true;
+}
+
 const Knobs &knobs()
 {
 	static const Knobs k = [] {

@@ -83,4 +83,24 @@ struct VariedExpandTableSet {
 };
 bool build_varied_expand_tables(const std::vector<uint32_t> &sizes, uint32_t filter, VariedExpandTableSet *out);
 
+// decode at reduced scale (pxz_scaled_expand.hip): one axis table per (target size, stored size) pair the call can meet -- for
+// target targets[i] the stored sizes 1 .. max_stored[i] but the target itself (an axis that keeps its size is not resampled):
+// dir[slot[target] * stride + stored], stride = max(max_stored) + 1.  A table whose axis grows is the one
+// build_varied_expand_tables makes for the pair; one whose axis shrinks is built without the upscale flag in `dir` and with it
+// in `mixed` (the other axis of the tile grows: block.rs:301-304 hands one flag to both) -- another kernel for Triangle, the
+// same entry for the other filters.  One table serves both axes.  Entries of pairs the call cannot meet are zero.
+struct ScaledExpandTableSet {
+	std::vector<uint32_t> slot;  // per target size 0 .. max(targets): its row in dir (0xffffffff: not a target of the call)
+	uint32_t stride = 0;
+	std::vector<ScaledTab> dir, mixed;
+	std::vector<uint16_t> starts, sizes;
+	std::vector<int16_t> coeffs;
+	uint32_t max_taps = 0;       // widest window of the set as built
+	uint32_t max_win_dw = 0;     // most dwords the staged windows of one axis take: max over the tables of target * wdw
+};
+bool build_scaled_expand_tables(const std::vector<uint32_t> &targets, const std::vector<uint32_t> &max_stored, uint32_t filter,
+                                ScaledExpandTableSet *out);
+// the support of a filter's kernel in source samples at scale 1 (0: Nearest; Triangle's two kernels share theirs)
+uint32_t filter_support(uint32_t filter);
+
 }  // namespace pxz
