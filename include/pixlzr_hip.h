@@ -734,6 +734,97 @@ int pxz_decode_windows_files_scaled(pxz_handle *h, const uint8_t *const *files, 
                                     const pxz_params *params, const uint32_t *scale_log2, uint8_t *out_base, uint64_t out_bytes,
                                     uint32_t *window_flags);
 
+/* ---- patch: new pixels into pixel windows of .pixlzr files, the rest untouched ---------------- */
+
+/* The write side of the windows.  The reference has the semantics: decode_block gives every stored block block_value: Some(..)
+ * (src/encoding/mod.rs:236-241), and Pixlzr::shrink_by returns such blocks as they are and shrinks only blocks without a value
+ * (src/data_types/pixlzr.rs:166-170).  So: open a file, replace the blocks a window covers by fresh full-size blocks -- the stored
+ * block resized to its place (PixlzrBlock::resize, as expand does) with the new pixels written over it --, shrink, save.  Exactly
+ * the covered blocks are measured and shrunk again; every other block keeps its stored size, its value bits and its bytes.
+ * The hull of a window is the tile-aligned rectangle of its covered tiles, clipped to the image.  pxz_window_layout of window k
+ * is pxz_varied_layout of ONE image of the hull's size -- same grid, same row-major order, same ragged edge tiles -- so whatever
+ * takes a varied batch (the writer, pxz_record_bytes_varied_device, ...) takes the covered tiles as they are, with one
+ * descriptor of the hull's size per window.
+ *
+ * pxz_patch_check (host only: no handle, no GPU, like pxz_window_layout): answers what pxz_window_layout answers, tile_offsets
+ * included, and PXZ_ERR_INVALID_ARG when two windows of one image cover a common tile: the covered tile rectangles of one image
+ * must be pairwise disjoint (pixel rectangles in different tiles of one tile row are fine; windows of different images never
+ * collide).  *bad_window (may be NULL) receives the index of the first window that covers a tile an earlier window of its image
+ * covers, PXZ_NO_WINDOW when the call succeeds or fails for another reason.  Every entry point below runs it first. */
+#define PXZ_NO_WINDOW 0xffffffffu
+int pxz_patch_check(const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows, uint32_t block_w,
+                    uint32_t block_h, uint64_t *tile_offsets, uint32_t *bad_window);
+
+/* Tiles to tiles.  Inputs: the covered tiles as pxz_decode_windows_device leaves them (d_tile_w, d_tile_h, d_slots in the
+ * pxz_window_layout order, slots of block_w*block_h*channels bytes) and the same descs and windows -- but for THIS call
+ * windows[k].pitch_bytes and offset_bytes describe the INPUT rectangle of new pixels at d_patch_base: width x height pixels of
+ * `channels` interleaved bytes, any alignment.  params carries what the shrink takes (block size, mode, filter, factor),
+ * expand_filter what to_image(filter) takes.  Outputs in the same layout: d_block_value, d_out_w, d_out_h, d_out_pixels (may be
+ * NULL: values and sizes only).
+ * For every window without a flagged tile the outputs equal, bit for bit (value bits, sizes, the valid bytes of every slot),
+ * this composition: pxz_expand_windows_device of the window's hull (a window struct with the hull's rectangle) with
+ * expand_filter into a tightly packed image; the new pixels written over their rectangle of that image;
+ * pxz_shrink_varied_frames_device with params over the hulls as a varied batch.  No image exists here: each covered tile is
+ * rebuilt in LDS, overlaid, measured and resampled by one block of one kernel; a tile the window covers wholly is not even
+ * expanded.  The overlay writes plain bytes over the finished tile image (RGBA: after the expand's un-premultiply, before the
+ * shrink's premultiply).
+ * A covered tile whose stored size is zero or exceeds its place is flagged and emptied exactly as by
+ * pxz_reshrink_varied_frames_device -- d_window_flags (n_windows dwords, may be NULL) receives 0 or 1 per window,
+ * pxz_decode_status reports bit 0, the tile gets d_out_w = d_out_h = 0 and value bits 0, its slot is left as it was -- also when
+ * the window covers the tile wholly, so that there is one rule.
+ * In place: d_out_w, d_out_h and d_out_pixels may be d_tile_w, d_tile_h and d_slots themselves, as in the re-shrink.
+ * Asynchronous on the handle's stream; ONE launch whatever n_windows.  Validation runs on the host before anything is launched,
+ * with the re-shrink's codes and texts and pxz_patch_check's; the texts name "window k"; a window's pitch below width*channels is
+ * PXZ_ERR_INVALID_ARG; PXZ_ERR_TILE_TOO_SMALL (shrink_directionally) is judged on the covered tiles, so an image whose edge tiles
+ * are narrower than 2 px can still be patched away from that edge.  On an error nothing is written.
+ * Limit: pxz_reshrink_lds_bytes (block_w*block_h*4 <= 65536 and the windows of both axes beside two planes); there is no HBM
+ * form.  The call reads and writes none of the state the single-geometry fast paths keep in the handle; pxz_trim gives back what
+ * it grew. */
+int pxz_patch_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows,
+                             uint32_t n_windows, uint32_t channels, const pxz_params *params, uint32_t expand_filter,
+                             const uint8_t *d_patch_base, const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots,
+                             float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels,
+                             uint32_t *d_window_flags);
+
+/* Files plus new covered tiles to files.  Inputs: the old files as the window reader took them (d_files, d_file_offsets), the same
+ * descs and windows (image and rectangle are read; of params block_w and block_h), the new covered tiles (d_block_value, d_tile_w,
+ * d_tile_h, d_slots in the pxz_window_layout order: what the call above leaves) and the two calls' window flags (d_reader_flags
+ * from pxz_decode_windows_device, d_patch_flags from the call above; either may be NULL).  The record bounds of the covered tiles
+ * are taken from the scratch pxz_decode_windows_device left in THIS handle: the call must follow that reader, with the same
+ * windows and with no other reader call between them (PXZ_ERR_INVALID_ARG when the handle holds no such scratch).
+ * Output: the new files back to back in d_out, file i = [d_out_file_offsets[i], d_out_file_offsets[i+1]) (n_images + 1 u64).  File
+ * i consists of the old 26-byte header verbatim (the filter byte stays); the line table, in which the length of every tile row a
+ * window touches is recomputed; in every tile row each record that no window covers as the OLD BYTES, span by span, never
+ * re-encoded; and each covered record as encode_block (src/encoding/mod.rs:168-200) of its new tile, by the writer of
+ * pxz_encode_varied_frames_device over the hulls.  An image without a window passes through byte for byte and unread.  An image
+ * with a flagged window -- a flag passed in, a covered tile the reader left without a record, a new tile of size zero -- gets a
+ * file of length zero; d_image_flags (n_images dwords, may be NULL) receives the OR of its windows' flags.  Damage outside what
+ * the windows' reader reads is copied as it is.
+ * Capacity as pxz_encode_varied_frames_device: the offsets are always exact and no byte at or beyond out_capacity is written
+ * (d_out may be NULL when out_capacity is 0: the size query).  Asynchronous on the handle's stream; the number of launches and
+ * copies depends on neither n_images nor n_windows, and nothing is read back to the host.  Validation on the host before any
+ * launch, pxz_patch_check's; PXZ_ERR_UNSUPPORTED for more than 2^32-1 pieces (spans of old bytes and rows of new records) in
+ * all.  pxz_trim returns the scratch, the staging of the new records included. */
+int pxz_splice_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows,
+                              uint32_t n_windows, uint32_t channels, const pxz_params *params, const uint8_t *d_files,
+                              const uint64_t *d_file_offsets, const float *d_block_value, const uint32_t *d_tile_w,
+                              const uint32_t *d_tile_h, const uint8_t *d_slots, const uint32_t *d_reader_flags,
+                              const uint32_t *d_patch_flags, uint8_t *d_out, uint64_t out_capacity, uint64_t *d_out_file_offsets,
+                              uint32_t *d_image_flags);
+
+/* Host files and host rectangles of new pixels in, host files out, synchronously.  files[i] / lens[i] is file i; patches[k] is
+ * window k's new pixels, windows[k].pitch_bytes their pitch (offset_bytes is ignored).  Every header is parsed on the host first
+ * and the descriptors come from them, as in pxz_transcode_varied_files: the files must share channels and block size, and
+ * params->block_w / block_h must be theirs (PXZ_ERR_INVALID_ARG: a patch keeps the block size).  Composition only: one upload
+ * (the files whole, the patches behind them), pxz_decode_windows_device, pxz_patch_windows_device in place,
+ * pxz_splice_windows_device, and the way down.  file_offsets (n_images + 1) and out follow the protocol of
+ * pxz_encode_varied_images: PXZ_ERR_BUFFER_TOO_SMALL with the offsets written and nothing in out when out_capacity is below
+ * file_offsets[n_images] (out may be NULL for that size query).  All or nothing: a flagged window gives PXZ_ERR_INVALID_ARG
+ * naming "window k", and nothing is written to out or file_offsets.  Errors and limits as pxz_patch_windows_device. */
+int pxz_patch_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images,
+                            const pxz_window *windows, uint32_t n_windows, const uint8_t *const *patches, const pxz_params *params,
+                            uint32_t expand_filter, uint8_t *out, uint64_t out_capacity, uint64_t *file_offsets);
+
 /* ---- rate and distortion: what a factor costs and what it loses ---------------- */
 
 /* The squared error of stored tiles against the frames they were shrunk from.  Nothing in the reference computes it:

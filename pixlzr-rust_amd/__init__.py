@@ -16,5 +16,6 @@ from .binding import (  # noqa: F401
     FIT_BYTES, FIT_SSE, fit_select, sse_for_psnr, reshrink_distortion_lds_bytes,
     TILEFIT_LAMBDA_MAX, TILEFIT_MISSED, TILEFIT_NO_CANDIDATE, TILEFIT_UNIFORM, fit_tiles_select,
     scaled_size, scaled_window_size, scaled_axis_table, expand_scaled_lds_bytes,
+    patch_check, NO_WINDOW,
 )
 from . import dist  # noqa: E402,F401  (torch.distributed plumbing: frame sharding + block-stream gather)

@@ -39,7 +39,9 @@ EXPORTED_SYMBOLS = [
     "pxz_retile_varied_files_fit", "pxz_retile_varied_files_fit_tiles",
     "pxz_scaled_size", "pxz_scaled_axis_table", "pxz_expand_scaled_lds_bytes", "pxz_expand_varied_scaled_frames_device",
     "pxz_expand_windows_scaled_device", "pxz_decode_varied_files_scaled", "pxz_decode_windows_files_scaled",
+    "pxz_patch_check", "pxz_patch_windows_device", "pxz_splice_windows_device", "pxz_patch_windows_files",
 ]
+NO_WINDOW = 0xffffffff  # PXZ_NO_WINDOW
 
 LADDER_MAX_RUNGS = 16  # PXZ_LADDER_MAX_RUNGS
 VARIED_LADDER_MAX_RUNGS = 32  # PXZ_VARIED_LADDER_MAX_RUNGS
@@ -195,6 +197,15 @@ def load_library():
         L.pxz_expand_windows_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params)] + [vp] * 5
         L.pxz_decode_windows_files.restype = C.c_int
         L.pxz_decode_windows_files.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, C.c_uint64, vp]
+    if hasattr(L, "pxz_patch_check"):  # (a build of an earlier commit named by PXZ_LIB lacks the patch)
+        L.pxz_patch_check.restype = C.c_int
+        L.pxz_patch_check.argtypes = [vp, u32, vp, u32, u32, u32, vp, C.POINTER(u32)]
+        L.pxz_patch_windows_device.restype = C.c_int
+        L.pxz_patch_windows_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), u32] + [vp] * 9
+        L.pxz_splice_windows_device.restype = C.c_int
+        L.pxz_splice_windows_device.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params)] + [vp] * 9 + [C.c_uint64, vp, vp]
+        L.pxz_patch_windows_files.restype = C.c_int
+        L.pxz_patch_windows_files.argtypes = [vp, vp, vp, u32, vp, u32, vp, C.POINTER(Params), u32, vp, C.c_uint64, vp]
     if hasattr(L, "pxz_shrink_varied_ladder_frames_device"):  # (a build of an earlier commit named by PXZ_LIB lacks the varied ladder)
         L.pxz_shrink_varied_ladder_frames_device.restype = C.c_int
         L.pxz_shrink_varied_ladder_frames_device.argtypes = [vp, vp, u32, u32, C.POINTER(Params), vp, u32] + [vp] * 5
@@ -361,6 +372,23 @@ def window_layout(sizes, windows, bw, bh):
                                           C.cast(window_descs(windows), C.c_void_p) if k else None, k, bw, bh, _p(out))
     if rc != 0:
         raise PxzError(rc)
+    return out
+
+
+def patch_check(sizes, windows, bw, bh):
+    """pxz_patch_check: window_layout, and the patch's rule that the covered tiles of the windows of one image are disjoint.
+    -> uint64[n_windows+1] offsets; raises PxzError whose .window is the first offending window (NO_WINDOW: another reason).
+    No GPU."""
+    n, k = len(sizes), len(windows)
+    geoms = [(w, h, 0, 0) for (w, h) in sizes]
+    out = np.zeros(k + 1, np.uint64)
+    bad = C.c_uint32(0)
+    rc = load_library().pxz_patch_check(C.cast(image_descs(geoms), C.c_void_p) if n else None, n,
+                                        C.cast(window_descs(windows), C.c_void_p) if k else None, k, bw, bh, _p(out), C.byref(bad))
+    if rc != 0:
+        err = PxzError(rc)
+        err.window = bad.value
+        raise err
     return out
 
 
@@ -1269,6 +1297,95 @@ class Handle:
             err.flags, err.crops = flags[:k], result
             raise err
         return result, flags[:k]
+
+    # ---- patch: new pixels into windows of files ----
+    def patch_windows_device(self, sizes, windows, channels, bw, bh, mode, filt, factor, expand_filter, patch, ow, oh, slots,
+                             want_pixels=True, out=None, window_flags=None):
+        """pxz_patch_windows_device: the covered tiles of the windows (w[T], h[T], slots[T, bw*bh*C], window_layout order, as
+        decode_windows_device leaves them) with the windows' new pixels written over them -- window k's width x height pixels
+        stand in the uint8 CUDA buffer `patch` at its offset_bytes with its pitch_bytes between rows -- shrunk again with (mode,
+        filt, factor) after the expand with expand_filter.  Returns (values[T], w[T], h[T], slots | None).  out: a 4-tuple of
+        such tensors (slots may be None); its w, h and slots may be the inputs themselves (in place).  window_flags (int32[k]
+        CUDA, optional) gets 0 | 1."""
+        import torch
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        if out is None:
+            T = ow.numel()
+            dev = ow.device
+            vals = torch.empty(T, dtype=torch.float32, device=dev)
+            nw = torch.empty(T, dtype=torch.int32, device=dev)
+            nh = torch.empty(T, dtype=torch.int32, device=dev)
+            nslots = torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, nw, nh, nslots = out
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_patch_windows_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), C.cast(window_descs(windows), C.c_void_p), len(windows),
+            channels, C.byref(pd), expand_filter, C.c_void_p(patch.data_ptr()), C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()),
+            C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()), C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()),
+            C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
+            C.c_void_p(window_flags.data_ptr()) if window_flags is not None else None))
+        return vals, nw, nh, nslots
+
+    def splice_windows_device(self, files, file_offsets, sizes, windows, channels, bw, bh, vals, ow, oh, slots, reader_flags=None,
+                              patch_flags=None, out=None, image_flags=None):
+        """pxz_splice_windows_device: the old files (files / file_offsets as decode_windows_device took them -- the call must
+        follow that reader on this handle) and the new covered tiles (values[T], w[T], h[T], slots, window_layout order) -> the
+        new files.  out: (file_offsets int64[n+1], bytes uint8[capacity]) CUDA tensors (bytes may be None: the size query); by
+        default the buffer holds the old files and every covered record at its largest.  Returns (file_offsets, bytes)."""
+        import torch
+        geoms = [(w, h, 0, 0) for (w, h) in sizes]
+        n = len(geoms)
+        if out is None:
+            T = vals.numel()
+            cap = files.numel() + T * (13 + 14 + bw * bh * (channels + 1) + 8)
+            offs = torch.empty(n + 1, dtype=torch.int64, device=vals.device)
+            buf = torch.empty(cap, dtype=torch.uint8, device=vals.device)
+        else:
+            offs, buf = out
+        opt = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        pd = Params(bw, bh, 0, 0, 0.0, 0)
+        self.use_torch_stream()
+        self._check(self._L.pxz_splice_windows_device(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), n, C.cast(window_descs(windows), C.c_void_p), len(windows), channels,
+            C.byref(pd), C.c_void_p(files.data_ptr()), C.c_void_p(file_offsets.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), opt(reader_flags), opt(patch_flags),
+            opt(buf), 0 if buf is None else buf.numel(), C.c_void_p(offs.data_ptr()), opt(image_flags)))
+        return offs, buf
+
+    def patch_windows_files(self, files, windows, patches, bw, bh, mode, filt, factor, expand_filter, out=None):
+        """pxz_patch_windows_files: a list of .pixlzr files (bytes) of one channel count and block size, windows = [(image, x, y,
+        width, height), ...] and patches = their new pixels (numpy uint8 [height, width, C]) -> the list of the patched files.
+        out: a numpy uint8 buffer to write into (the call raises PxzError -7 with .needed when it is too small; out of size 0 is
+        the size query), else the buffer is sized by a first call.  Raises PxzError naming the window when one is flagged."""
+        n, k = len(files), len(windows)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        pats = [p if p.strides[2] == 1 and p.strides[1] == p.shape[2] else np.ascontiguousarray(p) for p in patches]
+        pptrs = (C.c_void_p * max(k, 1))(*[p.ctypes.data for p in pats])
+        full = [(i, x, y, w, h, pats[j].strides[0], 0) for j, (i, x, y, w, h) in enumerate(windows)]
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        offs = np.zeros(n + 1, np.uint64)
+
+        def call(buf):
+            return self._L.pxz_patch_windows_files(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
+                                                   C.cast(window_descs(full), C.c_void_p), k, C.cast(pptrs, C.c_void_p), C.byref(pd),
+                                                   expand_filter, _p(buf) if buf is not None and buf.size else None,
+                                                   0 if buf is None else buf.size, _p(offs))
+        if out is None:
+            rc = call(None)
+            if rc == -7:
+                out = np.empty(int(offs[-1]), np.uint8)
+                rc = call(out)
+        else:
+            rc = call(out)
+        if rc != 0:
+            err = PxzError(rc, (self._L.pxz_last_error(self._h) or b"").decode())
+            err.needed, err.offsets = int(offs[-1]), offs.copy()
+            raise err
+        return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
 
     # ---- decode at reduced scale ----
     def expand_varied_scaled_frames_device(self, descs, channels, bw, bh, filt, scales, ow, oh, slots, out, image_flags=None):

@@ -3695,3 +3695,254 @@ int pxz_expand_windows_scaled_device(pxz_handle *h, const pxz_image_desc *descs,
 }
 
 }  // extern "C"
+
+// ---- patch of pixel windows (pxz_patch.hip): new pixels into the covered tiles of .pixlzr files ----------------------------
+namespace pxz_runtime {
+
+// window_plan, and the rule of the patch on top of it: the covered tile rectangles of one image are pairwise disjoint.
+// *bad_window (may be null): the first window that covers a tile an earlier window of its image covers, else PXZ_NO_WINDOW.
+int patch_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *w, uint32_t n_windows, uint32_t bw, uint32_t bh,
+               uint32_t channels, std::vector<pxz::WindowEntry> *entries, std::vector<uint32_t> *sides, uint32_t *bad_window)
+{
+	if (bad_window) *bad_window = PXZ_NO_WINDOW;
+	const int rc = window_plan(h, descs, n_images, w, n_windows, bw, bh, channels, entries, sides, nullptr);
+	if (rc != PXZ_OK) return rc;
+	// the windows of each image side by side, in the order of the call
+	std::vector<uint32_t> order(n_windows);
+	for (uint32_t k = 0; k < n_windows; ++k) order[k] = k;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (*entries)[a].image < (*entries)[b].image; });
+	uint32_t bad = PXZ_NO_WINDOW, with = 0;
+	for (size_t lo = 0; lo < order.size();) {
+		size_t hi = lo;
+		while (hi < order.size() && (*entries)[order[hi]].image == (*entries)[order[lo]].image) ++hi;
+		for (size_t i = lo + 1; i < hi && order[i] < bad; ++i) {
+			const pxz::WindowEntry &a = (*entries)[order[i]];
+			for (size_t j = lo; j < i; ++j) {
+				const pxz::WindowEntry &b = (*entries)[order[j]];
+				if (a.c0 < b.c0 + b.ccols && b.c0 < a.c0 + a.ccols && a.r0 < b.r0 + b.crows && b.r0 < a.r0 + a.crows) {
+					bad = order[i];
+					with = order[j];
+					break;
+				}
+			}
+			if (bad == order[i]) break;
+		}
+		lo = hi;
+	}
+	if (bad == PXZ_NO_WINDOW) return PXZ_OK;
+	if (bad_window) *bad_window = bad;
+	return fail(h, PXZ_ERR_INVALID_ARG, "window %u: covers a tile of image %u that window %u covers too (the covered tiles of a patch must be disjoint)",
+	            bad, (*entries)[bad].image, with);
+}
+
+}  // namespace pxz_runtime
+
+extern "C" {
+
+int pxz_patch_check(const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows, uint32_t block_w,
+                    uint32_t block_h, uint64_t *tile_offsets, uint32_t *bad_window)
+{
+	if (bad_window) *bad_window = PXZ_NO_WINDOW;
+	if (!tile_offsets) return PXZ_ERR_INVALID_ARG;
+	std::vector<pxz::WindowEntry> entries;
+	const int rc = patch_plan(nullptr, descs, n_images, windows, n_windows, block_w, block_h, 0, &entries, nullptr, bad_window);
+	if (rc != PXZ_OK) return rc;
+	for (uint32_t k = 0; k < n_windows; ++k) tile_offsets[k] = entries[k].tile0;
+	tile_offsets[n_windows] = window_n_tiles(entries);
+	return PXZ_OK;
+}
+
+int pxz_patch_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows,
+                             uint32_t channels, const pxz_params *params, uint32_t expand_filter, const uint8_t *d_patch_base,
+                             const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w,
+                             uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_window_flags)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_patch_base || !d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h)
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	const pxz_params p = *params;
+	int rc = check_params(h, &p);
+	if (rc != PXZ_OK) return rc;
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, 0u, 1u)) != PXZ_OK) return rc;
+	std::vector<pxz::WindowEntry> entries;
+	std::vector<uint32_t> sides;
+	if ((rc = patch_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, channels, &entries, &sides, nullptr)) != PXZ_OK) return rc;
+	if (p.mode == PXZ_MODE_SHRINK_DIRECTIONALLY)
+		for (uint32_t k = 0; k < n_windows; ++k) {
+			// the covered tiles' sizes: the block, and the image's edge where the window reaches its last column or row
+			const pxz::WindowEntry &e = entries[k];
+			const uint32_t least_w = e.c0 + e.ccols == e.cols ? e.edge_w : p.block_w, least_h = e.r0 + e.crows == e.rows ? e.edge_h : p.block_h;
+			if (least_w < 2 || least_h < 2 || p.block_w < 2 || p.block_h < 2)
+				return fail(h, PXZ_ERR_TILE_TOO_SMALL,
+				            "window %u: directional detector needs tiles of at least 2x2 px (a covered edge tile is %ux%u); the reference panics here", k,
+				            least_w, least_h);
+		}
+	PXZ_HIP(h, hipSetDevice(h->device));
+	const VariedTables *vt = nullptr;
+	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
+	pxz::PatchArgs a{};
+	pxz_params xp = p;
+	xp.filter = expand_filter;
+	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r.x)) != PXZ_OK) return rc;
+	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, 0u, a.r.x.wdw)) != PXZ_OK) return rc;
+	if ((rc = fresh_status(h, &a.r.x.status)) != PXZ_OK) return rc;
+	if ((rc = zero_owner_flags(h, d_window_flags, n_windows)) != PXZ_OK) return rc;
+	if ((rc = window_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
+	pxz::VariedArgs &v = a.r.v;
+	v.n_tiles = window_n_tiles(entries);
+	v.bw = p.block_w;
+	v.bh = p.block_h;
+	v.mode = p.mode;
+	v.filter = p.filter;
+	v.value = d_block_value;
+	v.out_w = d_out_w;
+	v.out_h = d_out_h;
+	v.out_px = d_out_pixels;
+	v.slot_bytes = p.block_w * p.block_h * channels;
+	v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane, as the re-shrink's
+	v.dir = vt->d_dir;
+	v.starts = vt->d_starts;
+	v.sizes = vt->d_sizes;
+	v.coeffs = vt->d_coeffs;
+	std::memcpy(v.thresholds, h->thresholds, sizeof v.thresholds);
+	a.r.x.n_tiles = v.n_tiles;
+	a.r.x.tile_w = d_tile_w;
+	a.r.x.tile_h = d_tile_h;
+	a.r.x.slots = d_slots;
+	a.n_windows = n_windows;
+	a.patch_base = d_patch_base;
+	a.window_flags = d_window_flags;
+	a.factor[0] = p.factor;
+	PXZ_HIP(h, pxz::launch_patch(a, channels, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+int pxz_splice_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *windows, uint32_t n_windows,
+                              uint32_t channels, const pxz_params *params, const uint8_t *d_files, const uint64_t *d_file_offsets,
+                              const float *d_block_value, const uint32_t *d_tile_w, const uint32_t *d_tile_h, const uint8_t *d_slots,
+                              const uint32_t *d_reader_flags, const uint32_t *d_patch_flags, uint8_t *d_out, uint64_t out_capacity,
+                              uint64_t *d_out_file_offsets, uint32_t *d_image_flags)
+{
+	using pxz::SpliceBound;
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
+	if (!d_files || !d_file_offsets || !d_block_value || !d_tile_w || !d_tile_h || !d_slots || !d_out_file_offsets || (!d_out && out_capacity))
+		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
+	const pxz_params p = decode_side_params(params, false);
+	std::vector<pxz::WindowEntry> entries;
+	int rc = patch_plan(h, descs, n_images, windows, n_windows, p.block_w, p.block_h, 0, &entries, nullptr, nullptr);
+	if (rc != PXZ_OK) return rc;
+	const uint32_t n_tiles = window_n_tiles(entries);
+	if ((uint64_t)p.block_w * p.block_h * channels > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "tile too large");
+	// the reader's scratch as pxz_decode_windows_device laid it out for these windows (reader_scratch)
+	if (h->dmeta.cap < (size_t)n_tiles * 16u)
+		return fail(h, PXZ_ERR_INVALID_ARG, "the splice reads the record bounds pxz_decode_windows_device leaves: call it with these windows on this handle first");
+
+	// ---- the structure of every new file: its pieces in file order, its touched tile rows
+	std::vector<std::vector<uint32_t>> of_image(n_images);
+	for (uint32_t k = 0; k < n_windows; ++k) of_image[entries[k].image].push_back(k);
+	std::vector<pxz::SplicePiece> pieces;
+	std::vector<pxz::SpliceRow> rows;
+	std::vector<pxz::SpliceRowPart> parts;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		const std::vector<uint32_t> &ws = of_image[i];
+		if (ws.empty()) {  // no window: the file as it is
+			pieces.push_back({{SpliceBound::kFileStart, i, 0}, {SpliceBound::kFileEnd, i, 0}, i, 1u});
+			continue;
+		}
+		const uint32_t any = ws[0], n_rows = entries[any].rows;
+		// the header and the line table (the touched rows' lengths are written over their copies), then what lies between the windows
+		SpliceBound cursor{SpliceBound::kRow, any, 0};
+		pieces.push_back({{SpliceBound::kFileStart, i, 0}, cursor, i, 1u});
+		std::map<uint32_t, std::vector<std::pair<uint32_t, uint32_t>>> touched;  // tile row -> (first covered column, window)
+		for (uint32_t k : ws)
+			for (uint32_t j = 0; j < entries[k].crows; ++j) touched[entries[k].r0 + j].push_back({entries[k].c0, k});
+		for (auto &row : touched) {
+			const uint32_t r = row.first;
+			std::sort(row.second.begin(), row.second.end());
+			rows.push_back({i, any, r, (uint32_t)parts.size(), (uint32_t)row.second.size()});
+			for (const auto &cw : row.second) {
+				const pxz::WindowEntry &e = entries[cw.second];
+				const uint32_t j = r - e.r0, t0 = e.tile0 + j * e.ccols, t1 = t0 + e.ccols - 1u;
+				const bool at_row_start = cursor.kind == SpliceBound::kRow && cursor.b == r && e.c0 == 0;
+				if (!at_row_start) pieces.push_back({cursor, {SpliceBound::kRecStart, t0, 0}, i, 0u});
+				pieces.push_back({{SpliceBound::kStageRow, cw.second, j}, {SpliceBound::kStageRow, cw.second, j + 1u}, i, 0u});
+				parts.push_back({cw.second, j});
+				cursor = e.c0 + e.ccols == e.cols ? SpliceBound{SpliceBound::kRow, any, r + 1u} : SpliceBound{SpliceBound::kRecEnd, t1, 0};
+			}
+		}
+		if (!(cursor.kind == SpliceBound::kRow && cursor.b == n_rows)) pieces.push_back({cursor, {SpliceBound::kFileEnd, i, 0}, i, 0u});
+	}
+	if (pieces.size() > 0xffffffffull || parts.size() > 0xffffffffull)
+		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 pieces in the spliced files");
+
+	PXZ_HIP(h, hipSetDevice(h->device));
+	// ---- the new records: the hulls as a varied batch through the writer, one staging file per window
+	std::vector<pxz_image_desc> hulls(n_windows);
+	uint64_t stage_cap = 0;
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const pxz::WindowEntry &e = entries[k];
+		const uint64_t x1 = std::min<uint64_t>((uint64_t)(e.c0 + e.ccols) * p.block_w, e.img_w), y1 = std::min<uint64_t>((uint64_t)(e.r0 + e.crows) * p.block_h, e.img_h);
+		const uint32_t hw = (uint32_t)(x1 - (uint64_t)e.c0 * p.block_w), hh = (uint32_t)(y1 - (uint64_t)e.r0 * p.block_h);
+		hulls[k] = pxz_image_desc{hw, hh, hw * channels, 0, 0};
+		stage_cap += 26u + 4ull * e.crows;
+	}
+	stage_cap += (uint64_t)n_tiles * (13u + pxz_qoi_bound(p.block_w, p.block_h, channels));
+	const size_t n_pieces = pieces.size();
+	const uint64_t src_at = 0, len_at = src_at + 8ull * n_pieces, dst_at = len_at + 8ull * n_pieces, so_at = dst_at + 8ull * (n_pieces + 1u),
+	               fl_at = so_at + 8ull * ((uint64_t)n_windows + 1u);
+	if ((rc = ensure(h, h->splice_work, fl_at + 4ull * n_images)) != PXZ_OK) return rc;
+	if ((rc = ensure(h, h->splice_stage, stage_cap)) != PXZ_OK) return rc;
+	uint8_t *work = (uint8_t *)h->splice_work.ptr;
+	uint64_t *d_stage_offsets = (uint64_t *)(work + so_at);
+	if ((rc = encode_varied(h, hulls.data(), n_windows, channels, &p, 0u, d_block_value, d_tile_w, d_tile_h, d_slots, (uint8_t *)h->splice_stage.ptr,
+	                        stage_cap, d_stage_offsets, nullptr)) != PXZ_OK)
+		return rc;
+
+	// ---- the tables up, the splice
+	const size_t rows_at = up256(n_pieces * sizeof(pxz::SplicePiece)), parts_at = rows_at + up256(rows.size() * sizeof(pxz::SpliceRow));
+	const size_t table_bytes = parts_at + up256(parts.size() * sizeof(pxz::SpliceRowPart));
+	std::vector<uint8_t> table(table_bytes);
+	std::memcpy(table.data(), pieces.data(), n_pieces * sizeof(pxz::SplicePiece));
+	if (!rows.empty()) std::memcpy(table.data() + rows_at, rows.data(), rows.size() * sizeof(pxz::SpliceRow));
+	if (!parts.empty()) std::memcpy(table.data() + parts_at, parts.data(), parts.size() * sizeof(pxz::SpliceRowPart));
+	if ((rc = ensure(h, h->splice, table_bytes)) != PXZ_OK) return rc;
+	PXZ_HIP(h, h->splice_table.send(table.data(), table_bytes, h->splice.ptr, h->stream));
+	pxz::SpliceArgs s{};
+	if ((rc = window_upload(h, entries, &s.windows)) != PXZ_OK) return rc;
+	s.n_windows = n_windows;
+	s.n_images = n_images;
+	s.n_tiles = n_tiles;
+	s.n_pieces = (uint32_t)n_pieces;
+	s.n_rows = (uint32_t)rows.size();
+	s.pieces = (const pxz::SplicePiece *)h->splice.ptr;
+	s.rows = (const pxz::SpliceRow *)((const uint8_t *)h->splice.ptr + rows_at);
+	s.parts = (const pxz::SpliceRowPart *)((const uint8_t *)h->splice.ptr + parts_at);
+	s.files = d_files;
+	s.file_offsets = (const unsigned long long *)d_file_offsets;
+	s.rec_off = (const unsigned long long *)h->dmeta.ptr;
+	s.rec_len = (const uint32_t *)((const uint8_t *)h->dmeta.ptr + (size_t)n_tiles * 8u);
+	s.new_w = d_tile_w;
+	s.new_h = d_tile_h;
+	s.reader_flags = d_reader_flags;
+	s.patch_flags = d_patch_flags;
+	s.stage = (const uint8_t *)h->splice_stage.ptr;
+	s.stage_offsets = (const unsigned long long *)d_stage_offsets;
+	s.stage_capacity = stage_cap;
+	s.piece_src = (unsigned long long *)(work + src_at);
+	s.piece_len = (unsigned long long *)(work + len_at);
+	s.piece_dst = (unsigned long long *)(work + dst_at);
+	s.image_flags = d_image_flags ? d_image_flags : (uint32_t *)(work + fl_at);
+	s.out = d_out;
+	s.capacity = out_capacity;
+	s.out_file_offsets = (unsigned long long *)d_out_file_offsets;
+	PXZ_HIP(h, hipMemsetAsync(s.image_flags, 0, 4ull * n_images, h->stream));
+	PXZ_HIP(h, pxz::launch_splice(s, h->n_cus, h->stream));
+	return PXZ_OK;
+}
+
+}  // extern "C"

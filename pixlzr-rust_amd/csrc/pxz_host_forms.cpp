@@ -1130,4 +1130,92 @@ int pxz_decode_windows_files_scaled(pxz_handle *h, const uint8_t *const *files, 
 	return PXZ_OK;
 }
 
+// ---- patch: host files and host rectangles of new pixels in, host files out.  Composition only: one upload (the files whole, the
+// patches behind them), reader of the windows, patch in place, splice, and what comes down: the offsets and flags, then the files.
+int pxz_patch_windows_files(pxz_handle *h, const uint8_t *const *files, const size_t *lens, uint32_t n_images, const pxz_window *windows,
+                            uint32_t n_windows, const uint8_t *const *patches, const pxz_params *params, uint32_t expand_filter, uint8_t *out,
+                            uint64_t out_capacity, uint64_t *file_offsets)
+{
+	if (!h) return PXZ_ERR_INVALID_ARG;
+	if (!files || !lens || !params || !file_offsets || !patches) return fail(h, PXZ_ERR_INVALID_ARG, "null pointer");
+	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	int rc = check_params(h, params);
+	if (rc != PXZ_OK) return rc;
+	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
+	FileScan scan;
+	if ((rc = scan_files(h, files, lens, n_images, &scan)) != PXZ_OK) return rc;
+	const uint32_t ch = scan.channels;
+	if (scan.block_w != params->block_w || scan.block_h != params->block_h)
+		return fail(h, PXZ_ERR_INVALID_ARG, "the files hold %ux%u blocks, params ask for %ux%u: a patch keeps the block size", scan.block_w, scan.block_h,
+		            params->block_w, params->block_h);
+	if ((rc = reshrink_check_block(h, params->mode, params->block_w, params->block_h, 0u, 1u)) != PXZ_OK) return rc;
+	std::vector<pxz::WindowEntry> entries;
+	if ((rc = patch_plan(h, scan.descs.data(), n_images, windows, n_windows, params->block_w, params->block_h, ch, &entries, nullptr, nullptr)) != PXZ_OK)
+		return rc;
+	for (uint32_t k = 0; k < n_windows; ++k)
+		if (!patches[k]) return fail(h, PXZ_ERR_INVALID_ARG, "window %u: null patch", k);
+	PXZ_HIP(h, hipSetDevice(h->device));
+
+	// device side, one buffer: the files back to back behind their offsets | the patches tightly packed | the covered tiles | both
+	// flag arrays, the new files' offsets | the new files, at most the old bytes and every covered record at its largest
+	std::vector<pxz_window> dev(windows, windows + n_windows);
+	const uint64_t patch_bytes = pack_owners(&dev, ch);
+	const uint32_t n_tiles = window_n_tiles(entries);
+	const uint64_t slot = (uint64_t)params->block_w * params->block_h * ch;
+	const uint64_t offs_bytes = 8ull * ((uint64_t)n_images + 1u);
+	const uint64_t patches_at = up256(offs_bytes + scan.file_bytes + 16u), tiles_at = patches_at + up256(patch_bytes);
+	const uint64_t flags_at = tiles_at + up256(TileSet::bytes(n_tiles, slot)), new_offs_at = flags_at + up256(8ull * n_windows);
+	const uint64_t new_files_at = new_offs_at + up256(offs_bytes);
+	const uint64_t room = scan.file_bytes + (uint64_t)n_tiles * (13u + pxz_qoi_bound(params->block_w, params->block_h, ch));
+	if ((rc = ensure(h, h->patch_host, new_files_at + room)) != PXZ_OK) return rc;
+	uint8_t *d = (uint8_t *)h->patch_host.ptr;
+	std::vector<uint8_t> stage((size_t)(patches_at + patch_bytes));
+	uint64_t *offs = reinterpret_cast<uint64_t *>(stage.data());
+	offs[0] = 0;
+	for (uint32_t i = 0; i < n_images; ++i) {
+		std::memcpy(stage.data() + offs_bytes + offs[i], files[i], lens[i]);
+		offs[i + 1] = offs[i] + lens[i];
+	}
+	for (uint32_t k = 0; k < n_windows; ++k) {
+		const size_t row = (size_t)windows[k].width * ch;
+		for (uint32_t y = 0; y < windows[k].height; ++y)
+			std::memcpy(stage.data() + patches_at + dev[k].offset_bytes + (size_t)y * row, patches[k] + (size_t)y * windows[k].pitch_bytes, row);
+	}
+	PXZ_HIP(h, hipMemcpyAsync(d, stage.data(), stage.size(), hipMemcpyHostToDevice, h->stream));
+	const uint64_t *d_offsets = (const uint64_t *)d;
+	const uint8_t *d_files = d + offs_bytes;
+	const TileSet m(d + tiles_at, n_tiles);
+	uint32_t *d_flags = (uint32_t *)(d + flags_at);
+	uint64_t *d_new_offs = (uint64_t *)(d + new_offs_at);
+	PXZ_HIP(h, hipMemsetAsync(m.value, 0, TileSet::meta_bytes(n_tiles), h->stream));  // (a tile the reader cannot reach keeps size 0 and is flagged)
+	pxz_params pin = *params;  // (the reader takes the block size alone)
+	if ((rc = pxz_decode_windows_device(h, scan.descs.data(), n_images, dev.data(), n_windows, ch, &pin, d_files, d_offsets, m.value, m.w, m.h, m.slots,
+	                                    d_flags)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_patch_windows_device(h, scan.descs.data(), n_images, dev.data(), n_windows, ch, params, expand_filter, d + patches_at, m.w, m.h, m.slots,
+	                                   m.value, m.w, m.h, m.slots, d_flags + n_windows)) != PXZ_OK)
+		return rc;
+	if ((rc = pxz_splice_windows_device(h, scan.descs.data(), n_images, dev.data(), n_windows, ch, params, d_files, d_offsets, m.value, m.w, m.h, m.slots,
+	                                    d_flags, d_flags + n_windows, d + new_files_at, room, d_new_offs, nullptr)) != PXZ_OK)
+		return rc;
+	// all or nothing: the flags and the offsets first
+	std::vector<uint32_t> flags(2u * (size_t)n_windows);
+	std::vector<uint64_t> got((size_t)n_images + 1u);
+	PXZ_HIP(h, hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipMemcpyAsync(got.data(), d_new_offs, got.size() * 8u, hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	for (uint32_t k = 0; k < n_windows; ++k)
+		if (flags[k] | flags[n_windows + k])
+			return fail(h, PXZ_ERR_INVALID_ARG, "window %u: malformed .pixlzr file or record in what it reads of image %u (flags %u); nothing was written", k,
+			            windows[k].image, flags[k] | flags[n_windows + k]);
+	if (got[n_images] > room) return fail(h, PXZ_ERR_INTERNAL, "the spliced files exceed their bound");
+	std::memcpy(file_offsets, got.data(), got.size() * 8u);
+	if (!out || out_capacity < got[n_images])
+		return fail(h, PXZ_ERR_BUFFER_TOO_SMALL, "the patched files need %llu bytes, the buffer has %llu", (unsigned long long)got[n_images],
+		            (unsigned long long)(out ? out_capacity : 0));
+	PXZ_HIP(h, hipMemcpyAsync(out, d + new_files_at, got[n_images], hipMemcpyDeviceToHost, h->stream));
+	PXZ_HIP(h, hipStreamSynchronize(h->stream));
+	return PXZ_OK;
+}
+
 }  // extern "C"

@@ -726,6 +726,70 @@ struct WindowExpandArgs : TileResizeArgs {
 	uint32_t *window_flags;           // per window 1 for a covered tile whose stored size is invalid, or null
 };
 
+// patch_kernel (pxz_patch.hip, pxz_patch_windows_device): the covered tiles of the call's windows rebuilt at full size in LDS,
+// the windows' new pixels written over them, and each shrunk again, one tile per block.  r is the re-shrink's argument set over
+// the windows' flat tile space: r.v the shrink side (r.v.images and r.v.n_images are unused: the owners are the windows;
+// r.v.factor is unused: the factor is factor[0], where the shared tail reads it), r.x the expand side, r.image_flags unused.
+struct PatchArgs {
+	ReshrinkArgs r;
+	const WindowEntry *windows;       // offset and pitch describe the INPUT rectangle of new pixels at patch_base
+	uint32_t n_windows;
+	const uint8_t *patch_base;
+	uint32_t *window_flags;           // per window 1 for a covered tile whose stored size is invalid, or null
+	float factor[1];
+};
+
+// The splice of pxz_splice_windows_device (pxz_patch.hip): old files and the new covered tiles' records -> new files.  The host
+// knows the STRUCTURE of every output file -- a list of pieces in file order, each a byte span of the old files or of the staging
+// files (the hulls' tiles written by the varied writer, one file per window) -- and the device the LENGTHS: a piece runs between
+// two bounds, each of which a kernel turns into a byte offset.
+//   kFileStart, kFileEnd  a = image: the old file's first byte / the byte behind its last;
+//   kRow                  a = a window of the image, b = tile row r of the IMAGE, 0 .. rows: where row r starts in the old file (the
+//                         header, the line table and the lengths of the rows before r); r = rows: where the last row ends;
+//   kRecStart, kRecEnd    a = covered tile: the first byte of its old record ("block") / the byte behind its end marker, from rec_off
+//                         and rec_len as window_index_kernel left them (rec_off: the first op byte, 23 bytes into the record;
+//                         rec_len: the op bytes, 8 bytes of end marker behind them);
+//   kStageRow             a = window, b = covered row j, 0 .. crows: where row j of the window's staging file starts.
+struct SpliceBound {
+	static constexpr uint32_t kFileStart = 0, kFileEnd = 1, kRow = 2, kRecStart = 3, kRecEnd = 4, kStageRow = 5;
+	uint32_t kind, a, b;
+};
+struct SplicePiece {
+	SpliceBound lo, hi;          // [lo, hi) of the old files, or of the staging files when lo.kind == kStageRow
+	uint32_t image;              // the output file the piece belongs to
+	uint32_t first;              // 1: the first piece of its file
+};
+// one tile row of an image that a window touches: its new length is the old one, minus the old records of the covered tiles of
+// each window in it, plus that window's staging row; the windows are parts [part0, part0 + n_parts)
+struct SpliceRow {
+	uint32_t image, window, row;  // window: any window of the image (it carries the image's geometry)
+	uint32_t part0, n_parts;
+};
+struct SpliceRowPart {
+	uint32_t window, crow;        // covered row crow of the window: tiles tile0 + crow * ccols .. + ccols - 1
+};
+struct SpliceArgs {
+	const WindowEntry *windows;
+	uint32_t n_windows, n_images, n_tiles, n_pieces, n_rows;
+	const SplicePiece *pieces;
+	const SpliceRow *rows;
+	const SpliceRowPart *parts;
+	const uint8_t *files;                          // the old files
+	const unsigned long long *file_offsets;        // n_images + 1
+	const unsigned long long *rec_off;             // the reader's scratch, per covered tile
+	const uint32_t *rec_len;
+	const uint32_t *new_w, *new_h;                 // the new covered tiles' stored sizes
+	const uint32_t *reader_flags, *patch_flags;    // per window, or null
+	const uint8_t *stage;                          // the staging files
+	const unsigned long long *stage_offsets;       // n_windows + 1
+	unsigned long long stage_capacity;
+	unsigned long long *piece_src, *piece_len, *piece_dst;  // per piece (piece_dst: n_pieces + 1); piece_src bit 63: a staging span
+	uint32_t *image_flags;                         // per image: the OR of its windows' flags (zeroed before the first kernel)
+	uint8_t *out;
+	unsigned long long capacity;
+	unsigned long long *out_file_offsets;          // n_images + 1
+};
+
 // Decode at reduced scale (pxz_expand_varied_scaled_frames_device, pxz_expand_windows_scaled_device; pxz_scaled_expand.hip):
 // the stored tiles of a flat tile space resized to ceil(full / 2^shift) on each axis and written at (x0, y0) >> shift, the
 // shift being the owner's (an image's, or a window's).

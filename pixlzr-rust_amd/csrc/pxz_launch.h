@@ -73,6 +73,10 @@ hipError_t launch_reshrink_ladder(const ReshrinkLadderArgs &a, uint32_t channels
 // count) for blocks of bw x bh whose staged windows take wdw dwords, from the layout function the kernels and their launches
 // use (what the host holds against kLdsPerCu before it launches); 0xffffffff: a plane of bw * bh dwords above 64 KB
 uint32_t reshrink_lds_bytes(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw);
+// patch of pixel windows (pxz_patch.hip): one launch whatever the windows; the block's LDS is reshrink_kernel's (rung_channels 0)
+hipError_t launch_patch(const PatchArgs &a, uint32_t channels, uint32_t n_cus, hipStream_t stream);
+// the splice behind it (pxz_patch.hip): five launches whatever the images, windows and pieces; s.image_flags zeroed by the caller
+hipError_t launch_splice(const SpliceArgs &s, uint32_t n_cus, hipStream_t stream);
 // re-tile (pxz_retile.hip): one launch; and the LDS bytes of one block of retile_kernel for source blocks of sbw x sbh whose staged
 // windows take wdw dwords and destination blocks of dbw x dbh, from retile_lds (pxz_varied_tile.h), the layout function the kernel and
 // its launch use (what the host holds against kLdsPerCu before it launches); 0xffffffff: a plane of either block above 64 KB

@@ -112,6 +112,10 @@ struct HandleScratch {
 	std::map<std::pair<uint32_t, std::vector<uint32_t>>, ScaledExpandTables> scaled_tables;  // (filter, target / largest stored size pairs)
 	DeviceBuffer scaled;              // decode at reduced scale: the per-owner table
 	PinnedStaging scaled_table;       //   and its pinned staging
+	DeviceBuffer splice, splice_work, splice_stage;  // pxz_splice_windows_device: the piece, row and part tables; the pieces' offsets, the
+	                                  //   images' flags and the staging files' offsets; the staging files (the hulls' records)
+	PinnedStaging splice_table;       //   pinned staging of the tables
+	DeviceBuffer patch_host;          // the patch form: the files, the patches, the covered tiles, the flags and the new files' offsets
 	DeviceBuffer transcode_files, transcode_tiles;  // the transcode and archive forms: the files that come in; their tiles when the block size changes
 	DeviceBuffer fit;                 // pxz_fit_varied_ladder_device: the images' targets
 	PinnedStaging fit_targets;        //   and their pinned staging
@@ -183,6 +187,9 @@ uint32_t varied_n_tiles(const std::vector<pxz::VariedImage> &images);
 int window_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *w, uint32_t n_windows, uint32_t bw,
                 uint32_t bh, uint32_t channels, std::vector<pxz::WindowEntry> *entries, std::vector<uint32_t> *sides, uint32_t *n_rows);
 uint32_t window_n_tiles(const std::vector<pxz::WindowEntry> &entries);
+// window_plan with the patch's rule on top: the covered tile rectangles of one image are pairwise disjoint (pxz_patch_check)
+int patch_plan(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, const pxz_window *w, uint32_t n_windows, uint32_t bw, uint32_t bh,
+               uint32_t channels, std::vector<pxz::WindowEntry> *entries, std::vector<uint32_t> *sides, uint32_t *bad_window);
 // decode at reduced scale: the rules of one owner's scale (s | block, "image i" / "window k") and a window's alignment, and
 // the scaled size of a full-resolution extent
 int scaled_check_shift(pxz_handle *h, const char *who, uint32_t index, uint32_t shift, uint32_t bw, uint32_t bh);
