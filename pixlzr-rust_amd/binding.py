@@ -439,64 +439,49 @@ def _u32s(values):
     return (C.c_uint32 * max(len(values), 1))(*[int(v) for v in values])
 
 
-def reshrink_lds_bytes(bw, bh, mode, expand_filter):
-    """pxz_reshrink_lds_bytes: LDS bytes of one block of the re-shrink kernel (host only; above 163840: unsupported)."""
-    out = C.c_uint32(0)
-    rc = load_library().pxz_reshrink_lds_bytes(bw, bh, mode, expand_filter, C.byref(out))
+def _lds_query(entry, *args, out=None):
+    """one of the pxz_*_lds_bytes size queries (host only): what it answers.  out: a ctypes c_uint32 to write into."""
+    out = C.c_uint32(0) if out is None else out
+    rc = getattr(load_library(), entry)(*args, C.byref(out))
     if rc != 0:
         raise PxzError(rc)
     return out.value
+
+
+def reshrink_lds_bytes(bw, bh, mode, expand_filter):
+    """pxz_reshrink_lds_bytes: LDS bytes of one block of the re-shrink kernel (host only; above 163840: unsupported)."""
+    return _lds_query("pxz_reshrink_lds_bytes", bw, bh, mode, expand_filter)
 
 
 def retile_lds_bytes(src_bw, src_bh, bw, bh, mode, expand_filter):
     """pxz_retile_lds_bytes: LDS bytes of one block of the re-tile kernel for source blocks of src_bw x src_bh and destination
     blocks of bw x bh (host only; above 163840: unsupported)."""
-    out = C.c_uint32(0)
-    rc = load_library().pxz_retile_lds_bytes(src_bw, src_bh, bw, bh, mode, expand_filter, C.byref(out))
-    if rc != 0:
-        raise PxzError(rc)
-    return out.value
+    return _lds_query("pxz_retile_lds_bytes", src_bw, src_bh, bw, bh, mode, expand_filter)
 
 
 def retile_ladder_lds_bytes(src_bw, src_bh, bw, bh, channels, mode, expand_filter):
     """pxz_retile_ladder_lds_bytes: LDS bytes of one block of the re-tile ladder kernel for source blocks of src_bw x src_bh and
     destination blocks of bw x bh (host only; above 163840: unsupported)."""
-    out = C.c_uint32(0)
-    rc = load_library().pxz_retile_ladder_lds_bytes(src_bw, src_bh, bw, bh, channels, mode, expand_filter, C.byref(out))
-    if rc != 0:
-        raise PxzError(rc)
-    return out.value
+    return _lds_query("pxz_retile_ladder_lds_bytes", src_bw, src_bh, bw, bh, channels, mode, expand_filter)
 
 
 def reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter):
     """pxz_reshrink_ladder_lds_bytes: LDS bytes of one block of the re-shrink ladder kernel (host only; above 163840:
     unsupported)."""
-    out = C.c_uint32(0)
-    rc = load_library().pxz_reshrink_ladder_lds_bytes(bw, bh, channels, mode, expand_filter, C.byref(out))
-    if rc != 0:
-        raise PxzError(rc)
-    return out.value
+    return _lds_query("pxz_reshrink_ladder_lds_bytes", bw, bh, channels, mode, expand_filter)
 
 
 def retile_distortion_lds_bytes(src_bw, src_bh, bw, bh, channels, expand_filter, filter_up, out=None):
     """pxz_retile_distortion_lds_bytes: LDS bytes of one block of retile_distortion_varied_device for source blocks of
     src_bw x src_bh and destination blocks of bw x bh (host only; above 163840: unsupported).  out: a ctypes c_uint32 to write
     into (for the error cases)."""
-    out = C.c_uint32(0) if out is None else out
-    rc = load_library().pxz_retile_distortion_lds_bytes(src_bw, src_bh, bw, bh, channels, expand_filter, filter_up, C.byref(out))
-    if rc != 0:
-        raise PxzError(rc)
-    return out.value
+    return _lds_query("pxz_retile_distortion_lds_bytes", src_bw, src_bh, bw, bh, channels, expand_filter, filter_up, out=out)
 
 
 def reshrink_distortion_lds_bytes(bw, bh, channels, expand_filter, filter_up, out=None):
     """pxz_reshrink_distortion_lds_bytes: LDS bytes of a one-wave block of reshrink_distortion_varied_device (host only; above
     163840: unsupported).  out: a ctypes c_uint32 to write into (for the error cases)."""
-    out = C.c_uint32(0) if out is None else out
-    rc = load_library().pxz_reshrink_distortion_lds_bytes(bw, bh, channels, expand_filter, filter_up, C.byref(out))
-    if rc != 0:
-        raise PxzError(rc)
-    return out.value
+    return _lds_query("pxz_reshrink_distortion_lds_bytes", bw, bh, channels, expand_filter, filter_up, out=out)
 
 
 def file_header(data):
@@ -1023,6 +1008,41 @@ class Handle:
             raise err
         return result, flags[:n]
 
+    # ---- the archive calls: stored tiles to stored tiles ----
+    def _tiles_to_tiles(self, entry, sizes, channels, src_block, bw, bh, mode, filt, factor, expand_filter, ow, oh, slots, want_pixels, out,
+                        image_flags, ladder=None):
+        """The re-shrink, the re-tile and their ladders: the library's `entry` with src_block = (src_bw, src_bh) where the block
+        changes (else ()) and ladder = (factors, n_factors) where it has rungs (outputs [K, T] then, else [T]).  Allocates the
+        outputs that `out` does not bring, marshals, returns what the four wrappers return."""
+        import torch
+        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
+        rungs = ()
+        if ladder is not None:
+            fac = None if ladder[0] is None else np.ascontiguousarray(ladder[0], np.float32)
+            K = ladder[1] if ladder[1] is not None else (0 if fac is None else fac.size)
+            rungs = (_p(fac) if fac is not None and fac.size else None, K)
+        offs = None
+        if out is None:
+            offs = varied_layout(geoms, bw, bh)
+            shape = rungs[1:] + (int(offs[-1]),)
+            dev = ow.device
+            vals = torch.empty(shape, dtype=torch.float32, device=dev)
+            nw = torch.empty(shape, dtype=torch.int32, device=dev)
+            nh = torch.empty(shape, dtype=torch.int32, device=dev)
+            nslots = torch.empty(shape + (bw * bh * channels,), dtype=torch.uint8, device=dev) if want_pixels else None
+        else:
+            vals, nw, nh, nslots = out
+        pd = Params(bw, bh, mode, filt, factor, 0)
+        self.use_torch_stream()
+        self._check(getattr(self._L, entry)(
+            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, *src_block, C.byref(pd), expand_filter, *rungs,
+            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
+            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
+            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
+        if offs is None:
+            offs = varied_layout(geoms, bw, bh)
+        return offs, vals, nw, nh, nslots
+
     # ---- re-shrink: stored tiles to stored tiles ----
     def reshrink_varied_frames_device(self, sizes, channels, bw, bh, mode, filt, factor, expand_filter, ow, oh, slots,
                                       want_pixels=True, out=None, image_flags=None):
@@ -1031,29 +1051,8 @@ class Handle:
         images.  Returns (tile_offsets uint64[n+1], values[T], w[T], h[T], slots | None).  out: a 4-tuple of such tensors
         (slots may be None); its w, h and slots may be the inputs themselves (in place).  image_flags (int32[n] CUDA,
         optional) gets 0 | 1."""
-        import torch
-        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
-        offs = None
-        if out is None:
-            offs = varied_layout(geoms, bw, bh)
-            T = int(offs[-1])
-            dev = ow.device
-            vals = torch.empty(T, dtype=torch.float32, device=dev)
-            nw = torch.empty(T, dtype=torch.int32, device=dev)
-            nh = torch.empty(T, dtype=torch.int32, device=dev)
-            nslots = torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
-        else:
-            vals, nw, nh, nslots = out
-        pd = Params(bw, bh, mode, filt, factor, 0)
-        self.use_torch_stream()
-        self._check(self._L.pxz_reshrink_varied_frames_device(
-            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), expand_filter,
-            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
-            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
-            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
-        if offs is None:
-            offs = varied_layout(geoms, bw, bh)
-        return offs, vals, nw, nh, nslots
+        return self._tiles_to_tiles("pxz_reshrink_varied_frames_device", sizes, channels, (), bw, bh, mode, filt, factor, expand_filter, ow, oh,
+                                    slots, want_pixels, out, image_flags)
 
     def transcode_varied_files(self, files, bw, bh, mode, filt, factor, expand_filter, filter_byte=0, out=None):
         """pxz_transcode_varied_files: a list of .pixlzr files (bytes) of one channel count and block size -> the list of the
@@ -1092,29 +1091,8 @@ class Handle:
         filt, factor) at the block bw x bh, without the images.  Returns (tile_offsets uint64[n+1], values[T], w[T], h[T],
         slots[T, bw*bh*C] | None) in the varied layout at bw x bh.  out: a 4-tuple of such tensors (slots may be None), none of
         them an input.  image_flags (int32[n] CUDA, optional) gets 0 | 1."""
-        import torch
-        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
-        offs = None
-        if out is None:
-            offs = varied_layout(geoms, bw, bh)
-            T = int(offs[-1])
-            dev = ow.device
-            vals = torch.empty(T, dtype=torch.float32, device=dev)
-            nw = torch.empty(T, dtype=torch.int32, device=dev)
-            nh = torch.empty(T, dtype=torch.int32, device=dev)
-            nslots = torch.empty((T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
-        else:
-            vals, nw, nh, nslots = out
-        pd = Params(bw, bh, mode, filt, factor, 0)
-        self.use_torch_stream()
-        self._check(self._L.pxz_retile_varied_frames_device(
-            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, src_bw, src_bh, C.byref(pd), expand_filter,
-            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
-            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
-            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
-        if offs is None:
-            offs = varied_layout(geoms, bw, bh)
-        return offs, vals, nw, nh, nslots
+        return self._tiles_to_tiles("pxz_retile_varied_frames_device", sizes, channels, (src_bw, src_bh), bw, bh, mode, filt, factor,
+                                    expand_filter, ow, oh, slots, want_pixels, out, image_flags)
 
     # ---- re-tile ladder: stored tiles at one block size to stored tiles at another, at several factors ----
     def retile_varied_ladder_frames_device(self, sizes, channels, src_bw, src_bh, bw, bh, mode, filt, factors, expand_filter, ow, oh, slots,
@@ -1123,32 +1101,8 @@ class Handle:
         1..32 of them) in one launch.  Returns (tile_offsets uint64[n+1], values[K,T], w[K,T], h[K,T], slots[K,T,bw*bh*C] |
         None) in the varied layout at bw x bh; rung r equals retile_varied_frames_device(..., factors[r], ...).  out: a 4-tuple
         of such tensors (slots may be None), none of them an input.  factors None with n_factors passes a null pointer."""
-        import torch
-        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
-        fac = None if factors is None else np.ascontiguousarray(factors, np.float32)
-        K = n_factors if n_factors is not None else (0 if fac is None else fac.size)
-        offs = None
-        if out is None:
-            offs = varied_layout(geoms, bw, bh)
-            T = int(offs[-1])
-            dev = ow.device
-            vals = torch.empty((K, T), dtype=torch.float32, device=dev)
-            nw = torch.empty((K, T), dtype=torch.int32, device=dev)
-            nh = torch.empty((K, T), dtype=torch.int32, device=dev)
-            nslots = torch.empty((K, T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
-        else:
-            vals, nw, nh, nslots = out
-        pd = Params(bw, bh, mode, filt, 0.0, 0)
-        self.use_torch_stream()
-        self._check(self._L.pxz_retile_varied_ladder_frames_device(
-            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, src_bw, src_bh, C.byref(pd), expand_filter,
-            _p(fac) if fac is not None and fac.size else None, K,
-            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
-            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
-            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
-        if offs is None:
-            offs = varied_layout(geoms, bw, bh)
-        return offs, vals, nw, nh, nslots
+        return self._tiles_to_tiles("pxz_retile_varied_ladder_frames_device", sizes, channels, (src_bw, src_bh), bw, bh, mode, filt, 0.0,
+                                    expand_filter, ow, oh, slots, want_pixels, out, image_flags, ladder=(factors, n_factors))
 
     # ---- re-shrink ladder: stored tiles to stored tiles at several factors ----
     def reshrink_varied_ladder_frames_device(self, sizes, channels, bw, bh, mode, filt, factors, expand_filter, ow, oh, slots,
@@ -1158,32 +1112,8 @@ class Handle:
         slots[K,T,bw*bh*C] | None); rung r equals reshrink_varied_frames_device(..., factors[r], ...).  out: a 4-tuple of such
         tensors (slots may be None); ow, oh and slots may be rung 0 of its w, h and slots (in place).  factors None with
         n_factors passes a null pointer."""
-        import torch
-        geoms = [(w, h, w * channels, 0) for (w, h) in sizes]
-        fac = None if factors is None else np.ascontiguousarray(factors, np.float32)
-        K = n_factors if n_factors is not None else (0 if fac is None else fac.size)
-        offs = None
-        if out is None:
-            offs = varied_layout(geoms, bw, bh)
-            T = int(offs[-1])
-            dev = ow.device
-            vals = torch.empty((K, T), dtype=torch.float32, device=dev)
-            nw = torch.empty((K, T), dtype=torch.int32, device=dev)
-            nh = torch.empty((K, T), dtype=torch.int32, device=dev)
-            nslots = torch.empty((K, T, bw * bh * channels), dtype=torch.uint8, device=dev) if want_pixels else None
-        else:
-            vals, nw, nh, nslots = out
-        pd = Params(bw, bh, mode, filt, 0.0, 0)
-        self.use_torch_stream()
-        self._check(self._L.pxz_reshrink_varied_ladder_frames_device(
-            self._h, C.cast(image_descs(geoms), C.c_void_p), len(geoms), channels, C.byref(pd), expand_filter,
-            _p(fac) if fac is not None and fac.size else None, K,
-            C.c_void_p(ow.data_ptr()), C.c_void_p(oh.data_ptr()), C.c_void_p(slots.data_ptr()), C.c_void_p(vals.data_ptr()),
-            C.c_void_p(nw.data_ptr()), C.c_void_p(nh.data_ptr()), C.c_void_p(nslots.data_ptr()) if nslots is not None else None,
-            C.c_void_p(image_flags.data_ptr()) if image_flags is not None else None))
-        if offs is None:
-            offs = varied_layout(geoms, bw, bh)
-        return offs, vals, nw, nh, nslots
+        return self._tiles_to_tiles("pxz_reshrink_varied_ladder_frames_device", sizes, channels, (), bw, bh, mode, filt, 0.0, expand_filter,
+                                    ow, oh, slots, want_pixels, out, image_flags, ladder=(factors, n_factors))
 
     def transcode_varied_ladder_files(self, files, bw, bh, mode, filt, factors, expand_filter, filter_byte=0, out=None, sizes_only=False):
         """pxz_transcode_varied_ladder_files: transcode_varied_files at every factor of `factors` -> a list per rung of the
@@ -1649,6 +1579,28 @@ class Handle:
         return files, choice[:n], flags[:n]
 
     # ---- fit an archive to a budget ----
+    def _archive_distortion(self, entry, sizes, channels, src_block, bw, bh, expand_filter, filter_up, ref_w, ref_h, ref_slots, ow, oh, slots,
+                            want_tiles, out, image_flags, n_sets):
+        """both archive distortions: the library's `entry` with src_block = (src_bw, src_bh) where the block changes (else ())"""
+        import torch
+        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
+        n = len(geoms)
+        T = int(varied_layout([g[:4] for g in geoms], bw, bh)[-1]) if n and out is None else 0
+        K = n_sets if n_sets is not None else (ow.numel() // T if T else ow.shape[0])
+        if out is None:
+            dev = torch.device("cuda", self.device_id)
+            tile_sse = torch.empty((K, T, channels), dtype=torch.int64, device=dev) if want_tiles else None
+            image_sse = torch.empty((K, n, channels), dtype=torch.int64, device=dev)
+        else:
+            tile_sse, image_sse = out
+        pd = Params(bw, bh, 0, filter_up, 0.0, 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self.use_torch_stream()
+        self._check(getattr(self._L, entry)(
+            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, *src_block, C.byref(pd), expand_filter, K, ptr(ref_w),
+            ptr(ref_h), ptr(ref_slots), ptr(ow), ptr(oh), ptr(slots), ptr(tile_sse), ptr(image_sse), ptr(image_flags)))
+        return tile_sse, image_sse
+
     def reshrink_distortion_varied_device(self, sizes, channels, bw, bh, expand_filter, filter_up, ref_w, ref_h, ref_slots, ow, oh,
                                           slots, want_tiles=True, out=None, image_flags=None, n_sets=None):
         """pxz_reshrink_distortion_varied_device: sizes = [(width, height), ...] of the images; the archive's stored tiles
@@ -1657,24 +1609,8 @@ class Handle:
         (expand(reference, expand_filter) - expand(set, filter_up))^2.  Returns (tile_sse int64[K,T,C] | None, image_sse
         int64[K,n,C]); all-ones entries read as -1; image_flags (int32[n] CUDA, optional) gets 0 | 1.  out: such a pair.
         n_sets overrides what ow's shape says; None for a tensor passes a null pointer."""
-        import torch
-        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
-        n = len(geoms)
-        T = int(varied_layout([g[:4] for g in geoms], bw, bh)[-1]) if n and out is None else 0
-        K = n_sets if n_sets is not None else (ow.numel() // T if T else ow.shape[0])
-        if out is None:
-            dev = torch.device("cuda", self.device_id)
-            tile_sse = torch.empty((K, T, channels), dtype=torch.int64, device=dev) if want_tiles else None
-            image_sse = torch.empty((K, n, channels), dtype=torch.int64, device=dev)
-        else:
-            tile_sse, image_sse = out
-        pd = Params(bw, bh, 0, filter_up, 0.0, 0)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        self.use_torch_stream()
-        self._check(self._L.pxz_reshrink_distortion_varied_device(
-            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, C.byref(pd), expand_filter, K, ptr(ref_w),
-            ptr(ref_h), ptr(ref_slots), ptr(ow), ptr(oh), ptr(slots), ptr(tile_sse), ptr(image_sse), ptr(image_flags)))
-        return tile_sse, image_sse
+        return self._archive_distortion("pxz_reshrink_distortion_varied_device", sizes, channels, (), bw, bh, expand_filter, filter_up, ref_w,
+                                        ref_h, ref_slots, ow, oh, slots, want_tiles, out, image_flags, n_sets)
 
     def retile_distortion_varied_device(self, sizes, channels, src_bw, src_bh, bw, bh, expand_filter, filter_up, ref_w, ref_h,
                                         ref_slots, ow, oh, slots, want_tiles=True, out=None, image_flags=None, n_sets=None):
@@ -1683,24 +1619,8 @@ class Handle:
         stored versions of the tiles of the bw x bh grid (ow[K,T], oh[K,T], slots[K,T,bw*bh*C], as
         retile_varied_ladder_frames_device leaves its rungs).  Returns, out, image_flags and n_sets as there, T being the tiles
         of the bw x bh grid."""
-        import torch
-        geoms = [tuple(s) if len(s) > 2 else (s[0], s[1], s[0] * channels, 0) for s in sizes]
-        n = len(geoms)
-        T = int(varied_layout([g[:4] for g in geoms], bw, bh)[-1]) if n and out is None else 0
-        K = n_sets if n_sets is not None else (ow.numel() // T if T else ow.shape[0])
-        if out is None:
-            dev = torch.device("cuda", self.device_id)
-            tile_sse = torch.empty((K, T, channels), dtype=torch.int64, device=dev) if want_tiles else None
-            image_sse = torch.empty((K, n, channels), dtype=torch.int64, device=dev)
-        else:
-            tile_sse, image_sse = out
-        pd = Params(bw, bh, 0, filter_up, 0.0, 0)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        self.use_torch_stream()
-        self._check(self._L.pxz_retile_distortion_varied_device(
-            self._h, C.cast(image_descs(geoms), C.c_void_p) if n else None, n, channels, src_bw, src_bh, C.byref(pd), expand_filter, K,
-            ptr(ref_w), ptr(ref_h), ptr(ref_slots), ptr(ow), ptr(oh), ptr(slots), ptr(tile_sse), ptr(image_sse), ptr(image_flags)))
-        return tile_sse, image_sse
+        return self._archive_distortion("pxz_retile_distortion_varied_device", sizes, channels, (src_bw, src_bh), bw, bh, expand_filter,
+                                        filter_up, ref_w, ref_h, ref_slots, ow, oh, slots, want_tiles, out, image_flags, n_sets)
 
     def rate_distortion_retile_files(self, files, bw, bh, mode, filter_down, expand_filter, filter_up, factors):
         """pxz_rate_distortion_retile_files: rate_distortion_varied_files with bw x bh the NEW block size (the files' own comes

@@ -171,18 +171,6 @@ uint32_t varied_n_tiles(const std::vector<pxz::VariedImage> &images)
 // the covered tiles of a planned call
 uint32_t window_n_tiles(const std::vector<pxz::WindowEntry> &entries) { return entries.back().tile0 + entries.back().ccols * entries.back().crows; }
 
-// the one place that says whether the re-shrink kernels take a block: the LDS footprint (what the launch asks for) against the
-// CU's.  rung_channels: 0 for reshrink_kernel, the tiles' channel count for reshrink_ladder_kernel, whose footprint depends on it
-// (its resampled images)
-int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
-{
-	if (pxz::reshrink_lds_bytes(mode, bw, bh, rung_channels, wdw) > kLdsPerCu)
-		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "a re-shrink%s keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
-		            "bytes, the whole 160 KB (%ux%u)", rung_channels ? " ladder" : "", bw, bh);
-	return PXZ_OK;
-}
-
 // LDS bytes of a one-wave block of reshrink_distortion_kernel: the wave's image of the launch's own layout function beside the
 // images' first tiles at their largest (kVxImages dwords, pxz_device.h) -- what the entry point and the size query hold against
 // kLdsPerCu, so that a block the query admits is launched whatever n_images is
@@ -190,6 +178,47 @@ uint64_t reshrink_distortion_bytes(uint32_t bw, uint32_t bh, uint32_t wdw)
 {
 	const uint32_t dw = pxz::reshrink_distortion_tile_dw(bw, bh, wdw);
 	return dw == 0xffffffffu ? 0xffffffffull : (uint64_t)dw * 4u + 8192u;
+}
+
+// The LDS footprint of one block of each archive kernel, as its launch asks for it: one callable per kernel, (dwords of a staged
+// window of the expand side's tables, the same of the sets' tables -- the distortions alone have a second set) -> bytes.  What
+// says whether a kernel takes its blocks is its footprint against the CU's: each size query (archive_lds_query) and each
+// admission check (beyond_lds under the call's own text) holds one of these against kLdsPerCu, first with windows of 1 dword,
+// then with the real ones.  rung_channels: 0 for the one-factor kernel, the tiles' channel count for the ladder kernel, whose
+// footprint depends on it (its resampled images).
+static auto reshrink_footprint(uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels)
+{
+	return [=](uint32_t wdw, uint32_t) -> uint64_t { return pxz::reshrink_lds_bytes(mode, bw, bh, rung_channels, wdw); };
+}
+static auto retile_footprint(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t rung_channels)
+{
+	return [=](uint32_t wdw, uint32_t) -> uint64_t {
+		return rung_channels == 0u ? pxz::retile_lds_bytes(mode, sbw, sbh, dbw, dbh, wdw)
+		                           : pxz::retile_ladder_lds_bytes(mode, sbw, sbh, dbw, dbh, rung_channels, wdw);
+	};
+}
+static auto reshrink_distortion_footprint(uint32_t bw, uint32_t bh)  // (one stride for the windows of both sets: the wider)
+{
+	return [=](uint32_t wdw_ref, uint32_t wdw_set) -> uint64_t { return reshrink_distortion_bytes(bw, bh, std::max(wdw_ref, wdw_set)); };
+}
+static auto retile_distortion_footprint(uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh)
+{
+	return [=](uint32_t wdw_src, uint32_t wdw_set) -> uint64_t { return pxz::retile_distortion_lds_bytes(sbw, sbh, dbw, dbh, wdw_src, wdw_set); };
+}
+template <class Footprint>
+static bool beyond_lds(const Footprint &bytes, uint32_t wdw, uint32_t wdw_set = 1u)
+{
+	return bytes(wdw, wdw_set) > kLdsPerCu;
+}
+
+// whether the re-shrink kernels (and the patch, which is reshrink_kernel's block) take a block
+int reshrink_check_block(pxz_handle *h, uint32_t mode, uint32_t bw, uint32_t bh, uint32_t rung_channels, uint32_t wdw)
+{
+	if (beyond_lds(reshrink_footprint(mode, bw, bh, rung_channels), wdw))
+		return fail(h, PXZ_ERR_UNSUPPORTED,
+		            "a re-shrink%s keeps two planes of block_w*block_h dwords and the windows of both axes in LDS: block_w*block_h*4 must not exceed 65536 "
+		            "bytes, the whole 160 KB (%ux%u)", rung_channels ? " ladder" : "", bw, bh);
+	return PXZ_OK;
 }
 
 }  // namespace pxz_runtime
@@ -2198,19 +2227,15 @@ int get_varied_tables(pxz_handle *h, uint32_t filter, const std::vector<uint32_t
 	}, out);
 }
 
-// what varied_kernel and varied_ladder_kernel are told about a planned batch (a->images is varied_upload's)
-void varied_fill_args(pxz_handle *h, const std::vector<pxz::VariedImage> &images, uint32_t channels, const pxz_params *params,
-                      const VariedTables *vt, const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
-                      uint8_t *d_out_pixels, pxz::VariedArgs *a)
+// the shrink side of a flat tile space whoever owns its tiles: the block, the outputs, the tables and the thresholds (all that
+// pxz_patch_windows_device fills of a VariedArgs: its owners are windows, its tile count theirs, its factor PatchArgs')
+void varied_fill_shrink(pxz_handle *h, uint32_t channels, const pxz_params *params, const VariedTables *vt, float *d_block_value,
+                        uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, pxz::VariedArgs *a)
 {
-	a->base = d_base;
-	a->n_images = (uint32_t)images.size();
-	a->n_tiles = varied_n_tiles(images);
 	a->bw = params->block_w;
 	a->bh = params->block_h;
 	a->mode = params->mode;
 	a->filter = params->filter;
-	a->factor = params->factor;
 	a->value = d_block_value;
 	a->out_w = d_out_w;
 	a->out_h = d_out_h;
@@ -2222,6 +2247,18 @@ void varied_fill_args(pxz_handle *h, const std::vector<pxz::VariedImage> &images
 	a->sizes = vt->d_sizes;
 	a->coeffs = vt->d_coeffs;
 	std::memcpy(a->thresholds, h->thresholds, sizeof a->thresholds);
+}
+
+// what varied_kernel and varied_ladder_kernel are told about a planned batch (a->images is varied_upload's)
+void varied_fill_args(pxz_handle *h, const std::vector<pxz::VariedImage> &images, uint32_t channels, const pxz_params *params,
+                      const VariedTables *vt, const uint8_t *d_base, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
+                      uint8_t *d_out_pixels, pxz::VariedArgs *a)
+{
+	a->base = d_base;
+	a->n_images = (uint32_t)images.size();
+	a->n_tiles = varied_n_tiles(images);
+	a->factor = params->factor;
+	varied_fill_shrink(h, channels, params, vt, d_block_value, d_out_w, d_out_h, d_out_pixels, a);
 }
 
 // The varied writer behind both of its entry points, past their null checks.  pxz_encode_varied_frames_device: d_out and
@@ -2466,6 +2503,30 @@ int fresh_status(pxz_handle *h, uint32_t **status)
 	return PXZ_OK;
 }
 
+// what every expand-side launch is given to report into: the status word and the optional per-owner flags, both zeroed on the
+// stream in this order; *flags_arg is the launch's field for the flags
+int fresh_status_and_flags(pxz_handle *h, uint32_t **status, uint32_t *d_flags, size_t n_owners, uint32_t **flags_arg)
+{
+	int rc = fresh_status(h, status);
+	if (rc == PXZ_OK) rc = zero_owner_flags(h, d_flags, n_owners);
+	*flags_arg = d_flags;
+	return rc;
+}
+
+// the stored tiles a launch reads: their count, stored sizes and slots
+struct StoredTiles {
+	const uint32_t *w, *h;
+	const uint8_t *slots;
+};
+template <class Args>  // TileResizeArgs, or a struct that names the same fields
+void put_stored_tiles(Args *a, uint32_t n_tiles, const StoredTiles &tiles)
+{
+	a->n_tiles = n_tiles;
+	a->tile_w = tiles.w;
+	a->tile_h = tiles.h;
+	a->slots = tiles.slots;
+}
+
 // The reader's arguments for a flat tile space of n_tiles tiles over n_images files: one "frame" of n_tiles tiles, no
 // geometry of its own (every image, or every window, carries its own).  Sets the device and carves the reader's scratch.
 int flat_decode_args(pxz_handle *h, const pxz_params &p, uint32_t channels, uint32_t n_images, uint32_t n_tiles, const uint8_t *d_files,
@@ -2538,10 +2599,7 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 	pxz::VariedExpandArgs a{};
 	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a)) != PXZ_OK) return rc;
 	a.n_images = n_images;
-	a.n_tiles = varied_n_tiles(images);
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
+	put_stored_tiles(&a, varied_n_tiles(images), {d_tile_w, d_tile_h, d_slots});
 	a.base = d_base;
 	// a wave's image beyond LDS (with the images' first tiles beside it) lives in HBM, one per wave of the grid
 	if (varied_image_beyond_lds(a.tile_dw)) {
@@ -2550,9 +2608,7 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 		a.big_scratch = (uint32_t *)h->bigscratch.ptr;
 		a.big_waves = (uint32_t)waves;
 	}
-	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.image_flags = d_image_flags;
+	if ((rc = fresh_status_and_flags(h, &a.status, d_image_flags, n_images, &a.image_flags)) != PXZ_OK) return rc;
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_varied_expand(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
@@ -2560,76 +2616,205 @@ int pxz_expand_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 
 }  // extern "C"
 
-// ---- re-shrink of stored tiles (pxz_reshrink.hip): the reference CLI's pix_to_pix (src/bin/main.rs:233-265) ---------------
+// ---- the archive calls: stored tiles in, stored tiles out.  Re-shrink (pxz_reshrink.hip, pxz_reshrink_ladder.hip): the reference
+// CLI's pix_to_pix (src/bin/main.rs:233-265); re-tile (pxz_retile.hip, pxz_retile_ladder.hip): pix_to_pix with -b, a block size
+// that changes; their distortions stand further down, behind the fit.  DESIGN.md 8u has the shape of this path. -------------
 namespace {
 
-// both size queries: the footprint with the windows of expand_filter's tables
-int reshrink_lds_query(uint32_t block_w, uint32_t block_h, uint32_t rung_channels, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes)
+// one table set of a size query: the expand tables of `filter` for a block alone (no edges: a query knows of no image)
+struct BlockTables {
+	uint32_t bw, bh, filter;
+};
+
+// The size query of an archive kernel: its footprint with windows of 1 dword -- beyond the limit then, it is beyond it whatever
+// the windows take -- else with the real windows of its tables (set: the distortions' second table set, else null).
+template <class Footprint>
+int archive_lds_query(const Footprint &bytes, const BlockTables &expand, const BlockTables *set, uint32_t *lds_bytes)
 {
-	if (!lds_bytes || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, rung_channels, 1u);
-	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
-	pxz::VariedExpandTableSet s;
-	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::reshrink_lds_bytes(mode, block_w, block_h, rung_channels, varied_window_dw(s.max_window));
+	uint64_t v = bytes(1u, 1u);
+	if (v <= kLdsPerCu) {
+		const BlockTables *const of[2] = {&expand, set};
+		uint32_t wdw[2] = {1u, 1u};
+		for (int k = 0; k < 2 && of[k]; ++k) {
+			pxz::VariedExpandTableSet s;
+			if (!pxz::build_varied_expand_tables(unique_sides({of[k]->bw, of[k]->bh}), of[k]->filter, &s)) return PXZ_ERR_INVALID_ARG;
+			wdw[k] = varied_window_dw(s.max_window);
+		}
+		v = bytes(wdw[0], wdw[1]);
+	}
+	*lds_bytes = (uint32_t)std::min<uint64_t>(v, 0xffffffffull);
 	return PXZ_OK;
 }
 
-// Both device forms of the re-shrink behind one body, from the check of the device pointers on (h, params and the ladder's
-// factors are checked by the entry points): factors == nullptr is pxz_reshrink_varied_frames_device (params->factor,
-// reshrink_kernel; n_factors is not read); otherwise pxz_reshrink_varied_ladder_frames_device (n_factors rungs, reshrink_ladder_kernel, outputs
-// rung-major).
-int reshrink_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, const pxz_params *params,
-                    uint32_t expand_filter, const float *factors, uint32_t n_factors, const uint32_t *d_tile_w, const uint32_t *d_tile_h,
-                    const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels,
-                    uint32_t *d_image_flags)
+// what every archive call is handed about its batch
+struct ArchiveBatch {
+	const pxz_image_desc *descs;
+	uint32_t n_images, channels;
+	bool retile;               // the stored tiles that come in have a block of their own:
+	uint32_t src_bw, src_bh;   //   theirs (not read otherwise: they have params')
+	const pxz_params *params;  // the block of what goes out (a distortion: of the sets)
+	uint32_t expand_filter;
+};
+
+// A planned archive batch: its images in the layout of params' block (the destination: what goes out, or the sets) and, for a
+// re-tile, in the layout of the source block (the stored tiles that come in).
+struct ArchivePlan {
+	std::vector<pxz::VariedImage> images, src_images;
+	std::vector<uint32_t> sides, src_sides;
+	bool retile = false;
+	// the layout of the stored tiles that come in
+	const std::vector<uint32_t> &in_sides() const { return retile ? src_sides : sides; }
+	uint32_t n_tiles() const { return varied_n_tiles(images); }
+	uint32_t n_in_tiles() const { return varied_n_tiles(retile ? src_images : images); }
+};
+
+// The planning step of every archive call, from the check of the descriptors on: the layouts for p's block and mode (p: the
+// call's params as it reads them) and for the source block, and the rule that n_sets (rungs or sets: `noun`) of the
+// destination's tiles can be counted.
+int archive_plan(pxz_handle *h, const ArchiveBatch &b, const pxz_params &p, uint32_t n_sets, const char *noun, ArchivePlan *plan)
 {
-	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	if (channels != 3 && channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", channels);
-	const bool ladder = factors != nullptr;
-	pxz_params p = *params;
-	if (ladder) p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
-	const uint32_t rung_channels = ladder ? channels : 0u;
-	int rc = check_params(h, &p);
-	if (rc != PXZ_OK) return rc;
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, rung_channels, 1u)) != PXZ_OK) return rc;
-	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
+	if (!b.descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
+	if (b.n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
 	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
-	std::vector<pxz_image_desc> sized(n_images);
-	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
-	std::vector<pxz::VariedImage> images;
-	std::vector<uint32_t> sides;
-	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
-	if (ladder && (uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
+	std::vector<pxz_image_desc> sized(b.n_images);
+	for (uint32_t i = 0; i < b.n_images; ++i)
+		sized[i] = pxz_image_desc{b.descs[i].width, b.descs[i].height, b.descs[i].width * b.channels, b.descs[i].reserved, 0};
+	plan->retile = b.retile;
+	int rc = varied_plan(h, sized.data(), b.n_images, p.block_w, p.block_h, b.channels, p.mode, &plan->images, &plan->sides, nullptr);
+	if (rc != PXZ_OK) return rc;
+	if (b.retile && (rc = varied_plan(h, sized.data(), b.n_images, b.src_bw, b.src_bh, 0, 0, &plan->src_images, &plan->src_sides, nullptr)) != PXZ_OK)
+		return rc;
+	if ((uint64_t)n_sets * plan->n_tiles() > 0xffffffffull) return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u %s", n_sets, noun);
+	return PXZ_OK;
+}
+
+// the per-image tables of a plan in ONE upload: the destination layout's, then (re-tile) the source layout's behind it
+int archive_upload(pxz_handle *h, const ArchivePlan &plan, const pxz::VariedImage **d_images, const pxz::VariedImage **d_src_images)
+{
+	*d_src_images = nullptr;
+	if (!plan.retile) return varied_upload(h, plan.images, d_images);
+	std::vector<pxz::VariedImage> both = plan.images;
+	both.insert(both.end(), plan.src_images.begin(), plan.src_images.end());
+	const int rc = varied_upload(h, both, d_images);
+	if (rc == PXZ_OK) *d_src_images = *d_images + plan.images.size();
+	return rc;
+}
+
+// the expand side of an archive call: the geometry and filter the stored tiles that come in are expanded with
+pxz_params archive_expand_params(const ArchiveBatch &b, const pxz_params &p)
+{
+	pxz_params xp = p;
+	if (b.retile) {
+		xp.block_w = b.src_bw;
+		xp.block_h = b.src_bh;
+	}
+	xp.filter = b.expand_filter;
+	return xp;
+}
+
+// Two expand table sets for one launch: r for (xp, r_sides), u for (p, u_sides).
+// Both sets live in one bounded cache, and a set that is built into a full cache empties it first: r's set may have gone
+// with it.  Asked for again it is found, or built into a cache that holds the sets' tables alone -- both stay.  (Sets of one
+// filter and the same sides are one set: nothing to ask again.)
+int put_both_expand_tables(pxz_handle *h, uint32_t channels, const pxz_params &xp, const std::vector<uint32_t> &r_sides, const pxz_params &p,
+                           const std::vector<uint32_t> &u_sides, pxz::TileResizeArgs *r, pxz::TileResizeArgs *u)
+{
+	int rc = put_varied_expand_tables(h, xp, channels, r_sides, r);
+	if (rc == PXZ_OK) rc = put_varied_expand_tables(h, p, channels, u_sides, u);
+	if (rc == PXZ_OK && (xp.filter != p.filter || r_sides != u_sides)) rc = put_varied_expand_tables(h, xp, channels, r_sides, r);
+	return rc;
+}
+
+// The four tile-to-tile calls behind one body, from the check of the device pointers on (h, params and the ladder's factors are
+// checked by the entry points).  b.retile: re-tile, else re-shrink; factors == nullptr: the one-factor call (params->factor;
+// n_factors is not read), else the ladder (n_factors rungs, outputs rung-major in the destination layout).  LadderArgs is the
+// ladder's struct of the family; the one-factor call launches its .r.  admit(wdw): the family's footprint against LDS under
+// its own text; launch(la, d_src_images): the family's launch (the source layout's table is a field of the re-tile alone).
+//
+// Two things differ between the families without a reason that this file knows; they are inherited, and decided here only:
+//  - the re-tile holds its block against the varied calls' rule (varied_check_params: block_w*block_h*channels within 64 KB),
+//    the re-shrink does not.  The rule refuses nothing that the footprints admit (both keep a plane of block_w*block_h dwords
+//    within 64 KB: kRetileMaxPlaneBytes, kReshrinkMaxPlaneBytes), so what it changes is the text, and that it is reported
+//    before a zero source block or a bad expand_filter.
+//  - v.tile_bytes is one plane of dwords in every call but the re-shrink ladder, which keeps varied_fill_args' value.  Of the
+//    kernels launched from here reshrink_kernel alone reads the field.
+template <class LadderArgs, class Admit, class Launch>
+int archive_resize(pxz_handle *h, const ArchiveBatch &b, const float *factors, uint32_t n_factors, const StoredTiles &in, float *d_block_value,
+                   uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags, Admit admit, Launch launch)
+{
+	if (!in.w || !in.h || !in.slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const bool ladder = factors != nullptr;
+	pxz_params p = *b.params;
+	if (ladder) p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
+	int rc;
+	if (b.retile) {
+		if ((rc = varied_check_params(h, b.channels, &p)) != PXZ_OK) return rc;
+		if (b.src_bw == 0 || b.src_bh == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
+	} else {
+		if (b.channels != 3 && b.channels != 4) return fail(h, PXZ_ERR_INVALID_ARG, "channels must be 3 or 4, got %u", b.channels);
+		if ((rc = check_params(h, &p)) != PXZ_OK) return rc;
+	}
+	if (b.expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", b.expand_filter);
+	if ((rc = admit(1u)) != PXZ_OK) return rc;
+	ArchivePlan plan;
+	if ((rc = archive_plan(h, b, p, ladder ? n_factors : 1u, "rungs", &plan)) != PXZ_OK) return rc;
 	PXZ_HIP(h, hipSetDevice(h->device));
 	const VariedTables *vt = nullptr;
-	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
-	pxz::ReshrinkLadderArgs a{};  // (the one-factor call launches its a.r)
-	pxz_params xp = p;
-	xp.filter = expand_filter;
-	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r.x)) != PXZ_OK) return rc;
-	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, rung_channels, a.r.x.wdw)) != PXZ_OK) return rc;
-	if ((rc = fresh_status(h, &a.r.x.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.r.image_flags = d_image_flags;
-	if ((rc = varied_upload(h, images, &a.r.v.images)) != PXZ_OK) return rc;
-	varied_fill_args(h, images, channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.r.v);
-	a.r.x.n_tiles = a.r.v.n_tiles;
-	a.r.x.tile_w = d_tile_w;
-	a.r.x.tile_h = d_tile_h;
-	a.r.x.slots = d_slots;
-	if (!ladder) {
-		a.r.v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is expanded
-		PXZ_HIP(h, pxz::launch_reshrink(a.r, channels, h->n_cus, h->stream));
-		return PXZ_OK;
+	if ((rc = get_varied_tables(h, p.filter, plan.sides, &vt)) != PXZ_OK) return rc;
+	LadderArgs la{};
+	auto &a = la.r;
+	if ((rc = put_varied_expand_tables(h, archive_expand_params(b, p), b.channels, plan.in_sides(), &a.x)) != PXZ_OK) return rc;
+	if ((rc = admit(a.x.wdw)) != PXZ_OK) return rc;
+	if ((rc = fresh_status_and_flags(h, &a.x.status, d_image_flags, b.n_images, &a.image_flags)) != PXZ_OK) return rc;
+	const pxz::VariedImage *d_src_images = nullptr;
+	if ((rc = archive_upload(h, plan, &a.v.images, &d_src_images)) != PXZ_OK) return rc;
+	varied_fill_args(h, plan.images, b.channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.v);
+	if (b.retile || !ladder) a.v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is put together
+	put_stored_tiles(&a.x, plan.n_in_tiles(), in);
+	if (ladder) {
+		la.n_factors = n_factors;
+		std::memcpy(la.factors, factors, n_factors * sizeof(float));
 	}
-	a.n_factors = n_factors;
-	std::memcpy(a.factors, factors, n_factors * sizeof(float));
-	PXZ_HIP(h, pxz::launch_reshrink_ladder(a, channels, h->n_cus, h->stream));
-	return PXZ_OK;
+	return launch(la, d_src_images);
+}
+
+int reshrink_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, const pxz_params *params,
+                    uint32_t expand_filter, const float *factors, uint32_t n_factors, const StoredTiles &in, float *d_block_value, uint32_t *d_out_w,
+                    uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	const ArchiveBatch b{descs, n_images, channels, false, 0u, 0u, params, expand_filter};
+	return archive_resize<pxz::ReshrinkLadderArgs>(
+	    h, b, factors, n_factors, in, d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags,
+	    [&](uint32_t wdw) { return reshrink_check_block(h, params->mode, params->block_w, params->block_h, factors ? channels : 0u, wdw); },
+	    [&](const pxz::ReshrinkLadderArgs &a, const pxz::VariedImage *) {
+		    if (factors) PXZ_HIP(h, pxz::launch_reshrink_ladder(a, channels, h->n_cus, h->stream));
+		    else PXZ_HIP(h, pxz::launch_reshrink(a.r, channels, h->n_cus, h->stream));
+		    return (int)PXZ_OK;
+	    });
+}
+
+int retile_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, uint32_t src_block_w, uint32_t src_block_h,
+                  const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors, const StoredTiles &in,
+                  float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, uint32_t *d_image_flags)
+{
+	const ArchiveBatch b{descs, n_images, channels, true, src_block_w, src_block_h, params, expand_filter};
+	return archive_resize<pxz::RetileLadderArgs>(
+	    h, b, factors, n_factors, in, d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags,
+	    [&](uint32_t wdw) {
+		    if (beyond_lds(retile_footprint(params->mode, src_block_w, src_block_h, params->block_w, params->block_h, factors ? channels : 0u), wdw))
+			    return fail(h, PXZ_ERR_UNSUPPORTED,
+			                "a re-tile keeps a %ux%u tile image (a dword per pixel), the staged parts of %ux%u source tiles and the source windows in LDS: "
+			                "they exceed a block's 160 KB (%s)", params->block_w, params->block_h, src_block_w, src_block_h,
+			                factors ? "pxz_retile_ladder_lds_bytes" : "pxz_retile_lds_bytes");
+		    return (int)PXZ_OK;
+	    },
+	    [&](pxz::RetileLadderArgs &la, const pxz::VariedImage *d_src_images) {
+		    pxz::RetileArgs &a = la.r;
+		    a.src_images = d_src_images;
+		    if (factors) PXZ_HIP(h, pxz::launch_retile_ladder(la, channels, h->n_cus, h->stream));
+		    else PXZ_HIP(h, pxz::launch_retile(a, channels, h->n_cus, h->stream));
+		    return (int)PXZ_OK;
+	    });
 }
 
 }  // namespace
@@ -2638,14 +2823,15 @@ extern "C" {
 
 int pxz_reshrink_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter, uint32_t *lds_bytes)
 {
-	return reshrink_lds_query(block_w, block_h, 0u, mode, expand_filter, lds_bytes);
+	if (!lds_bytes || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
+	return archive_lds_query(reshrink_footprint(mode, block_w, block_h, 0u), {block_w, block_h, expand_filter}, nullptr, lds_bytes);
 }
 
 int pxz_reshrink_ladder_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode, uint32_t expand_filter,
                                   uint32_t *lds_bytes)
 {
-	if (channels != 3 && channels != 4) return PXZ_ERR_INVALID_ARG;
-	return reshrink_lds_query(block_w, block_h, channels, mode, expand_filter, lds_bytes);
+	if (!lds_bytes || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || mode > 1 || expand_filter > 4) return PXZ_ERR_INVALID_ARG;
+	return archive_lds_query(reshrink_footprint(mode, block_w, block_h, channels), {block_w, block_h, expand_filter}, nullptr, lds_bytes);
 }
 
 int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -2655,7 +2841,7 @@ int pxz_reshrink_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
-	return reshrink_varied(h, descs, n_images, channels, params, expand_filter, nullptr, 0u, d_tile_w, d_tile_h, d_slots, d_block_value, d_out_w,
+	return reshrink_varied(h, descs, n_images, channels, params, expand_filter, nullptr, 0u, {d_tile_w, d_tile_h, d_slots}, d_block_value, d_out_w,
 	                       d_out_h, d_out_pixels, d_image_flags);
 }
 
@@ -2669,127 +2855,27 @@ int pxz_reshrink_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
 	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
 	if (rc != PXZ_OK) return rc;
-	return reshrink_varied(h, descs, n_images, channels, params, expand_filter, factors, n_factors, d_tile_w, d_tile_h, d_slots, d_block_value,
+	return reshrink_varied(h, descs, n_images, channels, params, expand_filter, factors, n_factors, {d_tile_w, d_tile_h, d_slots}, d_block_value,
 	                       d_out_w, d_out_h, d_out_pixels, d_image_flags);
 }
-
-}  // extern "C"
-
-// ---- re-tile of stored tiles (pxz_retile.hip, pxz_retile_ladder.hip): pix_to_pix with -b, a block size that changes -------
-namespace {
-
-// the footprint of one block for a pair of blocks whose staged windows take wdw dwords: retile_kernel's (rung_channels == 0) or
-// retile_ladder_kernel's for that channel count
-uint32_t retile_footprint(uint32_t mode, uint32_t sbw, uint32_t sbh, uint32_t dbw, uint32_t dbh, uint32_t rung_channels, uint32_t wdw)
-{
-	return rung_channels == 0u ? pxz::retile_lds_bytes(mode, sbw, sbh, dbw, dbh, wdw)
-	                           : pxz::retile_ladder_lds_bytes(mode, sbw, sbh, dbw, dbh, rung_channels, wdw);
-}
-
-// both size queries: the footprint with the windows of expand_filter's tables
-int retile_lds_query(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t rung_channels, uint32_t mode,
-                     uint32_t expand_filter, uint32_t *lds_bytes)
-{
-	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4)
-		return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = retile_footprint(mode, src_block_w, src_block_h, block_w, block_h, rung_channels, 1u);
-	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
-	pxz::VariedExpandTableSet s;
-	if (!pxz::build_varied_expand_tables(unique_sides({src_block_w, src_block_h}), expand_filter, &s)) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = retile_footprint(mode, src_block_w, src_block_h, block_w, block_h, rung_channels, varied_window_dw(s.max_window));
-	return PXZ_OK;
-}
-
-// Both device forms of the re-tile behind one body, from the check of the device pointers on (h, params and the ladder's factors
-// are checked by the entry points): factors == nullptr is pxz_retile_varied_frames_device (params->factor, retile_kernel;
-// n_factors is not read); otherwise pxz_retile_varied_ladder_frames_device (n_factors rungs, retile_ladder_kernel, outputs
-// rung-major in the destination layout).
-int retile_varied(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels, uint32_t src_block_w, uint32_t src_block_h,
-                  const pxz_params *params, uint32_t expand_filter, const float *factors, uint32_t n_factors, const uint32_t *d_tile_w,
-                  const uint32_t *d_tile_h, const uint8_t *d_slots, float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h,
-                  uint8_t *d_out_pixels, uint32_t *d_image_flags)
-{
-	if (!d_tile_w || !d_tile_h || !d_slots || !d_block_value || !d_out_w || !d_out_h) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	const bool ladder = factors != nullptr;
-	pxz_params p = *params;
-	if (ladder) p.factor = 1.0f;  // (a rung's factor enters nothing but its level)
-	const uint32_t rung_channels = ladder ? channels : 0u;
-	int rc = varied_check_params(h, channels, &p);
-	if (rc != PXZ_OK) return rc;
-	if (src_block_w == 0 || src_block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	// the one place that says whether the kernel takes a pair of blocks: its LDS footprint against the CU's
-	auto check_pair = [&](uint32_t wdw) {
-		if (retile_footprint(p.mode, src_block_w, src_block_h, p.block_w, p.block_h, rung_channels, wdw) > kLdsPerCu)
-			return fail(h, PXZ_ERR_UNSUPPORTED,
-			            "a re-tile keeps a %ux%u tile image (a dword per pixel), the staged parts of %ux%u source tiles and the source windows in LDS: "
-			            "they exceed a block's 160 KB (%s)", p.block_w, p.block_h, src_block_w, src_block_h,
-			            ladder ? "pxz_retile_ladder_lds_bytes" : "pxz_retile_lds_bytes");
-		return (int)PXZ_OK;
-	};
-	if ((rc = check_pair(1u)) != PXZ_OK) return rc;
-	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
-	std::vector<pxz_image_desc> sized(n_images);
-	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
-	std::vector<pxz::VariedImage> images, src_images;
-	std::vector<uint32_t> sides, src_sides;
-	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, p.mode, &images, &sides, nullptr)) != PXZ_OK) return rc;
-	if ((rc = varied_plan(h, sized.data(), n_images, src_block_w, src_block_h, 0, 0, &src_images, &src_sides, nullptr)) != PXZ_OK) return rc;
-	if (ladder && (uint64_t)n_factors * varied_n_tiles(images) > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u rungs", n_factors);
-	PXZ_HIP(h, hipSetDevice(h->device));
-	const VariedTables *vt = nullptr;
-	if ((rc = get_varied_tables(h, p.filter, sides, &vt)) != PXZ_OK) return rc;
-	pxz::RetileLadderArgs la{};  // (the one-factor call launches its la.r)
-	pxz::RetileArgs &a = la.r;
-	pxz_params xp = p;  // the expand side: the source geometry
-	xp.block_w = src_block_w;
-	xp.block_h = src_block_h;
-	xp.filter = expand_filter;
-	if ((rc = put_varied_expand_tables(h, xp, channels, src_sides, &a.x)) != PXZ_OK) return rc;
-	if ((rc = check_pair(a.x.wdw)) != PXZ_OK) return rc;
-	if ((rc = fresh_status(h, &a.x.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.image_flags = d_image_flags;
-	// both per-image tables in one upload: the destination layout's, then the source layout's
-	const uint32_t n_src_tiles = varied_n_tiles(src_images);
-	std::vector<pxz::VariedImage> both = images;
-	both.insert(both.end(), src_images.begin(), src_images.end());
-	if ((rc = varied_upload(h, both, &a.v.images)) != PXZ_OK) return rc;
-	a.src_images = a.v.images + n_images;
-	varied_fill_args(h, images, channels, &p, vt, nullptr, d_block_value, d_out_w, d_out_h, d_out_pixels, &a.v);
-	a.v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane: a dword per pixel while the tile is assembled
-	a.x.n_tiles = n_src_tiles;
-	a.x.tile_w = d_tile_w;
-	a.x.tile_h = d_tile_h;
-	a.x.slots = d_slots;
-	if (!ladder) {
-		PXZ_HIP(h, pxz::launch_retile(a, channels, h->n_cus, h->stream));
-		return PXZ_OK;
-	}
-	la.n_factors = n_factors;
-	std::memcpy(la.factors, factors, n_factors * sizeof(float));
-	PXZ_HIP(h, pxz::launch_retile_ladder(la, channels, h->n_cus, h->stream));
-	return PXZ_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int pxz_retile_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t mode, uint32_t expand_filter,
                          uint32_t *lds_bytes)
 {
-	return retile_lds_query(src_block_w, src_block_h, block_w, block_h, 0u, mode, expand_filter, lds_bytes);
+	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || mode > 1 || expand_filter > 4)
+		return PXZ_ERR_INVALID_ARG;
+	return archive_lds_query(retile_footprint(mode, src_block_w, src_block_h, block_w, block_h, 0u), {src_block_w, src_block_h, expand_filter}, nullptr,
+	                         lds_bytes);
 }
 
 int pxz_retile_ladder_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t mode,
                                 uint32_t expand_filter, uint32_t *lds_bytes)
 {
-	if (channels != 3 && channels != 4) return PXZ_ERR_INVALID_ARG;
-	return retile_lds_query(src_block_w, src_block_h, block_w, block_h, channels, mode, expand_filter, lds_bytes);
+	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || mode > 1 ||
+	    expand_filter > 4)
+		return PXZ_ERR_INVALID_ARG;
+	return archive_lds_query(retile_footprint(mode, src_block_w, src_block_h, block_w, block_h, channels), {src_block_w, src_block_h, expand_filter},
+	                         nullptr, lds_bytes);
 }
 
 int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -2799,7 +2885,7 @@ int pxz_retile_varied_frames_device(pxz_handle *h, const pxz_image_desc *descs, 
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
-	return retile_varied(h, descs, n_images, channels, src_block_w, src_block_h, params, expand_filter, nullptr, 0u, d_tile_w, d_tile_h, d_slots,
+	return retile_varied(h, descs, n_images, channels, src_block_w, src_block_h, params, expand_filter, nullptr, 0u, {d_tile_w, d_tile_h, d_slots},
 	                     d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags);
 }
 
@@ -2813,8 +2899,8 @@ int pxz_retile_varied_ladder_frames_device(pxz_handle *h, const pxz_image_desc *
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
 	const int rc = check_factors(h, factors, n_factors, PXZ_VARIED_LADDER_MAX_RUNGS);
 	if (rc != PXZ_OK) return rc;
-	return retile_varied(h, descs, n_images, channels, src_block_w, src_block_h, params, expand_filter, factors, n_factors, d_tile_w, d_tile_h,
-	                     d_slots, d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags);
+	return retile_varied(h, descs, n_images, channels, src_block_w, src_block_h, params, expand_filter, factors, n_factors,
+	                     {d_tile_w, d_tile_h, d_slots}, d_block_value, d_out_w, d_out_h, d_out_pixels, d_image_flags);
 }
 
 }  // extern "C"
@@ -2833,17 +2919,12 @@ int distortion_launch(pxz_handle *h, const std::vector<pxz::VariedImage> &images
 	int rc = put_varied_expand_tables(h, p, channels, sides, &a, true);
 	if (rc != PXZ_OK) return rc;
 	a.n_images = (uint32_t)images.size();
-	a.n_tiles = varied_n_tiles(images);
 	a.n_sets = n_sets;
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
+	put_stored_tiles(&a, varied_n_tiles(images), {d_tile_w, d_tile_h, d_slots});
 	a.base = d_base;
 	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
 	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
-	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, images.size())) != PXZ_OK) return rc;
-	a.image_flags = d_image_flags;
+	if ((rc = fresh_status_and_flags(h, &a.status, d_image_flags, images.size(), &a.image_flags)) != PXZ_OK) return rc;
 	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * images.size() * channels * 8u, h->stream));
 	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_distortion(a, channels, h->n_cus, h->stream));
@@ -3136,24 +3217,62 @@ int pxz_gather_varied_tile_rungs_device(pxz_handle *h, const pxz_image_desc *des
 	return PXZ_OK;
 }
 
-// ---- fit an archive to a budget: the error of re-shrunk tiles against the archive's own (pxz_reshrink_distortion.hip) -------
+}  // extern "C"
+
+// ---- fit an archive to a budget, at its own block size or a new one: the error of re-shrunk or re-tiled tiles against the
+// archive's own (pxz_reshrink_distortion.hip, pxz_retile_distortion.hip) ------------------------------------------------------
+namespace {
+
+// Both archive distortions behind one body, from the check of the device pointers on: the archive's stored tiles (ref; b.retile:
+// in the layout of the source block) against n_sets stored versions (sets) of the tiles of params' block.  Args is the
+// kernel's struct; admit(wdw_ref, wdw_set): its footprint against LDS under its own text; launch(a, d_src_images): its launch.
+template <class Args, class Admit, class Launch>
+int archive_distortion(pxz_handle *h, const ArchiveBatch &b, uint32_t n_sets, const StoredTiles &ref, const StoredTiles &sets, uint64_t *d_tile_sse,
+                       uint64_t *d_image_sse, uint32_t *d_image_flags, Admit admit, Launch launch)
+{
+	if (!ref.w || !ref.h || !ref.slots || !sets.w || !sets.h || !sets.slots || !d_image_sse) return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
+	const uint32_t n_images = b.n_images, channels = b.channels;
+	const pxz_params p = decode_side_params(b.params, true);
+	int rc = varied_check_params(h, channels, &p);
+	if (rc != PXZ_OK) return rc;
+	if (b.retile && (b.src_bw == 0 || b.src_bh == 0)) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
+	if (n_sets == 0) return fail(h, PXZ_ERR_INVALID_ARG, "n_sets must be at least 1");
+	if (b.expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", b.expand_filter);
+	// (each call's own order: the re-tile holds its blocks against LDS before it looks at the batch, the re-shrink behind that)
+	if (b.retile && (rc = admit(1u, 1u)) != PXZ_OK) return rc;
+	ArchivePlan plan;
+	if ((rc = archive_plan(h, b, p, n_sets, "sets", &plan)) != PXZ_OK) return rc;
+	if (!b.retile && (rc = admit(1u, 1u)) != PXZ_OK) return rc;
+	PXZ_HIP(h, hipSetDevice(h->device));
+	Args a{};
+	if ((rc = put_both_expand_tables(h, channels, archive_expand_params(b, p), plan.in_sides(), p, plan.sides, &a.r, &a.u)) != PXZ_OK) return rc;
+	if ((rc = admit(a.r.wdw, a.u.wdw)) != PXZ_OK) return rc;
+	a.n_images = n_images;
+	a.n_tiles = plan.n_tiles();
+	a.n_sets = n_sets;
+	put_stored_tiles(&a.r, plan.n_in_tiles(), ref);
+	put_stored_tiles(&a.u, a.n_tiles, sets);
+	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
+	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
+	if ((rc = fresh_status_and_flags(h, &a.r.status, d_image_flags, n_images, &a.image_flags)) != PXZ_OK) return rc;
+	a.u.status = a.r.status;
+	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * n_images * channels * 8u, h->stream));
+	const pxz::VariedImage *d_src_images = nullptr;
+	if ((rc = archive_upload(h, plan, &a.images, &d_src_images)) != PXZ_OK) return rc;
+	return launch(a, d_src_images);
+}
+
+}  // namespace
+
+extern "C" {
+
 int pxz_reshrink_distortion_lds_bytes(uint32_t block_w, uint32_t block_h, uint32_t channels, uint32_t expand_filter, uint32_t filter_up,
                                       uint32_t *lds_bytes)
 {
 	if (!lds_bytes || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || expand_filter > 4 || filter_up > 4)
 		return PXZ_ERR_INVALID_ARG;
-	uint64_t bytes = reshrink_distortion_bytes(block_w, block_h, 1u);
-	if (bytes <= kLdsPerCu) {  // (else: beyond the limit whatever the windows take)
-		uint32_t wdw = 0;
-		for (const uint32_t filter : {expand_filter, filter_up}) {
-			pxz::VariedExpandTableSet s;
-			if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), filter, &s)) return PXZ_ERR_INVALID_ARG;
-			wdw = std::max(wdw, varied_window_dw(s.max_window));
-		}
-		bytes = reshrink_distortion_bytes(block_w, block_h, wdw);
-	}
-	*lds_bytes = (uint32_t)std::min<uint64_t>(bytes, 0xffffffffull);
-	return PXZ_OK;
+	const BlockTables set{block_w, block_h, filter_up};
+	return archive_lds_query(reshrink_distortion_footprint(block_w, block_h), {block_w, block_h, expand_filter}, &set, lds_bytes);
 }
 
 int pxz_reshrink_distortion_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -3164,80 +3283,34 @@ int pxz_reshrink_distortion_varied_device(pxz_handle *h, const pxz_image_desc *d
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
-	if (!d_ref_w || !d_ref_h || !d_ref_slots || !d_tile_w || !d_tile_h || !d_slots || !d_image_sse)
-		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	const pxz_params p = decode_side_params(params, true);
-	int rc = varied_check_params(h, channels, &p);
-	if (rc != PXZ_OK) return rc;
-	if (n_sets == 0) return fail(h, PXZ_ERR_INVALID_ARG, "n_sets must be at least 1");
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
-	std::vector<pxz_image_desc> sized(n_images);
-	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
-	std::vector<pxz::VariedImage> images;
-	std::vector<uint32_t> sides;
-	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
-	if ((uint64_t)n_sets * varied_n_tiles(images) > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u sets", n_sets);
-	auto beyond = [&](uint32_t wdw) -> int {
-		const uint64_t bytes = reshrink_distortion_bytes(p.block_w, p.block_h, wdw);
-		if (bytes <= kLdsPerCu) return PXZ_OK;
-		return fail(h, PXZ_ERR_UNSUPPORTED,
-		            "a wave keeps three planes of block_w*block_h dwords and the windows of both axes in LDS: %llu bytes exceed the %u a block has (%ux%u)",
-		            (unsigned long long)bytes, kLdsPerCu, p.block_w, p.block_h);
-	};
-	if ((rc = beyond(1u)) != PXZ_OK) return rc;
-	PXZ_HIP(h, hipSetDevice(h->device));
-	pxz::ReshrinkDistortionArgs a{};
-	pxz_params xp = p;
-	xp.filter = expand_filter;
-	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r)) != PXZ_OK) return rc;
-	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a.u)) != PXZ_OK) return rc;
-	// Both sets live in one bounded cache, and a set that is built into a full cache empties it first: the reference's set may
-	// have gone with it.  Asked for again it is found, or built into a cache that holds the sets' tables alone -- both stay.
-	if (expand_filter != p.filter && (rc = put_varied_expand_tables(h, xp, channels, sides, &a.r)) != PXZ_OK) return rc;
-	a.wdw = std::max(a.r.wdw, a.u.wdw);
-	if ((rc = beyond(a.wdw)) != PXZ_OK) return rc;
-	a.tile_dw = pxz::reshrink_distortion_tile_dw(p.block_w, p.block_h, a.wdw);
-	a.n_images = n_images;
-	a.n_tiles = varied_n_tiles(images);
-	a.n_sets = n_sets;
-	a.r.n_tiles = a.u.n_tiles = a.n_tiles;
-	a.r.tile_w = d_ref_w;
-	a.r.tile_h = d_ref_h;
-	a.r.slots = d_ref_slots;
-	a.u.tile_w = d_tile_w;
-	a.u.tile_h = d_tile_h;
-	a.u.slots = d_slots;
-	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
-	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
-	if ((rc = fresh_status(h, &a.r.status)) != PXZ_OK) return rc;
-	a.u.status = a.r.status;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.image_flags = d_image_flags;
-	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * n_images * channels * 8u, h->stream));
-	if ((rc = varied_upload(h, images, &a.images)) != PXZ_OK) return rc;
-	PXZ_HIP(h, pxz::launch_reshrink_distortion(a, channels, h->n_cus, h->stream));
-	return PXZ_OK;
+	const ArchiveBatch b{descs, n_images, channels, false, 0u, 0u, params, expand_filter};
+	return archive_distortion<pxz::ReshrinkDistortionArgs>(
+	    h, b, n_sets, {d_ref_w, d_ref_h, d_ref_slots}, {d_tile_w, d_tile_h, d_slots}, d_tile_sse, d_image_sse, d_image_flags,
+	    [&](uint32_t wdw_ref, uint32_t wdw_set) {
+		    const auto bytes = reshrink_distortion_footprint(params->block_w, params->block_h);
+		    if (beyond_lds(bytes, wdw_ref, wdw_set))
+			    return fail(h, PXZ_ERR_UNSUPPORTED,
+			                "a wave keeps three planes of block_w*block_h dwords and the windows of both axes in LDS: %llu bytes exceed the %u a block has (%ux%u)",
+			                (unsigned long long)bytes(wdw_ref, wdw_set), kLdsPerCu, params->block_w, params->block_h);
+		    return (int)PXZ_OK;
+	    },
+	    [&](pxz::ReshrinkDistortionArgs &a, const pxz::VariedImage *) {
+		    a.wdw = std::max(a.r.wdw, a.u.wdw);
+		    a.tile_dw = pxz::reshrink_distortion_tile_dw(params->block_w, params->block_h, a.wdw);
+		    PXZ_HIP(h, pxz::launch_reshrink_distortion(a, channels, h->n_cus, h->stream));
+		    return (int)PXZ_OK;
+	    });
 }
 
-// ---- fit an archive to a budget at a new block size: the error of re-tiled tiles against the archive (pxz_retile_distortion.hip)
 int pxz_retile_distortion_lds_bytes(uint32_t src_block_w, uint32_t src_block_h, uint32_t block_w, uint32_t block_h, uint32_t channels,
                                     uint32_t expand_filter, uint32_t filter_up, uint32_t *lds_bytes)
 {
 	if (!lds_bytes || src_block_w == 0 || src_block_h == 0 || block_w == 0 || block_h == 0 || (channels != 3 && channels != 4) || expand_filter > 4 ||
 	    filter_up > 4)
 		return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::retile_distortion_lds_bytes(src_block_w, src_block_h, block_w, block_h, 1u, 1u);
-	if (*lds_bytes > kLdsPerCu) return PXZ_OK;  // (beyond the limit whatever the windows take)
-	pxz::VariedExpandTableSet rs, us;
-	if (!pxz::build_varied_expand_tables(unique_sides({src_block_w, src_block_h}), expand_filter, &rs)) return PXZ_ERR_INVALID_ARG;
-	if (!pxz::build_varied_expand_tables(unique_sides({block_w, block_h}), filter_up, &us)) return PXZ_ERR_INVALID_ARG;
-	*lds_bytes = pxz::retile_distortion_lds_bytes(src_block_w, src_block_h, block_w, block_h, varied_window_dw(rs.max_window),
-	                                              varied_window_dw(us.max_window));
-	return PXZ_OK;
+	const BlockTables set{block_w, block_h, filter_up};
+	return archive_lds_query(retile_distortion_footprint(src_block_w, src_block_h, block_w, block_h), {src_block_w, src_block_h, expand_filter}, &set,
+	                         lds_bytes);
 }
 
 int pxz_retile_distortion_varied_device(pxz_handle *h, const pxz_image_desc *descs, uint32_t n_images, uint32_t channels,
@@ -3248,72 +3321,22 @@ int pxz_retile_distortion_varied_device(pxz_handle *h, const pxz_image_desc *des
 {
 	if (!h) return PXZ_ERR_INVALID_ARG;
 	if (!params) return fail(h, PXZ_ERR_INVALID_ARG, "null params");
-	if (!d_ref_w || !d_ref_h || !d_ref_slots || !d_tile_w || !d_tile_h || !d_slots || !d_image_sse)
-		return fail(h, PXZ_ERR_INVALID_ARG, "null device pointer");
-	const pxz_params p = decode_side_params(params, true);
-	int rc = varied_check_params(h, channels, &p);
-	if (rc != PXZ_OK) return rc;
-	if (src_block_w == 0 || src_block_h == 0) return fail(h, PXZ_ERR_INVALID_ARG, "zero source block size");
-	if (n_sets == 0) return fail(h, PXZ_ERR_INVALID_ARG, "n_sets must be at least 1");
-	if (expand_filter > 4) return fail(h, PXZ_ERR_INVALID_ARG, "expand_filter must be 0..4, got %u", expand_filter);
-	// the one place that says whether the kernel takes a pair of blocks: its LDS footprint against the CU's
-	auto check_pair = [&](uint32_t wdw_src, uint32_t wdw_set) {
-		if (pxz::retile_distortion_lds_bytes(src_block_w, src_block_h, p.block_w, p.block_h, wdw_src, wdw_set) > kLdsPerCu)
-			return fail(h, PXZ_ERR_UNSUPPORTED,
-			            "the distortion of re-tiled tiles keeps two %ux%u tile images (a dword per pixel) and the staged parts and windows of %ux%u source "
-			            "tiles, or of a whole stored %ux%u tile, in LDS: they exceed a block's 160 KB (pxz_retile_distortion_lds_bytes)",
-			            p.block_w, p.block_h, src_block_w, src_block_h, p.block_w, p.block_h);
-		return (int)PXZ_OK;
-	};
-	if ((rc = check_pair(1u, 1u)) != PXZ_OK) return rc;
-	if (!descs) return fail(h, PXZ_ERR_INVALID_ARG, "null image descriptors");
-	if (n_images == 0) return fail(h, PXZ_ERR_INVALID_ARG, "empty image batch");
-	// (of an image only its size is read, and that reserved is 0: stored tiles have no pitch and no place)
-	std::vector<pxz_image_desc> sized(n_images);
-	for (uint32_t i = 0; i < n_images; ++i) sized[i] = pxz_image_desc{descs[i].width, descs[i].height, descs[i].width * channels, descs[i].reserved, 0};
-	std::vector<pxz::VariedImage> images, src_images;
-	std::vector<uint32_t> sides, src_sides;
-	if ((rc = varied_plan(h, sized.data(), n_images, p.block_w, p.block_h, channels, 0, &images, &sides, nullptr)) != PXZ_OK) return rc;
-	if ((rc = varied_plan(h, sized.data(), n_images, src_block_w, src_block_h, 0, 0, &src_images, &src_sides, nullptr)) != PXZ_OK) return rc;
-	if ((uint64_t)n_sets * varied_n_tiles(images) > 0xffffffffull)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "more than 2^32-1 tiles over the %u sets", n_sets);
-	PXZ_HIP(h, hipSetDevice(h->device));
-	pxz::RetileDistortionArgs a{};
-	pxz_params xp = p;  // the reference's side: the source geometry
-	xp.block_w = src_block_w;
-	xp.block_h = src_block_h;
-	xp.filter = expand_filter;
-	if ((rc = put_varied_expand_tables(h, xp, channels, src_sides, &a.r)) != PXZ_OK) return rc;
-	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a.u)) != PXZ_OK) return rc;
-	// Both sets live in one bounded cache, and a set that is built into a full cache empties it first: the reference's set may
-	// have gone with it.  Asked for again it is found, or built into a cache that holds the sets' tables alone -- both stay.
-	if ((expand_filter != p.filter || src_sides != sides) && (rc = put_varied_expand_tables(h, xp, channels, src_sides, &a.r)) != PXZ_OK) return rc;
-	if ((rc = check_pair(a.r.wdw, a.u.wdw)) != PXZ_OK) return rc;
-	a.n_images = n_images;
-	a.n_tiles = varied_n_tiles(images);
-	a.n_sets = n_sets;
-	a.r.n_tiles = varied_n_tiles(src_images);
-	a.u.n_tiles = a.n_tiles;
-	a.r.tile_w = d_ref_w;
-	a.r.tile_h = d_ref_h;
-	a.r.slots = d_ref_slots;
-	a.u.tile_w = d_tile_w;
-	a.u.tile_h = d_tile_h;
-	a.u.slots = d_slots;
-	a.tile_sse = reinterpret_cast<unsigned long long *>(d_tile_sse);
-	a.image_sse = reinterpret_cast<unsigned long long *>(d_image_sse);
-	if ((rc = fresh_status(h, &a.r.status)) != PXZ_OK) return rc;
-	a.u.status = a.r.status;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.image_flags = d_image_flags;
-	PXZ_HIP(h, hipMemsetAsync(d_image_sse, 0, (size_t)n_sets * n_images * channels * 8u, h->stream));
-	// both per-image tables in one upload: the destination layout's, then the source layout's
-	std::vector<pxz::VariedImage> both = images;
-	both.insert(both.end(), src_images.begin(), src_images.end());
-	if ((rc = varied_upload(h, both, &a.images)) != PXZ_OK) return rc;
-	a.src_images = a.images + n_images;
-	PXZ_HIP(h, pxz::launch_retile_distortion(a, channels, h->n_cus, h->stream));
-	return PXZ_OK;
+	const ArchiveBatch b{descs, n_images, channels, true, src_block_w, src_block_h, params, expand_filter};
+	return archive_distortion<pxz::RetileDistortionArgs>(
+	    h, b, n_sets, {d_ref_w, d_ref_h, d_ref_slots}, {d_tile_w, d_tile_h, d_slots}, d_tile_sse, d_image_sse, d_image_flags,
+	    [&](uint32_t wdw_src, uint32_t wdw_set) {
+		    if (beyond_lds(retile_distortion_footprint(src_block_w, src_block_h, params->block_w, params->block_h), wdw_src, wdw_set))
+			    return fail(h, PXZ_ERR_UNSUPPORTED,
+			                "the distortion of re-tiled tiles keeps two %ux%u tile images (a dword per pixel) and the staged parts and windows of %ux%u source "
+			                "tiles, or of a whole stored %ux%u tile, in LDS: they exceed a block's 160 KB (pxz_retile_distortion_lds_bytes)",
+			                params->block_w, params->block_h, src_block_w, src_block_h, params->block_w, params->block_h);
+		    return (int)PXZ_OK;
+	    },
+	    [&](pxz::RetileDistortionArgs &a, const pxz::VariedImage *d_src_images) {
+		    a.src_images = d_src_images;
+		    PXZ_HIP(h, pxz::launch_retile_distortion(a, channels, h->n_cus, h->stream));
+		    return (int)PXZ_OK;
+	    });
 }
 
 }  // extern "C"
@@ -3451,14 +3474,9 @@ int pxz_expand_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32
 	pxz::WindowExpandArgs a{};
 	if ((rc = put_varied_expand_tables(h, p, channels, sides, &a, true)) != PXZ_OK) return rc;
 	a.n_windows = n_windows;
-	a.n_tiles = window_n_tiles(entries);
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
+	put_stored_tiles(&a, window_n_tiles(entries), {d_tile_w, d_tile_h, d_slots});
 	a.base = d_base;
-	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_window_flags, n_windows)) != PXZ_OK) return rc;
-	a.window_flags = d_window_flags;
+	if ((rc = fresh_status_and_flags(h, &a.status, d_window_flags, n_windows, &a.window_flags)) != PXZ_OK) return rc;
 	if ((rc = window_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_window_expand(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
@@ -3636,14 +3654,9 @@ int pxz_expand_varied_scaled_frames_device(pxz_handle *h, const pxz_image_desc *
 	pxz::ScaledExpandArgs a{};
 	if ((rc = put_scaled_tables(h, p, channels, most, max_shift, &a)) != PXZ_OK) return rc;
 	a.n_owners = n_images;
-	a.n_tiles = varied_n_tiles(images);
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
+	put_stored_tiles(&a, varied_n_tiles(images), {d_tile_w, d_tile_h, d_slots});
 	a.base = d_base;
-	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_image_flags, n_images)) != PXZ_OK) return rc;
-	a.flags = d_image_flags;
+	if ((rc = fresh_status_and_flags(h, &a.status, d_image_flags, n_images, &a.flags)) != PXZ_OK) return rc;
 	if ((rc = scaled_upload(h, entries, &a.images)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_scaled_expand(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
@@ -3681,14 +3694,9 @@ int pxz_expand_windows_scaled_device(pxz_handle *h, const pxz_image_desc *descs,
 	pxz::ScaledExpandArgs a{};
 	if ((rc = put_scaled_tables(h, p, channels, most, max_shift, &a)) != PXZ_OK) return rc;
 	a.n_owners = n_windows;
-	a.n_tiles = window_n_tiles(plan);
-	a.tile_w = d_tile_w;
-	a.tile_h = d_tile_h;
-	a.slots = d_slots;
+	put_stored_tiles(&a, window_n_tiles(plan), {d_tile_w, d_tile_h, d_slots});
 	a.base = d_base;
-	if ((rc = fresh_status(h, &a.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_window_flags, n_windows)) != PXZ_OK) return rc;
-	a.flags = d_window_flags;
+	if ((rc = fresh_status_and_flags(h, &a.status, d_window_flags, n_windows, &a.flags)) != PXZ_OK) return rc;
 	if ((rc = scaled_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
 	PXZ_HIP(h, pxz::launch_scaled_expand(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
@@ -3788,33 +3796,15 @@ int pxz_patch_windows_device(pxz_handle *h, const pxz_image_desc *descs, uint32_
 	xp.filter = expand_filter;
 	if ((rc = put_varied_expand_tables(h, xp, channels, sides, &a.r.x)) != PXZ_OK) return rc;
 	if ((rc = reshrink_check_block(h, p.mode, p.block_w, p.block_h, 0u, a.r.x.wdw)) != PXZ_OK) return rc;
-	if ((rc = fresh_status(h, &a.r.x.status)) != PXZ_OK) return rc;
-	if ((rc = zero_owner_flags(h, d_window_flags, n_windows)) != PXZ_OK) return rc;
+	if ((rc = fresh_status_and_flags(h, &a.r.x.status, d_window_flags, n_windows, &a.window_flags)) != PXZ_OK) return rc;
 	if ((rc = window_upload(h, entries, &a.windows)) != PXZ_OK) return rc;
 	pxz::VariedArgs &v = a.r.v;
+	varied_fill_shrink(h, channels, &p, vt, d_block_value, d_out_w, d_out_h, d_out_pixels, &v);
 	v.n_tiles = window_n_tiles(entries);
-	v.bw = p.block_w;
-	v.bh = p.block_h;
-	v.mode = p.mode;
-	v.filter = p.filter;
-	v.value = d_block_value;
-	v.out_w = d_out_w;
-	v.out_h = d_out_h;
-	v.out_px = d_out_pixels;
-	v.slot_bytes = p.block_w * p.block_h * channels;
 	v.tile_bytes = (p.block_w * p.block_h * 4u + 15u) & ~15u;  // one plane, as the re-shrink's
-	v.dir = vt->d_dir;
-	v.starts = vt->d_starts;
-	v.sizes = vt->d_sizes;
-	v.coeffs = vt->d_coeffs;
-	std::memcpy(v.thresholds, h->thresholds, sizeof v.thresholds);
-	a.r.x.n_tiles = v.n_tiles;
-	a.r.x.tile_w = d_tile_w;
-	a.r.x.tile_h = d_tile_h;
-	a.r.x.slots = d_slots;
+	put_stored_tiles(&a.r.x, v.n_tiles, {d_tile_w, d_tile_h, d_slots});
 	a.n_windows = n_windows;
 	a.patch_base = d_patch_base;
-	a.window_flags = d_window_flags;
 	a.factor[0] = p.factor;
 	PXZ_HIP(h, pxz::launch_patch(a, channels, h->n_cus, h->stream));
 	return PXZ_OK;
