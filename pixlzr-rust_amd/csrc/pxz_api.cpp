@@ -32,6 +32,7 @@
 #include "pxz_internal.h"
 #include "pxz_launch.h"
 #include "pxz_runtime.h"
+#include "pxz_shrink_plan.h"
 #include "pxz_tables.h"
 #include "pxz_tilefit.h"
 
@@ -247,8 +248,6 @@ int launch_on_bins(pxz_handle *h, const uint32_t *&bins_clean, const uint32_t *b
 	return PXZ_OK;
 }
 
-uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-
 // magic number for unsigned division by d >= 1 (exact for every 32-bit dividend)
 pxz::FastDiv make_fastdiv(uint32_t d)
 {
@@ -258,24 +257,15 @@ pxz::FastDiv make_fastdiv(uint32_t d)
 	return pxz::FastDiv{(uint32_t)m, l < 1 ? l : 1u, l < 1 ? 0u : l - 1};
 }
 
-// The tile grid of a batch of equally sized frames.
-struct Grid {
-	uint32_t cols = 0, rows = 0;
-	uint32_t edge_w = 0, edge_h = 0;  // the last column's width, the last row's height
-	uint32_t tiles_per_frame = 0;
-	uint64_t tiles = 0;               // of all frames
-};
+// The tile grid of a batch of equally sized frames (pxz_shrink_plan.h has the arithmetic).
+using Grid = pxz::TileGrid;
 constexpr uint64_t kAnyTiles = ~0ull;  // make_grid without a limit
 
 // Fills *g with pxz_grid's grid (the caller has checked the sides); PXZ_ERR_UNSUPPORTED when the batch has more than
 // `limit` tiles.
 int make_grid(pxz_handle *h, uint32_t width, uint32_t height, uint32_t bw, uint32_t bh, uint32_t n_frames, uint64_t limit, Grid *g)
 {
-	pxz_grid(width, height, bw, bh, &g->cols, &g->rows);
-	g->edge_w = width - (g->cols - 1) * bw;
-	g->edge_h = height - (g->rows - 1) * bh;
-	g->tiles_per_frame = g->cols * g->rows;
-	g->tiles = (uint64_t)g->cols * g->rows * n_frames;
+	*g = pxz::tile_grid(width, height, bw, bh, n_frames);
 	return g->tiles > limit ? fail(h, PXZ_ERR_UNSUPPORTED, "too many tiles") : PXZ_OK;
 }
 
@@ -310,17 +300,6 @@ int download_tile_outputs(pxz_handle *h, size_t tiles, size_t slot_bytes, float 
 	PXZ_HIP(h, hipMemcpyAsync(tile_h, h->oh.ptr, tiles * 4, hipMemcpyDeviceToHost, h->stream));
 	if (pixels) PXZ_HIP(h, hipMemcpyAsync(pixels, h->out.ptr, tiles * slot_bytes, hipMemcpyDeviceToHost, h->stream));
 	return PXZ_OK;
-}
-
-// these frames as tightly packed RGBA with rows of a 16-byte multiple (what the fast kernels and the block-cooperative
-// Oklab detector want)
-pxz_frames rgba16_frames(const pxz_frames *frames)
-{
-	pxz_frames f = *frames;
-	f.channels = 4;
-	f.pitch_bytes = (frames->width * 4u + 15u) & ~15u;
-	f.frame_stride_bytes = (uint64_t)f.pitch_bytes * frames->height;
-	return f;
 }
 
 // The pitch of the device copy of a host image: rows of a 16-byte multiple when the caller's do not have one (tight rows
@@ -429,15 +408,16 @@ uint32_t level_of_sum(const pxz_handle *h, uint64_t sum, uint32_t w, uint32_t hh
 	return m;
 }
 
-// Fills a->breaks / a->breaks_asc.  Oklab mode: the key is the bit pattern of the (non-negative)
+// Fills a->breaks / a->breaks_asc of a kernel's arguments that name the block and the edges (ShrinkArgs, LadderArgs).  Oklab mode: the key is the bit pattern of the (non-negative)
 // parsed value, compared against the float thresholds' bit patterns.  Directional mode: the key is
 // the integer gradient sum; the float pipeline sum -> value -> level is monotone in the sum, so each
 // threshold becomes one integer breakpoint per tile class, found by bisection with the exact formula.
-void build_breaks(pxz_handle *h, pxz::ShrinkArgs *a)
+template <class Args>
+void build_breaks(pxz_handle *h, uint32_t mode, float factor, Args *a)
 {
 	uint32_t fbits;
-	std::memcpy(&fbits, &a->factor, 4);
-	const auto key = std::make_tuple(a->mode, fbits, a->bw, a->bh, a->edge_w, a->edge_h);
+	std::memcpy(&fbits, &factor, 4);
+	const auto key = std::make_tuple(mode, fbits, a->bw, a->bh, a->edge_w, a->edge_h);
 	auto it = h->breaks.find(key);
 	if (it != h->breaks.end()) {
 		std::memcpy(a->breaks, it->second.b, sizeof a->breaks);
@@ -445,7 +425,7 @@ void build_breaks(pxz_handle *h, pxz::ShrinkArgs *a)
 		return;
 	}
 	struct Saver {
-		pxz_handle *h; pxz::ShrinkArgs *a; decltype(key) k;
+		pxz_handle *h; Args *a; decltype(key) k;
 		~Saver() {
 			pxz_handle::Breaks br;
 			std::memcpy(br.b, a->breaks, sizeof br.b);
@@ -457,7 +437,7 @@ void build_breaks(pxz_handle *h, pxz::ShrinkArgs *a)
 		a->breaks_asc[cls] = 0;
 		for (int j = 0; j < kMaxLevel; ++j) std::memcpy(&a->breaks[cls][j], &h->thresholds[j], 4);
 	}
-	if (a->mode != PXZ_MODE_SHRINK_DIRECTIONALLY) return;
+	if (mode != PXZ_MODE_SHRINK_DIRECTIONALLY) return;
 	for (int cls = 0; cls < 4; ++cls) {
 		const uint32_t w = (cls & 1) ? a->edge_w : a->bw, hh = (cls & 2) ? a->edge_h : a->bh;
 		if (w <= 2 || hh <= 2) {  // 0/0 tiles are special-cased in the kernel
@@ -465,12 +445,12 @@ void build_breaks(pxz_handle *h, pxz::ShrinkArgs *a)
 			continue;
 		}
 		const uint64_t max_sum = (uint64_t)(w - 2) * (hh - 2) * 3u * 1020u;
-		const uint32_t m_lo = level_of_sum(h, 0, w, hh, a->factor), m_hi = level_of_sum(h, max_sum, w, hh, a->factor);
+		const uint32_t m_lo = level_of_sum(h, 0, w, hh, factor), m_hi = level_of_sum(h, max_sum, w, hh, factor);
 		const bool asc = m_hi > m_lo;  // level exponent grows with the sum (negative factors)
 		a->breaks_asc[cls] = asc ? 1u : 0u;
 		for (int j = 0; j < kMaxLevel; ++j) {
 			// predicate "v < T[j]"  <=>  level exponent > j
-			auto below = [&](uint64_t s) { return level_of_sum(h, s, w, hh, a->factor) > (uint32_t)j; };
+			auto below = [&](uint64_t s) { return level_of_sum(h, s, w, hh, factor) > (uint32_t)j; };
 			const bool at0 = below(0), atmax = below(max_sum);
 			uint32_t brk;
 			if (at0 == atmax) {
@@ -504,177 +484,85 @@ int check_frames(pxz_handle *h, const pxz_frames *f, const pxz_params *p)
 	return check_params(h, p);
 }
 
-// Fills the kernel arguments for a batch; returns the LDS bytes needed per block.
-int prepare(pxz_handle *h, const pxz_frames *f, const pxz_params *p, bool want_pixels, pxz::ShrinkArgs *a, bool no_lab = false)
+// an LDS layout -> the carve-up fields ShrinkArgs and LadderArgs name alike
+template <class Args>
+void put_layout(const pxz::ShrinkLayout &l, Args *a)
 {
-	int rc = check_frames(h, f, p);
-	if (rc != PXZ_OK) return rc;
-	const uint32_t bw = p->block_w, bh = p->block_h;
-	Grid g;
-	const int too_many = make_grid(h, f->width, f->height, bw, bh, f->n_frames, 0xffffffffull, &g);
-	const uint32_t cols = g.cols, edge_w = g.edge_w, edge_h = g.edge_h;
-	// (the detector's refusal is reported first, also for a batch of too many tiles)
-	if (p->mode == PXZ_MODE_SHRINK_DIRECTIONALLY && (edge_w < 2 || edge_h < 2 || bw < 2 || bh < 2))
-		return fail(h, PXZ_ERR_TILE_TOO_SMALL,
-		            "directional detector needs tiles of at least 2x2 px (edge tile is %ux%u); the reference panics here",
-		            edge_w, edge_h);
-	if (too_many != PXZ_OK) return too_many;
-	if (bw > 0xffffu || bh > 0xffffu) return fail(h, PXZ_ERR_UNSUPPORTED, "block side above 65535");
-
-	auto round2 = [](uint32_t v) { return (v + 1u) & ~1u; };
-	const bool conv = want_pixels && p->filter != PXZ_FILTER_NEAREST;
-	auto skew = [](uint32_t v) { return (v & 15u) == 0 ? v + 2u : v; };  // keep rows off a common LDS bank
-	a->rs = skew(round2(ceil_div(bw, 2)));
-	a->plane_dw = a->rs * bh;
-	a->hps = skew(round2(ceil_div(bh, 2)));
-	a->tmp_dw = conv ? ceil_div(bw, 2) * a->hps : 0;
-	// (no_lab: every tile's Oklab value will come from oklab_kernel launches -- the generic kernel then needs no f32
-	// planes of its own, which is what limits shrink_by to ~7000-pixel tiles otherwise)
-	a->lab_dw = p->mode == PXZ_MODE_SHRINK_BY && !no_lab ? 3 * bw * bh : 0;
-	// planes | max(transposed planes, Oklab scratch) | slack for zero-weight over-reads past the last row
-	const uint32_t scratch = 4 * a->tmp_dw > a->lab_dw ? 4 * a->tmp_dw : a->lab_dw;
-	a->tile_dw = (4 * a->plane_dw + scratch + 4 * a->rs + 4 * a->hps + 3u) & ~3u;
-	const uint32_t nw = pxz::waves_per_tile(bw, bh);
-	const uint64_t lds_bytes = (uint64_t)a->tile_dw * 4u + (nw > 1 ? 16u * nw : 0u);
-	a->big_scratch = nullptr;
-	a->big_blocks = 0;
-	if (lds_bytes > 160u * 1024u) {
-		// (round 4) a tile image beyond LDS lives in HBM, one per block of the generic kernel: any block size the reference's CLI
-		// accepts runs (src/bin/main.rs:19-24), at the speed of L2 round trips.  The kernel's index arithmetic (small_div, RowWalker)
-		// holds below 2^20 pixels per tile; the grid is capped so that the images stay under 2 GB.
-		if ((uint64_t)bw * bh >= (1u << 20) || pxz::knobs().no_big_tiles)
-			return fail(h, PXZ_ERR_UNSUPPORTED, "a %ux%u tile needs %llu B of LDS (limit 163840) and has too many pixels for the HBM-resident form (limit 2^20 - 1)", bw, bh,
-			            (unsigned long long)lds_bytes);
-		const uint64_t tile_bytes = (uint64_t)a->tile_dw * 4u;
-		uint64_t blocks = (2ull << 30) / tile_bytes;
-		if (blocks > 2ull * h->n_cus) blocks = 2ull * h->n_cus;
-		if (blocks < 1) blocks = 1;
-		a->big_blocks = (uint32_t)blocks;  // (capped by the tile count at launch)
-	}
-
-	a->frame_stride = f->n_frames > 1 ? f->frame_stride_bytes : (uint64_t)f->pitch_bytes * f->height;
-	a->pitch = f->pitch_bytes;
-	a->width = f->width;
-	a->height = f->height;
-	a->bw = bw;
-	a->bh = bh;
-	put_grid(g, a);
-	a->div_tpf = make_fastdiv(g.tiles_per_frame);
-	a->div_cols = make_fastdiv(cols);
-	a->mode = p->mode;
-	a->filter = p->filter;
-	a->factor = p->factor;
-	a->scale2 = 10.0f;  // BASE_FACTOR, pixlzr.rs:15
-	a->alpha_kernel = (p->reserved & PXZ_HINT_TRANSPARENCY) != 0 && !pxz::knobs().no_alpha_kernel;
-	a->list_a_too = 0;
-	a->clone_ahead = 0;
-	a->finish_scan = 1;
-	a->stats = nullptr;
-	a->slot_bytes = bw * bh * f->channels;
-	build_breaks(h, a);
-	std::memset(a->tabs, 0, sizeof a->tabs);
-	a->bounds = nullptr;
-	a->coeffs = nullptr;
-	a->ksums = nullptr;
-	a->trows = nullptr;
-	a->tab_dw = 0;
-	if (want_pixels) {
-		const TableSet *tsp = nullptr;
-		rc = get_tables(h, bw, bh, edge_w, edge_h, p->filter, &tsp);
-		if (rc != PXZ_OK) return rc;
-		const TableSet &ts = *tsp;
-		std::memcpy(a->tabs, ts.tabs.data(), sizeof a->tabs);
-		a->bounds = ts.d_bounds;
-		a->coeffs = ts.d_coeffs;
-		a->ksums = ts.d_ksums;
-		a->trows = ts.d_rows;
-		a->tab_dw = ts.rows_dw * 4u <= 48u * 1024u ? (ts.rows_dw + 3u) & ~3u : 0u;
-		a->mf64 = ts.d_mf64;
-	}
-	return PXZ_OK;
+	a->rs = l.rs;
+	a->plane_dw = l.plane_dw;
+	a->hps = l.hps;
+	a->tmp_dw = l.tmp_dw;
+	a->tile_dw = l.tile_dw;
 }
 
-// fused kernel + finishing kernel (stored value / raw detector outputs), timed together
-int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *value, float *lod0, float *lod1)
+// a table set -> the fields both name alike
+template <class Args>
+void put_tables(const TableSet &ts, Args *a)
 {
-	int rc = ensure(h, h->sums, (size_t)a.n_tiles * 8u);
-	if (rc != PXZ_OK) return rc;
-	a.sums = (uint32_t *)h->sums.ptr;
-	const void *work_before = h->work.ptr;
-	const size_t work_bytes = (2u * (size_t)a.n_tiles + pxz::kWorkList + 4u) * 4u + 64u + 4608u * 8u;  // + diagnostic stamps (8 phase sums + 256 blocks x 17 qwords)
-	// + the 2 KB spare bytes of the detector's copies (ahead_spare) + the list of clone_split64_kernel (8 + n_tiles dwords)
-	if ((rc = ensure(h, h->work, work_bytes + 2048u + 8u + (8u + (size_t)a.n_tiles) * 4u)) != PXZ_OK) return rc;
-	if (h->work.ptr != work_before) h->work_ready = false;
-	a.work = (uint32_t *)h->work.ptr;
-	a.ahead_spare = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(h->work.ptr) + ((work_bytes + 7u) & ~(size_t)7u));
-	a.clone_list = a.ahead_spare + 512u;
-	a.value = value;
-	a.lod0 = lod0;
-	a.lod1 = lod1;
-	if (a.big_blocks != 0u) {
-		if (a.big_blocks > a.n_tiles) a.big_blocks = a.n_tiles;
-		if ((rc = ensure(h, h->bigscratch, (size_t)a.big_blocks * a.tile_dw * 4u)) != PXZ_OK) return rc;
-		a.big_scratch = (uint32_t *)h->bigscratch.ptr;
+	static_assert(sizeof a->tabs == sizeof(AxisTab) * 4 * kMaxLevel, "tables");
+	std::memcpy(a->tabs, ts.tabs.data(), sizeof a->tabs);
+	a->bounds = ts.d_bounds;
+	a->coeffs = ts.d_coeffs;
+	a->ksums = ts.d_ksums;
+}
+
+// The kernel arguments of a planned single-geometry call, filled once: everything but the handle's scratch pointers and the
+// caller's outputs.  ts: the table set when pixels are wanted, else null.
+void fill_shrink_args(pxz_handle *h, const pxz::ShrinkRoute &r, const pxz_params *p, const TableSet *ts, pxz::ShrinkArgs *a)
+{
+	const Grid &g = r.grid;
+	a->frame_stride = r.frame_stride;
+	a->pitch = r.frames.pitch_bytes;
+	a->width = r.frames.width;
+	a->height = r.frames.height;
+	a->bw = p->block_w;
+	a->bh = p->block_h;
+	put_grid(g, a);
+	a->div_tpf = make_fastdiv(g.tiles_per_frame);
+	a->div_cols = make_fastdiv(g.cols);
+	{
+		// shrink16_kernel walks 2x2 groups of tiles
+		const uint32_t gcols = (g.cols + 1u) / 2u, grows = (g.rows + 1u) / 2u;
+		a->div_gpf = make_fastdiv(gcols * grows);
+		a->div_gcols = make_fastdiv(gcols);
+		a->n_frames_x_groups = gcols * grows * r.frames.n_frames;
 	}
-	// Transparency without the caller's hint: the last finished launch reported how many full tiles had any
-	// (one dword in pinned memory, written by the worklist kernel).  Past ~2000 tiles shrink32a_kernel pays for
-	// its launch.  Either way the results are the same; only the kernel that produces them differs.
-	a.stats = h->quiet_stats ? nullptr : h->dev_stats;
-	// (the counts are only trusted when they come from a launch of THIS configuration: the kernel writes the signature beside them)
-	uint32_t factor_bits;
-	std::memcpy(&factor_bits, &a.factor, 4);
-	a.stats_sig = ((a.n_tiles * 2654435761u) ^ (a.bw << 20) ^ (a.bh << 8) ^ (a.mode << 31) ^ (channels << 28) ^ a.width ^ (a.height * 40503u) ^
-	               (a.filter * 0x9e3779b1u) ^ (factor_bits * 31u)) | 1u;
-	volatile uint32_t *hs = h->host_stats ? const_cast<volatile uint32_t *>(h->host_stats) : nullptr;
-	const bool stats_ours = hs != nullptr && hs[2] == a.stats_sig;
-	const uint32_t seen_transparent = stats_ours ? hs[0] : 0u;
-	a.expect_listed = stats_ours ? hs[1] : 0xffffffffu;
-	if (!a.alpha_kernel && seen_transparent >= 2048u && !pxz::knobs().no_alpha_kernel)
-		a.alpha_kernel = 1;
-	// ... and past half of the tiles the lean kernel would only read, test and list them: the four-plane kernel goes first
-	a.alpha_first = a.alpha_kernel && seen_transparent >= a.n_tiles / 2u && seen_transparent >= 2048u && !pxz::knobs().no_alpha_first ? 1u : 0u;
-	if (!h->quiet_stats) {
-		h->last_alpha_kernel = a.alpha_kernel;
-		h->last_alpha_first = a.alpha_first;
+	a->mode = p->mode;
+	a->filter = p->filter;
+	a->finish_scan = 1;
+	a->slot_bytes = p->block_w * p->block_h * r.channels;
+	build_breaks(h, p->mode, p->factor, a);
+	a->factor = r.factor;
+	a->scale2 = r.scale2;
+	if (ts) {
+		put_tables(*ts, a);
+		a->trows = ts->d_rows;
+		a->tab_dw = ts->rows_dw * 4u <= 48u * 1024u ? (ts->rows_dw + 3u) & ~3u : 0u;
+		a->mf64 = ts->d_mf64;
 	}
-	// 32x32 fast path: which tiles are full-size, and whether every tile row of the batch is 16-byte aligned
-	a.full_cols = a.full_rows = a.ok_rows = 0;
-	const bool aligned16 = channels == 4 &&
-	    ((reinterpret_cast<uintptr_t>(a.src) | a.pitch | (a.n_tiles > a.tiles_per_frame ? a.frame_stride : 0)) & 15u) == 0;
-	const bool square_fast = a.bw == a.bh && (a.bw == 16 || a.bw == 32 || a.bw == 64);
-	// any other tile whose rows are whole pixel quads: the Oklab detector with run-time geometry takes the full tiles
-	// (64 .. 16384 pixels); the generic kernel then only stages and resamples them
-	const bool general_oklab = !square_fast && a.mode == PXZ_MODE_SHRINK_BY && a.bw % 4u == 0 && a.bw * a.bh >= 64u &&
-	                           a.bw * a.bh <= 16384u && !pxz::knobs().no_oklab_general;
-	a.ok_bands = (a.bw * a.bh + 255u) / 256u;
-	// rows of a ragged last tile row the square detectors can take: whole 256-px bands (oklab_kernel), for 64-px tiles
-	// whole 512-px super-bands (oklab2_kernel<64>: four producer waves x two rows)
-	const uint32_t ok_row_quantum = a.bw == 64u ? 8u : (a.bw != 0u && a.bw <= 256u ? 256u / a.bw : 1u);
-	// 64x64 tiles are converted by oklab2_kernel<64> (round 3), which parks nothing in HBM; PXZ_OKLAB_V1 keeps oklab_kernel<64>
-	const bool parks64 = !(a.bw == 64u && a.bh == 64u) || pxz::knobs().oklab_v1;
-	a.ok_region = 0;
-	a.ok_count = a.n_tiles;
-	a.ok_edges = 0;
-	// RGB frames on the square fast paths (round 2; both callers): 12-byte pixel quads, rows 4-byte aligned
-	const bool rgb_native = channels == 3 && square_fast && !pxz::knobs().no_native_rgb &&
-	    ((reinterpret_cast<uintptr_t>(a.src) | a.pitch | (a.n_tiles > a.tiles_per_frame ? a.frame_stride : 0)) & 3u) == 0;
-	if (rgb_native) {
-		a.full_cols = a.edge_w == a.bw ? a.cols : a.cols - 1;
-		a.full_rows = a.edge_h == a.bh ? a.rows : a.rows - 1;
-		a.ok_rows = a.edge_h % ok_row_quantum == 0 ? a.rows : a.full_rows;  // (a ragged last row of whole bands, as below)
-	}
-	if (aligned16 && (square_fast || general_oklab)) {
-		a.full_cols = a.edge_w == a.bw ? a.cols : a.cols - 1;
-		a.full_rows = a.edge_h == a.bh ? a.rows : a.rows - 1;
-		// the Oklab detector also takes a ragged last row of whole bands (256 pixels = 256/bw rows) of the square sizes
-		a.ok_rows = square_fast && a.edge_h % ok_row_quantum == 0 ? a.rows : a.full_rows;
-	}
-	// (a pitch whose lane offsets leave 32 bits: no fast path, as for an unaligned batch)
-	if (!pxz::fast32_lane_offset_fits(a.pitch)) a.full_cols = a.full_rows = a.ok_rows = 0;
-	const pxz::FinishArgs fin{a.sums, value, lod0, lod1, a.n_tiles, a.tiles_per_frame, a.cols, a.rows,
+	put_layout(r.layout, a);
+	a->lab_dw = r.layout.lab_dw;
+	a->big_blocks = r.big_blocks;
+	a->oklab_given = r.detector != pxz::ShrinkDetector::None ? 1u : 0u;
+	a->ok_bands = r.ok_bands;
+	a->ok_count = (uint32_t)g.tiles;  // (region 0: every tile is enumerated)
+	a->ok_rows = r.ok_rows;
+	a->clone_ahead = r.clone_ahead;
+	a->full_cols = r.full_cols;
+	a->full_rows = r.full_rows;
+	a->alpha_kernel = r.alpha_kernel;
+	a->alpha_first = r.alpha_first;
+	a->stats_sig = r.stats_sig;
+	a->expect_listed = r.expect_listed;
+}
+
+// The launches of a planned call, timed together: detector, its edge regions, the fused kernel (+ the finishing kernel where no
+// fast kernel finishes its own tiles).  a: filled, with its source, scratch and outputs set.
+int launch_route(pxz_handle *h, const pxz::ShrinkRoute &r, pxz::ShrinkArgs &a)
+{
+	const pxz::FinishArgs fin{a.sums, a.value, a.lod0, a.lod1, a.n_tiles, a.tiles_per_frame, a.cols, a.rows,
 	                          a.bw, a.bh, a.edge_w, a.edge_h, a.mode, a.factor};
 	hipEvent_t e0 = nullptr, e1 = nullptr, emid = nullptr;
-	a.mid_event = nullptr;
 	const bool record = !h->quiet_stats && h->timing && (h->timing_count++ % h->timing_stride) == 0;
 	if (record) {
 		if (h->events_used == h->events.size()) {
@@ -691,85 +579,29 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 		PXZ_HIP(h, hipEventRecord(e0, h->stream));
 		a.mid_event = emid;  // recorded behind the first kernel of the step (pxz_last_first_kernel_ms)
 	}
-	// shrink_by on the headline geometry: the block-cooperative Oklab detector first, then the
-	// fused kernel only stages + resamples (it still runs the generic detector on ragged-edge tiles)
-	a.oklab_given = 0;
-	if (a.mode == PXZ_MODE_SHRINK_BY && channels == 4 && (square_fast || general_oklab) &&
-	    a.full_cols != 0 && a.full_rows != 0 && !pxz::knobs().no_oklab32) {
-		// The ragged edge of the grid -- right column (edge_w x bh), bottom row (bw x edge_h), corner tile -- goes
-		// through the same detector with run-time geometry, one launch per region (tile rows that are not whole
-		// pixel quads are walked padded).  Without it the edge runs its chains in the generic kernel: four lanes per tile,
-		// ~0.1-0.5 ms of latency per launch whatever the batch.
-		const uint32_t n_frames = a.n_tiles / a.tiles_per_frame;
-		struct Region { uint32_t id, w, hh, per_frame, bit; bool wanted; } regions[3] = {
-		    {1u, a.edge_w, a.bh, a.full_rows, 1u, a.full_cols < a.cols},
-		    {2u, a.bw, a.edge_h, a.full_cols, 2u, a.full_rows < a.rows && a.ok_rows < a.rows},
-		    {3u, a.edge_w, a.edge_h, 1u, 4u, a.full_cols < a.cols && a.full_rows < a.rows}};
-		size_t scratch = a.ok_bands > 4u && parks64 ? (size_t)a.n_tiles * a.ok_bands * 3328u : 0u;
-		for (Region &r : regions) {
-			const uint32_t wp = (r.w + 3u) & ~3u;  // rows are walked in whole quads (the padding counts as zeros)
-			r.wanted = r.wanted && r.per_frame != 0u && a.bw % 4u == 0u && wp * r.hh <= 16384u && !pxz::knobs().no_oklab_edges;
-			const uint32_t bands = (wp * r.hh + 255u) / 256u;
-			if (r.wanted && bands > 4u) scratch = std::max(scratch, (size_t)n_frames * r.per_frame * bands * 3328u);
-		}
-		if (scratch != 0) {
-			// a tile of more than 1024 pixels does not fit the registers between the detector's two passes: 13 dwords
-			// per pixel quad in HBM
-			if ((rc = ensure(h, h->okscratch, scratch)) != PXZ_OK) return rc;
-			a.ok_scratch = (float *)h->okscratch.ptr;
-		}
-		a.oklab_given = 1;
-		// (round 4) the square detectors copy every tile into its slot while they have its pixels: the shrink kernel then
-		// skips the tiles that are stored at full size instead of reading them a second time
-		a.clone_ahead = square_fast && a.out_px != nullptr && !pxz::knobs().oklab_v1 && !pxz::knobs().no_clone_ahead ? 1u : 0u;
-		PXZ_HIP(h, pxz::launch_oklab(a, h->n_cus, h->stream));
+	// shrink_by: the block-cooperative Oklab detector first, then the fused kernel only stages + resamples (it still runs the
+	// generic detector on the tiles the route left it).  The square detectors copy every tile into its slot while they have its
+	// pixels (clone_ahead): the shrink kernel then skips the tiles that are stored at full size instead of reading them again
+	if (r.detector != pxz::ShrinkDetector::None) {
+		PXZ_HIP(h, pxz::launch_oklab(a, h->n_cus, h->stream, r.detector == pxz::ShrinkDetector::Rgba ? 4 : 3));
 		if (a.mid_event) {
 			PXZ_HIP(h, hipEventRecord(static_cast<hipEvent_t>(a.mid_event), h->stream));
 			a.mid_event = nullptr;
 		}
-		for (const Region &r : regions) {
-			if (!r.wanted) continue;
+		for (const pxz::ShrinkRegion &reg : r.regions) {
+			if (!reg.wanted) continue;
 			pxz::ShrinkArgs e = a;
-			e.ok_region = r.id;
-			e.ok_bands = (((r.w + 3u) & ~3u) * r.hh + 255u) / 256u;
-			e.ok_count = n_frames * r.per_frame;
+			e.ok_region = reg.id;
+			e.ok_bands = reg.bands;
+			e.ok_count = reg.count;
 			PXZ_HIP(h, pxz::launch_oklab(e, h->n_cus, h->stream));
-			a.ok_edges |= r.bit;
+			a.ok_edges |= reg.bit;
 		}
 	}
-	if (a.mode == PXZ_MODE_SHRINK_BY && rgb_native && a.full_cols != 0 && a.full_rows != 0 && !pxz::knobs().no_oklab32) {
-		// RGB, 16x16 / 32x32 / 64x64: oklab2_kernel<16 | 32, 3> / oklab_kernel<64, 0, 3> for the full tiles; a ragged edge
-		// keeps its chains in the generic kernel
-		if (a.ok_bands > 4u && parks64) {  // 64x64 with PXZ_OKLAB_V1: the converted tile is parked in HBM between the passes
-			if ((rc = ensure(h, h->okscratch, (size_t)a.n_tiles * a.ok_bands * 3328u)) != PXZ_OK) return rc;
-			a.ok_scratch = (float *)h->okscratch.ptr;
-		}
-		a.oklab_given = 1;
-		// (as for RGBA above; an RGB lane's six bytes are two stores, which costs the 16x16 detector more than its shrink kernel
-		// gains -- 8 x 8K: 1.151 against 1.141 ms; 32x32 1.052 against 1.072, 64x64 1.20 against 1.37)
-		a.clone_ahead = a.out_px != nullptr && a.bw != 16u && !pxz::knobs().oklab_v1 && !pxz::knobs().no_clone_ahead ? 1u : 0u;
-		PXZ_HIP(h, pxz::launch_oklab(a, h->n_cus, h->stream, 3));
-		if (a.mid_event) {
-			PXZ_HIP(h, hipEventRecord(static_cast<hipEvent_t>(a.mid_event), h->stream));
-			a.mid_event = nullptr;
-		}
-	}
-	if (a.mode == PXZ_MODE_SHRINK_BY && a.lab_dw == 0) {
-		// the generic kernel was sized without its own detector planes: every tile must have its value by now
-		const bool right = a.full_cols < a.cols, bottom = a.full_rows < a.rows && a.ok_rows < a.rows, corner = a.full_cols < a.cols && a.full_rows < a.rows;
-		const bool covered = a.oklab_given && (!right || (a.ok_edges & 1u)) && (!bottom || (a.ok_edges & 2u)) && (!corner || (a.ok_edges & 4u));
-		if (!covered) return fail(h, PXZ_ERR_UNSUPPORTED, "internal: Oklab values missing for a layout sized without detector planes");
-	}
-	// 32x32 RGBA flow: shrink32_kernel, then the worklist kernel, which also finishes every tile and
-	// zeroes the worklist counter of the next launch (two counters, used alternately)
-	{
-		// shrink16_kernel walks 2x2 groups of tiles
-		const uint32_t gcols = (a.cols + 1u) / 2u, grows = (a.rows + 1u) / 2u;
-		a.div_gpf = make_fastdiv(gcols * grows);
-		a.div_gcols = make_fastdiv(gcols);
-		a.n_frames_x_groups = gcols * grows * (a.n_tiles / a.tiles_per_frame);
-	}
-	const bool fast = pxz::fast32_applicable(a, channels) || pxz::fast64_applicable(a, channels) || pxz::fast16_applicable(a, channels);
+	// 32x32 RGBA flow: shrink32_kernel, then the worklist kernel, which also finishes every tile and zeroes the worklist counter
+	// of the next launch (two counters, used alternately).  Which kernel takes the batch depends on the table set (tab_dw, mf64)
+	// beside the route: the launchers' own predicates say
+	const bool fast = pxz::fast32_applicable(a, r.channels) || pxz::fast64_applicable(a, r.channels) || pxz::fast16_applicable(a, r.channels);
 	if (fast) {
 		if (!h->work_ready) {
 			PXZ_HIP(h, hipMemsetAsync(h->work.ptr, 0, pxz::kWorkList * 4u, h->stream));
@@ -778,7 +610,7 @@ int timed_launch(pxz_handle *h, pxz::ShrinkArgs &a, uint32_t channels, float *va
 		h->work_ready = false;  // stays false if a launch below fails: the counters are then re-zeroed next time
 		a.work_slot = h->work_slot;
 	}
-	PXZ_HIP(h, pxz::launch_shrink(a, channels, h->n_cus, h->stream));
+	PXZ_HIP(h, pxz::launch_shrink(a, r.channels, h->n_cus, h->stream));
 	if (!fast && a.mid_event) PXZ_HIP(h, hipEventRecord(static_cast<hipEvent_t>(a.mid_event), h->stream));  // the generic kernel is the step
 	if (fast) {
 		h->work_slot ^= 1u;
@@ -924,106 +756,96 @@ int pxz_grid(uint32_t width, uint32_t height, uint32_t block_w, uint32_t block_h
 	// it (and the reference's own two grids from each other), so larger images are refused here and by every entry
 	// point -- ONE grid, this one, is used throughout the library.
 	if (width > kMaxImageSide || height > kMaxImageSide) return PXZ_ERR_UNSUPPORTED;
-	*cols = (uint32_t)(((uint64_t)width + block_w - 1u) / block_w);
-	*rows = (uint32_t)(((uint64_t)height + block_h - 1u) / block_h);
+	const pxz::TileGrid g = pxz::tile_grid(width, height, block_w, block_h, 1);
+	*cols = g.cols;
+	*rows = g.rows;
 	return PXZ_OK;
 }
 
 // One shrink / detector pass over a batch.  identity: the closures of process() instead of shrink_by's.
-// RGB batches whose tile size has an RGBA fast path are widened to RGBA (alpha 255) in scratch memory, run
-// there, and their tile slots narrowed back (see rgb_to_rgba_kernel for why the results are the same).
+// The route -- input form, LDS layout, detector, fast region, transparency, scratch -- is planned once (pxz_shrink_plan.h);
+// this body validates, plans and executes it.  RGB batches whose tile size has an RGBA fast path are widened to RGBA (alpha
+// 255) in scratch memory, run there, and their tile slots narrowed back (see rgb_to_rgba_kernel for why the results are the same).
 static int run_shrink(pxz_handle *h, const pxz_frames *frames, const pxz_params *params, const uint8_t *d_pixels,
                       float *d_block_value, uint32_t *d_out_w, uint32_t *d_out_h, uint8_t *d_out_pixels, float *d_lod0,
                       float *d_lod1, bool identity)
 {
 	PXZ_HIP(h, hipSetDevice(h->device));
-	pxz::ShrinkArgs a{};
-	// RGBA, shrink_by, a tile shape the block-cooperative detector takes and at least one full tile each way: interior
-	// and edge launches of oklab_kernel cover every tile (rows are re-pitched below if they are not aligned)
-	const uint32_t pbw = params ? params->block_w : 0, pbh = params ? params->block_h : 0;
-	const bool covers_if_rgba = frames && params && params->mode == PXZ_MODE_SHRINK_BY && pbw != 0 && pbh != 0 &&
-	                            pbw % 4u == 0 && (uint64_t)pbw * pbh >= 64u && (uint64_t)pbw * pbh <= 16384u &&
-	                            frames->width >= pbw && frames->height >= pbh && !pxz::knobs().no_oklab32 &&
-	                            !pxz::knobs().no_oklab_general && !pxz::knobs().no_oklab_edges && !pxz::knobs().no_repitch;
-	const bool oklab_covers_all = covers_if_rgba && frames->channels == 4;
-	int rc = prepare(h, frames, params, d_out_pixels != nullptr, &a, oklab_covers_all);
-	bool rgb_must_widen = false;
-	if (rc == PXZ_ERR_UNSUPPORTED && covers_if_rgba && frames->channels == 3 && !pxz::knobs().no_widen) {
-		// the RGB layout with its own detector planes does not fit LDS; the widened RGBA one without them might
-		const pxz_frames fw = rgba16_frames(frames);
-		if (prepare(h, &fw, params, d_out_pixels != nullptr, &a, true) == PXZ_OK) {
-			rc = PXZ_OK;
-			rgb_must_widen = true;
-		} else {
-			(void)prepare(h, frames, params, d_out_pixels != nullptr, &a, false);  // (restore the first error text)
-		}
-	}
+	int rc = check_frames(h, frames, params);
 	if (rc != PXZ_OK) return rc;
-	// (also shrink_by on the tile sizes the run-time-geometry Oklab detector takes: it only exists for RGBA)
-	const bool square_fast = a.bw == a.bh && (a.bw == 16 || a.bw == 32 || a.bw == 64);
-	const bool general_oklab = a.mode == PXZ_MODE_SHRINK_BY && a.bw % 4u == 0 && a.bw * a.bh >= 64u && a.bw * a.bh <= 16384u;
-	bool widen = frames->channels == 3 && (square_fast || general_oklab) && !pxz::knobs().no_widen;
-	// (16x16, 32x32, 64x64 tiles: the fast kernels and the Oklab detector read RGB themselves, when the rows are 4-byte aligned)
-	if (widen && square_fast && !rgb_must_widen && !pxz::knobs().no_native_rgb &&
-	    ((reinterpret_cast<uintptr_t>(d_pixels) | frames->pitch_bytes | (frames->n_frames > 1 ? frames->frame_stride_bytes : 0)) & 3u) == 0)
-		widen = false;
-	if (widen && d_out_pixels && params->filter != PXZ_FILTER_NEAREST) {
-		const TableSet *tsp = nullptr;
-		if ((rc = get_tables(h, a.bw, a.bh, a.edge_w, a.edge_h, params->filter, &tsp)) != PXZ_OK) return rc;
-		widen = tsp->opaque_stays;
+	const pxz::Knobs &knobs = pxz::knobs();
+	pxz::ShrinkRequest q{};
+	q.frames = frames;
+	q.params = params;
+	q.want_pixels = d_out_pixels != nullptr;
+	q.identity = identity;
+	q.src_low_bits = (uint32_t)(reinterpret_cast<uintptr_t>(d_pixels) & 15u);
+	q.n_cus = h->n_cus;
+	if (volatile const uint32_t *hs = h->host_stats) {
+		q.have_stats = true;
+		for (int i = 0; i < 3; ++i) q.stats[i] = hs[i];
 	}
-	if (rgb_must_widen && !widen)
-		return fail(h, PXZ_ERR_UNSUPPORTED, "a %ux%u RGB tile needs more LDS than there is (and this filter cannot run it as RGBA)", a.bw, a.bh);
-	const pxz_frames f4 = rgba16_frames(frames);
-	const uint8_t *src = d_pixels;
-	uint8_t *out_px = d_out_pixels;
-	if (widen) {
-		pxz::ShrinkArgs probe{};
-		if (prepare(h, &f4, params, d_out_pixels != nullptr, &probe, covers_if_rgba) != PXZ_OK) widen = false;  // e.g. four planes of a large tile exceed LDS
+	q.quiet_stats = h->quiet_stats;
+	const TableSet *ts = nullptr;
+	const Grid g = pxz::tile_grid(frames->width, frames->height, params->block_w, params->block_h, frames->n_frames);
+	if (pxz::shrink_plan_needs_opaque_stays(q, knobs)) {
+		if ((rc = get_tables(h, params->block_w, params->block_h, g.edge_w, g.edge_h, params->filter, &ts)) != PXZ_OK) return rc;
+		q.opaque_stays = ts->opaque_stays;
 	}
-	if (widen) {
-		if ((rc = ensure(h, h->rgba, (size_t)f4.frame_stride_bytes * frames->n_frames)) != PXZ_OK) return rc;
-		const pxz::WidenArgs w{d_pixels, (uint8_t *)h->rgba.ptr,
-		                       frames->n_frames > 1 ? frames->frame_stride_bytes : (uint64_t)frames->pitch_bytes * frames->height,
-		                       f4.frame_stride_bytes, frames->pitch_bytes, f4.pitch_bytes, frames->width, frames->height,
-		                       frames->n_frames};
+	pxz::ShrinkRoute r;
+	char why[256];
+	if ((rc = pxz::shrink_plan(q, knobs, &r, why, sizeof why)) != PXZ_OK) return fail(h, rc, "%s", why);
+	if (q.want_pixels && !ts && (rc = get_tables(h, params->block_w, params->block_h, g.edge_w, g.edge_h, params->filter, &ts)) != PXZ_OK) return rc;
+
+	// ---- buffers ----
+	const void *work_before = h->work.ptr;
+	if ((rc = ensure(h, h->sums, r.sums_bytes)) != PXZ_OK || (rc = ensure(h, h->work, r.work_total_bytes)) != PXZ_OK) return rc;
+	if (h->work.ptr != work_before) h->work_ready = false;
+	if (r.bigscratch_bytes != 0 && (rc = ensure(h, h->bigscratch, r.bigscratch_bytes)) != PXZ_OK) return rc;
+	if (r.okscratch_bytes != 0 && (rc = ensure(h, h->okscratch, r.okscratch_bytes)) != PXZ_OK) return rc;
+	if (r.rgba_bytes != 0 && (rc = ensure(h, h->rgba, r.rgba_bytes)) != PXZ_OK) return rc;
+	if (r.slots4_bytes != 0 && (rc = ensure(h, h->slots4, r.slots4_bytes)) != PXZ_OK) return rc;
+
+	// ---- input form ----
+	const uint64_t src_stride = pxz::frame_stride_of(*frames);
+	if (r.input == pxz::ShrinkInput::Widened) {
+		const pxz::WidenArgs w{d_pixels, (uint8_t *)h->rgba.ptr, src_stride, r.frames.frame_stride_bytes, frames->pitch_bytes, r.frames.pitch_bytes,
+		                       frames->width, frames->height, frames->n_frames};
 		PXZ_HIP(h, pxz::launch_widen(w, h->stream));
-		if ((rc = prepare(h, &f4, params, d_out_pixels != nullptr, &a, covers_if_rgba)) != PXZ_OK) return rc;
-		src = (const uint8_t *)h->rgba.ptr;
-		if (d_out_pixels) {
-			if ((rc = ensure(h, h->slots4, (size_t)a.n_tiles * a.bw * a.bh * 4u)) != PXZ_OK) return rc;
-			out_px = (uint8_t *)h->slots4.ptr;
-		}
+	} else if (r.input == pxz::ShrinkInput::Repitched) {
+		for (uint32_t n = 0; n < frames->n_frames; ++n)
+			PXZ_HIP(h, hipMemcpy2DAsync((uint8_t *)h->rgba.ptr + (size_t)n * r.frames.frame_stride_bytes, r.frames.pitch_bytes,
+			                            d_pixels + (size_t)n * src_stride, frames->pitch_bytes, (size_t)frames->width * 4u, frames->height,
+			                            hipMemcpyDeviceToDevice, h->stream));
 	}
-	// RGBA frames whose rows (or first byte, or frame stride) are not 16-byte multiples would miss the fast kernels and
-	// the block-cooperative Oklab detector: one device-to-device 2D copy into aligned scratch first (0.4 ms per GB
-	// against 5-50x on the kernels)
-	if (!widen && frames->channels == 4 && (square_fast || general_oklab) && !pxz::knobs().no_repitch) {
-		const uint64_t fstride = frames->n_frames > 1 ? frames->frame_stride_bytes : (uint64_t)frames->pitch_bytes * frames->height;
-		const bool misaligned = ((reinterpret_cast<uintptr_t>(d_pixels) | frames->pitch_bytes | (frames->n_frames > 1 ? fstride : 0)) & 15u) != 0;
-		if (misaligned) {
-			const pxz_frames fa = rgba16_frames(frames);
-			if ((rc = ensure(h, h->rgba, (size_t)fa.frame_stride_bytes * frames->n_frames)) != PXZ_OK) return rc;
-			for (uint32_t n = 0; n < frames->n_frames; ++n)
-				PXZ_HIP(h, hipMemcpy2DAsync((uint8_t *)h->rgba.ptr + (size_t)n * fa.frame_stride_bytes, fa.pitch_bytes,
-				                            d_pixels + (size_t)n * fstride, frames->pitch_bytes, (size_t)frames->width * 4u,
-				                            frames->height, hipMemcpyDeviceToDevice, h->stream));
-			if ((rc = prepare(h, &fa, params, d_out_pixels != nullptr, &a, oklab_covers_all)) != PXZ_OK) return rc;
-			src = (const uint8_t *)h->rgba.ptr;
-		}
-	}
-	if (identity) {
-		a.factor = 1.0f;
-		a.scale2 = 1.0f;  // (x * 1) * 1 is x exactly: the identity closure
-	}
-	a.src = src;
+	const bool narrow = r.slots4_bytes != 0;
+
+	// ---- arguments ----
+	pxz::ShrinkArgs a{};
+	fill_shrink_args(h, r, params, ts, &a);
+	a.src = r.input == pxz::ShrinkInput::AsGiven ? d_pixels : (const uint8_t *)h->rgba.ptr;
 	a.out_w = d_out_w;
 	a.out_h = d_out_h;
-	a.out_px = out_px;
-	if ((rc = timed_launch(h, a, widen ? 4u : frames->channels, d_block_value, d_lod0, d_lod1)) != PXZ_OK) return rc;
-	if (widen && d_out_pixels) {
-		const pxz::NarrowArgs n{(const uint8_t *)h->slots4.ptr, d_out_pixels, d_out_w, d_out_h, a.n_tiles, a.bw * a.bh * 4u,
-		                        a.bw * a.bh * 3u};
+	a.out_px = narrow ? (uint8_t *)h->slots4.ptr : d_out_pixels;
+	a.value = d_block_value;
+	a.lod0 = d_lod0;
+	a.lod1 = d_lod1;
+	a.sums = (uint32_t *)h->sums.ptr;
+	a.work = (uint32_t *)h->work.ptr;
+	a.ahead_spare = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(h->work.ptr) + ((r.work_bytes + 7u) & ~(size_t)7u));
+	a.clone_list = a.ahead_spare + 512u;
+	if (r.big_blocks != 0u) a.big_scratch = (uint32_t *)h->bigscratch.ptr;
+	if (r.okscratch_bytes != 0) a.ok_scratch = (float *)h->okscratch.ptr;
+	a.stats = r.write_stats ? h->dev_stats : nullptr;
+	if (r.write_stats) {
+		h->last_alpha_kernel = r.alpha_kernel;
+		h->last_alpha_first = r.alpha_first;
+	}
+
+	// ---- launches ----
+	if ((rc = launch_route(h, r, a)) != PXZ_OK) return rc;
+	if (narrow) {
+		const pxz::NarrowArgs n{(const uint8_t *)h->slots4.ptr, d_out_pixels, d_out_w, d_out_h, a.n_tiles, a.bw * a.bh * 4u, a.bw * a.bh * 3u};
 		PXZ_HIP(h, pxz::launch_narrow(n, h->stream));
 	}
 	return PXZ_OK;
@@ -1067,14 +889,11 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 	int rc = check_frames(h, frames, &p);
 	if (rc != PXZ_OK) return rc;
 	const bool want = d_out_pixels != nullptr;
-	pxz::ShrinkArgs a{};
-	const bool ladder = p.mode == PXZ_MODE_SHRINK_BY && prepare(h, frames, &p, want, &a, false) == PXZ_OK && a.big_blocks == 0u &&
-	                    prepare(h, frames, &p, want, &a, true) == PXZ_OK && a.big_blocks == 0u;
-	if (!ladder) {
+	const Grid g = pxz::tile_grid(frames->width, frames->height, p.block_w, p.block_h, frames->n_frames);
+	pxz::ShrinkLayout bare{};  // ladder_kernel's LDS image
+	if (!pxz::shrink_ladder_in_lds(p, want, g.tiles, h->n_cus, pxz::knobs(), &bare)) {
 		// one single-factor flow per rung: no amortisation, the same results and errors by construction
-		Grid g;
-		(void)make_grid(h, frames->width, frames->height, p.block_w, p.block_h, frames->n_frames, kAnyTiles, &g);  // (the calls below check)
-		const size_t tiles = (size_t)g.tiles;
+		const size_t tiles = (size_t)g.tiles;  // (the calls below check)
 		const size_t slot = (size_t)p.block_w * p.block_h * frames->channels;
 		for (uint32_t r = 0; r < n_factors; ++r) {
 			pxz_params pr = *params;
@@ -1085,7 +904,9 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 		}
 		return PXZ_OK;
 	}
-	const size_t x_bytes = up256((size_t)a.n_tiles * 4u);
+	const TableSet *ts = nullptr;
+	if (want && (rc = get_tables(h, p.block_w, p.block_h, g.edge_w, g.edge_h, p.filter, &ts)) != PXZ_OK) return rc;
+	const size_t x_bytes = up256((size_t)g.tiles * 4u);
 	if ((rc = ensure(h, h->ladder, x_bytes + PXZ_LADDER_MAX_RUNGS * 4u)) != PXZ_OK) return rc;
 	float *d_x = (float *)h->ladder.ptr;
 	float *d_factors = (float *)((uint8_t *)h->ladder.ptr + x_bytes);
@@ -1096,22 +917,17 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 	rc = run_shrink(h, frames, &p, d_pixels, nullptr, nullptr, nullptr, nullptr, d_x, nullptr, true);
 	h->quiet_stats = false;
 	if (rc != PXZ_OK) return rc;
-	// stage 2: every rung of every tile
+	// stage 2: every rung of every tile, from the caller's frames as they are (any alignment, 3 or 4 channels)
 	pxz::LadderArgs l{};
 	l.src = d_pixels;
-	l.frame_stride = a.frame_stride;
-	l.pitch = a.pitch;
-	l.bw = a.bw;
-	l.bh = a.bh;
-	l.cols = a.cols;
-	l.rows = a.rows;
-	l.tiles_per_frame = a.tiles_per_frame;
-	l.n_tiles = a.n_tiles;
-	l.div_tpf = a.div_tpf;
-	l.div_cols = a.div_cols;
-	l.edge_w = a.edge_w;
-	l.edge_h = a.edge_h;
-	l.filter = a.filter;
+	l.frame_stride = pxz::frame_stride_of(*frames);
+	l.pitch = frames->pitch_bytes;
+	l.bw = p.block_w;
+	l.bh = p.block_h;
+	put_grid(g, &l);
+	l.div_tpf = make_fastdiv(g.tiles_per_frame);
+	l.div_cols = make_fastdiv(g.cols);
+	l.filter = p.filter;
 	l.n_rungs = n_factors;
 	l.x = d_x;
 	l.factors = d_factors;
@@ -1119,20 +935,11 @@ int pxz_shrink_ladder_frames_device(pxz_handle *h, const pxz_frames *frames, con
 	l.out_w = d_out_w;
 	l.out_h = d_out_h;
 	l.out_px = d_out_pixels;
-	l.slot_bytes = a.slot_bytes;
-	l.rs = a.rs;
-	l.plane_dw = a.plane_dw;
-	l.hps = a.hps;
-	l.tmp_dw = a.tmp_dw;
-	l.tile_dw = a.tile_dw;
-	static_assert(sizeof l.tabs == sizeof a.tabs && sizeof l.breaks == sizeof a.breaks, "ladder tables");
-	std::memcpy(l.tabs, a.tabs, sizeof l.tabs);
-	l.bounds = a.bounds;
-	l.coeffs = a.coeffs;
-	l.ksums = a.ksums;
-	std::memcpy(l.breaks, a.breaks, sizeof l.breaks);
-	std::memcpy(l.breaks_asc, a.breaks_asc, sizeof l.breaks_asc);
-	PXZ_HIP(h, pxz::launch_ladder(l, frames->channels, pxz::waves_per_tile(a.bw, a.bh), h->n_cus, h->stream));
+	l.slot_bytes = p.block_w * p.block_h * frames->channels;
+	put_layout(bare, &l);
+	if (ts) put_tables(*ts, &l);
+	build_breaks(h, p.mode, p.factor, &l);
+	PXZ_HIP(h, pxz::launch_ladder(l, frames->channels, pxz::waves_per_tile(l.bw, l.bh), h->n_cus, h->stream));
 	return PXZ_OK;
 }
 
@@ -1164,7 +971,7 @@ static int expand_launch(pxz_handle *h, const pxz_frames *frames, uint32_t slot_
 	a.tile_h = d_tile_h;
 	a.slots = d_slots;
 	a.dst = d_out_pixels;
-	a.frame_stride = frames->n_frames > 1 ? frames->frame_stride_bytes : (uint64_t)frames->pitch_bytes * frames->height;
+	a.frame_stride = pxz::frame_stride_of(*frames);
 	a.pitch = frames->pitch_bytes;
 	a.width = frames->width;
 	a.height = frames->height;
@@ -1385,7 +1192,7 @@ int pxz_tree_process_frames_device(pxz_handle *h, const pxz_frames *frames, cons
 	const uint32_t mbw = min_block_w > 4u ? min_block_w : 4u, mbh = min_block_h > 4u ? min_block_h : 4u;
 	std::vector<std::pair<uint32_t, uint32_t>> levels;
 	for (uint32_t bw = p.block_w, bh = p.block_h; bw > mbw && bh > mbh; bw >>= 1, bh >>= 1) levels.emplace_back(bw, bh);
-	const uint64_t src_stride = frames->n_frames > 1 ? frames->frame_stride_bytes : (uint64_t)frames->pitch_bytes * frames->height;
+	const uint64_t src_stride = pxz::frame_stride_of(*frames);
 	const uint64_t dst_stride = frames->n_frames > 1 ? out_frame_stride_bytes : (uint64_t)out_pitch_bytes * frames->height;
 	// A level's tiles are the children of the level before: they form that level's regular grid over the frame as long as
 	// a block is exactly two of the next (the recursion splits every tile from its own corner), and the per-level passes
@@ -2044,7 +1851,7 @@ int pxz_synth_frames_device(pxz_handle *h, const pxz_frames *frames, uint8_t *d_
 	if (frames->height > 65535u || frames->n_frames > 65535u) return fail(h, PXZ_ERR_UNSUPPORTED, "frame too tall for the synth grid");
 	PXZ_HIP(h, hipSetDevice(h->device));
 	pxz::SynthArgs s{d_pixels,
-	                 frames->n_frames > 1 ? frames->frame_stride_bytes : (uint64_t)frames->pitch_bytes * frames->height,
+	                 pxz::frame_stride_of(*frames),
 	                 frames->pitch_bytes, frames->width, frames->height, frames->channels, frames->n_frames,
 	                 first_frame_index, dist};
 	PXZ_HIP(h, pxz::launch_synth(s, h->stream));
