@@ -60,6 +60,8 @@ def lib():
         L.orc_lod_directional.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [f32p, f32p, u64p, u64p]
         L.orc_lod_oklab.restype = C.c_float
         L.orc_lod_oklab.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_float]
+        L.orc_lod_oklab_identity.restype = C.c_float
+        L.orc_lod_oklab_identity.argtypes = [C.c_void_p] + [C.c_uint32] * 4
         L.orc_oklab_pixel.restype = None
         L.orc_oklab_pixel.argtypes = [C.c_void_p, C.c_uint32, f32p]
         L.orc_oklab_pixels.restype = None
@@ -133,6 +135,13 @@ def lod_oklab(tile, factor):
     assert tile.strides[2] == 1 and tile.strides[1] == c
     return np.float32(lib().orc_lod_oklab(C.c_void_p(tile.ctypes.data), w, h, c, tile.strides[0],
                                           C.c_float(factor)))
+
+
+def lod_oklab_identity(tile):
+    """the value process() and tree::process decide on: |x - avg| before, the identity after"""
+    h, w, c = tile.shape
+    assert tile.strides[2] == 1 and tile.strides[1] == c
+    return np.float32(lib().orc_lod_oklab_identity(C.c_void_p(tile.ctypes.data), w, h, c, tile.strides[0]))
 
 
 def reduce_dims(v0, v1, w, h):

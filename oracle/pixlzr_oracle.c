@@ -224,6 +224,12 @@ float orc_lod_oklab(const uint8_t *tile, uint32_t w, uint32_t h, uint32_t c, uin
 	return lod_oklab_scaled(tile, w, h, c, pitch, factor, 10.0f);
 }
 
+float orc_lod_oklab_identity(const uint8_t *tile, uint32_t w, uint32_t h, uint32_t c, uint32_t pitch)
+{
+	/* the value process() and tree::process decide on (process/mod.rs:108-111) */
+	return lod_oklab_scaled(tile, w, h, c, pitch, 1.0f, 1.0f);
+}
+
 /* get_block_variance (operations.rs:26-126) with before = |x - avg| and after = (x * factor) * scale2;
  * factor = scale2 = 1 is the identity closure of process() (process/mod.rs:108-111): x * 1 * 1 == x */
 static float lod_oklab_scaled(const uint8_t *tile, uint32_t w, uint32_t h, uint32_t c, uint32_t pitch, float factor,

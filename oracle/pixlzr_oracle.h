@@ -54,6 +54,8 @@ void orc_lod_directional(const uint8_t *tile, uint32_t w, uint32_t h, uint32_t c
                          float *hz, float *vr, uint64_t *sum_hz, uint64_t *sum_vr);
 /* src/operations.rs:26-126 with the closures of Pixlzr::shrink_by (pixlzr.rs:160-162) */
 float orc_lod_oklab(const uint8_t *tile, uint32_t w, uint32_t h, uint32_t c, uint32_t pitch, float factor);
+/* the same with the identity closure of process() and tree::process (process/mod.rs:108-111) */
+float orc_lod_oklab_identity(const uint8_t *tile, uint32_t w, uint32_t h, uint32_t c, uint32_t pitch);
 /* one pixel -> Oklab (l,a,b) + alpha, palette 0.7.6 model */
 void orc_oklab_pixel(const uint8_t *px, uint32_t c, float out_laba[4]);
 void orc_oklab_pixels(const uint8_t *px, uint32_t c, uint64_t n, float *out_laba);

@@ -1889,28 +1889,40 @@ class Handle:
                                                      C.c_void_p(out.data_ptr())))
         return out
 
-    def process_frames_device(self, frames, bw, bh, filter_down=4, filter_up=0):
-        """process_custom with |x - avg| / identity (process/mod.rs:71-121): frames [N,H,W,C] -> RGBA [N,H,W,4]."""
+    @staticmethod
+    def _rgba_out(frames, out):
+        """-> (out, row pitch, frame stride in bytes): a packed tensor of its own, or the caller's [N,H,W,4] view as it lies"""
         import torch
+        N, H, W, _ = frames.shape
+        if out is None:
+            return torch.empty((N, H, W, 4), dtype=torch.uint8, device=frames.device), W * 4, W * 4 * H
+        assert out.is_cuda and out.dtype == torch.uint8 and out.device == frames.device and tuple(out.shape) == (N, H, W, 4)
+        assert out.stride(3) == 1 and out.stride(2) == 4 and out.stride(1) >= W * 4
+        assert N == 1 or out.stride(0) >= out.stride(1) * (H - 1) + W * 4
+        return out, out.stride(1), out.stride(0)
+
+    def process_frames_device(self, frames, bw, bh, filter_down=4, filter_up=0, out=None):
+        """process_custom with |x - avg| / identity (process/mod.rs:71-121): frames [N,H,W,C] -> RGBA [N,H,W,4].
+        out: a [N,H,W,4] uint8 view to write into (any row pitch and frame stride; bytes between the rows are left alone)."""
         fd, (N, H, W, Cc) = self._frames_desc(frames)
-        out = torch.empty((N, H, W, 4), dtype=torch.uint8, device=frames.device)
+        out, pitch, stride = self._rgba_out(frames, out)
         pd = Params(bw, bh, 0, filter_down, 1.0, 0)
         self.use_torch_stream()
         self._check(self._L.pxz_process_frames_device(self._h, C.byref(fd), C.byref(pd), filter_up,
                                                       C.c_void_p(frames.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                      W * 4, W * 4 * H))
+                                                      pitch, stride))
         return out
 
-    def tree_process_frames_device(self, frames, bw, bh, threshold, min_bw=4, min_bh=4, filter_down=4, filter_up=0):
-        """tree::process_custom with |x - avg| / identity (process/tree.rs:23-109): frames [N,H,W,C] -> RGBA [N,H,W,4]."""
-        import torch
+    def tree_process_frames_device(self, frames, bw, bh, threshold, min_bw=4, min_bh=4, filter_down=4, filter_up=0, out=None):
+        """tree::process_custom with |x - avg| / identity (process/tree.rs:23-109): frames [N,H,W,C] -> RGBA [N,H,W,4].
+        out: as in process_frames_device."""
         fd, (N, H, W, Cc) = self._frames_desc(frames)
-        out = torch.empty((N, H, W, 4), dtype=torch.uint8, device=frames.device)
+        out, pitch, stride = self._rgba_out(frames, out)
         pd = Params(bw, bh, 0, filter_down, 1.0, 0)
         self.use_torch_stream()
         self._check(self._L.pxz_tree_process_frames_device(self._h, C.byref(fd), C.byref(pd), filter_up, C.c_float(threshold),
                                                            min_bw, min_bh, C.c_void_p(frames.data_ptr()),
-                                                           C.c_void_p(out.data_ptr()), W * 4, W * 4 * H))
+                                                           C.c_void_p(out.data_ptr()), pitch, stride))
         return out
 
     def decode_status(self):

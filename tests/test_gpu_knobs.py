@@ -29,14 +29,20 @@ KNOBS = [
     ("PXZ_NO_EXPAND_FAST32", "test_expand_matches_oracle or test_expand_of_power_of_two_tiles or test_process_matches_oracle"),
     ("PXZ_NO_ALPHA_FIRST", "test_mostly_transparent_batches_go_to_the_four_plane_kernel_first or test_transparent_tiles_through_the_alpha_kernel"),
     ("PXZ_NO_ALPHA_KERNEL", "test_transparent_tiles_through_the_alpha_kernel or test_transparent_64x64_tiles_through_the_alpha_instance"),
+    # ("file::cases": another module's.  The value-domain frames of the two image-to-image filters: the rectangle lists on the cases the
+    # per-level grids take by default, the generic kernels on RGB without the widening, the general expand forms on RGBA)
+    ("PXZ_TREE_RECTS", "test_gpu_filter_domain.py::test_tree_grid_on_the_value_domain or test_grid_tree_reads_a_strided_batch"),
+    ("PXZ_NO_WIDEN", "test_gpu_filter_domain.py::(test_process_on_the_value_domain or test_tree_grid_on_the_value_domain) and c3"),
+    ("PXZ_NO_EXPAND_FAST32", "test_gpu_filter_domain.py::(test_process_on_the_value_domain or test_tree_grid_on_the_value_domain) and c4"),
 ]
 
 
 @pytest.mark.parametrize("knob,cases", KNOBS)
 def test_fallback_paths_behind_the_knobs(knob, cases):
+    module, _, cases = cases.rpartition("::")
     env = dict(os.environ)
     env[knob] = "1"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-x", "-q", "-m", "gpu",
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", module or "test_gpu_parity.py"), "-x", "-q", "-m", "gpu",
                         "-k", cases, "-p", "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     tail = "\n".join(r.stdout.splitlines()[-15:])
     assert r.returncode == 0, f"{knob}=1:\n{tail}\n{r.stderr[-2000:]}"
