@@ -74,9 +74,12 @@ def same_tiles(got, want, c, what):
 
 
 class Chain:
-    """reader of the windows -> patch -> splice over `sources` (one channel count and block size), everything kept"""
+    """reader of the windows -> patch -> splice over `sources` (one channel count and block size), everything kept.  lead: the files
+    start that many bytes into their allocation; out: (file offsets, bytes) of the splice, the bytes any view of the caller's (or
+    None, the size query); placement: (windows with pitch and offset, host buffer) made by the caller in place of place_patches'"""
 
-    def __init__(self, gpu, product, sources, c, bw, bh, p, rects, patches, in_place=False, out=None, lead=3, break_tile=None):
+    def __init__(self, gpu, product, sources, c, bw, bh, p, rects, patches, in_place=False, out=None, lead=3, break_tile=None,
+                 placement=None):
         import torch
         self.sizes = [(s.w, s.h) for s in sources]
         plain = [(i, x, y, w, h, 0, 0) for (i, x, y, w, h) in rects]
@@ -88,8 +91,8 @@ class Chain:
         if break_tile is not None:  # a stored size that cannot be
             self.old[1][break_tile] = 0
         self.old_host = tiles_to_host(self.old)
-        self.windows, host_patch = place_patches(rects, patches, c)
-        self.patch = torch.from_numpy(host_patch).cuda()
+        self.windows, self.host_patch = place_patches(rects, patches, c) if placement is None else placement
+        self.patch = torch.from_numpy(self.host_patch).cuda()
         self.pflags = torch.full((len(rects),), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
         if in_place:
             vals = torch.full((self.T,), 0x7F7F7F7F, dtype=torch.int32, device="cuda").view(torch.float32)
