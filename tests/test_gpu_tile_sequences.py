@@ -8,7 +8,8 @@ The loops' steady state is reached by the SAME tests in child processes with a s
   PXZ_WPB=1 PXZ_CHUNK_LG=6             one wave of shrink32_kernel walks 64 adjacent tiles in flat order; one wave per block elsewhere
   PXZ_CUS=1                            every grid is that of a one-CU chip: a handful of blocks, each walks tiles b, b + G, b + 2G, ...
   PXZ_CUS=1 PXZ_WPB=1 PXZ_CHUNK_LG=0   two blocks of one wave: stride 2, one wave's list batches fill
-  PXZ_CUS=1 PXZ_NO_CLONE_AHEAD=1       shrink_by without the detector's copies (frames b and d)
+  PXZ_CUS=1 PXZ_NO_CLONE_AHEAD=1       shrink_by without the detector's copies (frames b, d and e)
+  PXZ_CUS=1 PXZ_OKLAB_V1=1             frames e on oklab_kernel<16 | 32 | 64>: 15 tiles per batch, 64x64 tiles parked in HBM
 
 and the directed suites that were there before run once more under PXZ_CUS=1.  The children run one at a time, each under a time
 limit of four times its measured wall time; after a child that ended abnormally, or whose output reports a GPU fault, no
@@ -270,6 +271,75 @@ def test_detector_batch_seams(gpu, oracle, geom, channels):
         assert_same_tiles(got, exp, channels, f"{n} tiles of {bw}x{bh} c{channels}")
 
 
+# ---- e. detector alpha sequences ----------------------------------------------------------------------------------------------------
+# ("seams" in the names: the PXZ_NO_CLONE_AHEAD child selects them with frames d)
+
+def alpha_frame(oracle, bw, bh, edge_w=0, edge_h=0):
+    key = ("alpha", bw, bh, edge_w, edge_h)
+    if key not in _frames:
+        _frames[key] = ts.alpha_sequence_frame(oracle, bw, bh, edge_w, edge_h)[0]
+    return _frames[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("block", BLOCKS)
+def test_detector_alpha_seams_square(gpu, oracle, block):
+    """oklab2_kernel<16 | 32 | 64> (PXZ_OKLAB_V1: oklab_kernel<16 | 32 | 64>, the last one parked in HBM): cur_opaque / old_opaque /
+    band_opaque, al_cur[] / al_old[] and their hand-over, alpha_px[] and the parked alpha word.  Tiles that are opaque, transparent
+    everywhere, in their first, their last or one inner row only, or in one pixel of alpha 254, in every order of two (and of
+    three over opaque / not opaque) at the strides 3, 14 and 15 at which a one-block launch hands a producer wave its tiles.  The
+    host form, then two frames in one device batch, the second with its tile rows in reverse order; 32 and 64: once more with a
+    row of tiles transparent everywhere and a last row 8 px high behind it, twice in one batch (a short tile after a full one, a
+    full tile of the next frame after a short one)."""
+    import torch
+    img = alpha_frame(oracle, block, block)
+    exp = expected(oracle, ("alpha",), img, block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+    got = gpu.shrink_image(img, block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+    assert_same_tiles(got, exp, 4, f"alpha sequence {block}, host form")
+    rows = img.reshape(ts.ALPHA_ROWS, block, img.shape[1], 4)
+    flipped = np.ascontiguousarray(rows[::-1]).reshape(img.shape)
+    exp2 = expected(oracle, ("alpha flipped",), flipped, block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+    out = gpu.shrink_frames_device(upload([img, flipped]), block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+    torch.cuda.synchronize()
+    assert_same_tiles(fetch(out, 0), exp, 4, f"alpha sequence {block}, device form, frame 0")
+    assert_same_tiles(fetch(out, 1), exp2, 4, f"alpha sequence {block}, device form, frame 1")
+    if block in (32, 64):
+        short = alpha_frame(oracle, block, block, 0, ts.ALPHA_SHORT_ROW)
+        exp = expected(oracle, ("alpha short row",), short, block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+        got = gpu.shrink_image(short, block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+        assert_same_tiles(got, exp, 4, f"alpha sequence {block} with a short last row, host form")
+        out = gpu.shrink_frames_device(upload([short, short]), block, block, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+        torch.cuda.synchronize()
+        for n in range(2):
+            assert_same_tiles(fetch(out, n), exp, 4, f"alpha sequence {block} with a short last row, device form, frame {n}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geom", sorted(ts.ALPHA_RAGGED), ids=lambda g: f"{g[0]}x{g[1]}")
+def test_detector_alpha_seams_run_time_geometry(gpu, oracle, geom):
+    """oklab_kernel<0, 3> (24x24: three bands, alpha_px[] in registers) and oklab_kernel<0, 0> (40x32: five bands, the alpha word
+    parked in HBM and read back through tile_prev a period later), 15 tiles per batch; the 6 px right column (rows padded to whole
+    quads, masked by `have`), the ragged bottom row and the corner go through the three edge-region launches, transparent pixels
+    in all of them."""
+    bw, bh = geom
+    img = alpha_frame(oracle, bw, bh, *ts.ALPHA_RAGGED[geom])
+    exp = expected(oracle, ("alpha ragged",), img, bw, bh, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+    got = gpu.shrink_image(img, bw, bh, ts.SHRINK_BY, ts.LANCZOS3, ts.BY_FACTOR)
+    assert_same_tiles(got, exp, 4, f"alpha sequence {bw}x{bh} with ragged edges")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("block", BLOCKS)
+def test_detector_alpha_seams_on_the_ladder(gpu, oracle, block):
+    """pxz_shrink_image_ladder: one detector pass over the alpha sequence, three shrink_by factors decided from its values"""
+    img = alpha_frame(oracle, block, block)
+    factors = (ts.BY_FACTOR, 0.5, 4.0)
+    vals, ow, oh, slots = gpu.shrink_image_ladder(img, block, block, ts.SHRINK_BY, ts.LANCZOS3, factors)
+    for r, k in enumerate(factors):
+        exp = expected(oracle, ("alpha",), img, block, block, ts.SHRINK_BY, ts.LANCZOS3, k)
+        assert_same_tiles((vals[r], ow[r], oh[r], slots[r]), exp, 4, f"alpha sequence {block}, ladder rung {r} (k={k})")
+
+
 # ---- the same under small launches: child processes -----------------------------------------------------------------------------
 
 ABNORMAL = (124, 134, 137, 139)
@@ -280,10 +350,11 @@ _abnormal = []   # the first child that ended abnormally: no child is started af
 
 # (id, environment, -k expression over this file, measured wall time of the child on an MI355X in seconds: DESIGN §8r)
 OWN = [
-    ("wpb1-chunk6", {"PXZ_WPB": "1", "PXZ_CHUNK_LG": "6"}, "not child", 5.9),
-    ("cus1", {"PXZ_CUS": "1"}, "not child", 5.5),
-    ("cus1-wpb1-chunk0", {"PXZ_CUS": "1", "PXZ_WPB": "1", "PXZ_CHUNK_LG": "0"}, "not child", 6.1),
-    ("cus1-no-clone-ahead", {"PXZ_CUS": "1", "PXZ_NO_CLONE_AHEAD": "1"}, "(triples or seams) and not child", 5.0),
+    ("wpb1-chunk6", {"PXZ_WPB": "1", "PXZ_CHUNK_LG": "6"}, "not child", 6.1),
+    ("cus1", {"PXZ_CUS": "1"}, "not child", 5.9),
+    ("cus1-wpb1-chunk0", {"PXZ_CUS": "1", "PXZ_WPB": "1", "PXZ_CHUNK_LG": "0"}, "not child", 6.0),
+    ("cus1-no-clone-ahead", {"PXZ_CUS": "1", "PXZ_NO_CLONE_AHEAD": "1"}, "(triples or seams) and not child", 5.3),
+    ("cus1-oklab-v1", {"PXZ_CUS": "1", "PXZ_OKLAB_V1": "1"}, "alpha_seams and not child", 4.3),
 ]
 # (file, -k expression: the directed cases without the full-size, 8K and 2049-image ones, measured seconds under PXZ_CUS=1)
 OTHERS = [

@@ -2,11 +2,12 @@
 
 Every hot kernel is a persistent loop: a wave or block walks many tiles and carries state from one to the next -- the parked
 output of the previous tile, prefetched pixels, values that travel two tiles ahead, list batches of 16 entries, the detectors'
-software pipeline over batches of 15 / 14 / 3 tiles.  The frames here put tile KINDS in a known sequence along the flat tile
+software pipeline over batches of 15 / 14 / 3 tiles and the alpha bytes a producer wave keeps from one of them to the next.  The frames here put tile KINDS in a known sequence along the flat tile
 order, so that with a small launch (PXZ_CUS, PXZ_WPB, PXZ_CHUNK_LG) one wave meets "a clone followed by a skipped tile", "the
 16th listed tile" or "a partial batch after two full ones" by construction.
 
-A kind is what the ORACLE does with a tile (its stored size), never what the product does.  Tiles are drawn from a two-parameter
+A kind is what the ORACLE does with a tile (its stored size), never what the product does (section e: the alpha plane laid over a
+tile, which is the input itself).  Tiles are drawn from a two-parameter
 family -- a 0/1 profile along x times an amplitude plus a profile along y times another -- whose members the oracle classifies;
 every draw is a hash of an index (value_patterns.hash32), no generator state is involved."""
 import numpy as np
@@ -304,3 +305,121 @@ def seam_frame(oracle, bw, bh, channels, n):
     """one row of n full tiles, whole and reduced ones in a drawn order"""
     kinds = [("whole", "reduced")[k] for k in draws(n, 900 + n, 2)]
     return sequence_frame(oracle, bw, bh, channels, kinds, n, 900 + n), kinds
+
+
+# ---- e. detector alpha sequences --------------------------------------------------------------------------------------------------
+
+# The pipelined Oklab detectors carry a tile's alpha from period to period per PRODUCER WAVE (pxz_oklab.hip: al_cur / al_old and
+# the three opaque flags of oklab2_kernel, alpha_px[] or the parked alpha word of oklab_kernel), and a one-block launch hands a
+# wave the items w, w + b, w + 2b, ... with b tiles per batch.  A kind is an alpha plane laid over an opaque base tile; the
+# alpha plane is summed on its own, so what a tile's value tells is the MULTISET of alphas the tile was credited with -- every
+# tile therefore has a signature (pixel count, alpha value) of its own.
+ALPHA_KINDS = ("opaque", "full", "top", "bottom", "middle", "one 254")
+ALPHA_DRAWN = ("opaque",) + ALPHA_KINDS           # opaque twice in seven: (opaque, opaque, opaque) is a wanted triple
+ALPHA_PIXELS = {"top": 3, "bottom": 2, "middle": 5, "one 254": 1}   # pixels that are not opaque (full: all of them)
+ALPHA_BASE = {"top": 0, "bottom": 80, "middle": 160}               # their alpha is (base + 7 item) % 240: never that of item - 3, 14, 15
+ALPHA_STRIDES = (3, 14, 15)                       # = sorted DETECTOR_BATCHES
+ALPHA_COLS, ALPHA_ROWS = 14, 15                   # 210 full tiles, a multiple of 3, 14 and 15
+ALPHA_SHORT_ROW = 8                               # 32x32, 64x64: a last tile row the square detectors still take (whole bands)
+ALPHA_RAGGED = {(24, 24): (6, 10), (40, 32): (6, 12)}   # run-time geometry: (width of the right column, height of the bottom row)
+ALPHA_GEOMS = ((16, 16), (32, 32), (64, 64), (24, 24), (40, 32))
+# the first seed at which missing_alpha_pairs() is empty (find_alpha_seed, on the CPU).  Square frames: every stride; the run-time
+# geometry is oklab_kernel's alone (15 tiles per batch), and its 14th grid column is the ragged one
+ALPHA_SEEDS = {(16, 16): 7, (32, 32): 7, (64, 64): 7, (24, 24): 6, (40, 32): 6}
+
+
+def planned_alpha_kinds(seed, n):
+    return [ALPHA_DRAWN[k] for k in draws(n, seed + 700, len(ALPHA_DRAWN))]
+
+
+def missing_alpha_pairs(kinds, strides=ALPHA_STRIDES, sequenced=None):
+    """[(stride, kind at i, kind at i + stride)] and [(stride, o at i, o at i + stride, o at i + 2 stride)], o = "opaque" | "not
+    opaque", that do NOT occur among the items flagged in `sequenced` (all of them when None).  Wanted at every stride: all 36
+    ordered pairs of kinds, and all eight triples over {opaque, not opaque} -- the state lives across three periods (conversion,
+    re-delivery, the band that awaits its store)."""
+    n = len(kinds)
+    ok = [True] * n if sequenced is None else list(sequenced)
+    o = ["opaque" if k == "opaque" else "not opaque" for k in kinds]
+    missing = []
+    for g in strides:
+        seen = {(kinds[i], kinds[i + g]) for i in range(n - g) if ok[i] and ok[i + g]}
+        missing += [(g, a, b) for a in ALPHA_KINDS for b in ALPHA_KINDS if (a, b) not in seen]
+        seen3 = {(o[i], o[i + g], o[i + 2 * g]) for i in range(n - 2 * g) if ok[i] and ok[i + g] and ok[i + 2 * g]}
+        both = ("opaque", "not opaque")
+        missing += [(g, a, b, c) for a in both for b in both for c in both if (a, b, c) not in seen3]
+    return missing
+
+
+def alpha_layout(bw, bh, edge_w=0, edge_h=0):
+    """(grid columns, grid rows, per item: is it one of the SEQUENCED tiles -- those the detector's main launch takes, whose item
+    number is the flat tile index).  Without a ragged column 14 x 15 full tiles; with one, 13 full columns and the ragged one.
+    A short last row without a ragged column (the square variants) stands behind one more full row, see alpha_sequence_frame."""
+    cols = ALPHA_COLS
+    full_cols = cols if edge_w == 0 else cols - 1
+    full_rows = ALPHA_ROWS + (1 if edge_h and not edge_w else 0)
+    rows = full_rows + (1 if edge_h else 0)
+    # the square detectors take a last row of whole bands (8 rows: two bands of 32x32, one super-band of 64x64)
+    taken_rows = rows if edge_h and not edge_w and bw == bh and bw in (32, 64) and edge_h % 8 == 0 else full_rows
+    return cols, rows, [c < full_cols and r < taken_rows for r in range(rows) for c in range(cols)]
+
+
+def find_alpha_seed(ragged=False, limit=20000):
+    cols, rows, seq = alpha_layout(24, 24, *ALPHA_RAGGED[(24, 24)]) if ragged else alpha_layout(32, 32)
+    for seed in range(limit):
+        if not missing_alpha_pairs(planned_alpha_kinds(seed, cols * rows), (15,) if ragged else ALPHA_STRIDES, seq):
+            return seed
+    raise AssertionError("no seed")
+
+
+def alpha_plane(kind, t, w, h):
+    """the alpha bytes [h, w] of item t's kind.  top / bottom / middle: ALPHA_PIXELS[kind] pixels of ONE row, in drawn columns, all
+    of one alpha that no neighbour at the detectors' strides shares.  middle: a row r with r % 8 // 2 in (1, 2) -- for 64x64 tiles
+    rows 0, r and h - 1 then belong to three different producer waves of oklab2_kernel<64> (wave j: rows 8k + 2j, 8k + 2j + 1).
+    one 254: the SAME pixel in every tile of a shape, so two of them in a row carry equal planes."""
+    assert h >= 8 and w >= 4
+    a = np.full((h, w), 255, np.uint8)
+    if kind == "opaque":
+        return a
+    if kind == "full":
+        i = np.arange(h * w, dtype=np.uint64).reshape(h, w)
+        return (vp.hash32(i, 0xA1FA + 977 * t) % 255).astype(np.uint8)
+    if kind == "one 254":
+        i = int(vp.hash32(np.array([w], np.uint64), 0x254 + h)[0] % (w * h))
+        a[i // w, i % w] = 254
+        return a
+    if kind == "middle":
+        d = int(vp.hash32(np.array([t], np.uint64), 0x3D)[0])
+        row = 8 * (d % (h // 8)) + 2 + (d >> 8) % 4
+    else:
+        row = 0 if kind == "top" else h - 1
+    cols = np.argsort(vp.hash32(np.arange(w, dtype=np.uint64), 0xC015 + 131 * t), kind="stable")[:ALPHA_PIXELS[kind]]
+    a[row, cols] = (ALPHA_BASE[kind] + 7 * t) % 240
+    return a
+
+
+def alpha_sequence_frame(oracle, bw, bh, edge_w=0, edge_h=0):
+    """(image, planned kind of every grid tile in flat order).  RGBA; the bases are opaque tiles of by_pools(), drawn from the tiles
+    the oracle stores whole and from those it reduces alike, so transparent tiles are both copied ahead and resampled.
+    edge_w, edge_h = 0: 14 x 15 full tiles, the flat index is the detector's item number.
+    edge_h alone (square tiles): the same 210 tiles, then a row of `full` tiles, then a row edge_h px high of drawn kinds -- with
+    14 tiles per batch a short tile follows a tile that is transparent in every band in every wave.
+    edge_w and edge_h (run-time geometry): 13 full columns and one edge_w px wide, 15 full rows and one edge_h px high; the ragged
+    tiles are cut from the top left of full ones and get the alpha plane of their kind at their own size."""
+    cols, rows, _ = alpha_layout(bw, bh, edge_w, edge_h)
+    seed = ALPHA_SEEDS[(bw, bh)]
+    kinds = planned_alpha_kinds(seed, cols * rows)
+    if edge_h and not edge_w:
+        kinds[ALPHA_ROWS * cols:(ALPHA_ROWS + 1) * cols] = ["full"] * cols
+    whole, reduced = by_pools(oracle, bw, bh, 4)
+    pick = draws(cols * rows, seed + 81, 1 << 20)
+    W = cols * bw if edge_w == 0 else (cols - 1) * bw + edge_w
+    H = rows * bh if edge_h == 0 else (rows - 1) * bh + edge_h
+    img = np.zeros((H, W, 4), np.uint8)
+    for t, kind in enumerate(kinds):
+        src = whole if pick[t] & 1 else reduced
+        r, c = t // cols, t % cols
+        paste(img, r, c, bw, bh, src[(pick[t] >> 1) % len(src)])
+        part = img[r * bh:(r + 1) * bh, c * bw:(c + 1) * bw]
+        part[..., 3] = alpha_plane(kind, t, part.shape[1], part.shape[0])
+    img.setflags(write=False)
+    return img, kinds
