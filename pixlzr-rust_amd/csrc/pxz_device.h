@@ -312,8 +312,8 @@ __device__ __forceinline__ uint32_t level_count(uint32_t key, const uint32_t *br
 }
 
 // LDS accesses spelled one by one (base + 16-bit immediate): left to itself the compiler pairs neighbouring accesses
-// into ds_read2 / ds_write2, whose 8-bit offsets cost a vector add per new base -- 16 of them per tile in the detector of
-// shrink32_kernel, which is bound by vector instructions, not by LDS instructions.
+// into ds_read2 / ds_write2, whose 8-bit offsets cost a vector add per new base -- 16 of them per tile in the pair form of
+// shrink32_kernel's detector (sobel32_quads below reads aligned 8-byte quads with lds_load2).
 typedef const volatile __attribute__((address_space(3))) uint32_t *lds_cptr;
 __device__ __forceinline__ uint32_t lds_dword(const uint32_t *p) { return *(lds_cptr)p; }
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -341,6 +341,83 @@ constexpr uint32_t kRS32 = 18, kPD32 = 18 * 32, kHS32 = 18;
 // through the matrix cores; the rare 16 x (2|1) tile is handed to the worklist)
 constexpr uint32_t kTD32 = 8 * 18;
 constexpr uint32_t kOut32 = 512;  // dwords of the region after the planes: transposed planes / parked output pixels
+
+// ---------------------------------------------------------------------------
+// The directional detector of a staged 32x32 tile (three planes of u16 pairs, rows of kRS32 dwords) on pixel QUADS: per lane
+// the integer sums of |hz| and |vr| over the 3x3 windows it owns; the caller sums them over the wave.
+// Lane map: j = tid & 7 is the quad (columns 4j..4j+3 = dwords 2j, 2j+1 of a row: ONE aligned ds_read_b64 per row and
+// channel -- 18 per tile where the pair form issues 60 ds_read_b32 and fetches every dword twice), G = tid >> 3 one of eight
+// row groups with base row R = 8 (G & 3) + 4 (G >> 2).  The four groups of a 32-lane half lie 8 rows = 144 dwords = 16
+// (mod 64) apart: disjoint 16-bank ranges, no conflicts.  A group reads rows R..R+5 and owns window rows R..R+3 (two steps
+// of two rows; R = 28 owns 28 and 29 and runs one step -- rows 32, 33 are neither read nor counted).
+// Pair A = windows x = 4j, 4j+1, pair B = x = 4j+2, 4j+3.  Pair B needs the next quad's first pixel pair (1-2-1 along x) and
+// its pair-A column sum (|vr|): DPP row_shl:1.  Quad 7 has no pair-B window (x = 30, 31) and its DPP source is another
+// group's lane or zero: pair B keeps accumulators of its own, cleared for j == 7 before they are added.
+// The sums are integers: whatever the order, bit for bit those of the pair form.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void sobel32_quads(const uint32_t *s_pl, uint32_t tid, uint32_t &sum_hz, uint32_t &sum_vr)
+{
+	const uint32_t j = tid & 7u, G = tid >> 3;
+	const uint32_t *pq = s_pl + (8u * (G & 3u) + 4u * (G >> 2)) * kRS32 + 2u * j;
+	const uint32_t two = 0x00020002u;
+	// (compared afresh where it is used: hoisted out of the tile loop the lane mask would sit in two scalar registers, and
+	// those are spilled -- two v_readlane per use instead of one v_cmp)
+	auto second_step = [](uint32_t grp) -> bool {
+		asm volatile("" : "+v"(grp));
+		return grp != 7u;
+	};
+	// 1-2-1 along x of a row's quad: .x = pair A (p0 + 2 p1 + p2, p1 + 2 p2 + p3), .y = pair B (p2 + 2 p3 + p4, p3 + 2 p4 + p5)
+	auto smooth_row = [&](uint2 d) -> uint2 {
+		const uint32_t nx = dpp_mov<0x101>(d.x);  // row_shl:1 = (p4, p5), the quad to the right
+		return make_uint2(pk_mad_u16(__builtin_amdgcn_alignbit(d.y, d.x, 16), two, add2x16(d.x, d.y)),
+		                  pk_mad_u16(__builtin_amdgcn_alignbit(nx, d.y, 16), two, add2x16(d.y, nx)));
+	};
+	uint32_t hzA = 0, vrA = 0, hzB = 0, vrB = 0;
+	uint2 rA[3], rB[3], tP[3], dP[3];
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const uint2 a = lds_load2(pq + c * kPD32), b = lds_load2(pq + c * kPD32 + kRS32);
+		rA[c] = smooth_row(a);
+		rB[c] = smooth_row(b);
+		tP[c] = make_uint2(add2x16(a.x, b.x), add2x16(a.y, b.y));
+		dP[c] = b;
+	}
+#pragma unroll
+	for (int st = 0; st < 2; ++st) {
+		if (st < 1 || second_step(G)) {
+#pragma unroll
+			for (int c = 0; c < 3; ++c) {
+				const uint32_t *pr = pq + c * kPD32 + (2 + 2 * st) * (int)kRS32;
+				const uint2 n = lds_load2(pr), o = lds_load2(pr + kRS32);
+				const uint2 rN = smooth_row(n);
+				hzA = sad16(rN.x, rA[c].x, hzA);
+				hzB = sad16(rN.y, rA[c].y, hzB);
+				const uint2 tN = make_uint2(add2x16(dP[c].x, n.x), add2x16(dP[c].y, n.y));
+				const uint2 c0 = make_uint2(add2x16(tP[c].x, tN.x), add2x16(tP[c].y, tN.y));
+				vrA = sad16(c0.y, c0.x, vrA);                   // the neighbour columns are pair B's, in this lane
+				vrB = sad16(dpp_mov<0x101>(c0.x), c0.y, vrB);  // pair A's of the quad to the right
+				const uint2 rO = smooth_row(o);
+				hzA = sad16(rO.x, rB[c].x, hzA);
+				hzB = sad16(rO.y, rB[c].y, hzB);
+				const uint2 tO = make_uint2(add2x16(n.x, o.x), add2x16(n.y, o.y));
+				const uint2 e0 = make_uint2(add2x16(tN.x, tO.x), add2x16(tN.y, tO.y));
+				vrA = sad16(e0.y, e0.x, vrA);
+				vrB = sad16(dpp_mov<0x101>(e0.x), e0.y, vrB);
+				rA[c] = rN;
+				rB[c] = rO;
+				tP[c] = tO;
+				dP[c] = o;
+			}
+		}
+	}
+	{
+		uint32_t jj = j;
+		asm volatile("" : "+v"(jj));  // (a fresh compare, not a hoisted and spilled lane mask)
+		if (jj == 7u) hzB = vrB = 0;  // quad 7 starts no pair-B window (x = 30, 31)
+	}
+	sum_hz = hzA + hzB;
+	sum_vr = vrA + vrB;
+}
 
 template <int LPI>
 __device__ __forceinline__ int32_t group_sum(int32_t v)

@@ -263,61 +263,8 @@ __global__ void __launch_bounds__(1024) shrink32_kernel(const Fast32Args a)
 		uint32_t key0 = 0, key1 = 0;
 		if constexpr (MODE == 1) {
 			uint32_t sum_hz = 0, sum_vr = 0;
-			// 16 lanes (pixel pairs) per row group, 4 groups of 8 window rows (the last one 6).  Per
-			// channel and window row: r = 1-2-1 along x (perm, add, mad), |hz| (sad), column smoothing
-			// c = t(y)+t(y+1) (2 adds), the neighbour pair's c by DPP, |vr| (sad).  Fully unrolled:
-			// every LDS address is a per-channel base + immediate, no loop-carried register moves.
-			const uint32_t q = tid & 15u, g = tid >> 4;
-			// (compared afresh where it is used: hoisted out of the tile loop the lane mask would sit in two scalar
-			// registers, and those are spilled -- two v_readlane per use instead of one v_cmp)
-			auto last_rows = [](uint32_t grp) -> bool {
-				asm volatile("" : "+v"(grp));
-				return grp != 3u;
-			};
-			const uint32_t two = 0x00020002u;
-			const uint32_t *pc[3];
-			pc[0] = s_pl + g * (8u * kRS32) + q;
-			pc[1] = pc[0] + kPD32;
-			pc[2] = pc[1] + kPD32;
-			uint32_t rA[3], rB[3], tP[3], dP[3];
-#pragma unroll
-			for (int c = 0; c < 3; ++c) {
-				const uint32_t a0 = lds_dword(pc[0] + c * kPD32), a1 = lds_dword(pc[0] + c * kPD32 + 1);
-				const uint32_t b0 = lds_dword(pc[0] + c * kPD32 + kRS32), b1 = lds_dword(pc[0] + c * kPD32 + kRS32 + 1);
-				rA[c] = pk_mad_u16(__builtin_amdgcn_alignbit(a1, a0, 16), two, add2x16(a0, a1));
-				rB[c] = pk_mad_u16(__builtin_amdgcn_alignbit(b1, b0, 16), two, add2x16(b0, b1));
-				tP[c] = add2x16(a0, b0);
-				dP[c] = b0;
-			}
-#pragma unroll
-			for (int st = 0; st < 4; ++st) {
-				if (st < 3 || last_rows(g)) {  // the last group has 6 window rows = 3 steps
-#pragma unroll
-					for (int c = 0; c < 3; ++c) {
-						const uint32_t *pr = pc[0] + c * kPD32 + (2 + 2 * st) * (int)kRS32;
-						const uint32_t n0 = lds_dword(pr), n1 = lds_dword(pr + 1), o0 = lds_dword(pr + kRS32), o1 = lds_dword(pr + kRS32 + 1);
-						const uint32_t rN = pk_mad_u16(__builtin_amdgcn_alignbit(n1, n0, 16), two, add2x16(n0, n1));
-						sum_hz = sad16(rN, rA[c], sum_hz);
-						const uint32_t tN = add2x16(dP[c], n0);
-						const uint32_t c0 = add2x16(tP[c], tN);
-						sum_vr = sad16(dpp_mov<0x101>(c0), c0, sum_vr);  // row_shl:1 = the pair to the right
-						const uint32_t rO = pk_mad_u16(__builtin_amdgcn_alignbit(o1, o0, 16), two, add2x16(o0, o1));
-						sum_hz = sad16(rO, rB[c], sum_hz);
-						const uint32_t tO = add2x16(n0, o0);
-						const uint32_t e0 = add2x16(tN, tO);
-						sum_vr = sad16(dpp_mov<0x101>(e0), e0, sum_vr);
-						rA[c] = rN;
-						rB[c] = rO;
-						tP[c] = tO;
-						dP[c] = o0;
-					}
-				}
-			}
-			{
-				uint32_t qq = q;
-				asm volatile("" : "+v"(qq));  // (a fresh compare, not a hoisted and spilled lane mask)
-				if (qq == 15u) sum_hz = sum_vr = 0;  // pair 15 starts no window (x = 30, 31)
-			}
+			// on pixel quads, one aligned 8-byte LDS read per row and channel: sobel32_quads (pxz_device.h)
+			sobel32_quads(s_pl, tid, sum_hz, sum_vr);
 			sum_hz = wave_sum_sgpr_bcast(sum_hz);
 			sum_vr = wave_sum_sgpr_bcast(sum_vr);
 			m0 = level_of(sum_hz);
@@ -550,46 +497,7 @@ __global__ void __launch_bounds__(1024) shrink32a_kernel(const Fast32Args a)
 		uint32_t m0, m1;
 		if constexpr (MODE == 1) {
 			uint32_t sum_hz = 0, sum_vr = 0;
-			const uint32_t q = tid & 15u, g = tid >> 4;
-			const uint32_t two = 0x00020002u;
-			const uint32_t *pc[3];
-			pc[0] = s_pl + g * (8u * kRS32) + q;
-			pc[1] = pc[0] + kPD32;
-			pc[2] = pc[1] + kPD32;
-			uint32_t rA[3], rB[3], tP[3], dP[3];
-#pragma unroll
-			for (int c = 0; c < 3; ++c) {
-				const uint32_t a0 = pc[c][0], a1 = pc[c][1], b0 = pc[c][kRS32], b1 = pc[c][kRS32 + 1];
-				rA[c] = pk_mad_u16(__builtin_amdgcn_alignbit(a1, a0, 16), two, add2x16(a0, a1));
-				rB[c] = pk_mad_u16(__builtin_amdgcn_alignbit(b1, b0, 16), two, add2x16(b0, b1));
-				tP[c] = add2x16(a0, b0);
-				dP[c] = b0;
-			}
-#pragma unroll
-			for (int st = 0; st < 4; ++st) {
-				if (st < 3 || g != 3u) {
-#pragma unroll
-					for (int c = 0; c < 3; ++c) {
-						const uint32_t *pr = pc[c] + (2 + 2 * st) * (int)kRS32;
-						const uint32_t n0 = pr[0], n1 = pr[1], o0 = pr[kRS32], o1 = pr[kRS32 + 1];
-						const uint32_t rN = pk_mad_u16(__builtin_amdgcn_alignbit(n1, n0, 16), two, add2x16(n0, n1));
-						sum_hz = sad16(rN, rA[c], sum_hz);
-						const uint32_t tN = add2x16(dP[c], n0);
-						const uint32_t c0 = add2x16(tP[c], tN);
-						sum_vr = sad16(dpp_mov<0x101>(c0), c0, sum_vr);
-						const uint32_t rO = pk_mad_u16(__builtin_amdgcn_alignbit(o1, o0, 16), two, add2x16(o0, o1));
-						sum_hz = sad16(rO, rB[c], sum_hz);
-						const uint32_t tO = add2x16(n0, o0);
-						const uint32_t e0 = add2x16(tN, tO);
-						sum_vr = sad16(dpp_mov<0x101>(e0), e0, sum_vr);
-						rA[c] = rN;
-						rB[c] = rO;
-						tP[c] = tO;
-						dP[c] = o0;
-					}
-				}
-			}
-			if (q == 15u) sum_hz = sum_vr = 0;
+			sobel32_quads(s_pl, tid, sum_hz, sum_vr);  // (the fourth plane is not its business)
 			sum_hz = wave_sum_sgpr(sum_hz);
 			sum_vr = wave_sum_sgpr(sum_vr);
 			m0 = level_of(sum_hz);
